@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- MFCC frames/sec of the fused HIP hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--config {2,3,5}]
+    python bench.py --gpus N --steps K --warmup W [--config {2,3,5}] [--dump-outputs DIR] [--full]
 
 Workload (default BASELINE.json configs[1]; configs[3] = the same per GPU when N > 1): per GPU, 1000 synthetic
 10 s clips @22050 Hz, frame_length=1024, hop_length=256, n_mfcc=13 (SURVEY.md 8(d) generator), already resident in
@@ -20,7 +20,14 @@ under the other step's kernels.  --inflight 1 is one afx_extract_batch call at a
 form (the clips cut into S runs, one context / stream / host thread each -- how batch_process drives a GPU).
 A step is always one pass over all of the rank's clips.
 
-Prints ONE JSON line on rank 0 (contract in the task statement), including
+A plain run does only what the headline figure needs: it sets up, warms up, times the K steps, writes the last step's
+outputs if --dump-outputs is given, and prints ONE JSON line on rank 0: metric, value (frames/s over the timed steps),
+unit, higher_is_better, dtype, ms_per_step (wall-clock milliseconds of one timed step) and the workload description.
+--dump-outputs DIR writes what the last timed step returned for rank 0's clips -- stats [clips, 4*n_mfcc+3] as
+DIR/stats.npy (float32), status, trim [clips, 2] and nframes as float64 -- at most 64 MB in all (above that, a fixed
+seeded sample of the clips, their indices in DIR/sample_index.npy).  The clips depend only on the arguments, so two
+builds run with the same arguments can be compared output for output.
+--full adds everything else the benchmark measures, to the same line:
   roofline     -- the frame kernel (dominant): algorithmic bytes = 4*hop per frame (each input sample read once) /
                   average launch duration.  Durations come from HIP events recorded on the kernel's own stream around
                   every launch of the timed region; with several streams in flight the launches overlap, so the time
@@ -33,7 +40,10 @@ Prints ONE JSON line on rank 0 (contract in the task statement), including
   distinct_batches_frames_per_s -- the timed region repeated over --distinct different ragged batches (every submit uploads
                   new clip records; the device rebuilds its block list): what a window pipeline over real files sees;
   cpu_baseline -- the numpy/scipy oracle (a port of the reference's librosa path) timed on this box's host cores over a
-                  bounded sample of the same workload: one core, and a pool over every core this process may use.
+                  bounded sample of the same workload: one core, and a pool over every core this process may use;
+  host_to_result_frames_per_s -- one pass from host memory (PCIe-inclusive).
+--cpu-clips, --cpu-pool-seconds, --distinct and --no-timing-events shape those extra measurements and take effect only
+with --full.
 """
 from __future__ import annotations
 
@@ -166,6 +176,28 @@ def union_ms(spans) -> float:
     return tot
 
 
+OUTPUT_KEYS = ("stats", "status", "trim", "nframes")     # what extract_batch / extract_collect hand a caller, per clip
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path: str, arrays: dict, limit: int = DUMP_LIMIT_BYTES, seed: int = 0) -> None:
+    """Writes path/<name>.npy for every per-clip array (float32 kept, everything else as float64).  When they would
+    exceed `limit` bytes in all, a fixed seeded sample of the clips (rows) is written instead, the sampled clip indices
+    as path/sample_index.npy."""
+    import numpy as np
+    arrs = {k: np.ascontiguousarray(v if v.dtype == np.float32 else v.astype(np.float64)) for k, v in arrays.items()}
+    n = len(next(iter(arrs.values())))
+    row_bytes = sum(v.nbytes for v in arrs.values()) / max(n, 1)
+    if row_bytes * n > limit:
+        keep = max(1, int(limit // (row_bytes + 8)))           # + 8: the float64 index of every sampled row
+        idx = np.sort(np.random.default_rng(seed).choice(n, keep, replace=False))
+        arrs = {k: v[idx] for k, v in arrs.items()}
+        arrs["sample_index"] = idx.astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    for k, v in arrs.items():
+        np.save(os.path.join(path, k + ".npy"), v)
+
+
 def self_launch(args) -> int:
     """`python bench.py --gpus N` without a launcher: start the N ranks as children (this process has not touched the GPU)."""
     import socket
@@ -211,7 +243,16 @@ def main() -> None:
     ap.add_argument("--queue", choices=("shared", "own"), default="own",
                     help="with --inflight > 1: the steps in flight share one stream (back to back) or have one each "
                          "(the tail of one step's frame kernel under the start of the next)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned for rank 0's clips as DIR/<name>.npy "
+                         "(stats float32; status, trim, nframes float64; at most 64 MB)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline figure: roofline (HIP events in the timed region "
+                         "and an exclusive run), the CPU baseline, the host-memory pass and the distinct-batch region")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    timing = args.full and not args.no_timing_events
     if args.streams > 1:
         args.inflight = 1          # sub-batches on their own streams: one step at a time each
 
@@ -233,9 +274,9 @@ def main() -> None:
     workers = max(1, min(16, usable_cpus() // max(1, world)))
     samples, offsets, lengths = make_batch(n_clips, SR, SECONDS, first_index=rank * n_clips, workers=workers)
 
-    # CPU baseline first (rank 0, N=1 only), before this process touches the GPU
+    # CPU baseline first (--full, rank 0, N=1 only), before this process touches the GPU
     cpu = None
-    if rank == 0 and world == 1 and args.cpu_clips > 0:
+    if args.full and rank == 0 and world == 1 and args.cpu_clips > 0:
         cpu = cpu_baseline(samples, offsets, lengths, cfg, args.cpu_clips, args.cpu_pool_seconds)
 
     import torch
@@ -365,16 +406,17 @@ def main() -> None:
         assert int((ln["out"]["status"] != 0).sum()) == 0, "synthetic clips must all succeed"
     frames_per_step = int(sum(int(ln["out"]["nframes"].sum()) for ln in (lanes[:1] if D > 1 else lanes)))
 
-    # PCIe-inclusive rate (host float32 -> stats), reported beside the HBM-resident value
-    h0 = time.perf_counter()
-    hres = lanes[0]["plan"].extract_batch(samples[:int(offsets[cut[1] - 1] + lengths[cut[1] - 1])], offsets[:cut[1]], lengths[:cut[1]])
-    host_dt = time.perf_counter() - h0
-    host_frames = int(hres["nframes"].sum())
+    # PCIe-inclusive rate (host float32 -> stats), reported beside the HBM-resident value (--full)
+    host_rate = None
+    if args.full:
+        h0 = time.perf_counter()
+        hres = lanes[0]["plan"].extract_batch(samples[:int(offsets[cut[1] - 1] + lengths[cut[1] - 1])], offsets[:cut[1]], lengths[:cut[1]])
+        host_rate = int(hres["nframes"].sum()) / (time.perf_counter() - h0)
 
     # The frame kernel alone on the GPU: the WHOLE batch on one stream, a few launches outside the timed region
     # (a separate context; the same figure a single-stream rocprofv3 kernel trace of this command gives).
     exclusive = None
-    if not args.no_timing_events and rank == 0:
+    if timing and rank == 0:
         xc = N.Context(device)
         xp = N.Plan(xc, params())
         xb = N.DeviceBuffer(xc, samples.nbytes)
@@ -398,14 +440,14 @@ def main() -> None:
     # the untimed warm-up steps sit directly in front of the timed region: the two measurements above ran on other plans /
     # from host memory, and the lanes' first steps after them pay for it (their workspace is out of the TLB and the caches)
     # (with the frame-kernel events already switched on: their first records are not free either)
-    if not args.no_timing_events:
+    if timing:
         for ln in lanes:
             ln["plan"].set_timing(True, frames_only=True)      # one event pair per step: the kernel the roofline is about
     # at least 32 of them whatever --warmup says (about 20 ms): after the idle gaps of the set-up the clocks take about that
     # long to come back -- a 20-step region behind 8 warm-up steps ran 4-5 % below the same region behind 20 (same-box,
     # profiles/r03_ab_runs.txt); a job that streams batches is in the warmed state
     run_steps(max(args.warmup, 32))
-    if not args.no_timing_events:
+    if timing:
         for ln in lanes:
             ln["plan"].timings(reset=True)
     fence()
@@ -413,8 +455,15 @@ def main() -> None:
     run_steps(args.steps)
     fence()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        # the last timed step's results, before anything below reuses the lanes' output arrays
+        if D > 1:
+            last = lanes[(step_no[0] - 1) % D]["out"]
+            dump_outputs(args.dump_outputs, {k: last[k] for k in OUTPUT_KEYS})
+        else:                # one step = every lane once, the lanes' clips in order
+            dump_outputs(args.dump_outputs, {k: np.concatenate([ln["out"][k] for ln in lanes]) for k in OUTPUT_KEYS})
     kt, spans = None, None
-    if not args.no_timing_events:
+    if timing:
         kt, spans = {}, []
         for ln in lanes:
             spans.extend(map(tuple, ln["plan"].intervals("frames")))
@@ -424,7 +473,7 @@ def main() -> None:
 
     # ---- the same steps over DISTINCT ragged batches (no plan ever meets the clip lengths of its previous batch)
     distinct = None
-    if D > 1 and args.distinct >= 2:
+    if args.full and D > 1 and args.distinct >= 2:
         rng = np.random.default_rng(4242)          # the same cuts on every rank: equal frame counts
         variants = []
         for _ in range(args.distinct):
@@ -521,10 +570,11 @@ def main() -> None:
                        "parallelism": (f"file-shard x{world}, no collective; {S} in-flight sub-batches per GPU" if D == 1 else
                                        f"file-shard x{world}, no collective; {D} whole-batch steps in flight on {'one stream' if args.queue == 'shared' else 'their own streams'} (submit / collect)"),
                        "input": "HBM-resident float32"},
-            "roofline": roof,
-            "cpu_baseline": cpu,
-            "host_to_result_frames_per_s": host_frames / host_dt,
         }
+        if args.full:
+            line["roofline"] = roof
+            line["cpu_baseline"] = cpu
+            line["host_to_result_frames_per_s"] = host_rate
         if distinct is not None:
             dv = distinct["frames"] * world / distinct["elapsed"]
             line["distinct_batches_frames_per_s"] = dv

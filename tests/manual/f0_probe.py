@@ -1,4 +1,4 @@
-import sys, time; import os; sys.path.insert(0, os.environ.get('GRAFT_REPO_ROOT', '/root/repo'))
+import sys, time; import os; sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import numpy as np
 from audio_feature_extraction_amd import _native as N
 from audio_feature_extraction_amd.synth import make_batch, make_clip

@@ -181,3 +181,31 @@ def test_bench_interval_union():
     assert abs(bench.union_ms([(0.0, 1.0), (0.5, 2.0), (3.0, 3.5)]) - 2.5) < 1e-12
     assert abs(bench.union_ms([(2.0, 3.0), (0.0, 1.0), (0.25, 0.5)]) - 2.0) < 1e-12
     assert 1 <= bench.usable_cpus() <= (os.cpu_count() or 1)
+
+
+def test_bench_dump_outputs(tmp_path):
+    """bench.py --dump-outputs: float32 kept, integers as float64; above the byte limit a fixed seeded sample of rows."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    n = 1000
+    arrays = {"stats": np.arange(n * 55, dtype=np.float32).reshape(n, 55), "status": np.zeros(n, np.int32),
+              "trim": np.stack([np.arange(n), np.arange(n) + 7], 1).astype(np.int64), "nframes": np.arange(n, dtype=np.int32)}
+    bench.dump_outputs(str(tmp_path / "all"), arrays)
+    got = {k: np.load(tmp_path / "all" / (k + ".npy")) for k in arrays}
+    assert got["stats"].dtype == np.float32 and all(got[k].dtype == np.float64 for k in ("status", "trim", "nframes"))
+    for k in arrays:
+        np.testing.assert_array_equal(got[k], arrays[k])
+    assert not (tmp_path / "all" / "sample_index.npy").exists()
+    limit = 64 * 1024
+    for name in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / name), arrays, limit=limit)
+    a = {k: np.load(tmp_path / "s1" / (k + ".npy")) for k in list(arrays) + ["sample_index"]}
+    b = {k: np.load(tmp_path / "s2" / (k + ".npy")) for k in a}
+    assert sum(v.nbytes for v in a.values()) <= limit
+    idx = a["sample_index"].astype(np.int64)
+    assert 0 < idx.size < n and (np.diff(idx) > 0).all()
+    for k in arrays:
+        np.testing.assert_array_equal(a[k], b[k])
+        np.testing.assert_array_equal(a[k], arrays[k][idx])

@@ -1,6 +1,6 @@
 """Device-resident timing of the other BASELINE configs (parity cases, not bench lines): python tools/cfg_time.py"""
 import os, sys, time
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 from audio_feature_extraction_amd import _native as N
 from audio_feature_extraction_amd.synth import make_batch

@@ -1,7 +1,7 @@
 """Where a batch_process worker's device phase goes: one window of 16-bit clips (default 683 x 10 s @22050 Hz):
 python tools/device_phase.py [clips]"""
 import os, sys, time
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 from audio_feature_extraction_amd import _native as N
 

@@ -2,7 +2,7 @@
 changes): save the other version as audio_feature_extraction_amd/_parallel_prev.py (not tracked), then
 python tools/e2e_ab.py n_files  -> four interleaved rounds of process_files with and without pYIN for each version."""
 import os, sys, tempfile, time, logging
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 from pathlib import Path
 from audio_feature_extraction_amd import AudioFeatureExtractor

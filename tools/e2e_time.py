@@ -1,7 +1,7 @@
 """End-to-end batch_process on a directory of PCM16 WAV files (decode + MFCC/RMS + pYIN + dict building), files/s.
 python tools/e2e_time.py [n_files] [seconds]   -- writes synthetic clips to a temp dir first (not timed)."""
 import os, sys, tempfile, time, logging
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 from audio_feature_extraction_amd import AudioFeatureExtractor
 from audio_feature_extraction_amd.synth import make_clip

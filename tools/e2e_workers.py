@@ -1,6 +1,6 @@
 """End-to-end time of process_files against workers per GPU and window size: python tools/e2e_workers.py n_files"""
 import os, sys, tempfile, time, logging
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 from pathlib import Path
 from audio_feature_extraction_amd import AudioFeatureExtractor, parallel

@@ -3,7 +3,7 @@ trailing silence on a third of them) through afx_f0_batch with pre-emphasis + tr
 that two builds of libafx.so (AFX_LIB) or two workspace chunkings (AFX_TEST_F0_CHUNK_FRAMES) can be compared bit for bit:
 python tools/f0_soak.py out.npz [n]; python tools/f0_soak.py --cmp a.npz b.npz"""
 import os, sys
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 if sys.argv[1] == "--cmp":
     a, b = np.load(sys.argv[2]), np.load(sys.argv[3])

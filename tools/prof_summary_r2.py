@@ -32,7 +32,7 @@ for cfg in (2, 3, 5):
     tr = os.path.join(root, f"cfg{cfg}_trace")
     if not os.path.isdir(tr):
         continue
-    print(f"== config {cfg}: kernel stats, single stream (rocprofv3 --kernel-trace --stats; bench.py --config {cfg} --steps 20 --warmup 3 --cpu-clips 0 --streams 1 --inflight 1) ==")
+    print(f"== config {cfg}: kernel stats, single stream (rocprofv3 --kernel-trace --stats; bench.py --full --config {cfg} --steps 20 --warmup 3 --cpu-clips 0 --streams 1 --inflight 1) ==")
     rows = kernel_stats(tr)
     with open(os.path.join(root, f"cfg{cfg}_kernel_stats.csv"), "w") as fh:
         for r in rows:
@@ -45,7 +45,7 @@ for cfg in (2, 3, 5):
                 k = row.get("Kernel_Name", "")
                 if "afx" in k:
                     acc[short(k)][row["Counter_Name"]].append(float(row["Counter_Value"]))
-    lines = [f"== config {cfg}: PMC, per-dispatch average (separate rocprofv3 --pmc passes; bench.py --config {cfg} --steps 5 --warmup 2 --cpu-clips 0 --streams 1 --inflight 1) =="]
+    lines = [f"== config {cfg}: PMC, per-dispatch average (separate rocprofv3 --pmc passes; bench.py --full --config {cfg} --steps 5 --warmup 2 --cpu-clips 0 --streams 1 --inflight 1) =="]
     for k in sorted(acc):
         lines.append(k)
         for c in sorted(acc[k]):
@@ -82,7 +82,7 @@ for cfg in (2, 3, 5):
     print(json.dumps({k: tj[k] for k in ("pipeline_hbm_bytes_per_step", "algorithmic_bytes_per_step", "pipeline_over_algorithmic")}))
 s3 = os.path.join(root, "cfg2_default_trace")
 if os.path.isdir(s3):
-    print("== config 2: kernel stats, the default run: two steps in flight on their own streams (bench.py --steps 20 --warmup 3 --cpu-clips 0) ==")
+    print("== config 2: kernel stats, the default run: two steps in flight on their own streams (bench.py --full --steps 20 --warmup 3 --cpu-clips 0) ==")
     rows = kernel_stats(s3)
     with open(os.path.join(root, "cfg2_default_kernel_stats.csv"), "w") as fh:
         for r in rows:

@@ -3,7 +3,7 @@
 # usage (on the GPU box): tools/profile_f0_pmc.sh <tag>   -> gpurun_out/prof_<tag>/f0_pmc.txt
 set -u
 TAG=${1:-r03f0}
-ROOT=${GRAFT_REPO_ROOT:-/root/repo}
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$ROOT/gpurun_out/prof_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp

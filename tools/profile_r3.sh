@@ -7,24 +7,24 @@
 set -u
 TAG=${1:-r03}; shift
 CFGS=${@:-2 3 5}
-ROOT=${GRAFT_REPO_ROOT:-/root/repo}
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$ROOT/gpurun_out/prof_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 for C in $CFGS; do
-  BENCH="python3 $ROOT/bench.py --config $C --steps 20 --warmup 3 --cpu-clips 0 --streams 1 --inflight 1 --distinct 0"
+  BENCH="python3 $ROOT/bench.py --full --config $C --steps 20 --warmup 3 --cpu-clips 0 --streams 1 --inflight 1 --distinct 0"
   rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/cfg${C}_trace -- $BENCH > $OUT/cfg${C}_trace.log 2>&1
   echo "cfg$C trace rc=$?"
   for grp in "SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR" \
              "SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_ANY SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_WAIT_INST_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE" \
              "FETCH_SIZE" "WRITE_SIZE" "GRBM_GUI_ACTIVE SQ_INSTS_SMEM"; do
     name=$(echo $grp | tr ' ' '_' | cut -c1-40)
-    rocprofv3 --pmc $grp --output-format csv -d $OUT/cfg${C}_pmc_$name -- python3 $ROOT/bench.py --config $C --steps 5 --warmup 2 --cpu-clips 0 --streams 1 --inflight 1 --distinct 0 > $OUT/cfg${C}_pmc_$name.log 2>&1
+    rocprofv3 --pmc $grp --output-format csv -d $OUT/cfg${C}_pmc_$name -- python3 $ROOT/bench.py --full --config $C --steps 5 --warmup 2 --cpu-clips 0 --streams 1 --inflight 1 --distinct 0 > $OUT/cfg${C}_pmc_$name.log 2>&1
     echo "cfg$C pmc [$grp] rc=$?"
   done
 done
 if echo " $CFGS " | grep -q " 2 "; then
-  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/cfg2_default_trace -- python3 $ROOT/bench.py --steps 20 --warmup 3 --cpu-clips 0 --distinct 0 > $OUT/cfg2_default_trace.log 2>&1
+  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/cfg2_default_trace -- python3 $ROOT/bench.py --full --steps 20 --warmup 3 --cpu-clips 0 --distinct 0 > $OUT/cfg2_default_trace.log 2>&1
   echo "cfg2 default (two steps in flight) trace rc=$?"
 fi
 # extract_f0 (pYIN) of the same 1000 clips: the GPU time batch_process actually spends

@@ -1,6 +1,6 @@
 """int16 vs float32 device-resident batches through afx_extract_batch: python tools/s16_time.py"""
 import os, sys, time
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 from audio_feature_extraction_amd import _native as N
 from audio_feature_extraction_amd.synth import make_batch

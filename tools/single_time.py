@@ -1,6 +1,6 @@
 """Latency of extract_features on one 5 s PCM16 WAV (BASELINE configs[0]): python tools/single_time.py"""
 import os, sys, tempfile, time, logging
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 from audio_feature_extraction_amd import AudioFeatureExtractor
 from audio_feature_extraction_amd.synth import make_clip

@@ -1,10 +1,10 @@
 #!/bin/bash
 # kernel timeline of a multi-stream run (rocprofv3 --kernel-trace): tools/timeline.sh <streams> <waves> <tag>
-ROOT=${GRAFT_REPO_ROOT:-/root/repo}
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
 S=${1:-2}; W=${2:-16}; TAG=${3:-tl}
 OUT=$ROOT/gpurun_out/$TAG; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-AFX_F3_WAVES=$W rocprofv3 --kernel-trace --output-format csv -d $OUT/trace -- python3 $ROOT/bench.py --steps 12 --warmup 3 --cpu-clips 0 --streams $S --no-timing-events ${EXTRA:-} > $OUT/run.log 2>&1
+AFX_F3_WAVES=$W rocprofv3 --kernel-trace --output-format csv -d $OUT/trace -- python3 $ROOT/bench.py --full --steps 12 --warmup 3 --cpu-clips 0 --streams $S --no-timing-events ${EXTRA:-} > $OUT/run.log 2>&1
 python3 - $OUT <<'PY'
 import csv, glob, os, sys
 rows = []
