@@ -19,6 +19,10 @@ WINDOW_HAMMING, WINDOW_HANN = 0, 1
 FMT_F32, FMT_S16 = 0, 1
 MEM_HOST, MEM_DEVICE = 0, 1
 FLAG_PREEMPH, FLAG_TRIM = 1, 2
+DTW_OK, DTW_NONFINITE, DTW_NO_PATH = 0, 1, 2
+DTW_METRICS = {"euclidean": 0, "sqeuclidean": 1, "cosine": 2}
+DTW_BACKTRACK, DTW_STORE_D = 1, 2
+DTW_MAX_DIM = 128
 K_NAMES = ("trim_blocks", "trim_decide", "frames", "dct", "stats")
 K_FRAMES = 2
 
@@ -28,7 +32,7 @@ SYMBOLS = (
     "afx_malloc", "afx_free", "afx_host_alloc", "afx_host_free", "afx_memcpy_h2d", "afx_memcpy_d2h", "afx_synchronize",
     "afx_default_params", "afx_plan_create", "afx_plan_destroy", "afx_build_tables", "afx_build_mel_schedule",
     "afx_extract_batch", "afx_extract_submit", "afx_extract_collect", "afx_f0_batch", "afx_zcr_batch", "afx_spectral_batch", "afx_f0_build_tables", "afx_preprocess", "afx_plan_set_timing", "afx_plan_get_timings", "afx_plan_get_intervals",
-    "afx_wav_probe", "afx_wav_read_s16", "afx_batch_geometry",
+    "afx_wav_probe", "afx_wav_read_s16", "afx_batch_geometry", "afx_dtw_batch",
 )
 
 
@@ -96,6 +100,7 @@ def lib() -> C.CDLL:
         L.afx_batch_geometry.argtypes = [C.POINTER(Params), vp, vp, i32, vp, vp]
         L.afx_wav_probe.argtypes = [vp, i32, i32, vp, vp, vp, vp]
         L.afx_wav_read_s16.argtypes = [vp, i32, i32, vp, vp, vp, C.c_int64, vp, vp]
+        L.afx_dtw_batch.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp]
         _lib = L
     return _lib
 
@@ -291,6 +296,56 @@ class Context:
             self.close()
         except Exception:
             pass
+
+    def dtw_batch(self, feats, x_off, x_len, y_off, y_len, band_r=None, metric: str = "euclidean",
+                  backtrack: bool = True, store_d: bool = False) -> dict:
+        """afx_dtw_batch: DTW of pairs of frame sequences held in one frame-major float32 buffer ``feats`` [frames, dim]
+        (pair p aligns frames x_off[p] .. + x_len[p] with y_off[p] .. + y_len[p]).  ``band_r``: None, or per pair the
+        band radius (< 0: unconstrained).  Returns cost [n] float64, status [n] int32 and, when asked, ``paths`` (list of
+        [L, 2] int arrays, end to start; None for a failed pair) and ``D`` (list of [N, M] float64 arrays)."""
+        feats = np.ascontiguousarray(feats, np.float32)
+        if feats.ndim != 2:
+            raise ValueError("feats must be [frames, dim]")
+        dim = int(feats.shape[1])
+        xo, xl, yo, yl = (np.ascontiguousarray(a, np.int64).reshape(-1) for a in (x_off, x_len, y_off, y_len))
+        n = int(xo.shape[0])
+        if not (xl.shape[0] == yo.shape[0] == yl.shape[0] == n):
+            raise ValueError("x_off, x_len, y_off, y_len must have one entry per pair")
+        if n and (int(np.maximum(xo + xl, yo + yl).max()) > feats.shape[0] or xo.min() < 0 or yo.min() < 0):
+            raise ValueError("a pair extends past the feature buffer")
+        if metric not in DTW_METRICS:
+            raise ValueError(f"unsupported metric {metric!r} ({', '.join(DTW_METRICS)})")
+        br = None if band_r is None else np.ascontiguousarray(band_r, np.int32).reshape(-1)
+        if br is not None and br.shape[0] != n:
+            raise ValueError("band_r must have one entry per pair")
+        cost, status = np.zeros(n, np.float64), np.zeros(n, np.int32)
+        flags = (DTW_BACKTRACK if backtrack else 0) | (DTW_STORE_D if store_d else 0)
+        path = poff = plen = dmat = doff = None
+        if backtrack:
+            steps = xl + yl - 1
+            poff = np.zeros(n, np.int64)
+            if n:
+                poff[1:] = np.cumsum(steps)[:-1]
+            path = np.zeros((int(steps.sum()) if n else 0, 2), np.int32)
+            plen = np.zeros(n, np.int32)
+        if store_d:
+            cells = xl * yl
+            doff = np.zeros(n, np.int64)
+            if n:
+                doff[1:] = np.cumsum(cells)[:-1]
+            dmat = np.empty(int(cells.sum()) if n else 0, np.float64)
+        ptr = (lambda a: None if a is None else a.ctypes.data)
+        _check(lib().afx_dtw_batch(self.handle, feats.ctypes.data, dim, xo.ctypes.data, xl.ctypes.data, yo.ctypes.data,
+                                   yl.ctypes.data, ptr(br), n, DTW_METRICS[metric], flags, cost.ctypes.data,
+                                   status.ctypes.data, ptr(path), ptr(poff), ptr(plen), ptr(dmat), ptr(doff)),
+               "afx_dtw_batch")
+        out = {"cost": cost, "status": status}
+        if backtrack:
+            path = path.astype(np.int64)
+            out["paths"] = [path[poff[p]:poff[p] + plen[p]] if status[p] == DTW_OK else None for p in range(n)]
+        if store_d:
+            out["D"] = [dmat[doff[p]:doff[p] + xl[p] * yl[p]].reshape(int(xl[p]), int(yl[p])) for p in range(n)]
+        return out
 
 
 class Plan:

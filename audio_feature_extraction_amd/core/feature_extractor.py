@@ -314,6 +314,63 @@ class AudioFeatureExtractor:
         """``np.savez(npz_path, **features)`` -- the reference's on-disk schema for frame-level features."""
         np.savez(npz_path, **features)
 
+    # ------------------------------------------------------------------ alignment (05_dtw_alignment_experiment)
+    def _frames_of(self, paths: Sequence[str], stack_deltas: bool) -> Dict[str, np.ndarray]:
+        """(features, frames) MFCC matrices of the given files: ``.npz`` files written by ``save_frame_features`` are read
+        (``npz['mfcc']``), ``.wav`` files go through one ``extract_batch(want_frames=True)`` pass on the GPU."""
+        out: Dict[str, np.ndarray] = {}
+        wavs = []
+        K = self.n_mfcc
+        for p in dict.fromkeys(str(q) for q in paths):
+            if p.lower().endswith(".npz"):
+                with np.load(p, allow_pickle=False) as z:
+                    m = np.asarray(z["mfcc"], np.float32)
+                out[p] = m if stack_deltas or m.shape[0] != 3 * K else m[:K]
+            else:
+                wavs.append(p)
+        if wavs:
+            ys = [np.ascontiguousarray(self.load_audio(p)[0], np.float32) for p in wavs]
+            lengths = np.array([y.size for y in ys], np.int64)
+            offsets = np.zeros(len(ys), np.int64)
+            offsets[1:] = np.cumsum(lengths)[:-1]
+            res = self._plan().extract_batch(np.concatenate(ys), offsets, lengths,
+                                             flags=_native.FLAG_PREEMPH | _native.FLAG_TRIM, want_frames=True)
+            for i, p in enumerate(wavs):
+                st = int(res["status"][i])
+                if st != _native.CLIP_OK:
+                    raise _status_error(st, f"align: {p}", int(res["nframes"][i]))
+                fr = res["frames"][i]
+                rows = [fr["mfcc"], fr["mfcc_delta"], fr["mfcc_delta2"]] if stack_deltas else [fr["mfcc"]]
+                out[p] = np.ascontiguousarray(np.vstack(rows), np.float32)
+        return out
+
+    @staticmethod
+    def _alignment(teacher: str, student: str, cost: float, wp: np.ndarray) -> Dict[str, Any]:
+        return {"teacher_path": teacher, "student_path": student, "dtw_distance": float(cost),
+                "normalized_distance": float(cost) / len(wp), "path": wp}
+
+    def align_files(self, teacher: str, student: str, *, stack_deltas: bool = True, **dtw_kwargs) -> Dict[str, Any]:
+        """DTW alignment of a student's utterance to a teacher's, the step the reference's aligner runs
+        (05_dtw_alignment_experiment/dtw_alignment.py:1206-1250 loads ``npz['mfcc']``, :930-970 aligns it).
+        ``teacher`` / ``student``: ``.wav`` files (MFCC, with ``stack_deltas`` + delta + delta2, computed on the GPU) or
+        ``.npz`` files written by ``save_frame_features``.  ``dtw_kwargs`` go to ``sequence.dtw`` (metric,
+        global_constraints, band_rad).  Returns teacher_path, student_path, dtw_distance, normalized_distance (distance
+        over path length) and path (L x 2, teacher frame, student frame, end to start)."""
+        from .. import sequence
+        f = self._frames_of([teacher, student], stack_deltas)
+        cost, wp = sequence.dtw(f[str(teacher)], f[str(student)], **dtw_kwargs)
+        return self._alignment(teacher, student, cost, wp)
+
+    def align_batch(self, pairs: Sequence[Tuple[str, str]], *, stack_deltas: bool = True,
+                    **dtw_kwargs) -> List[Optional[Dict[str, Any]]]:
+        """``align_files`` of many (teacher, student) pairs: every distinct file is extracted once (one GPU pass for the
+        ``.wav`` files) and all pairs are aligned in one ``sequence.dtw_batch`` call.  The list is aligned with ``pairs``;
+        a pair that fails is logged and None."""
+        from .. import sequence
+        f = self._frames_of([p for pr in pairs for p in pr], stack_deltas)
+        res = sequence.dtw_batch([(f[str(t)], f[str(s)]) for t, s in pairs], **dtw_kwargs)
+        return [None if r is None else self._alignment(t, s, r[0], r[1]) for (t, s), r in zip(pairs, res)]
+
     def batch_process(self, audio_dir: str, *, features_to_extract: Optional[Sequence[str]] = None) -> List[Dict[str, Any]]:
         """批量處理音頻文件 (feature_extractor.py:215-237): every ``*.wav`` directly inside
         ``audio_dir`` in glob order; a failing file is logged and left out.  Files are

@@ -15,6 +15,7 @@
 
 #include "afx_device.h"
 #include "afx_devenv.h"
+#include "afx_dtw.h"
 #include "afx_f0.h"
 #include "afx_frames3.h"
 #include "afx_internal.h"
@@ -33,6 +34,7 @@ using namespace afx;
 struct afx_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
+  DevBuf dtw_raw, dtw_feats, dtw_norms, dtw_pairs, dtw_codes, dtw_rows, dtw_d, dtw_path, dtw_cost, dtw_status, dtw_len;   // afx_dtw_batch
 };
 
 struct afx_plan {
@@ -115,6 +117,7 @@ DevEnv::DevEnv() {
   if (const char* v = getenv("AFX_TAIL_MODE")) tail_mode = atoi(v);
   if (const char* v = getenv("AFX_TEST_CHUNK_CLIPS")) chunk_clips = std::max(1, std::min(32768, atoi(v)));
   if (const char* v = getenv("AFX_TEST_F0_CHUNK_FRAMES")) f0_chunk_frames = std::max<int64_t>(64, atoll(v));
+  if (const char* v = getenv("AFX_TEST_DTW_BUDGET")) dtw_budget = std::max<int64_t>(1, atoll(v));
   f0_dump = getenv("AFX_F0_DUMP");
 }
 const DevEnv& dev_env() { static const DevEnv e; return e; }
@@ -172,6 +175,9 @@ extern "C" int afx_init(int device, afx_ctx** out) {
 extern "C" void afx_destroy(afx_ctx* ctx) {
   if (!ctx) return;
   (void)hipSetDevice(ctx->device);
+  for (DevBuf* b : {&ctx->dtw_raw, &ctx->dtw_feats, &ctx->dtw_norms, &ctx->dtw_pairs, &ctx->dtw_codes, &ctx->dtw_rows, &ctx->dtw_d,
+                    &ctx->dtw_path, &ctx->dtw_cost, &ctx->dtw_status, &ctx->dtw_len})
+    release(*b);
   if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
   delete ctx;
 }
@@ -1140,5 +1146,136 @@ extern "C" int afx_preprocess(afx_plan* pl, const float* y, int64_t n, float* ou
   // T is about the MFCC stage; preprocess_audio itself only fails on < 2 samples / non-finite input
   *start = ci.start; *end = ci.end;
   *status = (n < 2) ? AFX_CLIP_TOO_SHORT : (ci.nonfinite ? AFX_CLIP_NONFINITE : AFX_CLIP_OK);
+  return AFX_OK;
+}
+
+// ---- batched DTW (librosa.sequence.dtw): the alignment step the reference runs on the extracted MFCC frames ----------
+extern "C" int afx_dtw_batch(afx_ctx* ctx, const float* feats, int dim,
+                             const int64_t* x_off, const int64_t* x_len, const int64_t* y_off, const int64_t* y_len,
+                             const int32_t* band_r, int n_pairs, int metric, int flags,
+                             double* out_cost, int32_t* out_status,
+                             int32_t* out_path, const int64_t* path_off, int32_t* out_path_len,
+                             double* out_D, const int64_t* d_off) {
+  const bool bt = (flags & AFX_DTW_BACKTRACK) != 0, sd = (flags & AFX_DTW_STORE_D) != 0;
+  if (!ctx || n_pairs < 0 || (n_pairs > 0 && (!feats || !x_off || !x_len || !y_off || !y_len || !out_cost || !out_status))) {
+    set_error("afx_dtw_batch: null/invalid argument");
+    return AFX_ERR_INVALID;
+  }
+  if (flags & ~(AFX_DTW_BACKTRACK | AFX_DTW_STORE_D)) { set_error("afx_dtw_batch: unknown flag"); return AFX_ERR_INVALID; }
+  if (metric != AFX_DTW_EUCLIDEAN && metric != AFX_DTW_SQEUCLIDEAN && metric != AFX_DTW_COSINE) {
+    set_error("afx_dtw_batch: unknown metric");
+    return AFX_ERR_INVALID;
+  }
+  if (n_pairs > 0 && bt && (!out_path || !path_off || !out_path_len)) {
+    set_error("afx_dtw_batch: AFX_DTW_BACKTRACK needs out_path, path_off and out_path_len");
+    return AFX_ERR_INVALID;
+  }
+  if (n_pairs > 0 && sd && (!out_D || !d_off)) { set_error("afx_dtw_batch: AFX_DTW_STORE_D needs out_D and d_off"); return AFX_ERR_INVALID; }
+  if (dim < 1) { set_error("afx_dtw_batch: dim must be >= 1"); return AFX_ERR_INVALID; }
+  if (dim > kDtwMaxDim) { set_error("afx_dtw_batch: dim > 128 is not supported by the DTW kernel"); return AFX_ERR_UNSUPPORTED; }
+  int64_t n_frames = 0;
+  for (int p = 0; p < n_pairs; ++p) {
+    if (x_off[p] < 0 || y_off[p] < 0 || x_len[p] < 1 || y_len[p] < 1 || x_off[p] > INT64_MAX / 2 || y_off[p] > INT64_MAX / 2 ||
+        x_len[p] > INT32_MAX || y_len[p] > INT32_MAX) {
+      set_error("afx_dtw_batch: pair " + std::to_string(p) + ": offsets must be >= 0 and lengths >= 1");
+      return AFX_ERR_INVALID;
+    }
+    if (x_len[p] * y_len[p] > ((int64_t)1 << 31) || x_len[p] > (1 << 30) || y_len[p] > (1 << 30)) {
+      set_error("afx_dtw_batch: pair " + std::to_string(p) + ": N * M > 2^31 cells is not supported");
+      return AFX_ERR_UNSUPPORTED;
+    }
+    if ((bt && path_off[p] < 0) || (sd && d_off[p] < 0)) {
+      set_error("afx_dtw_batch: pair " + std::to_string(p) + ": negative output offset");
+      return AFX_ERR_INVALID;
+    }
+    n_frames = std::max(n_frames, std::max(x_off[p] + x_len[p], y_off[p] + y_len[p]));
+  }
+  if (n_pairs == 0) return AFX_OK;
+  if (n_frames > INT64_MAX / 4 / dim) { set_error("afx_dtw_batch: feature buffer too large"); return AFX_ERR_INVALID; }
+
+  (void)hipGetLastError();
+  HIP_TRY(hipSetDevice(ctx->device));
+  hipStream_t s = ctx->stream;
+  int rc;
+  // the caller's frames are uploaded once and re-strided on the device to the padded width the DP kernel reads
+  const size_t feat_bytes = (size_t)n_frames * dim * sizeof(float);
+  if ((rc = ensure(ctx->dtw_raw, feat_bytes)) != AFX_OK) return rc;
+  if ((rc = ensure(ctx->dtw_feats, (size_t)n_frames * dtw_dimp(dim) * sizeof(float))) != AFX_OK) return rc;
+  if ((rc = ensure(ctx->dtw_norms, (size_t)n_frames * sizeof(float))) != AFX_OK) return rc;
+  HIP_TRY(hipMemcpyAsync(ctx->dtw_raw.p, feats, feat_bytes, hipMemcpyHostToDevice, s));
+  HIP_TRY(launch_dtw_pack(s, (const float*)ctx->dtw_raw.p, dim, n_frames, (float*)ctx->dtw_feats.p, (float*)ctx->dtw_norms.p));
+  const float* d_norms = (const float*)ctx->dtw_norms.p;
+
+  const int64_t budget = dev_env().dtw_budget;
+  std::vector<DtwPair> recs;
+  std::vector<int32_t> h_path, h_len;
+  for (int c0 = 0; c0 < n_pairs;) {
+    // one chunk: as many pairs as the workspace budget holds (at least one)
+    recs.clear();
+    int64_t codes = 0, dcells = 0, paths = 0, rows = 0, bytes = 0;
+    int c1 = c0;
+    while (c1 < n_pairs) {
+      const int n = (int)x_len[c1], m = (int)y_len[c1];
+      const int64_t pc = bt ? dtw_code_words(n, m) : 0, pd = sd ? (int64_t)n * m : 0, pp = bt ? (int64_t)n + m - 1 : 0;
+      const int64_t pb = pc * 4 + pd * 8 + pp * 8 + (int64_t)m * 8 + (int64_t)sizeof(DtwPair) + 16;
+      if (c1 > c0 && bytes + pb > budget) break;
+      DtwPair r{};
+      r.x_frame = x_off[c1]; r.y_frame = y_off[c1];
+      r.codes = bt ? codes : -1; r.d = sd ? dcells : -1; r.path = paths; r.row = rows;
+      r.n = n; r.m = m; r.qn = dtw_qn(m);
+      const int64_t rad = band_r ? band_r[c1] : -1;
+      if (rad < 0) {
+        r.lo = -(1 << 30); r.hi = 1 << 30;
+      } else {
+        const int64_t rr = std::min<int64_t>(rad, (int64_t)n + m), off = std::abs(n - m);
+        r.lo = (int32_t)(-rr - (n >= m ? off : 0));
+        r.hi = (int32_t)(rr + (n < m ? off : 0));
+      }
+      recs.push_back(r);
+      codes += pc; dcells += pd; paths += pp; rows += m; bytes += pb;
+      ++c1;
+    }
+    const int n = c1 - c0;
+    if ((rc = ensure(ctx->dtw_pairs, n * sizeof(DtwPair))) != AFX_OK) return rc;
+    if ((rc = ensure(ctx->dtw_rows, (size_t)rows * sizeof(double))) != AFX_OK) return rc;
+    if ((rc = ensure(ctx->dtw_cost, n * sizeof(double))) != AFX_OK) return rc;
+    if ((rc = ensure(ctx->dtw_status, n * sizeof(int32_t))) != AFX_OK) return rc;
+    if (bt) {
+      if ((rc = ensure(ctx->dtw_codes, (size_t)codes * sizeof(uint32_t))) != AFX_OK) return rc;
+      if ((rc = ensure(ctx->dtw_path, (size_t)paths * 2 * sizeof(int32_t))) != AFX_OK) return rc;
+      if ((rc = ensure(ctx->dtw_len, n * sizeof(int32_t))) != AFX_OK) return rc;
+    }
+    if (sd) {
+      if ((rc = ensure(ctx->dtw_d, (size_t)dcells * sizeof(double))) != AFX_OK) return rc;
+      HIP_TRY(launch_dtw_fill_inf(s, (double*)ctx->dtw_d.p, dcells));
+    }
+    HIP_TRY(hipMemcpyAsync(ctx->dtw_pairs.p, recs.data(), n * sizeof(DtwPair), hipMemcpyHostToDevice, s));
+    const DtwPair* d_pairs = (const DtwPair*)ctx->dtw_pairs.p;
+    HIP_TRY(launch_dtw(s, (const float*)ctx->dtw_feats.p, d_norms, dim, metric, d_pairs, n, (uint32_t*)ctx->dtw_codes.p,
+                       (double*)ctx->dtw_rows.p, (double*)ctx->dtw_d.p, (double*)ctx->dtw_cost.p,
+                       (int32_t*)ctx->dtw_status.p, bt, sd));
+    if (bt)
+      HIP_TRY(launch_dtw_backtrack(s, d_pairs, n, (const uint32_t*)ctx->dtw_codes.p, (const int32_t*)ctx->dtw_status.p,
+                                   (int32_t*)ctx->dtw_path.p, (int32_t*)ctx->dtw_len.p));
+    HIP_TRY(hipMemcpyAsync(out_cost + c0, ctx->dtw_cost.p, n * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(out_status + c0, ctx->dtw_status.p, n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    if (bt) {
+      h_path.resize((size_t)paths * 2);
+      h_len.resize(n);
+      HIP_TRY(hipMemcpyAsync(h_path.data(), ctx->dtw_path.p, (size_t)paths * 2 * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+      HIP_TRY(hipMemcpyAsync(h_len.data(), ctx->dtw_len.p, n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    }
+    if (sd)
+      for (int q = 0; q < n; ++q)
+        HIP_TRY(hipMemcpyAsync(out_D + d_off[c0 + q], (const double*)ctx->dtw_d.p + recs[q].d,
+                               (size_t)recs[q].n * recs[q].m * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (bt)
+      for (int q = 0; q < n; ++q) {
+        out_path_len[c0 + q] = h_len[q];
+        std::memcpy(out_path + 2 * path_off[c0 + q], h_path.data() + 2 * recs[q].path, (size_t)h_len[q] * 2 * sizeof(int32_t));
+      }
+    c0 = c1;
+  }
   return AFX_OK;
 }

@@ -20,6 +20,7 @@ struct DevEnv {
   int f3_waves = 0;                   // 12 / 16: force the workgroup size of the wave-level frame kernels
   int chunk_clips = 32768;
   int64_t f0_chunk_frames = 1280 * 1024;
+  int64_t dtw_budget = (int64_t)2 << 30;   // device workspace bytes of one afx_dtw_batch chunk
   const char* f0_dump = nullptr;
   DevEnv();
 };

@@ -41,4 +41,8 @@ int afx_preprocess(afx_plan*, const float*, int64_t, float*, int64_t*, int64_t*,
 int afx_plan_set_timing(afx_plan*, int) { return no_device("afx_plan_set_timing"); }
 int afx_plan_get_timings(afx_plan*, float*, int32_t*, int) { return no_device("afx_plan_get_timings"); }
 int afx_plan_get_intervals(afx_plan*, int, double*, double*, int, int32_t*) { return no_device("afx_plan_get_intervals"); }
+int afx_dtw_batch(afx_ctx*, const float*, int, const int64_t*, const int64_t*, const int64_t*, const int64_t*, const int32_t*,
+                  int, int, int, double*, int32_t*, int32_t*, const int64_t*, int32_t*, double*, const int64_t*) {
+  return no_device("afx_dtw_batch");
+}
 }

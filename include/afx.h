@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define AFX_VERSION 104      /* 104: afx_batch_geometry, afx_host_alloc / afx_host_free */
+#define AFX_VERSION 105      /* 105: afx_dtw_batch; 104: afx_batch_geometry, afx_host_alloc / afx_host_free */
 
 typedef enum afx_status {
   AFX_OK = 0,
@@ -48,6 +48,18 @@ typedef enum afx_clip_status {
                               librosa.feature.delta raises ParameterError (F:137) */
   AFX_CLIP_NONFINITE = 2   /* NaN/Inf sample: librosa.util.valid_audio raises */
 } afx_clip_status;
+
+/* per-pair status of afx_dtw_batch */
+typedef enum afx_dtw_status {
+  AFX_DTW_OK = 0,
+  AFX_DTW_NONFINITE = 1,   /* NaN / inf feature, or a zero-norm frame under AFX_DTW_COSINE (librosa raises) */
+  AFX_DTW_NO_PATH = 2      /* D[N-1, M-1] is inf: the band admits no path (band radius 0) */
+} afx_dtw_status;
+
+/* local cost of afx_dtw_batch: scipy.spatial.distance.cdist's metrics of the same names */
+enum { AFX_DTW_EUCLIDEAN = 0, AFX_DTW_SQEUCLIDEAN = 1, AFX_DTW_COSINE = 2 };
+/* flags for afx_dtw_batch */
+enum { AFX_DTW_BACKTRACK = 1, AFX_DTW_STORE_D = 2 };
 
 enum { AFX_WINDOW_HAMMING = 0, AFX_WINDOW_HANN = 1 };
 enum { AFX_FMT_F32 = 0, AFX_FMT_S16 = 1 };           /* S16: value / 32768 (libsndfile) */
@@ -235,6 +247,33 @@ int afx_spectral_batch(afx_plan* plan,
                        const void* samples, int sample_fmt, int mem_kind,
                        const int64_t* offsets, const int64_t* lengths, int n_clips, int flags,
                        float* out_desc, const int64_t* desc_offsets, int32_t* out_status);
+
+/* Batched DTW alignment (librosa.sequence.dtw at its defaults: step sizes (1,1), (0,1), (1,0) in that order, the first
+ * minimum winning a tie), the step the reference's aligner runs on pairs of MFCC(+delta+delta2) frame matrices
+ * (05_dtw_alignment_experiment/dtw_alignment.py:930-970, :1092-1130, :1206-1250).
+ *   feats     host float32, frame-major: frame t is feats[t * dim .. t * dim + dim); X and Y of pair p are the frames
+ *             x_off[p] .. + x_len[p] and y_off[p] .. + y_len[p] (a teacher shared by many students is held once)
+ *   dim       1 .. 128 (AFX_ERR_UNSUPPORTED above); every N * M must be <= 2^31 and N, M <= 2^30
+ *             (AFX_ERR_UNSUPPORTED otherwise)
+ *   band_r    NULL, or per pair the band radius r = round_half_even(band_rad * min(N, M)) of librosa's
+ *             global_constraints (fill_off_diagonal); r < 0: unconstrained
+ *   metric    AFX_DTW_EUCLIDEAN / AFX_DTW_SQEUCLIDEAN / AFX_DTW_COSINE, evaluated in float32 from direct differences;
+ *             the accumulation is float64
+ *   flags     AFX_DTW_BACKTRACK: the warping path; AFX_DTW_STORE_D: the accumulated cost matrix
+ *   out_cost  host double[n_pairs]: D[N-1, M-1]   (NaN for a NONFINITE pair, inf for NO_PATH)
+ *   out_status host int32[n_pairs]: afx_dtw_status; a failed pair never affects the others
+ *   out_path, path_off, out_path_len  (AFX_DTW_BACKTRACK) pair p's path as L int32 (i, j) pairs at
+ *             out_path[2 * path_off[p] ..], end to start (wp[0] = (N-1, M-1), wp[L-1] = (0, 0)); N + M - 1 pairs
+ *             must be reserved; out_path_len[p] = L (0 for a failed pair)
+ *   out_D, d_off  (AFX_DTW_STORE_D) row-major float64 N x M at out_D[d_off[p] ..], inf outside the band
+ * The batch runs in chunks whose device workspace (step codes at 2 bits per cell, D when stored, one boundary row per
+ * pair) stays within 2 GiB; a pair larger than that runs alone. */
+int afx_dtw_batch(afx_ctx* ctx, const float* feats, int dim,
+                  const int64_t* x_off, const int64_t* x_len, const int64_t* y_off, const int64_t* y_len,
+                  const int32_t* band_r, int n_pairs, int metric, int flags,
+                  double* out_cost, int32_t* out_status,
+                  int32_t* out_path, const int64_t* path_off, int32_t* out_path_len,
+                  double* out_D, const int64_t* d_off);
 
 /* Host-only (no device needed): the tables afx_f0_batch uploads, for inspection and tests.
  * info[8] = min_period, max_period, n_pitch_bins, band (transition half-width), candidate
