@@ -23,6 +23,8 @@ DTW_OK, DTW_NONFINITE, DTW_NO_PATH = 0, 1, 2
 DTW_METRICS = {"euclidean": 0, "sqeuclidean": 1, "cosine": 2}
 DTW_BACKTRACK, DTW_STORE_D = 1, 2
 DTW_MAX_DIM = 128
+HPSS_STORE_SPEC = 4
+HPSS_BINS = 1025
 K_NAMES = ("trim_blocks", "trim_decide", "frames", "dct", "stats")
 K_FRAMES = 2
 
@@ -32,7 +34,7 @@ SYMBOLS = (
     "afx_malloc", "afx_free", "afx_host_alloc", "afx_host_free", "afx_memcpy_h2d", "afx_memcpy_d2h", "afx_synchronize",
     "afx_default_params", "afx_plan_create", "afx_plan_destroy", "afx_build_tables", "afx_build_mel_schedule",
     "afx_extract_batch", "afx_extract_submit", "afx_extract_collect", "afx_f0_batch", "afx_zcr_batch", "afx_spectral_batch", "afx_f0_build_tables", "afx_preprocess", "afx_plan_set_timing", "afx_plan_get_timings", "afx_plan_get_intervals",
-    "afx_wav_probe", "afx_wav_read_s16", "afx_batch_geometry", "afx_dtw_batch",
+    "afx_wav_probe", "afx_wav_read_s16", "afx_batch_geometry", "afx_dtw_batch", "afx_hpss_batch",
 )
 
 
@@ -101,6 +103,7 @@ def lib() -> C.CDLL:
         L.afx_wav_probe.argtypes = [vp, i32, i32, vp, vp, vp, vp]
         L.afx_wav_read_s16.argtypes = [vp, i32, i32, vp, vp, vp, C.c_int64, vp, vp]
         L.afx_dtw_batch.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp]
+        L.afx_hpss_batch.argtypes = [vp, vp, i32, i32, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp]
         _lib = L
     return _lib
 
@@ -552,6 +555,55 @@ class Plan:
             out.append({"centroid": m[:, 0].copy(), "bandwidth": m[:, 1].copy(), "rolloff": m[:, 2].copy(),
                         "valley": m[:, 3:10].T.copy(), "peak": m[:, 10:17].T.copy()})
         return {"clips": out, "status": status}
+
+    def hpss_batch(self, samples, offsets, lengths, flags=0, fmt=FMT_F32, mem=MEM_HOST, want_harm: bool = True,
+                   want_perc: bool = False, want_stats: bool = True, store_spec: bool = False) -> dict:
+        """afx_hpss_batch: librosa.effects.hpss of a ragged batch (plan: frame_length 2048, hop_length 512, Hann).
+        ``samples``: a C-contiguous host array, or with ``mem=MEM_DEVICE`` a device address (int) of ``fmt`` samples.
+        Returns status [n] int32 and, as asked, ``harm`` / ``perc`` (lists of float32 arrays), ``stats`` [n, 4] float64
+        (sum h^2, sum y^2, mean and std of h's spectral centroid) and ``spec`` (per clip S, Hm, Pm as [3, 1025, T])."""
+        offsets = np.ascontiguousarray(offsets, np.int64).reshape(-1)
+        lengths = np.ascontiguousarray(lengths, np.int64).reshape(-1)
+        n = int(offsets.shape[0])
+        if lengths.shape[0] != n:
+            raise ValueError("offsets and lengths must have one entry per clip")
+        if mem == MEM_HOST:
+            want = np.int16 if fmt == FMT_S16 else np.float32
+            if not isinstance(samples, np.ndarray) or samples.dtype != want or not samples.flags.c_contiguous:
+                raise ValueError(f"samples must be a C-contiguous {want.__name__} array")
+            if n and int((offsets + lengths).max()) > samples.size:
+                raise ValueError("a clip extends past the sample buffer")
+            sptr = samples.ctypes.data
+        else:
+            sptr = int(samples)
+        total = int((offsets + lengths).max()) if n else 0
+        harm = np.zeros(total, np.float32) if want_harm else None
+        perc = np.zeros(total, np.float32) if want_perc else None
+        stats = np.zeros((n, 4), np.float64) if want_stats else None
+        status = np.zeros(n, np.int32)
+        spec = soff = None
+        T = 1 + lengths // self.params.hop
+        if store_spec:
+            flags |= HPSS_STORE_SPEC
+            cnt = 3 * HPSS_BINS * T
+            soff = np.zeros(n, np.int64)
+            if n:
+                soff[1:] = np.cumsum(cnt)[:-1]
+            spec = np.zeros(int(cnt.sum()) if n else 0, np.float32)
+        ptr = (lambda a: None if a is None else a.ctypes.data)
+        _check(lib().afx_hpss_batch(self.handle, sptr, int(fmt), int(mem), offsets.ctypes.data, lengths.ctypes.data, n,
+                                    int(flags), ptr(harm), ptr(perc), ptr(stats), ptr(spec), ptr(soff),
+                                    status.ctypes.data), "afx_hpss_batch")
+        out = {"status": status}
+        if want_harm:
+            out["harm"] = [harm[o:o + l] for o, l in zip(offsets, lengths)]
+        if want_perc:
+            out["perc"] = [perc[o:o + l] for o, l in zip(offsets, lengths)]
+        if want_stats:
+            out["stats"] = stats
+        if store_spec:
+            out["spec"] = [spec[soff[i]:soff[i] + 3 * HPSS_BINS * T[i]].reshape(3, HPSS_BINS, int(T[i])) for i in range(n)]
+        return out
 
     def preprocess(self, y: np.ndarray):
         y = np.ascontiguousarray(y, np.float32)

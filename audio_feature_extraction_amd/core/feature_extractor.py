@@ -309,6 +309,34 @@ class AudioFeatureExtractor:
             out[k + "_std"] = float(np.std(f[k]))
         return out
 
+    _HARMONIC_KEYS = ("harmonic_energy", "harmonic_ratio", "harmonic_freq_mean", "harmonic_freq_std")
+
+    def extract_harmonic_features_batch(self, signals: Sequence[np.ndarray]) -> List[Dict[str, Any]]:
+        """``extract_harmonic_features`` of many signals in one device pass (a failing clip raises)."""
+        ys = [np.ascontiguousarray(y, dtype=np.float32) for y in signals]
+        if not ys:
+            return []
+        for y in ys:
+            if y.ndim != 1:
+                raise ValueError(f"signals must be 1-D (mono), got shape {y.shape}")
+        lengths = np.array([y.size for y in ys], np.int64)
+        offsets = np.zeros(len(ys), np.int64)
+        offsets[1:] = np.cumsum(lengths)[:-1]
+        out = self._spectral_plan().hpss_batch(np.concatenate(ys), offsets, lengths, want_harm=False)
+        res = []
+        for i, st in enumerate(out["status"]):
+            if st != _native.CLIP_OK:
+                raise _status_error(int(st), "extract_harmonic_features")
+            eh, ey, fm, fs = (float(v) for v in out["stats"][i])
+            res.append(dict(zip(self._HARMONIC_KEYS, (eh, eh / (ey + 1e-8), fm, fs))))
+        return res
+
+    def extract_harmonic_features(self, y: np.ndarray) -> Dict[str, Any]:
+        """提取諧波特徵 (04_feature_extraction_experiment/feature_extractor.py:525-556): the energy of
+        ``librosa.effects.harmonic(y)``, its ratio to the energy of ``y`` and the mean / std of the harmonic signal's
+        spectral centroid, all on the GPU."""
+        return self.extract_harmonic_features_batch([y])[0]
+
     @staticmethod
     def save_frame_features(features: Dict[str, np.ndarray], npz_path: str) -> None:
         """``np.savez(npz_path, **features)`` -- the reference's on-disk schema for frame-level features."""

@@ -18,6 +18,7 @@
 #include "afx_dtw.h"
 #include "afx_f0.h"
 #include "afx_frames3.h"
+#include "afx_hpss.h"
 #include "afx_internal.h"
 
 namespace afx {
@@ -63,6 +64,7 @@ struct afx_plan {
   F0Tables f0_dt{};
   std::vector<void*> f0_allocs;
   DevBuf f0_in, f0_ysig, f0_energy, f0_cnt, f0_vp, f0_bin, f0_prob, f0_lprob, f0_lu, f0_ptr, f0_best, f0_states, f0_stats, f0_out, f0_offs;
+  DevBuf hp_clips, hp_y, hp_h, hp_p, hp_x, hp_yh, hp_yp, hp_bad, hp_stats, hp_spec;   // afx_hpss_batch
   // cached per-batch descriptors
   std::vector<int64_t> c_off, c_len;
   std::vector<ClipDesc> h_clips;
@@ -118,6 +120,7 @@ DevEnv::DevEnv() {
   if (const char* v = getenv("AFX_TEST_CHUNK_CLIPS")) chunk_clips = std::max(1, std::min(32768, atoi(v)));
   if (const char* v = getenv("AFX_TEST_F0_CHUNK_FRAMES")) f0_chunk_frames = std::max<int64_t>(64, atoll(v));
   if (const char* v = getenv("AFX_TEST_DTW_BUDGET")) dtw_budget = std::max<int64_t>(1, atoll(v));
+  if (const char* v = getenv("AFX_TEST_HPSS_BUDGET")) hpss_budget = std::max<int64_t>(1, atoll(v));
   f0_dump = getenv("AFX_F0_DUMP");
 }
 const DevEnv& dev_env() { static const DevEnv e; return e; }
@@ -357,6 +360,8 @@ extern "C" void afx_plan_destroy(afx_plan* pl) {
   release(pl->logmel); release(pl->rms); release(pl->mfcc); release(pl->frames);
   release(pl->frame_offs); release(pl->stamps);
   release(pl->blocks_spec); release(pl->blockmax); release(pl->items); release(pl->n_items);
+  for (DevBuf* b : {&pl->hp_clips, &pl->hp_y, &pl->hp_h, &pl->hp_p, &pl->hp_x, &pl->hp_yh, &pl->hp_yp, &pl->hp_bad, &pl->hp_stats, &pl->hp_spec})
+    release(*b);
   if (pl->h_pin) (void)hipHostFree(pl->h_pin);
   if (pl->h_clips_pin) (void)hipHostFree(pl->h_clips_pin);
   if (pl->clips_ev) (void)hipEventDestroy(pl->clips_ev);
@@ -1030,6 +1035,30 @@ extern "C" int afx_zcr_batch(afx_plan* pl, const void* samples, int sample_fmt, 
   return AFX_OK;
 }
 
+// octave bands of librosa.feature.spectral_contrast(fmin=200, n_bands=6, quantile=0.02) as bin ranges (n_fft 2048)
+static bool spectral_bands(int sr_hz, SpecBands& sb) {
+  sb = SpecBands{};
+  const int NB = 1025;
+  const double sr = (double)sr_hz, df = sr / 2048.0;
+  double octa[8];
+  octa[0] = 0.0;
+  for (int i = 1; i < 8; ++i) octa[i] = 200.0 * std::pow(2.0, (double)(i - 1));
+  for (int i = 0; i < 7; ++i)
+    if (octa[i] >= 0.5 * sr) { set_error("spectral_contrast: frequency band exceeds Nyquist (sr too low for 6 octave bands from 200 Hz)"); return false; }
+  for (int k = 0; k < 7; ++k) {
+    int b0 = -1, b1 = -1;
+    for (int b = 0; b < NB; ++b) { const double f = (double)b * df; if (f >= octa[k] && f <= octa[k + 1]) { if (b0 < 0) b0 = b; b1 = b; } }
+    if (b0 < 0) { set_error("spectral_contrast: empty band"); return false; }
+    if (k > 0) b0 -= 1;
+    if (k == 6) b1 = NB - 1;
+    const int n_cur = b1 - b0 + 1;
+    sb.cnt[k] = std::max(1, (int)std::nearbyint(0.02 * (double)n_cur));
+    sb.lo[k] = b0; sb.hi[k] = (k < 6) ? b1 - 1 : b1;
+  }
+  sb.hz_per_bin = (float)df; sb.roll_percent = 0.85f;
+  return true;
+}
+
 // ---- spectral descriptors (librosa.feature.spectral_centroid / _bandwidth / _rolloff / _contrast at their defaults) ------
 extern "C" int afx_spectral_batch(afx_plan* pl, const void* samples, int sample_fmt, int mem_kind,
                                   const int64_t* offsets, const int64_t* lengths, int n_clips, int flags,
@@ -1047,28 +1076,8 @@ extern "C" int afx_spectral_batch(afx_plan* pl, const void* samples, int sample_
   if (flags & AFX_FLAG_TRIM) { set_error("afx_spectral_batch: trim is not applied here; pass the preprocessed signal"); return AFX_ERR_UNSUPPORTED; }
   if (n_clips == 0) return AFX_OK;
   if (n_clips > 32768) { set_error("afx_spectral_batch: at most 32768 clips per call"); return AFX_ERR_INVALID; }
-  // octave bands of librosa.feature.spectral_contrast(fmin=200, n_bands=6, quantile=0.02) as bin ranges
   SpecBands sb{};
-  {
-    const int NB = 1025;
-    const double sr = (double)pl->p.sr, df = sr / 2048.0;
-    double octa[8];
-    octa[0] = 0.0;
-    for (int i = 1; i < 8; ++i) octa[i] = 200.0 * std::pow(2.0, (double)(i - 1));
-    for (int i = 0; i < 7; ++i)
-      if (octa[i] >= 0.5 * sr) { set_error("spectral_contrast: frequency band exceeds Nyquist (sr too low for 6 octave bands from 200 Hz)"); return AFX_ERR_UNSUPPORTED; }
-    for (int k = 0; k < 7; ++k) {
-      int b0 = -1, b1 = -1;
-      for (int b = 0; b < NB; ++b) { const double f = (double)b * df; if (f >= octa[k] && f <= octa[k + 1]) { if (b0 < 0) b0 = b; b1 = b; } }
-      if (b0 < 0) { set_error("spectral_contrast: empty band"); return AFX_ERR_UNSUPPORTED; }
-      if (k > 0) b0 -= 1;
-      if (k == 6) b1 = NB - 1;
-      const int n_cur = b1 - b0 + 1;
-      sb.cnt[k] = std::max(1, (int)std::nearbyint(0.02 * (double)n_cur));
-      sb.lo[k] = b0; sb.hi[k] = (k < 6) ? b1 - 1 : b1;
-    }
-    sb.hz_per_bin = (float)df; sb.roll_percent = 0.85f;
-  }
+  if (!spectral_bands(pl->p.sr, sb)) return AFX_ERR_UNSUPPORTED;
   (void)hipGetLastError();
   HIP_TRY(hipSetDevice(pl->device));
   if (pl->pend.active) { set_error("afx_spectral_batch: the plan has a submitted batch that has not been collected"); return AFX_ERR_INVALID; }
@@ -1275,6 +1284,176 @@ extern "C" int afx_dtw_batch(afx_ctx* ctx, const float* feats, int dim,
         out_path_len[c0 + q] = h_len[q];
         std::memcpy(out_path + 2 * path_off[c0 + q], h_path.data() + 2 * recs[q].path, (size_t)h_len[q] * 2 * sizeof(int32_t));
       }
+    c0 = c1;
+  }
+  return AFX_OK;
+}
+
+// ---- harmonic-percussive separation (librosa.effects.hpss / harmonic) and the harmonic features -----------------------
+extern "C" int afx_hpss_batch(afx_plan* pl, const void* samples, int sample_fmt, int mem_kind,
+                              const int64_t* offsets, const int64_t* lengths, int n_clips, int flags,
+                              float* out_harm, float* out_perc, double* out_stats,
+                              float* out_spec, const int64_t* spec_off, int32_t* out_status) {
+  const bool sd = (flags & AFX_HPSS_STORE_SPEC) != 0;
+  if (!pl || n_clips < 0 || (n_clips > 0 && (!samples || !offsets || !lengths || !out_status))) {
+    set_error("afx_hpss_batch: null/invalid argument");
+    return AFX_ERR_INVALID;
+  }
+  if (sample_fmt != AFX_FMT_F32 && sample_fmt != AFX_FMT_S16) { set_error("unknown sample format"); return AFX_ERR_INVALID; }
+  if (mem_kind != AFX_MEM_HOST && mem_kind != AFX_MEM_DEVICE) { set_error("unknown mem_kind"); return AFX_ERR_INVALID; }
+  if (pl->p.n_fft != 2048 || pl->p.hop != 512 || pl->p.window != AFX_WINDOW_HANN || !pl->use_f3) {
+    set_error("afx_hpss_batch: the plan must have frame_length 2048, hop_length 512 and the Hann window (librosa's defaults)");
+    return AFX_ERR_UNSUPPORTED;
+  }
+  if (flags & AFX_FLAG_TRIM) { set_error("afx_hpss_batch: trim is not applied here; pass the preprocessed signal"); return AFX_ERR_UNSUPPORTED; }
+  if (flags & ~(AFX_FLAG_PREEMPH | AFX_FLAG_TRIM | AFX_HPSS_STORE_SPEC)) { set_error("afx_hpss_batch: unknown flag"); return AFX_ERR_INVALID; }
+  if (sd && n_clips > 0 && (!out_spec || !spec_off)) { set_error("afx_hpss_batch: AFX_HPSS_STORE_SPEC needs out_spec and spec_off"); return AFX_ERR_INVALID; }
+  for (int i = 0; i < n_clips; ++i) {
+    if (offsets[i] < 0 || lengths[i] < 0 || offsets[i] > INT64_MAX / 4 || (sd && spec_off[i] < 0)) {
+      set_error("afx_hpss_batch: clip " + std::to_string(i) + ": offsets and lengths must be >= 0");
+      return AFX_ERR_INVALID;
+    }
+    if (lengths[i] > ((int64_t)1 << 31)) {
+      set_error("afx_hpss_batch: clip " + std::to_string(i) + ": more than 2^31 samples is not supported");
+      return AFX_ERR_UNSUPPORTED;
+    }
+  }
+  const double nan = std::nan("");
+  for (int i = 0; i < n_clips; ++i) {
+    out_status[i] = lengths[i] == 0 ? AFX_CLIP_TOO_SHORT : AFX_CLIP_OK;
+    if (out_stats) for (int k = 0; k < 4; ++k) out_stats[4 * i + k] = nan;
+  }
+  if (n_clips == 0) return AFX_OK;
+  // the centroid runs k_frames3s<DESC>, which also forms the contrast bands; below 12.8 kHz they do not exist and are
+  // replaced by a harmless single bin (only the centroid is read here)
+  SpecBands sb{};
+  if (out_stats && !spectral_bands(pl->p.sr, sb)) {
+    sb = SpecBands{};
+    for (int k = 0; k < 8; ++k) { sb.lo[k] = 0; sb.hi[k] = 0; sb.cnt[k] = 1; }
+    sb.hz_per_bin = (float)((double)pl->p.sr / 2048.0); sb.roll_percent = 0.85f;
+  }
+  (void)hipGetLastError();
+  HIP_TRY(hipSetDevice(pl->device));
+  if (pl->pend.active) { set_error("afx_hpss_batch: the plan has a submitted batch that has not been collected"); return AFX_ERR_INVALID; }
+  hipStream_t s = pl->ctx->stream;
+  const bool want_p = out_perc != nullptr;
+  const int nsig = want_p ? 3 : 2;                  // y, h (, p) and X, Yh (, Yp)
+  const size_t esz = sample_fmt == AFX_FMT_S16 ? 2 : 4;
+  const int64_t budget = dev_env().hpss_budget;
+  const HpssTabs tb{pl->f3.window, pl->f3.w1024, pl->f3.w2048};
+  std::vector<HpssClip> recs;
+  std::vector<int> idx;
+  std::vector<int64_t> h_off, h_len, d_off;
+  std::vector<uint32_t> h_bad;
+  std::vector<double> h_stats;
+  int rc;
+  for (int c0 = 0; c0 < n_clips;) {
+    // one chunk: as many clips as the workspace budget holds (at least one); zero-length clips take no work
+    recs.clear(); idx.clear();
+    int64_t frames = 0, ysz = 0, specf = 0, bytes = 0, lo = INT64_MAX, hi = 0, max_len = 0;
+    int tiles = 0;
+    int c1 = c0;
+    for (; c1 < n_clips && (int)recs.size() < 32768; ++c1) {
+      const int64_t L = lengths[c1];
+      if (L == 0) continue;
+      const int64_t T = 1 + L / 512, nt = (T + kHpssTile - 1) / kHpssTile;
+      const int64_t pb = T * kHpssPitch * 8 * nsig + L * 4 * nsig + (mem_kind == AFX_MEM_HOST ? L * (int64_t)esz : 0) +
+                         T * kSpecFloats * 4 + (sd ? 3 * kHpssBins * T * 4 : 0) + 128;
+      if (!recs.empty() && (bytes + pb > budget || tiles + nt > 65535)) break;
+      HpssClip r{};
+      r.in_off = offsets[c1]; r.y_off = ysz; r.len = L; r.frame_base = frames; r.spec_off = specf;
+      r.T = (int32_t)T; r.tile_base = tiles;
+      recs.push_back(r); idx.push_back(c1);
+      frames += T; ysz += L; specf += sd ? 3 * kHpssBins * T : 0; tiles += (int)nt; bytes += pb;
+      lo = std::min(lo, offsets[c1]); hi = std::max(hi, offsets[c1] + L); max_len = std::max(max_len, L);
+    }
+    const int n = (int)recs.size();
+    if (n == 0) { c0 = c1; continue; }
+    const void* d_in = samples;
+    if (mem_kind == AFX_MEM_HOST) {
+      if ((rc = ensure(pl->samples, (size_t)(hi - lo) * esz + 16)) != AFX_OK) return rc;
+      HIP_TRY(hipMemcpyAsync(pl->samples.p, (const char*)samples + (size_t)lo * esz, (size_t)(hi - lo) * esz, hipMemcpyHostToDevice, s));
+      for (HpssClip& r : recs) r.in_off -= lo;
+      d_in = pl->samples.p;
+    }
+    const size_t spec_bytes = (size_t)frames * kHpssPitch * sizeof(float2), sig_bytes = (size_t)ysz * sizeof(float) + 64;
+    if ((rc = ensure(pl->hp_clips, n * sizeof(HpssClip))) != AFX_OK) return rc;
+    if ((rc = ensure(pl->hp_bad, n * sizeof(uint32_t))) != AFX_OK) return rc;
+    if ((rc = ensure(pl->hp_y, sig_bytes)) != AFX_OK) return rc;
+    if ((rc = ensure(pl->hp_h, sig_bytes)) != AFX_OK) return rc;
+    if ((rc = ensure(pl->hp_x, spec_bytes)) != AFX_OK) return rc;
+    if ((rc = ensure(pl->hp_yh, spec_bytes)) != AFX_OK) return rc;
+    if (want_p) {
+      if ((rc = ensure(pl->hp_p, sig_bytes)) != AFX_OK) return rc;
+      if ((rc = ensure(pl->hp_yp, spec_bytes)) != AFX_OK) return rc;
+    }
+    if (sd && (rc = ensure(pl->hp_spec, (size_t)specf * sizeof(float))) != AFX_OK) return rc;
+    if (out_stats && (rc = ensure(pl->hp_stats, (size_t)n * 4 * sizeof(double))) != AFX_OK) return rc;
+    const HpssClip* d_clips = (const HpssClip*)pl->hp_clips.p;
+    uint32_t* d_bad = (uint32_t*)pl->hp_bad.p;
+    float* d_y = (float*)pl->hp_y.p;
+    float* d_h = (float*)pl->hp_h.p;
+    float* d_p = want_p ? (float*)pl->hp_p.p : nullptr;
+    float2* d_yp = want_p ? (float2*)pl->hp_yp.p : nullptr;
+    HIP_TRY(hipMemcpyAsync(pl->hp_clips.p, recs.data(), n * sizeof(HpssClip), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemsetAsync(d_bad, 0, n * sizeof(uint32_t), s));
+    HIP_TRY(launch_hpss_prep(s, d_in, sample_fmt, flags, pl->kp.preemph_b1, d_clips, n, max_len, d_y, d_bad));
+    HIP_TRY(launch_hpss_stft(s, d_y, d_clips, d_bad, n, frames, tb, (float2*)pl->hp_x.p));
+    HIP_TRY(launch_hpss_mask(s, (const float2*)pl->hp_x.p, d_clips, n, tiles, (float2*)pl->hp_yh.p, d_yp,
+                             sd ? (float*)pl->hp_spec.p : nullptr));
+    HIP_TRY(launch_hpss_irfft(s, (float2*)pl->hp_yh.p, d_yp, frames, tb));
+    HIP_TRY(launch_hpss_ola(s, (const float2*)pl->hp_yh.p, d_yp, d_clips, n, max_len, tb, d_h, d_p));
+    if (out_stats) {
+      // spectral_centroid(y=h): k_frames3s<DESC> over the device-resident h, then the per-clip reduction
+      h_off.resize(n); h_len.resize(n); d_off.resize(n);
+      for (int q = 0; q < n; ++q) { h_off[q] = recs[q].y_off; h_len[q] = recs[q].len; d_off[q] = kSpecFloats * recs[q].frame_base; }
+      if ((rc = prepare_descriptors(pl, h_off.data(), h_len.data(), n)) != AFX_OK) return rc;
+      if ((rc = ensure(pl->info, n * sizeof(ClipInfo))) != AFX_OK) return rc;
+      if ((rc = ensure(pl->frames, (size_t)frames * kSpecFloats * sizeof(float))) != AFX_OK) return rc;
+      if ((rc = ensure(pl->frame_offs, n * sizeof(int64_t))) != AFX_OK) return rc;
+      HIP_TRY(hipMemcpyAsync(pl->frame_offs.p, d_off.data(), n * sizeof(int64_t), hipMemcpyHostToDevice, s));
+      HIP_TRY(hipMemsetAsync(pl->frames.p, 0, (size_t)frames * kSpecFloats * sizeof(float), s));
+      HIP_TRY(hipMemsetAsync(pl->info.p, 0, n * sizeof(ClipInfo), s));
+      pl->info_clean_n = 0;      // this path leaves the clip records used
+      KParams kp = pl->kp;
+      kp.flags = 0; kp.fmt = AFX_FMT_F32;
+      if (pl->nblocks > 0)
+        HIP_TRY(launch_spectral(s, d_h, (ClipInfo*)pl->info.p, (const BlockDesc*)pl->blocks_spec.p, pl->nblocks, pl->f3, kp,
+                                (float*)pl->frames.p, (const int64_t*)pl->frame_offs.p, sb, pl->n_cu));
+      HIP_TRY(launch_hpss_stats(s, d_y, d_h, d_clips, n, (const float*)pl->frames.p, (const int64_t*)pl->frame_offs.p,
+                                (double*)pl->hp_stats.p));
+      h_stats.resize((size_t)n * 4);
+      HIP_TRY(hipMemcpyAsync(h_stats.data(), pl->hp_stats.p, (size_t)n * 4 * sizeof(double), hipMemcpyDeviceToHost, s));
+    }
+    // the signals: one copy when the caller's layout is the chunk's (packed clips in order), else one per clip
+    bool packed = true;
+    for (int q = 0; q < n && packed; ++q) packed = offsets[idx[q]] - offsets[idx[0]] == recs[q].y_off;
+    for (int which = 0; which < 2; ++which) {
+      float* dst = which ? out_perc : out_harm;
+      const float* src = which ? d_p : d_h;
+      if (!dst) continue;
+      if (packed) {
+        HIP_TRY(hipMemcpyAsync(dst + offsets[idx[0]], src, (size_t)ysz * sizeof(float), hipMemcpyDeviceToHost, s));
+      } else {
+        for (int q = 0; q < n; ++q)
+          HIP_TRY(hipMemcpyAsync(dst + offsets[idx[q]], src + recs[q].y_off, (size_t)recs[q].len * sizeof(float), hipMemcpyDeviceToHost, s));
+      }
+    }
+    if (sd)
+      for (int q = 0; q < n; ++q)
+        HIP_TRY(hipMemcpyAsync(out_spec + spec_off[idx[q]], (const float*)pl->hp_spec.p + recs[q].spec_off,
+                               (size_t)3 * kHpssBins * recs[q].T * sizeof(float), hipMemcpyDeviceToHost, s));
+    h_bad.resize(n);
+    HIP_TRY(hipMemcpyAsync(h_bad.data(), d_bad, n * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    for (int q = 0; q < n; ++q) {
+      const int i = idx[q];
+      out_status[i] = h_bad[q] ? AFX_CLIP_NONFINITE : AFX_CLIP_OK;
+      if (out_stats && !h_bad[q]) {
+        for (int k = 0; k < 4; ++k) out_stats[4 * i + k] = h_stats[4 * (size_t)q + k];
+        if (recs[q].len < 2) out_stats[4 * i + 2] = out_stats[4 * i + 3] = nan;   // k_frames3s skips clips of one sample
+      }
+    }
     c0 = c1;
   }
   return AFX_OK;

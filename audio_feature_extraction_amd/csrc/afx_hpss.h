@@ -1,0 +1,51 @@
+// Harmonic-percussive separation (afx_hpss.hip): librosa.effects.hpss at librosa 0.11's defaults on a 2048 / 512 Hann
+// STFT.  Workspace geometry, the per-clip record and the launchers.  Internal to libafx.so.
+#pragma once
+#include <cstdint>
+
+#include <hip/hip_runtime_api.h>
+
+namespace afx {
+
+constexpr int kHpssBins = 1025;            // n_fft / 2 + 1
+constexpr int kHpssPitch = 1032;           // complex64 per frame row of the spectrum workspace (8256 B, 64-byte aligned rows)
+constexpr int kHpssTile = 64;              // k_hpss_mask: 64 frames x 64 bins per workgroup
+constexpr int kHpssBinTiles = 17;          // ceil(1025 / 64)
+constexpr int kHpssHalo = 15;              // kernel_size 31
+
+// One per clip of a chunk (host-built).  Clips of length 0 are not in the list.
+struct HpssClip {
+  int64_t in_off;       // element offset of sample 0 in the input the kernels read (the chunk's upload, or the caller's buffer)
+  int64_t y_off;        // offset of sample 0 in the chunk's float32 signal buffers (y, h, p)
+  int64_t len;          // samples
+  int64_t frame_base;   // first row of the clip in the spectrum workspace
+  int64_t spec_off;     // AFX_HPSS_STORE_SPEC: float offset of S, Hm, Pm (3 x 1025 x T) in the chunk's debug buffer
+  int32_t T;            // 1 + len / 512
+  int32_t tile_base;    // first 64-frame tile of the clip (k_hpss_mask)
+};
+
+struct HpssTabs {
+  const float* window;  // periodic Hann, 2048 floats
+  const float* w1024;   // exp(-2 pi i k / 1024), k < 1024, float2
+  const float* w2048;   // exp(-2 pi i k / 2048), k < 1024, float2
+};
+
+// y[y_off + i] = sample i (pre-emphasised when flags has AFX_FLAG_PREEMPH); bad[c] = 1 when clip c holds a NaN / inf
+hipError_t launch_hpss_prep(hipStream_t s, const void* in, int fmt, int flags, float preemph_b1, const HpssClip* clips,
+                            int n, int64_t max_len, float* y, uint32_t* bad);
+// the complex spectrum of every frame into rows of X (zeros for a bad clip)
+hipError_t launch_hpss_stft(hipStream_t s, const float* y, const HpssClip* clips, const uint32_t* bad, int n,
+                            int64_t n_frames, HpssTabs tb, float2* X);
+// both medians of |X|, the soft masks, Yh = X mh and (Yp != nullptr) Yp = X mp; spec != nullptr: S, Hm, Pm as well
+hipError_t launch_hpss_mask(hipStream_t s, const float2* X, const HpssClip* clips, int n, int n_tiles, float2* Yh,
+                            float2* Yp, float* spec);
+// irfft x window of every row of Yh (and Yp), in place: row r then holds 2048 float samples
+hipError_t launch_hpss_irfft(hipStream_t s, float2* Yh, float2* Yp, int64_t n_frames, HpssTabs tb);
+// overlap-add as a gather, window-sum-square normalisation, cut to length: h (and p) at y_off
+hipError_t launch_hpss_ola(hipStream_t s, const float2* Yh, const float2* Yp, const HpssClip* clips, int n, int64_t max_len,
+                           HpssTabs tb, float* h, float* p);
+// per clip, in float64 and in a fixed order: sum h^2, sum y^2, mean and std of the centroid frames desc[desc_off[c] + 17 t]
+hipError_t launch_hpss_stats(hipStream_t s, const float* y, const float* h, const HpssClip* clips, int n,
+                             const float* desc, const int64_t* desc_off, double* stats);
+
+}  // namespace afx

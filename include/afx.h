@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define AFX_VERSION 105      /* 105: afx_dtw_batch; 104: afx_batch_geometry, afx_host_alloc / afx_host_free */
+#define AFX_VERSION 106      /* 106: afx_hpss_batch; 105: afx_dtw_batch; 104: afx_batch_geometry, afx_host_alloc / afx_host_free */
 
 typedef enum afx_status {
   AFX_OK = 0,
@@ -60,6 +60,8 @@ typedef enum afx_dtw_status {
 enum { AFX_DTW_EUCLIDEAN = 0, AFX_DTW_SQEUCLIDEAN = 1, AFX_DTW_COSINE = 2 };
 /* flags for afx_dtw_batch */
 enum { AFX_DTW_BACKTRACK = 1, AFX_DTW_STORE_D = 2 };
+/* afx_hpss_batch: with the AFX_FLAG_* bits, the debug output of the median stage */
+enum { AFX_HPSS_STORE_SPEC = 4 };
 
 enum { AFX_WINDOW_HAMMING = 0, AFX_WINDOW_HANN = 1 };
 enum { AFX_FMT_F32 = 0, AFX_FMT_S16 = 1 };           /* S16: value / 32768 (libsndfile) */
@@ -274,6 +276,25 @@ int afx_dtw_batch(afx_ctx* ctx, const float* feats, int dim,
                   double* out_cost, int32_t* out_status,
                   int32_t* out_path, const int64_t* path_off, int32_t* out_path_len,
                   double* out_D, const int64_t* d_off);
+
+/* librosa.effects.hpss / harmonic at librosa 0.11's defaults (kernel_size 31, power 2, margin 1) and the harmonic
+ * features of 04_feature_extraction_experiment/feature_extractor.py:525-556 (librosa.effects.harmonic, then
+ * librosa.feature.spectral_centroid of the harmonic signal at its defaults).  The plan must be n_fft 2048 / hop 512 with
+ * AFX_WINDOW_HANN; flags: AFX_FLAG_PREEMPH (the plan's pre-emphasis is applied to the input first) and / or
+ * AFX_HPSS_STORE_SPEC (AFX_FLAG_TRIM is unsupported).  The time-axis median follows scipy's 'reflect' mirror repeated
+ * with period 2T for every clip of T frames.
+ *   out_harm / out_perc  NULL or host float: clip i's signal at out_*[offsets[i] .. + lengths[i]]
+ *   out_stats            NULL or host double[4 n_clips]: sum h^2, sum y^2, mean and std (ddof 0) of h's spectral
+ *                        centroid (Hz); NaN for a failed clip, centroid fields NaN for a clip of one sample
+ *   out_spec, spec_off   AFX_HPSS_STORE_SPEC only (no performance requirement): S, Hm, Pm as float32 3 x 1025 x T_i
+ *                        (bin-major) at out_spec[spec_off[i] ..], T_i = 1 + lengths[i] / 512
+ *   out_status           afx_clip_status per clip: AFX_CLIP_TOO_SHORT for length 0, AFX_CLIP_NONFINITE for a NaN / inf
+ *                        sample; a failed clip's signals are zero and never affect the other clips
+ * The batch runs in chunks whose device workspace stays within 2 GiB; a clip larger than that runs alone. */
+int afx_hpss_batch(afx_plan* plan, const void* samples, int sample_fmt, int mem_kind,
+                   const int64_t* offsets, const int64_t* lengths, int n_clips, int flags,
+                   float* out_harm, float* out_perc, double* out_stats,
+                   float* out_spec, const int64_t* spec_off, int32_t* out_status);
 
 /* Host-only (no device needed): the tables afx_f0_batch uploads, for inspection and tests.
  * info[8] = min_period, max_period, n_pitch_bins, band (transition half-width), candidate

@@ -1,0 +1,216 @@
+"""GPU checks of afx_hpss_batch / effects.hpss / AudioFeatureExtractor.extract_harmonic_features against the oracle
+(tests/hpss_ref.py)."""
+import json
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+from tests import hpss_ref as R
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+@pytest.fixture(scope="module")
+def N():
+    from audio_feature_extraction_amd import _native
+    if _native.device_count() < 1:
+        pytest.fail("no GPU visible")
+    return _native
+
+
+@pytest.fixture(scope="module")
+def plan(N):
+    return N.Plan(N.Context(0), N.make_params(22050, 2048, 512, 13, 128, "hann"))
+
+
+def _pack(sigs):
+    lengths = np.array([s.size for s in sigs], np.int64)
+    offsets = np.zeros(len(sigs), np.int64)
+    offsets[1:] = np.cumsum(lengths)[:-1]
+    return np.concatenate(sigs).astype(np.float32), offsets, lengths
+
+
+def _tone(sr, n, f=440.0):
+    return (0.5 * np.sin(2 * np.pi * f * np.arange(n) / sr)).astype(np.float32)
+
+
+def _cases():
+    from audio_feature_extraction_amd.synth import make_clip
+    rng = np.random.default_rng(11)
+    out = []
+    for sr in (16000, 22050, 44100):
+        n = sr * 2 + 333
+        out += [(f"clip{sr}", sr, make_clip(sr, sr, 2.0)), (f"speech{sr}", sr, make_clip(sr + 1, sr, 1.7, speechy=True)),
+                (f"bintone{sr}", sr, _tone(sr, n, 100 * sr / 2048)), (f"noise{sr}", sr, (0.3 * rng.standard_normal(n)).astype(np.float32)),
+                (f"clicks{sr}", sr, R.click_train(n)), (f"toneclicks{sr}", sr, _tone(sr, n) + R.click_train(n))]
+    return out
+
+
+def test_median_stage_is_exact(plan):
+    rng = np.random.default_rng(2)
+    lengths = [300, 700, 1500, 7500, 8000, 8500, 40001]        # T = 1, 2, 3, 15, 16, 17, 79 (two time tiles)
+    sigs = [(0.5 * rng.standard_normal(n)).astype(np.float32) for n in lengths]
+    y, off, ln = _pack(sigs)
+    out = plan.hpss_batch(y, off, ln, want_stats=False, store_spec=True)
+    assert (out["status"] == 0).all()
+    for sp, n in zip(out["spec"], lengths):
+        assert sp.shape == (3, 1025, 1 + n // 512)
+        np.testing.assert_array_equal(sp[1], R.median_time(sp[0]), err_msg=f"Hm, length {n}")
+        np.testing.assert_array_equal(sp[2], R.median_freq(sp[0]), err_msg=f"Pm, length {n}")
+        S64 = np.abs(R.stft(sigs[lengths.index(n)]))
+        assert np.max(np.abs(sp[0] - S64)) <= 1e-5 * np.max(S64)
+
+
+def test_signals_match_the_oracle(plan):
+    cases = _cases()
+    y, off, ln = _pack([c[2] for c in cases])
+    out = plan.hpss_batch(y, off, ln, want_perc=True, want_stats=False)
+    assert (out["status"] == 0).all()
+    for (name, sr, s), h, p in zip(cases, out["harm"], out["perc"]):
+        h64, p64 = R.hpss(s)[:2]
+        h32 = R.hpss(s, f32=True)[0]
+        ulp = float(np.spacing(np.float32(np.max(np.abs(s)))))
+        # the bound: 4 x the float32 restatement's own error, and never below 4 ulps of max|y| (what rounding the
+        # STFT itself to float32 costs: the restatement's STFT is float64 before its one rounding)
+        bound = 4.0 * max(float(np.max(np.abs(h32 - h64))), ulp)
+        assert np.max(np.abs(h - h64)) <= bound, (name, np.max(np.abs(h - h64)) / ulp, bound / ulp)
+        assert np.max(np.abs(p - p64)) <= bound, (name, np.max(np.abs(p - p64)) / ulp, bound / ulp)
+        # masks sum to one and the window reconstructs: h + p is the float32 round trip of y
+        assert np.max(np.abs((h.astype(np.float64) + p) - s)) <= 16 * ulp, name
+        if name.startswith("clicks"):
+            assert np.all(h == 0.0), name
+
+
+def test_stats_match_the_oracle(N):
+    from audio_feature_extraction_amd import AudioFeatureExtractor
+    cases = _cases()
+    for sr in (16000, 22050, 44100):
+        fx = AudioFeatureExtractor(sr=sr)
+        mine = [c for c in cases if c[1] == sr]
+        res = fx.extract_harmonic_features_batch([c[2] for c in mine])
+        for (name, _, s), d in zip(mine, res):
+            assert list(d) == ["harmonic_energy", "harmonic_ratio", "harmonic_freq_mean", "harmonic_freq_std"]
+            assert all(type(v) is float for v in d.values())
+            json.dumps(d)
+            ref = R.harmonic_features(s, sr)
+            if name.startswith("clicks"):
+                assert d["harmonic_energy"] == 0.0 and d["harmonic_ratio"] == 0.0
+                continue
+            for k in ("harmonic_energy", "harmonic_ratio"):
+                assert abs(d[k] - ref[k]) <= 1e-4 * abs(ref[k]) + 1e-9, (name, k, d[k], ref[k])
+            assert abs(d["harmonic_freq_mean"] - ref["harmonic_freq_mean"]) <= 1e-3 * ref["harmonic_freq_mean"] + 1e-3, (name, d, ref)
+            assert abs(d["harmonic_freq_std"] - ref["harmonic_freq_std"]) <= 2e-3 * ref["harmonic_freq_mean"] + 1e-3, (name, d, ref)
+        one = fx.extract_harmonic_features(mine[0][2])
+        assert one == res[0]
+
+
+def _batch50():
+    from audio_feature_extraction_amd.synth import make_clip
+    sigs = [make_clip(i, 22050, 0.3 + 0.05 * (i % 7), speechy=bool(i % 2)) for i in range(50)]
+    sigs[20] = sigs[20].copy()
+    sigs[20][777] = np.nan
+    sigs[30] = np.zeros(0, np.float32)
+    return sigs
+
+
+def test_failed_clips_are_isolated_and_runs_are_deterministic(plan, N):
+    sigs = _batch50()
+    y, off, ln = _pack(sigs)
+    a = plan.hpss_batch(y, off, ln, want_perc=True)
+    b = plan.hpss_batch(y, off, ln, want_perc=True)
+    assert a["status"][20] == N.CLIP_NONFINITE and a["status"][30] == N.CLIP_TOO_SHORT
+    assert (np.delete(a["status"], [20, 30]) == 0).all()
+    assert np.isnan(a["stats"][20]).all() and np.isnan(a["stats"][30]).all()
+    for k in ("harm", "perc"):
+        for u, v in zip(a[k], b[k]):
+            np.testing.assert_array_equal(u, v)
+    np.testing.assert_array_equal(a["stats"], b["stats"])
+    for i in (0, 19, 21, 29, 31, 49):
+        solo = plan.hpss_batch(sigs[i], np.zeros(1, np.int64), np.array([sigs[i].size], np.int64), want_perc=True)
+        np.testing.assert_array_equal(solo["harm"][0], a["harm"][i])
+        np.testing.assert_array_equal(solo["perc"][0], a["perc"][i])
+        np.testing.assert_array_equal(solo["stats"][0], a["stats"][i])
+
+
+_CHILD = r"""
+import sys
+import numpy as np
+sys.path.insert(0, sys.argv[1])
+from tests.test_gpu_hpss import _batch50, _pack
+from audio_feature_extraction_amd import _native as N
+plan = N.Plan(N.Context(0), N.make_params(22050, 2048, 512, 13, 128, "hann"))
+y, off, ln = _pack(_batch50())
+o = plan.hpss_batch(y, off, ln, want_perc=True)
+np.savez(sys.argv[2], harm=np.concatenate(o["harm"]), perc=np.concatenate(o["perc"]), stats=o["stats"], status=o["status"])
+"""
+
+
+def test_chunked_batch_equals_one_chunk(plan, tmp_path):
+    y, off, ln = _pack(_batch50())
+    ref = plan.hpss_batch(y, off, ln, want_perc=True)
+    env = dict(os.environ, AFX_TEST_HPSS_BUDGET="2000000")      # a few clips per chunk
+    dst = str(tmp_path / "chunked.npz")
+    subprocess.run([sys.executable, "-c", _CHILD, ROOT, dst], env=env, check=True, timeout=300)
+    z = np.load(dst)
+    np.testing.assert_array_equal(z["status"], ref["status"])
+    np.testing.assert_array_equal(z["harm"], np.concatenate(ref["harm"]))
+    np.testing.assert_array_equal(z["perc"], np.concatenate(ref["perc"]))
+    np.testing.assert_array_equal(z["stats"], ref["stats"])
+
+
+def test_s16_and_device_inputs_match_host_f32(plan, N):
+    rng = np.random.default_rng(4)
+    q = [rng.integers(-20000, 20000, n).astype(np.int16) for n in (5000, 12345, 700)]
+    f = [x.astype(np.float32) / 32768.0 for x in q]
+    y, off, ln = _pack(f)
+    ref = plan.hpss_batch(y, off, ln, want_perc=True)
+    s16 = plan.hpss_batch(np.concatenate(q), off, ln, fmt=N.FMT_S16, want_perc=True)
+    dev = plan.device_buffer(y.nbytes)
+    dev.upload(y)
+    d = plan.hpss_batch(dev.ptr, off, ln, mem=N.MEM_DEVICE, want_perc=True)
+    dev.free()
+    for o in (s16, d):
+        for k in ("harm", "perc"):
+            for u, v in zip(o[k], ref[k]):
+                np.testing.assert_array_equal(u, v)
+        np.testing.assert_array_equal(o["stats"], ref["stats"])
+
+
+def test_preemphasis_flag_equals_preemphasised_input(plan, N):
+    y = (0.3 * np.random.default_rng(9).standard_normal(9000)).astype(np.float32)
+    one = np.zeros(1, np.int64), np.array([y.size], np.int64)
+    a = plan.hpss_batch(y, *one, flags=N.FLAG_PREEMPH)
+    yp = np.ascontiguousarray(plan.preprocess(y)[0], np.float32)      # the plan's pre-emphasis (trim off: full span)
+    b = plan.hpss_batch(yp, *one)
+    np.testing.assert_array_equal(a["harm"][0], b["harm"][0])
+
+
+def test_effects_api(N):
+    from audio_feature_extraction_amd import effects
+    y = _tone(22050, 30000) + R.click_train(30000)
+    h, p = effects.hpss(y)
+    assert h.dtype == np.float32 and h.shape == y.shape and p.shape == y.shape
+    np.testing.assert_array_equal(effects.harmonic(y), h)
+    np.testing.assert_array_equal(effects.percussive(y), p)
+    pairs = effects.hpss_batch([y, y[:1000]])
+    np.testing.assert_array_equal(pairs[0][0], h)
+    assert pairs[1][0].shape == (1000,)
+
+
+def test_long_clip(plan):
+    from audio_feature_extraction_amd.synth import make_clip
+    y = np.concatenate([make_clip(70 + i, 22050, 10.0, speechy=True) for i in range(7)])     # 70 s
+    out = plan.hpss_batch(y, np.zeros(1, np.int64), np.array([y.size], np.int64), want_perc=True)
+    h64, p64 = R.hpss(y)[:2]
+    h32 = R.hpss(y, f32=True)[0]
+    ulp = float(np.spacing(np.float32(np.max(np.abs(y)))))
+    bound = 4.0 * max(float(np.max(np.abs(h32 - h64))), ulp)
+    assert np.max(np.abs(out["harm"][0] - h64)) <= bound
+    assert np.max(np.abs(out["perc"][0] - p64)) <= bound
+    ref = R.harmonic_features(y, 22050, h64)
+    assert abs(out["stats"][0][0] - ref["harmonic_energy"]) <= 1e-4 * ref["harmonic_energy"]
