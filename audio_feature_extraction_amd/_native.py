@@ -35,6 +35,7 @@ SYMBOLS = (
     "afx_default_params", "afx_plan_create", "afx_plan_destroy", "afx_build_tables", "afx_build_mel_schedule",
     "afx_extract_batch", "afx_extract_submit", "afx_extract_collect", "afx_f0_batch", "afx_zcr_batch", "afx_spectral_batch", "afx_f0_build_tables", "afx_preprocess", "afx_plan_set_timing", "afx_plan_get_timings", "afx_plan_get_intervals",
     "afx_wav_probe", "afx_wav_read_s16", "afx_batch_geometry", "afx_dtw_batch", "afx_hpss_batch",
+    "afx_resample_design", "afx_resample_batch",
 )
 
 
@@ -104,6 +105,9 @@ def lib() -> C.CDLL:
         L.afx_wav_read_s16.argtypes = [vp, i32, i32, vp, vp, vp, C.c_int64, vp, vp]
         L.afx_dtw_batch.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp]
         L.afx_hpss_batch.argtypes = [vp, vp, i32, i32, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp]
+        if hasattr(L, "afx_resample_batch"):                 # absent from a library older than version 107
+            L.afx_resample_design.argtypes = [i32, i32, vp, vp]
+            L.afx_resample_batch.argtypes = [vp, vp, i32, i32, vp, vp, i32, i32, i32, vp, i32, vp, i32, vp, vp]
         _lib = L
     return _lib
 
@@ -169,6 +173,23 @@ def f0_build_tables(sr: int, n_fft: int, hop: int, fmin: float, fmax: float) -> 
                                      freqs.ctypes.data), "afx_f0_build_tables")
     keys = ("min_period", "max_period", "n_bins", "band", "cap", "n_lag", "R", "slots")
     return {**{k: int(v) for k, v in zip(keys, info)}, "beta": beta, "lt": lt.reshape(2, w, w), "freqs": freqs}
+
+
+def resample_design(sr_in: int, sr_out: int) -> dict:
+    """Host-only: the polyphase filter afx_resample_batch applies for a rate pair (wavio._resample_filter's design)."""
+    info = np.zeros(4, np.int32)
+    _check(lib().afx_resample_design(int(sr_in), int(sr_out), info.ctypes.data, None), "afx_resample_design")
+    taps = np.zeros(int(info[2]), np.float64)
+    _check(lib().afx_resample_design(int(sr_in), int(sr_out), info.ctypes.data, taps.ctypes.data), "afx_resample_design")
+    return {"up": int(info[0]), "down": int(info[1]), "n_taps": int(info[2]), "half": int(info[3]), "taps": taps}
+
+
+def resample_lengths(lengths, sr_in: int, sr_out: int) -> np.ndarray:
+    """ceil(n * sr_out / sr_in) per clip, in integers (librosa's length rule)."""
+    sr_in = np.asarray(sr_in, np.int64)              # a scalar, or one rate per clip
+    g = np.gcd(sr_in, int(sr_out))
+    up, down = int(sr_out) // g, sr_in // g
+    return (np.asarray(lengths, np.int64) * up + down - 1) // down
 
 
 def _check(rc: int, what: str):
@@ -351,6 +372,62 @@ class Context:
         return out
 
 
+    def resample_batch(self, samples, offsets, lengths, sr_in: int, sr_out: int, fmt=None, taps=None, out=None,
+                       out_offsets=None) -> dict:
+        """afx_resample_batch: clips samples[offsets[i] .. + lengths[i]) at sr_in -> float32 at sr_out, as wavio.resample.
+        ``samples``: numpy int16 / float32 array (host) or a DeviceBuffer / device pointer (then ``fmt`` says which).
+        ``out``: None (a new host array), a float32 numpy array, or a DeviceBuffer the result stays in; ``out_offsets``:
+        where each clip goes (default: packed with 4-element alignment, as parallel._pack).  Returns out, offsets, lengths."""
+        offsets = np.ascontiguousarray(offsets, np.int64).reshape(-1)
+        lengths = np.ascontiguousarray(lengths, np.int64).reshape(-1)
+        n = int(offsets.shape[0])
+        if lengths.shape[0] != n:
+            raise ValueError("offsets and lengths must have one entry per clip")
+        if int(sr_in) <= 0 or int(sr_out) <= 0:
+            raise ValueError("sample rates must be positive")
+        if isinstance(samples, np.ndarray):
+            if fmt is None:
+                fmt = FMT_S16 if samples.dtype == np.int16 else FMT_F32
+            want = np.int16 if fmt == FMT_S16 else np.float32
+            if samples.dtype != want or not samples.flags.c_contiguous:
+                raise ValueError(f"samples must be C-contiguous {want.__name__}")
+            if n and lengths.min() >= 0 and int((offsets + lengths).max()) > samples.size:
+                raise ValueError("clip extends past the sample buffer")
+            sptr, kind = samples.ctypes.data, MEM_HOST
+        else:
+            if fmt is None:
+                raise ValueError("fmt is required for device-resident samples")
+            sptr, kind = (samples.ptr if isinstance(samples, DeviceBuffer) else int(samples)), MEM_DEVICE
+        olen = resample_lengths(np.maximum(lengths, 0), sr_in, sr_out)
+        if out_offsets is None:
+            out_offsets = np.zeros(n, np.int64)
+            if n:
+                out_offsets[1:] = np.cumsum((olen + 3) // 4 * 4)[:-1]
+        out_offsets = np.ascontiguousarray(out_offsets, np.int64).reshape(-1)
+        if out_offsets.shape[0] != n:
+            raise ValueError("out_offsets must have one entry per clip")
+        need = int((out_offsets + olen).max()) if n else 0
+        if out is None:
+            out = np.zeros(need, np.float32)
+        if isinstance(out, np.ndarray):
+            if out.dtype != np.float32 or not out.flags.c_contiguous or out.size < need:
+                raise ValueError("out must be a C-contiguous float32 array that holds every clip")
+            optr, okind = out.ctypes.data, MEM_HOST
+        else:
+            if isinstance(out, DeviceBuffer) and out.nbytes < 4 * need:
+                raise ValueError("the output DeviceBuffer is too small")
+            optr, okind = (out.ptr if isinstance(out, DeviceBuffer) else int(out)), MEM_DEVICE
+        tp = None if taps is None else np.ascontiguousarray(taps, np.float64).reshape(-1)
+        got = np.zeros(n, np.int64)
+        if not hasattr(lib(), "afx_resample_batch"):
+            raise NotImplementedError("this libafx has no afx_resample_batch")
+        _check(lib().afx_resample_batch(self.handle, sptr, int(fmt), kind, offsets.ctypes.data, lengths.ctypes.data, n,
+                                        int(sr_in), int(sr_out), None if tp is None else tp.ctypes.data,
+                                        0 if tp is None else int(tp.size), optr, okind, out_offsets.ctypes.data,
+                                        got.ctypes.data), "afx_resample_batch")
+        return {"out": out, "offsets": out_offsets, "lengths": got}
+
+
 class Plan:
     def __init__(self, ctx: Context, params: Params):
         self.ctx, self.params = ctx, params
@@ -378,6 +455,10 @@ class Plan:
     def pinned_buffer(self, nbytes: int) -> "PinnedBuffer":
         """Page-locked host block on this plan's device context (what a window of files is packed into)."""
         return PinnedBuffer(self.ctx, nbytes)
+
+    def resample_batch(self, samples, offsets, lengths, sr_in: int, sr_out: int, **kw) -> dict:
+        """Context.resample_batch on this plan's context (synchronous on return: any plan may read the result)."""
+        return self.ctx.resample_batch(samples, offsets, lengths, sr_in, sr_out, **kw)
 
     def set_timing(self, on, frames_only: bool = False):
         """HIP events around every kernel of a batch (or, frames_only, around the frame kernel alone)."""

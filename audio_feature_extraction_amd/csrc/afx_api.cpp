@@ -8,6 +8,7 @@
 #include <cstring>
 #include <atomic>
 #include <mutex>
+#include <numeric>
 #include <string>
 #include <vector>
 
@@ -20,6 +21,7 @@
 #include "afx_frames3.h"
 #include "afx_hpss.h"
 #include "afx_internal.h"
+#include "afx_resample.h"
 
 namespace afx {
 
@@ -36,6 +38,14 @@ struct afx_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
   DevBuf dtw_raw, dtw_feats, dtw_norms, dtw_pairs, dtw_codes, dtw_rows, dtw_d, dtw_path, dtw_cost, dtw_status, dtw_len;   // afx_dtw_batch
+  // afx_resample_batch: the tables of the last rate pair (or caller-supplied filter) used, and the staging of host batches
+  struct {
+    bool valid = false, custom = false;
+    int up = 0, down = 0;
+    std::vector<double> taps;        // the caller's filter the tables were built from (custom only)
+    RsTables t;
+  } rs;
+  DevBuf rs_g, rs_tstart, rs_clips, rs_in, rs_out;
 };
 
 struct afx_plan {
@@ -179,7 +189,8 @@ extern "C" void afx_destroy(afx_ctx* ctx) {
   if (!ctx) return;
   (void)hipSetDevice(ctx->device);
   for (DevBuf* b : {&ctx->dtw_raw, &ctx->dtw_feats, &ctx->dtw_norms, &ctx->dtw_pairs, &ctx->dtw_codes, &ctx->dtw_rows, &ctx->dtw_d,
-                    &ctx->dtw_path, &ctx->dtw_cost, &ctx->dtw_status, &ctx->dtw_len})
+                    &ctx->dtw_path, &ctx->dtw_cost, &ctx->dtw_status, &ctx->dtw_len, &ctx->rs_g, &ctx->rs_tstart, &ctx->rs_clips,
+                    &ctx->rs_in, &ctx->rs_out})
     release(*b);
   if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
   delete ctx;
@@ -1285,6 +1296,128 @@ extern "C" int afx_dtw_batch(afx_ctx* ctx, const float* feats, int dim,
         std::memcpy(out_path + 2 * path_off[c0 + q], h_path.data() + 2 * recs[q].path, (size_t)h_len[q] * 2 * sizeof(int32_t));
       }
     c0 = c1;
+  }
+  return AFX_OK;
+}
+
+// ---- batched polyphase resampling (wavio.resample: the resampling half of librosa.load(path, sr=...)) -------------------
+extern "C" int afx_resample_batch(afx_ctx* ctx, const void* samples, int sample_fmt, int mem_kind,
+                                  const int64_t* offsets, const int64_t* lengths, int n_clips, int sr_in, int sr_out,
+                                  const double* taps, int n_taps, float* out, int out_mem_kind,
+                                  const int64_t* out_offsets, int64_t* out_lengths) {
+  if (!ctx || n_clips < 0 || (n_clips > 0 && (!offsets || !lengths || !out_offsets))) {
+    set_error("afx_resample_batch: null/invalid argument");
+    return AFX_ERR_INVALID;
+  }
+  if (sample_fmt != AFX_FMT_F32 && sample_fmt != AFX_FMT_S16) { set_error("afx_resample_batch: unknown sample format"); return AFX_ERR_INVALID; }
+  if ((mem_kind != AFX_MEM_HOST && mem_kind != AFX_MEM_DEVICE) || (out_mem_kind != AFX_MEM_HOST && out_mem_kind != AFX_MEM_DEVICE)) {
+    set_error("afx_resample_batch: unknown mem_kind");
+    return AFX_ERR_INVALID;
+  }
+  if (sr_in <= 0 || sr_out <= 0) { set_error("afx_resample_batch: sample rates must be positive"); return AFX_ERR_INVALID; }
+  if (taps && (n_taps < 1 || !(n_taps & 1))) { set_error("afx_resample_batch: a caller-supplied filter needs an odd number of taps"); return AFX_ERR_INVALID; }
+  int64_t total_in = 0, total_out = 0;
+  for (int i = 0; i < n_clips; ++i) {
+    if (offsets[i] < 0 || lengths[i] < 0 || out_offsets[i] < 0 || offsets[i] > INT64_MAX / 8 || out_offsets[i] > INT64_MAX / 8) {
+      set_error("afx_resample_batch: clip " + std::to_string(i) + ": offsets and lengths must be >= 0");
+      return AFX_ERR_INVALID;
+    }
+    if (lengths[i] > ((int64_t)1 << 31)) {
+      set_error("afx_resample_batch: clip " + std::to_string(i) + ": more than 2^31 samples is not supported");
+      return AFX_ERR_UNSUPPORTED;
+    }
+    total_in += lengths[i];
+  }
+  const int g = std::gcd(sr_in, sr_out);
+  const int up = sr_out / g, down = sr_in / g;
+  const bool copy = up == down;
+  int rc;
+  if (!copy) {
+    auto& rs = ctx->rs;
+    const bool same = rs.valid && rs.up == up && rs.down == down && rs.custom == (taps != nullptr) &&
+                      (!taps || ((int)rs.taps.size() == n_taps && std::memcmp(rs.taps.data(), taps, sizeof(double) * n_taps) == 0));
+    if (!same) {
+      std::string why;
+      RsDesign d;
+      if (!taps) {
+        if ((rc = resample_design(sr_in, sr_out, d, true, why)) != AFX_OK) { set_error("afx_resample_batch: " + why); return rc; }
+      }
+      rs.valid = false;
+      if ((rc = resample_tables(up, down, taps ? taps : d.h.data(), taps ? n_taps : d.n_taps, rs.t, why)) != AFX_OK) {
+        set_error("afx_resample_batch: " + why);
+        return rc;
+      }
+      rs.up = up; rs.down = down; rs.custom = taps != nullptr;
+      rs.taps.assign(taps ? taps : nullptr, taps ? taps + n_taps : nullptr);
+    }
+  }
+  if (n_clips > 0 && !out) {
+    bool any = false;
+    for (int i = 0; i < n_clips; ++i) any = any || lengths[i] > 0;
+    if (any) { set_error("afx_resample_batch: null out"); return AFX_ERR_INVALID; }
+  }
+  if (n_clips > 0 && total_in > 0 && !samples) { set_error("afx_resample_batch: null samples"); return AFX_ERR_INVALID; }
+  // clip records; a host batch is staged packed (4-element alignment), so only the clips themselves cross the link
+  const RsParams& P = ctx->rs.t.p;
+  const int64_t per_block = copy ? kRsCopyChunk : (int64_t)P.tile_sp * P.opp;
+  std::vector<RsClip> recs((size_t)n_clips);
+  int64_t n_blocks = 0, in_pos = 0;
+  for (int i = 0; i < n_clips; ++i) {
+    RsClip& r = recs[i];
+    r.in_len = lengths[i];
+    r.out_len = copy ? lengths[i] : resample_out_len(lengths[i], up, down);
+    if (out_lengths) out_lengths[i] = r.out_len;
+    r.in_off = mem_kind == AFX_MEM_HOST ? in_pos : offsets[i];
+    r.out_off = out_mem_kind == AFX_MEM_HOST ? total_out : out_offsets[i];
+    r.first_block = (int32_t)n_blocks; r.pad_ = 0;
+    in_pos += (lengths[i] + 3) / 4 * 4;
+    total_out += r.out_len;
+    n_blocks += (r.out_len + per_block - 1) / per_block;
+    if (n_blocks > INT32_MAX / 2) { set_error("afx_resample_batch: batch too large for one launch"); return AFX_ERR_UNSUPPORTED; }
+  }
+  if (n_clips == 0 || total_out == 0) return AFX_OK;
+  (void)hipGetLastError();
+  HIP_TRY(hipSetDevice(ctx->device));
+  hipStream_t s = ctx->stream;
+  if (!copy && !ctx->rs.valid) {
+    const RsTables& t = ctx->rs.t;
+    if ((rc = ensure(ctx->rs_g, t.G.size() * sizeof(double))) != AFX_OK) return rc;
+    if ((rc = ensure(ctx->rs_tstart, t.tstart.size() * sizeof(int32_t))) != AFX_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(ctx->rs_g.p, t.G.data(), t.G.size() * sizeof(double), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(ctx->rs_tstart.p, t.tstart.data(), t.tstart.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    ctx->rs.valid = true;
+  }
+  const size_t esz = sample_fmt == AFX_FMT_S16 ? 2 : 4;
+  const void* d_in = samples;
+  std::vector<char> h_in;
+  if (mem_kind == AFX_MEM_HOST) {
+    h_in.assign((size_t)in_pos * esz + 16, 0);
+    for (int i = 0; i < n_clips; ++i)
+      if (lengths[i]) std::memcpy(h_in.data() + (size_t)recs[i].in_off * esz, (const char*)samples + (size_t)offsets[i] * esz, (size_t)lengths[i] * esz);
+    if ((rc = ensure(ctx->rs_in, h_in.size())) != AFX_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(ctx->rs_in.p, h_in.data(), h_in.size(), hipMemcpyHostToDevice, s));
+    d_in = ctx->rs_in.p;
+  }
+  float* d_out = out;
+  if (out_mem_kind == AFX_MEM_HOST) {
+    if ((rc = ensure(ctx->rs_out, (size_t)total_out * sizeof(float))) != AFX_OK) return rc;
+    d_out = (float*)ctx->rs_out.p;
+  }
+  if ((rc = ensure(ctx->rs_clips, recs.size() * sizeof(RsClip))) != AFX_OK) return rc;
+  HIP_TRY(hipMemcpyAsync(ctx->rs_clips.p, recs.data(), recs.size() * sizeof(RsClip), hipMemcpyHostToDevice, s));
+  const RsClip* d_clips = (const RsClip*)ctx->rs_clips.p;
+  if (copy) HIP_TRY(launch_resample_copy(s, d_in, sample_fmt, d_out, d_clips, n_clips, (int)n_blocks));
+  else HIP_TRY(launch_resample(s, d_in, sample_fmt, d_out, d_clips, n_clips, (int)n_blocks, (const double*)ctx->rs_g.p,
+                               (const int32_t*)ctx->rs_tstart.p, P));
+  if (out_mem_kind == AFX_MEM_HOST) {
+    std::vector<float> h_out((size_t)total_out);
+    HIP_TRY(hipMemcpyAsync(h_out.data(), d_out, (size_t)total_out * sizeof(float), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    for (int i = 0; i < n_clips; ++i)
+      if (recs[i].out_len) std::memcpy(out + out_offsets[i], h_out.data() + recs[i].out_off, (size_t)recs[i].out_len * sizeof(float));
+  } else {
+    HIP_TRY(hipStreamSynchronize(s));
   }
   return AFX_OK;
 }

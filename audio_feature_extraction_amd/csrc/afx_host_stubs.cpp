@@ -1,6 +1,6 @@
 // Device entry points of the HOST-ONLY build (libafx_host_asan.so, `make asan`): every one fails loudly with
 // AFX_ERR_NO_DEVICE.  The sanitizer build exists to run the host-side parsers and table builders (afx_wav.cpp,
-// afx_tables.cpp, afx_f0_tables.cpp, afx_host.cpp) under AddressSanitizer + UBSan on the CPU; GPU sanitizers are not
+// afx_tables.cpp, afx_f0_tables.cpp, afx_resample_tables.cpp, afx_host.cpp) under AddressSanitizer + UBSan on the CPU; GPU sanitizers are not
 // available on the target pool.  Never linked into libafx.so.
 #include <cstddef>
 #include <cstdint>
@@ -48,5 +48,9 @@ int afx_dtw_batch(afx_ctx*, const float*, int, const int64_t*, const int64_t*, c
 int afx_hpss_batch(afx_plan*, const void*, int, int, const int64_t*, const int64_t*, int, int, float*, float*, double*, float*,
                    const int64_t*, int32_t*) {
   return no_device("afx_hpss_batch");
+}
+int afx_resample_batch(afx_ctx*, const void*, int, int, const int64_t*, const int64_t*, int, int, int, const double*, int, float*,
+                       int, const int64_t*, int64_t*) {
+  return no_device("afx_resample_batch");
 }
 }

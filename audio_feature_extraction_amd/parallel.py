@@ -78,6 +78,15 @@ def _decode(path: str, sr: int):
     return "f32", y
 
 
+def _decode_raw(path: str, sr: int):
+    """As _decode, but a file at another rate is left at its own rate for the device resampler:
+    -> ('s16'|'f32', mono array, file rate)."""
+    a, rate, kind = wavio.read_wav_raw(path)
+    if kind == "s16" and a.shape[1] == 1 and rate == sr:
+        return "s16", np.ascontiguousarray(a[:, 0]), rate
+    return "f32", wavio.to_mono(wavio.to_float32(a, kind)), rate
+
+
 def _pack(clips: List[np.ndarray], dtype) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
     """Packs clips with 4-element alignment (enables the kernels' 16-byte loads)."""
     lengths = np.array([c.size for c in clips], np.int64)
@@ -210,6 +219,13 @@ def process_files(extractor, files: Sequence, max_batch_samples: int = 80 * 1024
     decode window k + 1 on the shared host pool while window k is packed, uploaded and extracted ->
     dicts in input (glob) order.  Host memory holds at most two windows per worker, not the directory.
 
+    Files at another sample rate than the extractor's are resampled on the device (afx_resample_batch, the arithmetic of
+    wavio.resample): 16-bit PCM mono ones are read natively like the rest and uploaded as int16, files Python decodes are
+    uploaded as float32 at their own rate; a sub-batch holds one file rate, its resampled clips go to a second pooled device
+    buffer (4-aligned, as _pack) that both passes read.  Sub-batches are cut so that neither their input nor their
+    resampled samples exceed ``max_batch_samples``.  A plan without ``resample_batch``, or a rate pair the device
+    resampler does not hold (NotImplementedError), leaves those files to wavio.resample on the host.
+
     On the device a worker owns two plans (own stream each): the MFCC / RMS pass of a sub-batch is queued with
     afx_extract_submit on the first and collected only after the pYIN pass of the same sub-batch (afx_f0_batch, second
     plan) has run beside it -- one upload serves both.  ``features_to_extract`` (README.md:141-146) leaves out the passes
@@ -251,9 +267,11 @@ def process_files(extractor, files: Sequence, max_batch_samples: int = 80 * 1024
     phase = {"decode_wait": 0.0, "device": 0.0}
     phase_lock = threading.Lock()
 
-    def dec(i):
+    def dec(i, raw=False):
         try:
-            return _decode(str(files[i]), extractor.sr)
+            if raw:                      # the device resamples: keep the file's rate
+                return _decode_raw(str(files[i]), extractor.sr)
+            return _decode(str(files[i]), extractor.sr) + (extractor.sr,)
         except Exception as e:          # load_audio: log + the file is dropped
             log.error(f"載入音頻文件失敗: {str(e)}")
             errors[i] = e
@@ -266,18 +284,21 @@ def process_files(extractor, files: Sequence, max_batch_samples: int = 80 * 1024
     native_threads = max(1, min(host_cpus, DECODE_THREADS_PER_GPU * len(devices)) // max(1, min(len(lanes), 4)))
     win_pool = ThreadPoolExecutor(max(1, len(lanes)))
 
-    def load_window(win, pin=None):
+    def load_window(win, pin=None, can_rs=False):
         """-> (packed 16-bit group or None, indices decoded by wavio, their decoded clips); pin: the worker's pool of
-        page-locked buffers (None: ordinary memory)"""
+        page-locked buffers (None: ordinary memory); can_rs: the plan resamples on the device, so 16-bit mono files of
+        any rate are read natively (laid out rate by rate, the extractor's own rate first) and decoded files keep theirs"""
         rest = list(win)
         packed = None
         held = None
         try:
             paths = [str(files[i]) for i in win]
             pr = _native.wav_probe(paths, native_threads)
-            ok = ((pr["status"] == 0) & (pr["tag"] == 1) & (pr["bits"] == 16) & (pr["channels"] == 1) &
-                  (pr["rate"] == extractor.sr))
+            ok = (pr["status"] == 0) & (pr["tag"] == 1) & (pr["bits"] == 16) & (pr["channels"] == 1)
+            ok &= (pr["rate"] > 0) if can_rs else (pr["rate"] == extractor.sr)
             sel = np.nonzero(ok)[0]
+            if sel.size and (pr["rate"][sel] != extractor.sr).any():
+                sel = sel[np.lexsort((sel, pr["rate"][sel], pr["rate"][sel] != extractor.sr))]
             if sel.size:
                 lens = pr["frames"][sel].astype(np.int64)
                 padded = (lens + 3) // 4 * 4                      # 4-element alignment, as _pack
@@ -294,7 +315,8 @@ def process_files(extractor, files: Sequence, max_batch_samples: int = 80 * 1024
                     buf[o + ln: o + pd] = 0
                 good = st == 0
                 if good.any():
-                    packed = ([win[j] for j in sel[good]], buf, offs[good], lens[good], held)
+                    packed = ([win[j] for j in sel[good]], buf, offs[good], lens[good], held,
+                              pr["rate"][sel[good]].astype(np.int64))
                     held = None
                     taken = set(packed[0])
                     rest = [i for i in win if i not in taken]
@@ -302,19 +324,49 @@ def process_files(extractor, files: Sequence, max_batch_samples: int = 80 * 1024
             rest, packed = list(win), None
         if held is not None:
             pin.put(held)
-        decoded = list(pool.map(dec, rest)) if rest else []
+        decoded = list(pool.map(lambda i: dec(i, can_rs), rest)) if rest else []
         return packed, rest, decoded
 
     timeline: List[Any] = []                                      # (lane, clips, t_begin, t_uploaded, t_f0_done, t_collected) per sub-batch
     finished: Any = queue.SimpleQueue()                          # index lists of sub-batches whose results are in the arrays
     recs: List[Any] = [None] * n
 
-    def run_group(plans, cur, buf, offs, lens, fmt, dev):
+    def run_group(plans, cur, buf, offs, lens, fmt, dev, rate=None, dev_in=None):
+        """One sub-batch: upload, (resample on the device when ``rate`` is another rate than the extractor's,) both passes."""
         plan, plan_f0 = plans
         tl = [None, len(cur), time.perf_counter() - t_start, 0.0, 0.0, 0.0]
-        dbuf = dev.get(max(buf.nbytes, 16))                       # one PCIe copy for both passes
+        sr = int(extractor.sr)
+        if rate is not None and int(rate) != sr:
+            olens = _native.resample_lengths(lens, int(rate), sr)         # known on the host: no read-back
+            ooffs = np.zeros(len(cur), np.int64)
+            ooffs[1:] = np.cumsum((olens + 3) // 4 * 4)[:-1]
+            din = dev_in.get(max(buf.nbytes, 16))
+            dbuf = None
+            try:
+                din.upload(buf)
+                dbuf = dev.get(max(4 * int(ooffs[-1] + (olens[-1] + 3) // 4 * 4), 16))
+                plan.resample_batch(din, offs, lens, int(rate), sr, fmt=fmt, out=dbuf, out_offsets=ooffs)
+            except NotImplementedError:                               # a rate pair the device resampler does not hold
+                if dbuf is not None:
+                    dev.put(dbuf)
+                dev_in.put(din)
+                f = np.float32(1.0 / 32768.0) if fmt == _native.FMT_S16 else None
+                ys = [wavio.resample(buf[o:o + ln].astype(np.float32) * f if f is not None else buf[o:o + ln], int(rate), sr)
+                      for o, ln in zip(offs, lens)]
+                hb, ho, hl = _pack(ys, np.float32)
+                return run_group(plans, cur, hb, ho, hl, _native.FMT_F32, dev)
+            except BaseException:
+                if dbuf is not None:
+                    dev.put(dbuf)
+                dev_in.put(din)
+                raise
+            dev_in.put(din)                                           # the resampler is synchronous: the input is done with
+            offs, lens, fmt = ooffs, olens, _native.FMT_F32
+        else:
+            dbuf = dev.get(max(buf.nbytes, 16))                       # one PCIe copy for both passes
         try:
-            dbuf.upload(buf)
+            if rate is None or int(rate) == sr:
+                dbuf.upload(buf)
             tl[3] = time.perf_counter() - t_start
             submitted = False
             if want_stats:                                        # MFCC / RMS pass: queued, runs beside the pYIN pass below
@@ -346,12 +398,16 @@ def process_files(extractor, files: Sequence, max_batch_samples: int = 80 * 1024
 
     def worker(lane, idxs):
         wins = _windows(sizes, idxs, max_batch_samples)
-        plan = pin = dev = None
+        plan = pin = dev = dev_in = None
+        can_rs = False
         try:                                                      # (MFCC / RMS plan, pYIN plan): own context and stream each
             plan = (extractor._plan(lane[0], lane[1]),
                     extractor._plan(lane[0], (lane[1], "f0")) if want_f0 else None)
             dpools = extractor.__dict__.setdefault("_dev_pools", {})
             dev = dpools.get(lane) or dpools.setdefault(lane, _DevPool(plan[0]))
+            can_rs = hasattr(plan[0], "resample_batch")
+            if can_rs:                                            # the resampler's input: a second pooled device buffer
+                dev_in = dpools.get((lane, "in")) or dpools.setdefault((lane, "in"), _DevPool(plan[0]))
             if hasattr(plan[0], "pinned_buffer"):                 # page-locked window buffers, kept with the extractor
                 pools = extractor.__dict__.setdefault("_pin_pools", {})
                 pin = pools.get(lane) or pools.setdefault(lane, _PinPool(plan[0]))
@@ -359,36 +415,42 @@ def process_files(extractor, files: Sequence, max_batch_samples: int = 80 * 1024
             for i in idxs:
                 errors[i] = e
             return
-        pending = win_pool.submit(load_window, wins[0], pin) if wins else None
+        pending = win_pool.submit(load_window, wins[0], pin, can_rs) if wins else None
         for k, win in enumerate(wins):
             t0 = time.perf_counter()
             packed, rest, decoded = pending.result()
             # next window loads while this one is on the device
-            pending = win_pool.submit(load_window, wins[k + 1], pin) if k + 1 < len(wins) else None
+            pending = win_pool.submit(load_window, wins[k + 1], pin, can_rs) if k + 1 < len(wins) else None
             t1 = time.perf_counter()
             try:
                 if packed is not None:                            # the natively packed 16-bit clips, in budget-sized runs
-                    ids, buf, offs, lens, _held = packed
+                    ids, buf, offs, lens, _held, rates = packed
+                    olens = np.maximum(lens, _native.resample_lengths(lens, rates, extractor.sr))
                     pos = 0
-                    while pos < len(ids):
+                    while pos < len(ids):          # runs of one file rate, within the budget before and after resampling
                         tot, end = 0, pos
-                        while end < len(ids) and (end == pos or tot + int(lens[end]) <= max_batch_samples):
-                            tot += int(lens[end])
+                        while end < len(ids) and (end == pos or (rates[end] == rates[pos] and
+                                                                 tot + int(olens[end]) <= max_batch_samples)):
+                            tot += int(olens[end])
                             end += 1
                         lo = int(offs[pos])
                         hi = int(offs[end - 1] + (lens[end - 1] + 3) // 4 * 4)
-                        run_group(plan, ids[pos:end], buf[lo:hi], offs[pos:end] - lo, lens[pos:end], _native.FMT_S16, dev)
+                        run_group(plan, ids[pos:end], buf[lo:hi], offs[pos:end] - lo, lens[pos:end], _native.FMT_S16, dev,
+                                  int(rates[pos]), dev_in)
                         pos = end
-                for kind, fmt, dt in (("s16", _native.FMT_S16, np.int16), ("f32", _native.FMT_F32, np.float32)):
-                    sel = [(i, d[1]) for i, d in zip(rest, decoded) if d is not None and d[0] == kind]
+                groups = sorted({(d[2] != extractor.sr, d[2], d[0] != "s16") for d in decoded if d is not None})
+                for _, rate, is_f32 in groups:
+                    kind, fmt, dt = (("f32", _native.FMT_F32, np.float32) if is_f32 else ("s16", _native.FMT_S16, np.int16))
+                    sel = [(i, d[1]) for i, d in zip(rest, decoded) if d is not None and d[0] == kind and d[2] == rate]
+                    osz = [max(y.size, int(_native.resample_lengths(y.size, rate, extractor.sr))) for _, y in sel]
                     pos = 0
                     while pos < len(sel):          # a window may still exceed the budget (sizes were estimates)
                         tot, end = 0, pos
-                        while end < len(sel) and (end == pos or tot + sel[end][1].size <= max_batch_samples):
-                            tot += sel[end][1].size
+                        while end < len(sel) and (end == pos or tot + osz[end] <= max_batch_samples):
+                            tot += osz[end]
                             end += 1
                         buf, offs, lens = _pack([y for _, y in sel[pos:end]], dt)
-                        run_group(plan, [i for i, _ in sel[pos:end]], buf, offs, lens, fmt, dev)
+                        run_group(plan, [i for i, _ in sel[pos:end]], buf, offs, lens, fmt, dev, int(rate), dev_in)
                         pos = end
             except Exception as e:          # a device-level failure drops the files of the sub-batch it hit, and the
                 for i in win:               # rest of this window; later windows are still attempted

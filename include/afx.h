@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define AFX_VERSION 106      /* 106: afx_hpss_batch; 105: afx_dtw_batch; 104: afx_batch_geometry, afx_host_alloc / afx_host_free */
+#define AFX_VERSION 107      /* 107: afx_resample_design, afx_resample_batch; 106: afx_hpss_batch; 105: afx_dtw_batch; 104: afx_batch_geometry, afx_host_alloc / afx_host_free */
 
 typedef enum afx_status {
   AFX_OK = 0,
@@ -316,6 +316,34 @@ int afx_wav_probe(const char* const* paths, int n, int threads, int32_t* info /*
                   int64_t* data_off, int32_t* status);
 int afx_wav_read_s16(const char* const* paths, int n, int threads, const int64_t* data_off, const int64_t* frames,
                      int16_t* out, int64_t out_len, const int64_t* offsets, int32_t* status);
+
+/* Resampling to the extractor's rate, the other half of load_audio (F:52: librosa.load(path, sr=self.sr)).  The filter is
+ * the engine's own (parity with librosa's soxr_hq is not claimed): a linear-phase Kaiser-windowed sinc, 125 dB, transition
+ * band 0.913 .. 1.0 of the lower Nyquist rate, applied as a polyphase filter.  With g = gcd(sr_in, sr_out), up = sr_out / g,
+ * down = sr_in / g, taps h[0 .. L) of odd length L and half = (L - 1) / 2, a clip x[0 .. n) gives ceil(n * up / down) samples
+ *   out[m] = float32( sum_i x[i] * (up * h[m * down + half - i * up]) ),    0 <= i < n, tap index within [0, L)
+ * with x taken as float64 (S16: value / 32768), the products and the sum in float64, one rounding to float32; samples
+ * outside the clip are zero.
+ *
+ * afx_resample_design (host-only, no device needed): info[4] = up, down, L, half; taps[L] (NULL: sizes only) from
+ * scipy.signal.kaiserord(125, ...) / firwin with a Kaiser window, unity DC gain.  sr_in == sr_out: 1, 1, 1, 0 and the tap 1.
+ * AFX_ERR_INVALID for a non-positive rate; AFX_ERR_UNSUPPORTED for a rate pair outside the table bounds of the device
+ * resampler: up <= 2048, L <= 2^21 (22051 -> 22050 has up = 22050 and 10^7 taps).
+ *
+ * afx_resample_batch: clip i = samples[offsets[i] .. + lengths[i]) (AFX_FMT_F32 / AFX_FMT_S16, host or device memory) is
+ * written as float32 to out[out_offsets[i] .. + ceil(lengths[i] * up / down)) in host or device memory (out_mem_kind);
+ * out_lengths (host, NULL ok) receives those lengths.  A clip of length 0 writes nothing.  taps: NULL = the design above,
+ * else n_taps (odd) caller-supplied taps of unity DC gain.  sr_in == sr_out converts / copies.  A clip's sum never reads
+ * its neighbours in the packed buffer.  NaN / inf samples propagate into the outputs whose filter span (widened to the
+ * eight adjacent outputs a lane computes together) holds them; there is no per-clip status -- the extract passes behind
+ * report AFX_CLIP_NONFINITE.  Results are bit-reproducible (no atomics, one fixed summation order).
+ * AFX_ERR_UNSUPPORTED beyond the bounds above, when ceil(8 / up) * down > 2048, or when the filter's span does not fit the
+ * kernel's LDS tile; AFX_ERR_INVALID for negative offsets / lengths or an even n_taps. */
+int afx_resample_design(int sr_in, int sr_out, int32_t* info /*[4]*/, double* taps);
+int afx_resample_batch(afx_ctx* ctx, const void* samples, int sample_fmt, int mem_kind,
+                       const int64_t* offsets, const int64_t* lengths, int n_clips, int sr_in, int sr_out,
+                       const double* taps, int n_taps, float* out, int out_mem_kind,
+                       const int64_t* out_offsets, int64_t* out_lengths);
 
 /* preprocess_audio(y) (F:58-74): pre-emphasis + trim of ONE host clip.
  * out_y receives the n pre-emphasised samples (host, n floats); the kept span
