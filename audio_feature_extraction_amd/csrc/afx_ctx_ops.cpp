@@ -1,0 +1,257 @@
+// The entry points of libafx.so that work on a context, not a plan: batched DTW and batched polyphase resampling.
+#include <algorithm>
+#include <cmath>
+#include <cstdlib>
+#include <cstring>
+#include <numeric>
+#include <string>
+#include <vector>
+
+#include <hip/hip_runtime.h>
+
+#include "afx_devenv.h"
+#include "afx_dtw.h"
+#include "afx_internal.h"
+#include "afx_plan.h"
+#include "afx_resample.h"
+
+// ---- batched DTW (librosa.sequence.dtw): the alignment step the reference runs on the extracted MFCC frames ----------
+extern "C" int afx_dtw_batch(afx_ctx* ctx, const float* feats, int dim,
+                             const int64_t* x_off, const int64_t* x_len, const int64_t* y_off, const int64_t* y_len,
+                             const int32_t* band_r, int n_pairs, int metric, int flags,
+                             double* out_cost, int32_t* out_status,
+                             int32_t* out_path, const int64_t* path_off, int32_t* out_path_len,
+                             double* out_D, const int64_t* d_off) {
+  const bool bt = (flags & AFX_DTW_BACKTRACK) != 0, sd = (flags & AFX_DTW_STORE_D) != 0;
+  if (!ctx || n_pairs < 0 || (n_pairs > 0 && (!feats || !x_off || !x_len || !y_off || !y_len || !out_cost || !out_status))) {
+    set_error("afx_dtw_batch: null/invalid argument");
+    return AFX_ERR_INVALID;
+  }
+  if (flags & ~(AFX_DTW_BACKTRACK | AFX_DTW_STORE_D)) { set_error("afx_dtw_batch: unknown flag"); return AFX_ERR_INVALID; }
+  if (metric != AFX_DTW_EUCLIDEAN && metric != AFX_DTW_SQEUCLIDEAN && metric != AFX_DTW_COSINE) {
+    set_error("afx_dtw_batch: unknown metric");
+    return AFX_ERR_INVALID;
+  }
+  if (n_pairs > 0 && bt && (!out_path || !path_off || !out_path_len)) {
+    set_error("afx_dtw_batch: AFX_DTW_BACKTRACK needs out_path, path_off and out_path_len");
+    return AFX_ERR_INVALID;
+  }
+  if (n_pairs > 0 && sd && (!out_D || !d_off)) { set_error("afx_dtw_batch: AFX_DTW_STORE_D needs out_D and d_off"); return AFX_ERR_INVALID; }
+  if (dim < 1) { set_error("afx_dtw_batch: dim must be >= 1"); return AFX_ERR_INVALID; }
+  if (dim > kDtwMaxDim) { set_error("afx_dtw_batch: dim > 128 is not supported by the DTW kernel"); return AFX_ERR_UNSUPPORTED; }
+  int64_t n_frames = 0;
+  for (int p = 0; p < n_pairs; ++p) {
+    if (x_off[p] < 0 || y_off[p] < 0 || x_len[p] < 1 || y_len[p] < 1 || x_off[p] > INT64_MAX / 2 || y_off[p] > INT64_MAX / 2 ||
+        x_len[p] > INT32_MAX || y_len[p] > INT32_MAX) {
+      set_error("afx_dtw_batch: pair " + std::to_string(p) + ": offsets must be >= 0 and lengths >= 1");
+      return AFX_ERR_INVALID;
+    }
+    if (x_len[p] * y_len[p] > ((int64_t)1 << 31) || x_len[p] > (1 << 30) || y_len[p] > (1 << 30)) {
+      set_error("afx_dtw_batch: pair " + std::to_string(p) + ": N * M > 2^31 cells is not supported");
+      return AFX_ERR_UNSUPPORTED;
+    }
+    if ((bt && path_off[p] < 0) || (sd && d_off[p] < 0)) {
+      set_error("afx_dtw_batch: pair " + std::to_string(p) + ": negative output offset");
+      return AFX_ERR_INVALID;
+    }
+    n_frames = std::max(n_frames, std::max(x_off[p] + x_len[p], y_off[p] + y_len[p]));
+  }
+  if (n_pairs == 0) return AFX_OK;
+  if (n_frames > INT64_MAX / 4 / dim) { set_error("afx_dtw_batch: feature buffer too large"); return AFX_ERR_INVALID; }
+
+  (void)hipGetLastError();
+  HIP_TRY(hipSetDevice(ctx->device));
+  hipStream_t s = ctx->stream;
+  int rc;
+  // the caller's frames are uploaded once and re-strided on the device to the padded width the DP kernel reads
+  const size_t feat_bytes = (size_t)n_frames * dim * sizeof(float);
+  if ((rc = ensure(ctx->dtw_raw, feat_bytes)) != AFX_OK) return rc;
+  if ((rc = ensure(ctx->dtw_feats, (size_t)n_frames * dtw_dimp(dim) * sizeof(float))) != AFX_OK) return rc;
+  if ((rc = ensure(ctx->dtw_norms, (size_t)n_frames * sizeof(float))) != AFX_OK) return rc;
+  HIP_TRY(hipMemcpyAsync(ctx->dtw_raw.p, feats, feat_bytes, hipMemcpyHostToDevice, s));
+  HIP_TRY(launch_dtw_pack(s, (const float*)ctx->dtw_raw.p, dim, n_frames, (float*)ctx->dtw_feats.p, (float*)ctx->dtw_norms.p));
+  const float* d_norms = (const float*)ctx->dtw_norms.p;
+
+  const int64_t budget = dev_env().dtw_budget;
+  std::vector<DtwPair> recs;
+  std::vector<int32_t> h_path, h_len;
+  for (int c0 = 0; c0 < n_pairs;) {
+    // one chunk: as many pairs as the workspace budget holds (at least one)
+    recs.clear();
+    int64_t codes = 0, dcells = 0, paths = 0, rows = 0, bytes = 0;
+    int c1 = c0;
+    while (c1 < n_pairs) {
+      const int n = (int)x_len[c1], m = (int)y_len[c1];
+      const int64_t pc = bt ? dtw_code_words(n, m) : 0, pd = sd ? (int64_t)n * m : 0, pp = bt ? (int64_t)n + m - 1 : 0;
+      const int64_t pb = pc * 4 + pd * 8 + pp * 8 + (int64_t)m * 8 + (int64_t)sizeof(DtwPair) + 16;
+      if (c1 > c0 && bytes + pb > budget) break;
+      DtwPair r{};
+      r.x_frame = x_off[c1]; r.y_frame = y_off[c1];
+      r.codes = bt ? codes : -1; r.d = sd ? dcells : -1; r.path = paths; r.row = rows;
+      r.n = n; r.m = m; r.qn = dtw_qn(m);
+      const int64_t rad = band_r ? band_r[c1] : -1;
+      if (rad < 0) {
+        r.lo = -(1 << 30); r.hi = 1 << 30;
+      } else {
+        const int64_t rr = std::min<int64_t>(rad, (int64_t)n + m), off = std::abs(n - m);
+        r.lo = (int32_t)(-rr - (n >= m ? off : 0));
+        r.hi = (int32_t)(rr + (n < m ? off : 0));
+      }
+      recs.push_back(r);
+      codes += pc; dcells += pd; paths += pp; rows += m; bytes += pb;
+      ++c1;
+    }
+    const int n = c1 - c0;
+    if ((rc = ensure(ctx->dtw_pairs, n * sizeof(DtwPair))) != AFX_OK) return rc;
+    if ((rc = ensure(ctx->dtw_rows, (size_t)rows * sizeof(double))) != AFX_OK) return rc;
+    if ((rc = ensure(ctx->dtw_cost, n * sizeof(double))) != AFX_OK) return rc;
+    if ((rc = ensure(ctx->dtw_status, n * sizeof(int32_t))) != AFX_OK) return rc;
+    if (bt) {
+      if ((rc = ensure(ctx->dtw_codes, (size_t)codes * sizeof(uint32_t))) != AFX_OK) return rc;
+      if ((rc = ensure(ctx->dtw_path, (size_t)paths * 2 * sizeof(int32_t))) != AFX_OK) return rc;
+      if ((rc = ensure(ctx->dtw_len, n * sizeof(int32_t))) != AFX_OK) return rc;
+    }
+    if (sd) {
+      if ((rc = ensure(ctx->dtw_d, (size_t)dcells * sizeof(double))) != AFX_OK) return rc;
+      HIP_TRY(launch_dtw_fill_inf(s, (double*)ctx->dtw_d.p, dcells));
+    }
+    HIP_TRY(hipMemcpyAsync(ctx->dtw_pairs.p, recs.data(), n * sizeof(DtwPair), hipMemcpyHostToDevice, s));
+    const DtwPair* d_pairs = (const DtwPair*)ctx->dtw_pairs.p;
+    HIP_TRY(launch_dtw(s, (const float*)ctx->dtw_feats.p, d_norms, dim, metric, d_pairs, n, (uint32_t*)ctx->dtw_codes.p,
+                       (double*)ctx->dtw_rows.p, (double*)ctx->dtw_d.p, (double*)ctx->dtw_cost.p,
+                       (int32_t*)ctx->dtw_status.p, bt, sd));
+    if (bt)
+      HIP_TRY(launch_dtw_backtrack(s, d_pairs, n, (const uint32_t*)ctx->dtw_codes.p, (const int32_t*)ctx->dtw_status.p,
+                                   (int32_t*)ctx->dtw_path.p, (int32_t*)ctx->dtw_len.p));
+    HIP_TRY(hipMemcpyAsync(out_cost + c0, ctx->dtw_cost.p, n * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(out_status + c0, ctx->dtw_status.p, n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    if (bt) {
+      h_path.resize((size_t)paths * 2);
+      h_len.resize(n);
+      HIP_TRY(hipMemcpyAsync(h_path.data(), ctx->dtw_path.p, (size_t)paths * 2 * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+      HIP_TRY(hipMemcpyAsync(h_len.data(), ctx->dtw_len.p, n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    }
+    if (sd)
+      for (int q = 0; q < n; ++q)
+        HIP_TRY(hipMemcpyAsync(out_D + d_off[c0 + q], (const double*)ctx->dtw_d.p + recs[q].d,
+                               (size_t)recs[q].n * recs[q].m * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (bt)
+      for (int q = 0; q < n; ++q) {
+        out_path_len[c0 + q] = h_len[q];
+        std::memcpy(out_path + 2 * path_off[c0 + q], h_path.data() + 2 * recs[q].path, (size_t)h_len[q] * 2 * sizeof(int32_t));
+      }
+    c0 = c1;
+  }
+  return AFX_OK;
+}
+
+// ---- batched polyphase resampling (wavio.resample: the resampling half of librosa.load(path, sr=...)) -------------------
+extern "C" int afx_resample_batch(afx_ctx* ctx, const void* samples, int sample_fmt, int mem_kind,
+                                  const int64_t* offsets, const int64_t* lengths, int n_clips, int sr_in, int sr_out,
+                                  const double* taps, int n_taps, float* out, int out_mem_kind,
+                                  const int64_t* out_offsets, int64_t* out_lengths) {
+  if (!ctx || n_clips < 0 || (n_clips > 0 && (!offsets || !lengths || !out_offsets))) {
+    set_error("afx_resample_batch: null/invalid argument");
+    return AFX_ERR_INVALID;
+  }
+  int rc;
+  if ((rc = check_sample_format("afx_resample_batch", sample_fmt, mem_kind)) != AFX_OK) return rc;
+  if ((rc = check_sample_format("afx_resample_batch", sample_fmt, out_mem_kind)) != AFX_OK) return rc;
+  if (sr_in <= 0 || sr_out <= 0) { set_error("afx_resample_batch: sample rates must be positive"); return AFX_ERR_INVALID; }
+  if (taps && (n_taps < 1 || !(n_taps & 1))) { set_error("afx_resample_batch: a caller-supplied filter needs an odd number of taps"); return AFX_ERR_INVALID; }
+  if ((rc = check_clip_ranges("afx_resample_batch", offsets, lengths, out_offsets, n_clips, INT64_MAX / 8)) != AFX_OK) return rc;
+  int64_t total_in = 0, total_out = 0;
+  for (int i = 0; i < n_clips; ++i) total_in += lengths[i];
+  const int g = std::gcd(sr_in, sr_out);
+  const int up = sr_out / g, down = sr_in / g;
+  const bool copy = up == down;
+  if (!copy) {
+    auto& rs = ctx->rs;
+    const bool same = rs.valid && rs.up == up && rs.down == down && rs.custom == (taps != nullptr) &&
+                      (!taps || ((int)rs.taps.size() == n_taps && std::memcmp(rs.taps.data(), taps, sizeof(double) * n_taps) == 0));
+    if (!same) {
+      std::string why;
+      RsDesign d;
+      if (!taps) {
+        if ((rc = resample_design(sr_in, sr_out, d, true, why)) != AFX_OK) { set_error("afx_resample_batch: " + why); return rc; }
+      }
+      rs.valid = false;
+      if ((rc = resample_tables(up, down, taps ? taps : d.h.data(), taps ? n_taps : d.n_taps, rs.t, why)) != AFX_OK) {
+        set_error("afx_resample_batch: " + why);
+        return rc;
+      }
+      rs.up = up; rs.down = down; rs.custom = taps != nullptr;
+      rs.taps.assign(taps ? taps : nullptr, taps ? taps + n_taps : nullptr);
+    }
+  }
+  if (n_clips > 0 && !out) {
+    bool any = false;
+    for (int i = 0; i < n_clips; ++i) any = any || lengths[i] > 0;
+    if (any) { set_error("afx_resample_batch: null out"); return AFX_ERR_INVALID; }
+  }
+  if (n_clips > 0 && total_in > 0 && !samples) { set_error("afx_resample_batch: null samples"); return AFX_ERR_INVALID; }
+  // clip records; a host batch is staged packed (4-element alignment), so only the clips themselves cross the link
+  const RsParams& P = ctx->rs.t.p;
+  const int64_t per_block = copy ? kRsCopyChunk : (int64_t)P.tile_sp * P.opp;
+  std::vector<RsClip> recs((size_t)n_clips);
+  int64_t n_blocks = 0, in_pos = 0;
+  for (int i = 0; i < n_clips; ++i) {
+    RsClip& r = recs[i];
+    r.in_len = lengths[i];
+    r.out_len = copy ? lengths[i] : resample_out_len(lengths[i], up, down);
+    if (out_lengths) out_lengths[i] = r.out_len;
+    r.in_off = mem_kind == AFX_MEM_HOST ? in_pos : offsets[i];
+    r.out_off = out_mem_kind == AFX_MEM_HOST ? total_out : out_offsets[i];
+    r.first_block = (int32_t)n_blocks; r.pad_ = 0;
+    in_pos += (lengths[i] + 3) / 4 * 4;
+    total_out += r.out_len;
+    n_blocks += (r.out_len + per_block - 1) / per_block;
+    if (n_blocks > INT32_MAX / 2) { set_error("afx_resample_batch: batch too large for one launch"); return AFX_ERR_UNSUPPORTED; }
+  }
+  if (n_clips == 0 || total_out == 0) return AFX_OK;
+  (void)hipGetLastError();
+  HIP_TRY(hipSetDevice(ctx->device));
+  hipStream_t s = ctx->stream;
+  if (!copy && !ctx->rs.valid) {
+    const RsTables& t = ctx->rs.t;
+    if ((rc = ensure(ctx->rs_g, t.G.size() * sizeof(double))) != AFX_OK) return rc;
+    if ((rc = ensure(ctx->rs_tstart, t.tstart.size() * sizeof(int32_t))) != AFX_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(ctx->rs_g.p, t.G.data(), t.G.size() * sizeof(double), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(ctx->rs_tstart.p, t.tstart.data(), t.tstart.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    ctx->rs.valid = true;
+  }
+  const size_t esz = sample_fmt == AFX_FMT_S16 ? 2 : 4;
+  const void* d_in = samples;
+  std::vector<char> h_in;
+  if (mem_kind == AFX_MEM_HOST) {
+    h_in.assign((size_t)in_pos * esz + 16, 0);
+    for (int i = 0; i < n_clips; ++i)
+      if (lengths[i]) std::memcpy(h_in.data() + (size_t)recs[i].in_off * esz, (const char*)samples + (size_t)offsets[i] * esz, (size_t)lengths[i] * esz);
+    if ((rc = ensure(ctx->rs_in, h_in.size())) != AFX_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(ctx->rs_in.p, h_in.data(), h_in.size(), hipMemcpyHostToDevice, s));
+    d_in = ctx->rs_in.p;
+  }
+  float* d_out = out;
+  if (out_mem_kind == AFX_MEM_HOST) {
+    if ((rc = ensure(ctx->rs_out, (size_t)total_out * sizeof(float))) != AFX_OK) return rc;
+    d_out = (float*)ctx->rs_out.p;
+  }
+  if ((rc = ensure(ctx->rs_clips, recs.size() * sizeof(RsClip))) != AFX_OK) return rc;
+  HIP_TRY(hipMemcpyAsync(ctx->rs_clips.p, recs.data(), recs.size() * sizeof(RsClip), hipMemcpyHostToDevice, s));
+  const RsClip* d_clips = (const RsClip*)ctx->rs_clips.p;
+  if (copy) HIP_TRY(launch_resample_copy(s, d_in, sample_fmt, d_out, d_clips, n_clips, (int)n_blocks));
+  else HIP_TRY(launch_resample(s, d_in, sample_fmt, d_out, d_clips, n_clips, (int)n_blocks, (const double*)ctx->rs_g.p,
+                               (const int32_t*)ctx->rs_tstart.p, P));
+  if (out_mem_kind == AFX_MEM_HOST) {
+    std::vector<float> h_out((size_t)total_out);
+    HIP_TRY(hipMemcpyAsync(h_out.data(), d_out, (size_t)total_out * sizeof(float), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    for (int i = 0; i < n_clips; ++i)
+      if (recs[i].out_len) std::memcpy(out + out_offsets[i], h_out.data() + recs[i].out_off, (size_t)recs[i].out_len * sizeof(float));
+  } else {
+    HIP_TRY(hipStreamSynchronize(s));
+  }
+  return AFX_OK;
+}

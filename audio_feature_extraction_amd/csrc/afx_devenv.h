@@ -1,7 +1,8 @@
 // Developer switches of libafx.so, read ONCE per process when the first caller asks (never on the per-call path:
 // getenv is not safe against a host program that writes os.environ from other threads, and a batch must not pay for it).
 // They exist for same-box A/B runs (tools/ab_env.sh) and for tests that exercise the multi-chunk paths with small
-// batches; none of them is part of the ABI.  Internal to libafx.so.
+// batches; none of them is part of the ABI.  Internal to libafx.so.  (Round 1's 4-wave 1024 / 256 frame kernel and
+// the switch that chose between it and k_frames<1024> were removed: see git log.)
 #pragma once
 #include <cstdint>
 
@@ -12,7 +13,6 @@ struct DevEnv {
   bool stamps = false, f3_debug = false, no_spec = false, no_tickets = false;
   bool no_frames3 = false, no_frames3s = false, no_frames3d = false;   // fall back to round 1's kernels (A/B)
   bool f3_generic_mel = false;        // the generic mel walk instead of the compiled-in schedule (A/B)
-  bool generic_1024 = false;          // k_frames<1024> instead of k_frames2 on the two-pass path (A/B)
   bool no_dct16l = false;             // k_dct16<2|3> instead of k_dct16l (A/B)
   bool host_blocks = false;           // build the speculative block list on the host and upload it (A/B of k_build_blocks3)
   bool no_fused_tail = false;         // k_dct16* + k_stats instead of the fused per-clip DCT + statistics kernel (A/B)

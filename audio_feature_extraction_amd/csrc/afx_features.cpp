@@ -1,0 +1,412 @@
+// The plan-based feature entry points of libafx.so beside the MFCC / RMS pipeline (afx_api.cpp): pYIN f0, zero-crossing
+// rate, the spectral descriptors, preprocess_audio and harmonic-percussive separation.  Each reads: check -> begin ->
+// stage -> its own work -> finish, on the front end of afx_plan.h.
+#include <algorithm>
+#include <cmath>
+#include <cstdio>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include <hip/hip_runtime.h>
+
+#include "afx_device.h"
+#include "afx_devenv.h"
+#include "afx_f0.h"
+#include "afx_frames3.h"
+#include "afx_hpss.h"
+#include "afx_internal.h"
+#include "afx_plan.h"
+
+// ---- extract_f0 ---------------------------------------------------------------------------------
+static int f0_setup(afx_plan* pl, double fmin, double fmax) {
+  if (pl->f0_ready && pl->f0_fmin == fmin && pl->f0_fmax == fmax) return AFX_OK;
+  std::string why;
+  HostF0Tables ht;
+  if (!build_f0_tables(pl->p.sr, pl->p.n_fft, pl->p.hop, fmin, fmax, ht, why)) {
+    set_error("afx_f0_batch: " + why);
+    return AFX_ERR_UNSUPPORTED;
+  }
+  if (f0_energy_lds_bytes(ht.p) > 160 * 1024 || f0_yin_lds_bytes(ht.p) > 160 * 1024 ||
+      f0_viterbi_lds_bytes(ht.p) > 160 * 1024 || f0_backtrack_lds_bytes(ht.p) > 160 * 1024 || 2 * ht.p.band + 1 > 64) {
+    set_error("afx_f0_batch: frame_length / f0 range needs more than 160 KiB of LDS");
+    return AFX_ERR_UNSUPPORTED;
+  }
+  for (void* q : pl->f0_allocs) (void)hipFree(q);
+  pl->f0_allocs.clear();
+  pl->f0_ready = false;
+  auto up = [&](const std::vector<double>& v, const double** dst) -> int {
+    void* d = nullptr;
+    HIP_TRY(hipMalloc(&d, v.size() * sizeof(double)));
+    pl->f0_allocs.push_back(d);
+    HIP_TRY(hipMemcpy(d, v.data(), v.size() * sizeof(double), hipMemcpyHostToDevice));
+    *dst = (const double*)d;
+    return AFX_OK;
+  };
+  int rc;
+  if ((rc = up(ht.thr, &pl->f0_dt.thr)) != AFX_OK || (rc = up(ht.beta, &pl->f0_dt.beta)) != AFX_OK ||
+      (rc = up(ht.cumbeta, &pl->f0_dt.cumbeta)) != AFX_OK || (rc = up(ht.bfact, &pl->f0_dt.bfact)) != AFX_OK ||
+      (rc = up(ht.bexp, &pl->f0_dt.bexp)) != AFX_OK || (rc = up(ht.lt, &pl->f0_dt.lt)) != AFX_OK || (rc = up(ht.ltw, &pl->f0_dt.ltw)) != AFX_OK ||
+      (rc = up(ht.freqs, &pl->f0_dt.freqs)) != AFX_OK)
+    return rc;
+  if (dev_env().f0_debug) ht.p.debug = dev_env().f0_debug;
+  pl->f0_ht = ht;
+  pl->f0_fmin = fmin; pl->f0_fmax = fmax;
+  pl->f0_ready = true;
+  return AFX_OK;
+}
+
+static int f0_chunk(afx_plan* pl, const void* d_samples, int fmt, const int64_t* offsets, const int64_t* lengths,
+                    int n, int flags, double* out_stats, int32_t* out_status, double* out_f0,
+                    const int64_t* f0_offsets) {
+  hipStream_t s = pl->ctx->stream;
+  const F0Params& fp = pl->f0_ht.p;
+  int rc;
+  if ((rc = prepare_descriptors(pl, offsets, lengths, n)) != AFX_OK) return rc;
+  const int64_t frames = std::max<int64_t>(pl->total_tpad, 1);
+  if ((rc = ensure(pl->f0_energy, (size_t)frames * fp.n_tau_pad * sizeof(float))) != AFX_OK) return rc;
+  if ((rc = ensure(pl->f0_cnt, (size_t)frames * sizeof(int32_t))) != AFX_OK) return rc;
+  if ((rc = ensure(pl->f0_vp, (size_t)frames * sizeof(double))) != AFX_OK) return rc;
+  if ((rc = ensure(pl->f0_bin, f0_cand_bins_bytes(fp, frames))) != AFX_OK) return rc;
+  const bool dump_obs = dev_env().f0_dump != nullptr;        // the linear probabilities are kept for the diagnostic dump only
+  if (dump_obs && (rc = ensure(pl->f0_prob, f0_cand_prob_bytes(fp, frames))) != AFX_OK) return rc;
+  if ((rc = ensure(pl->f0_ptr, f0_vrows_bytes(fp, frames))) != AFX_OK) return rc;
+  if ((rc = ensure(pl->f0_best, (size_t)frames * sizeof(VitBest))) != AFX_OK) return rc;
+  if ((rc = ensure(pl->f0_lprob, f0_cand_prob_bytes(fp, frames))) != AFX_OK) return rc;
+  if ((rc = ensure(pl->f0_lu, (size_t)frames * sizeof(double))) != AFX_OK) return rc;
+  if ((rc = ensure(pl->f0_states, (size_t)frames * sizeof(uint16_t))) != AFX_OK) return rc;
+  if ((rc = ensure(pl->f0_stats, (size_t)n * 4 * sizeof(double))) != AFX_OK) return rc;
+  // per-frame f0 of this chunk: [o_lo, o_hi) of the caller's buffer, device copy rebased to it (rebase_offsets)
+  double* d_f0 = nullptr;
+  int64_t o_lo = 0, o_hi = 0;
+  std::vector<int64_t> rebased;
+  if (out_f0) {
+    if (!f0_offsets) { set_error("out_f0 given without f0_offsets"); return AFX_ERR_INVALID; }
+    if ((rc = rebase_offsets(pl, "f0", f0_offsets, n, 1, rebased, &o_lo, &o_hi)) != AFX_OK) return rc;
+    // 0xff: NaN wherever no clip writes
+    if ((rc = upload_frame_range(pl, rebased.data(), n, pl->f0_offs, pl->f0_out, (size_t)(o_hi - o_lo) * sizeof(double), 0xff)) != AFX_OK) return rc;
+    d_f0 = (double*)pl->f0_out.p;
+  }
+  KParams kp = pl->kp;
+  kp.flags = flags; kp.fmt = fmt;
+  const ClipDesc* d_clips = (const ClipDesc*)pl->clips.p;
+  if ((rc = run_preprocess(pl, d_samples, n, kp, true)) != AFX_OK) return rc;
+  ClipInfo* d_info = (ClipInfo*)pl->info.p;
+  HIP_TRY(launch_f0_energy(s, (const float*)pl->f0_ysig.p, d_clips, d_info, (float*)pl->f0_energy.p, n, pl->max_tmax, fp));
+  HIP_TRY(launch_f0_yin(s, (const float*)pl->f0_ysig.p, d_clips, d_info, (const float*)pl->f0_energy.p, pl->f0_dt, fp,
+                        (int32_t*)pl->f0_cnt.p, (double*)pl->f0_vp.p, (int16_t*)pl->f0_bin.p,
+                        dump_obs ? (double*)pl->f0_prob.p : nullptr, (double*)pl->f0_lprob.p, (double*)pl->f0_lu.p, n, pl->max_tmax));
+  HIP_TRY(launch_f0_viterbi(s, d_clips, d_info, pl->f0_dt, fp, (const int32_t*)pl->f0_cnt.p,
+                            (const int16_t*)pl->f0_bin.p, (const double*)pl->f0_lprob.p,
+                            (const double*)pl->f0_lu.p, (double*)pl->f0_ptr.p, (VitBest*)pl->f0_best.p,
+                            (uint16_t*)pl->f0_states.p, (double*)pl->f0_stats.p, d_f0, (const int64_t*)pl->f0_offs.p, n));
+  HIP_TRY(hipMemcpyAsync(out_stats, pl->f0_stats.p, (size_t)n * 4 * sizeof(double), hipMemcpyDeviceToHost, s));
+  if (out_f0 && o_hi > o_lo) HIP_TRY(hipMemcpyAsync(out_f0 + o_lo, d_f0, (size_t)(o_hi - o_lo) * sizeof(double), hipMemcpyDeviceToHost, s));
+  if ((rc = statuses_from_info(pl, n, out_status)) != AFX_OK) return rc;
+  if (const char* dump = dev_env().f0_dump) {                       // diagnostics: the sparse observation columns
+    std::vector<int32_t> cnt(frames); std::vector<double> vp(frames), pr((size_t)frames * fp.cap);
+    std::vector<int16_t> bn((size_t)frames * fp.cap);
+    HIP_TRY(hipMemcpy(cnt.data(), pl->f0_cnt.p, frames * sizeof(int32_t), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(vp.data(), pl->f0_vp.p, frames * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(pr.data(), pl->f0_prob.p, pr.size() * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(bn.data(), pl->f0_bin.p, bn.size() * sizeof(int16_t), hipMemcpyDeviceToHost));
+    if (FILE* f = fopen(dump, "wb")) {
+      const int64_t hdr[2] = {frames, fp.cap};
+      fwrite(hdr, sizeof(hdr), 1, f);
+      fwrite(cnt.data(), sizeof(int32_t), cnt.size(), f); fwrite(vp.data(), sizeof(double), vp.size(), f);
+      fwrite(bn.data(), sizeof(int16_t), bn.size(), f); fwrite(pr.data(), sizeof(double), pr.size(), f);
+      fclose(f);
+    }
+  }
+  return AFX_OK;
+}
+
+extern "C" int afx_f0_batch(afx_plan* pl, const void* samples, int sample_fmt, int mem_kind,
+                            const int64_t* offsets, const int64_t* lengths, int n_clips, int flags,
+                            double fmin, double fmax, double* out_f0stats, int32_t* out_status,
+                            double* out_f0, const int64_t* f0_offsets) {
+  if (!out_f0stats || !out_status) return null_arg("afx_f0_batch");
+  int rc = check_batch_args("afx_f0_batch", pl, samples, sample_fmt, mem_kind, offsets, lengths, n_clips);
+  if (rc != AFX_OK) return rc;
+  if (n_clips == 0) return AFX_OK;
+  if ((rc = begin_plan_call("afx_f0_batch", pl)) != AFX_OK) return rc;
+  if ((rc = f0_setup(pl, fmin, fmax)) != AFX_OK) return rc;
+  const void* d_samples = nullptr;
+  if ((rc = stage_samples(pl, pl->f0_in, samples, sample_fmt, mem_kind, offsets, lengths, n_clips, &d_samples)) != AFX_OK) return rc;
+  // the stage keeps ~14 KB of workspace per frame (Viterbi value columns 9.6 KB, candidates and their logs, energies): bound it
+  // per chunk (18 GB; a chunk should still hold several clips per CU so that every CU runs two Viterbi workgroups)
+  const int64_t kMaxFrames = dev_env().f0_chunk_frames;
+  int c0 = 0;
+  while (c0 < n_clips) {
+    int n = 0;
+    int64_t fr = 0;
+    while (c0 + n < n_clips && n < dev_env().chunk_clips) {
+      const int64_t t = 1 + lengths[c0 + n] / pl->p.hop + kFramesPerBlock;
+      if (n > 0 && fr + t > kMaxFrames) break;
+      fr += t; ++n;
+    }
+    rc = f0_chunk(pl, d_samples, sample_fmt, offsets + c0, lengths + c0, n, flags, out_f0stats + (size_t)c0 * 4,
+                  out_status + c0, out_f0, f0_offsets ? f0_offsets + c0 : nullptr);
+    if (rc != AFX_OK) return rc;
+    c0 += n;
+  }
+  return AFX_OK;
+}
+
+// ---- zero-crossing rate per frame (the sibling feature the reference's experiment scripts store) ---------
+extern "C" int afx_zcr_batch(afx_plan* pl, const void* samples, int sample_fmt, int mem_kind,
+                             const int64_t* offsets, const int64_t* lengths, int n_clips, int flags,
+                             double* out_zcr, const int64_t* zcr_offsets, int32_t* out_status) {
+  if (!out_zcr || !zcr_offsets || !out_status) return null_arg("afx_zcr_batch");
+  int rc = check_batch_args("afx_zcr_batch", pl, samples, sample_fmt, mem_kind, offsets, lengths, n_clips);
+  if (rc != AFX_OK) return rc;
+  if (n_clips == 0) return AFX_OK;
+  if (n_clips > 32768) { set_error("afx_zcr_batch: at most 32768 clips per call"); return AFX_ERR_INVALID; }
+  if ((rc = begin_plan_call("afx_zcr_batch", pl)) != AFX_OK) return rc;
+  hipStream_t s = pl->ctx->stream;
+  const int n = n_clips;
+  const void* d_samples = nullptr;
+  if ((rc = stage_samples(pl, pl->f0_in, samples, sample_fmt, mem_kind, offsets, lengths, n, &d_samples)) != AFX_OK) return rc;
+  if ((rc = prepare_descriptors(pl, offsets, lengths, n)) != AFX_OK) return rc;
+  size_t count = 0;
+  for (int i = 0; i < n; ++i) count = std::max<size_t>(count, (size_t)zcr_offsets[i] + (size_t)pl->h_clips[i].tmax);
+  if ((rc = upload_frame_range(pl, zcr_offsets, n, pl->f0_offs, pl->f0_out, std::max<size_t>(count, 1) * sizeof(double), 0)) != AFX_OK) return rc;
+  KParams kp = pl->kp;
+  kp.flags = flags; kp.fmt = sample_fmt;
+  if ((rc = run_preprocess(pl, d_samples, n, kp, true)) != AFX_OK) return rc;
+  HIP_TRY(launch_zcr(s, (const float*)pl->f0_ysig.p, (const ClipDesc*)pl->clips.p, (const ClipInfo*)pl->info.p, pl->p.n_fft, pl->p.hop,
+                     (double*)pl->f0_out.p, (const int64_t*)pl->f0_offs.p, n, pl->max_tmax));
+  HIP_TRY(hipMemcpyAsync(out_zcr, pl->f0_out.p, count * sizeof(double), hipMemcpyDeviceToHost, s));
+  return statuses_from_info(pl, n, out_status);
+}
+
+// octave bands of librosa.feature.spectral_contrast(fmin=200, n_bands=6, quantile=0.02) as bin ranges (n_fft 2048)
+static bool spectral_bands(int sr_hz, SpecBands& sb) {
+  sb = SpecBands{};
+  const int NB = 1025;
+  const double sr = (double)sr_hz, df = sr / 2048.0;
+  double octa[8];
+  octa[0] = 0.0;
+  for (int i = 1; i < 8; ++i) octa[i] = 200.0 * std::pow(2.0, (double)(i - 1));
+  for (int i = 0; i < 7; ++i)
+    if (octa[i] >= 0.5 * sr) { set_error("spectral_contrast: frequency band exceeds Nyquist (sr too low for 6 octave bands from 200 Hz)"); return false; }
+  for (int k = 0; k < 7; ++k) {
+    int b0 = -1, b1 = -1;
+    for (int b = 0; b < NB; ++b) { const double f = (double)b * df; if (f >= octa[k] && f <= octa[k + 1]) { if (b0 < 0) b0 = b; b1 = b; } }
+    if (b0 < 0) { set_error("spectral_contrast: empty band"); return false; }
+    if (k > 0) b0 -= 1;
+    if (k == 6) b1 = NB - 1;
+    const int n_cur = b1 - b0 + 1;
+    sb.cnt[k] = std::max(1, (int)std::nearbyint(0.02 * (double)n_cur));
+    sb.lo[k] = b0; sb.hi[k] = (k < 6) ? b1 - 1 : b1;
+  }
+  sb.hz_per_bin = (float)df; sb.roll_percent = 0.85f;
+  return true;
+}
+
+// ---- spectral descriptors (librosa.feature.spectral_centroid / _bandwidth / _rolloff / _contrast at their defaults) ------
+extern "C" int afx_spectral_batch(afx_plan* pl, const void* samples, int sample_fmt, int mem_kind,
+                                  const int64_t* offsets, const int64_t* lengths, int n_clips, int flags,
+                                  float* out_desc, const int64_t* desc_offsets, int32_t* out_status) {
+  if (!out_desc || !desc_offsets || !out_status) return null_arg("afx_spectral_batch");
+  int rc = check_batch_args("afx_spectral_batch", pl, samples, sample_fmt, mem_kind, offsets, lengths, n_clips);
+  if (rc != AFX_OK) return rc;
+  if (pl->p.n_fft != 2048 || pl->p.hop != 512 || !pl->use_f3) {
+    set_error("afx_spectral_batch: the plan must have frame_length 2048 and hop_length 512 (librosa's defaults for these features)");
+    return AFX_ERR_UNSUPPORTED;
+  }
+  if (flags & AFX_FLAG_TRIM) { set_error("afx_spectral_batch: trim is not applied here; pass the preprocessed signal"); return AFX_ERR_UNSUPPORTED; }
+  if (n_clips == 0) return AFX_OK;
+  if (n_clips > 32768) { set_error("afx_spectral_batch: at most 32768 clips per call"); return AFX_ERR_INVALID; }
+  SpecBands sb{};
+  if (!spectral_bands(pl->p.sr, sb)) return AFX_ERR_UNSUPPORTED;
+  if ((rc = begin_plan_call("afx_spectral_batch", pl)) != AFX_OK) return rc;
+  hipStream_t s = pl->ctx->stream;
+  const int n = n_clips;
+  const void* d_samples = nullptr;
+  if ((rc = stage_samples(pl, pl->samples, samples, sample_fmt, mem_kind, offsets, lengths, n, &d_samples)) != AFX_OK) return rc;
+  if ((rc = prepare_descriptors(pl, offsets, lengths, n)) != AFX_OK) return rc;
+  int64_t d_lo = 0, d_hi = 0;
+  std::vector<int64_t> rebased;
+  if ((rc = rebase_offsets(pl, "descriptor", desc_offsets, n, kSpecFloats, rebased, &d_lo, &d_hi)) != AFX_OK) return rc;
+  KParams kp = pl->kp;
+  kp.flags = flags; kp.fmt = sample_fmt;
+  if ((rc = run_spectral(pl, d_samples, n, kp, rebased.data(), (size_t)(d_hi - d_lo), sb)) != AFX_OK) return rc;
+  HIP_TRY(hipMemcpyAsync(out_desc + d_lo, pl->frames.p, (size_t)(d_hi - d_lo) * sizeof(float), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  for (int i = 0; i < n; ++i) out_status[i] = lengths[i] < 2 ? AFX_CLIP_TOO_SHORT : AFX_CLIP_OK;
+  return AFX_OK;
+}
+
+extern "C" int afx_preprocess(afx_plan* pl, const float* y, int64_t n, float* out_y,
+                              int64_t* start, int64_t* end, int32_t* status) {
+  if (!pl || !y || !out_y || !start || !end || !status || n < 0) return null_arg("afx_preprocess");
+  int rc = begin_plan_call("afx_preprocess", pl);
+  if (rc != AFX_OK) return rc;
+  hipStream_t s = pl->ctx->stream;
+  const int64_t off = 0;
+  if ((rc = prepare_descriptors(pl, &off, &n, 1)) != AFX_OK) return rc;
+  if ((rc = ensure(pl->samples, (size_t)n * 4 + 16)) != AFX_OK) return rc;
+  if ((rc = ensure(pl->logmel, (size_t)std::max<int64_t>(n, 1) * sizeof(float))) != AFX_OK) return rc;   // y_pre scratch
+  if (n > 0) HIP_TRY(hipMemcpyAsync(pl->samples.p, y, (size_t)n * 4, hipMemcpyHostToDevice, s));
+  KParams kp = pl->kp;
+  kp.flags = AFX_FLAG_PREEMPH | AFX_FLAG_TRIM; kp.fmt = AFX_FMT_F32;
+  if ((rc = run_preprocess(pl, pl->samples.p, 1, kp, false)) != AFX_OK) return rc;
+  if (n > 0) {
+    HIP_TRY(launch_preemph(s, (const float*)pl->samples.p, (float*)pl->logmel.p, n, kp.preemph_b1));
+    HIP_TRY(hipMemcpyAsync(out_y, pl->logmel.p, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+  }
+  ClipInfo ci{};
+  HIP_TRY(hipMemcpyAsync(&ci, pl->info.p, sizeof(ClipInfo), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  // T is about the MFCC stage; preprocess_audio itself only fails on < 2 samples / non-finite input
+  *start = ci.start; *end = ci.end;
+  *status = (n < 2) ? AFX_CLIP_TOO_SHORT : (ci.nonfinite ? AFX_CLIP_NONFINITE : AFX_CLIP_OK);
+  return AFX_OK;
+}
+
+// ---- harmonic-percussive separation (librosa.effects.hpss / harmonic) and the harmonic features -----------------------
+extern "C" int afx_hpss_batch(afx_plan* pl, const void* samples, int sample_fmt, int mem_kind,
+                              const int64_t* offsets, const int64_t* lengths, int n_clips, int flags,
+                              float* out_harm, float* out_perc, double* out_stats,
+                              float* out_spec, const int64_t* spec_off, int32_t* out_status) {
+  const bool sd = (flags & AFX_HPSS_STORE_SPEC) != 0;
+  if (n_clips > 0 && !out_status) return null_arg("afx_hpss_batch");
+  int rc = check_batch_args("afx_hpss_batch", pl, samples, sample_fmt, mem_kind, offsets, lengths, n_clips, true);
+  if (rc != AFX_OK) return rc;
+  if (pl->p.n_fft != 2048 || pl->p.hop != 512 || pl->p.window != AFX_WINDOW_HANN || !pl->use_f3) {
+    set_error("afx_hpss_batch: the plan must have frame_length 2048, hop_length 512 and the Hann window (librosa's defaults)");
+    return AFX_ERR_UNSUPPORTED;
+  }
+  if (flags & AFX_FLAG_TRIM) { set_error("afx_hpss_batch: trim is not applied here; pass the preprocessed signal"); return AFX_ERR_UNSUPPORTED; }
+  if (flags & ~(AFX_FLAG_PREEMPH | AFX_FLAG_TRIM | AFX_HPSS_STORE_SPEC)) { set_error("afx_hpss_batch: unknown flag"); return AFX_ERR_INVALID; }
+  if (sd && n_clips > 0 && (!out_spec || !spec_off)) { set_error("afx_hpss_batch: AFX_HPSS_STORE_SPEC needs out_spec and spec_off"); return AFX_ERR_INVALID; }
+  if ((rc = check_clip_ranges("afx_hpss_batch", offsets, lengths, sd ? spec_off : nullptr, n_clips, INT64_MAX / 4)) != AFX_OK) return rc;
+  const double nan = std::nan("");
+  for (int i = 0; i < n_clips; ++i) {
+    out_status[i] = lengths[i] == 0 ? AFX_CLIP_TOO_SHORT : AFX_CLIP_OK;
+    if (out_stats) for (int k = 0; k < 4; ++k) out_stats[4 * i + k] = nan;
+  }
+  if (n_clips == 0) return AFX_OK;
+  // the centroid runs k_frames3s<DESC>, which also forms the contrast bands; below 12.8 kHz they do not exist and are
+  // replaced by a harmless single bin (only the centroid is read here)
+  SpecBands sb{};
+  if (out_stats && !spectral_bands(pl->p.sr, sb)) {
+    sb = SpecBands{};
+    for (int k = 0; k < 8; ++k) { sb.lo[k] = 0; sb.hi[k] = 0; sb.cnt[k] = 1; }
+    sb.hz_per_bin = (float)((double)pl->p.sr / 2048.0); sb.roll_percent = 0.85f;
+  }
+  if ((rc = begin_plan_call("afx_hpss_batch", pl)) != AFX_OK) return rc;
+  hipStream_t s = pl->ctx->stream;
+  const bool want_p = out_perc != nullptr;
+  const int nsig = want_p ? 3 : 2;                  // y, h (, p) and X, Yh (, Yp)
+  const size_t esz = sample_fmt == AFX_FMT_S16 ? 2 : 4;
+  const int64_t budget = dev_env().hpss_budget;
+  const HpssTabs tb{pl->f3.window, pl->f3.w1024, pl->f3.w2048};
+  std::vector<HpssClip> recs;
+  std::vector<int> idx;
+  std::vector<int64_t> h_off, h_len, d_off;
+  std::vector<uint32_t> h_bad;
+  std::vector<double> h_stats;
+  for (int c0 = 0; c0 < n_clips;) {
+    // one chunk: as many clips as the workspace budget holds (at least one); zero-length clips take no work
+    recs.clear(); idx.clear();
+    int64_t frames = 0, ysz = 0, specf = 0, bytes = 0, lo = INT64_MAX, hi = 0, max_len = 0;
+    int tiles = 0;
+    int c1 = c0;
+    for (; c1 < n_clips && (int)recs.size() < 32768; ++c1) {
+      const int64_t L = lengths[c1];
+      if (L == 0) continue;
+      const int64_t T = 1 + L / 512, nt = (T + kHpssTile - 1) / kHpssTile;
+      const int64_t pb = T * kHpssPitch * 8 * nsig + L * 4 * nsig + (mem_kind == AFX_MEM_HOST ? L * (int64_t)esz : 0) +
+                         T * kSpecFloats * 4 + (sd ? 3 * kHpssBins * T * 4 : 0) + 128;
+      if (!recs.empty() && (bytes + pb > budget || tiles + nt > 65535)) break;
+      HpssClip r{};
+      r.in_off = offsets[c1]; r.y_off = ysz; r.len = L; r.frame_base = frames; r.spec_off = specf;
+      r.T = (int32_t)T; r.tile_base = tiles;
+      recs.push_back(r); idx.push_back(c1);
+      frames += T; ysz += L; specf += sd ? 3 * kHpssBins * T : 0; tiles += (int)nt; bytes += pb;
+      lo = std::min(lo, offsets[c1]); hi = std::max(hi, offsets[c1] + L); max_len = std::max(max_len, L);
+    }
+    const int n = (int)recs.size();
+    if (n == 0) { c0 = c1; continue; }
+    const void* d_in = samples;
+    if (mem_kind == AFX_MEM_HOST) {
+      if ((rc = ensure(pl->samples, (size_t)(hi - lo) * esz + 16)) != AFX_OK) return rc;
+      HIP_TRY(hipMemcpyAsync(pl->samples.p, (const char*)samples + (size_t)lo * esz, (size_t)(hi - lo) * esz, hipMemcpyHostToDevice, s));
+      for (HpssClip& r : recs) r.in_off -= lo;
+      d_in = pl->samples.p;
+    }
+    const size_t spec_bytes = (size_t)frames * kHpssPitch * sizeof(float2), sig_bytes = (size_t)ysz * sizeof(float) + 64;
+    if ((rc = ensure(pl->hp_clips, n * sizeof(HpssClip))) != AFX_OK) return rc;
+    if ((rc = ensure(pl->hp_bad, n * sizeof(uint32_t))) != AFX_OK) return rc;
+    if ((rc = ensure(pl->hp_y, sig_bytes)) != AFX_OK) return rc;
+    if ((rc = ensure(pl->hp_h, sig_bytes)) != AFX_OK) return rc;
+    if ((rc = ensure(pl->hp_x, spec_bytes)) != AFX_OK) return rc;
+    if ((rc = ensure(pl->hp_yh, spec_bytes)) != AFX_OK) return rc;
+    if (want_p) {
+      if ((rc = ensure(pl->hp_p, sig_bytes)) != AFX_OK) return rc;
+      if ((rc = ensure(pl->hp_yp, spec_bytes)) != AFX_OK) return rc;
+    }
+    if (sd && (rc = ensure(pl->hp_spec, (size_t)specf * sizeof(float))) != AFX_OK) return rc;
+    if (out_stats && (rc = ensure(pl->hp_stats, (size_t)n * 4 * sizeof(double))) != AFX_OK) return rc;
+    const HpssClip* d_clips = (const HpssClip*)pl->hp_clips.p;
+    uint32_t* d_bad = (uint32_t*)pl->hp_bad.p;
+    float* d_y = (float*)pl->hp_y.p;
+    float* d_h = (float*)pl->hp_h.p;
+    float* d_p = want_p ? (float*)pl->hp_p.p : nullptr;
+    float2* d_yp = want_p ? (float2*)pl->hp_yp.p : nullptr;
+    HIP_TRY(hipMemcpyAsync(pl->hp_clips.p, recs.data(), n * sizeof(HpssClip), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemsetAsync(d_bad, 0, n * sizeof(uint32_t), s));
+    HIP_TRY(launch_hpss_prep(s, d_in, sample_fmt, flags, pl->kp.preemph_b1, d_clips, n, max_len, d_y, d_bad));
+    HIP_TRY(launch_hpss_stft(s, d_y, d_clips, d_bad, n, frames, tb, (float2*)pl->hp_x.p));
+    HIP_TRY(launch_hpss_mask(s, (const float2*)pl->hp_x.p, d_clips, n, tiles, (float2*)pl->hp_yh.p, d_yp,
+                             sd ? (float*)pl->hp_spec.p : nullptr));
+    HIP_TRY(launch_hpss_irfft(s, (float2*)pl->hp_yh.p, d_yp, frames, tb));
+    HIP_TRY(launch_hpss_ola(s, (const float2*)pl->hp_yh.p, d_yp, d_clips, n, max_len, tb, d_h, d_p));
+    if (out_stats) {
+      // spectral_centroid(y=h): k_frames3s<DESC> over the device-resident h, then the per-clip reduction
+      h_off.resize(n); h_len.resize(n); d_off.resize(n);
+      for (int q = 0; q < n; ++q) { h_off[q] = recs[q].y_off; h_len[q] = recs[q].len; d_off[q] = kSpecFloats * recs[q].frame_base; }
+      if ((rc = prepare_descriptors(pl, h_off.data(), h_len.data(), n)) != AFX_OK) return rc;
+      KParams kp = pl->kp;
+      kp.flags = 0; kp.fmt = AFX_FMT_F32;
+      if ((rc = run_spectral(pl, d_h, n, kp, d_off.data(), (size_t)frames * kSpecFloats, sb)) != AFX_OK) return rc;
+      HIP_TRY(launch_hpss_stats(s, d_y, d_h, d_clips, n, (const float*)pl->frames.p, (const int64_t*)pl->frame_offs.p,
+                                (double*)pl->hp_stats.p));
+      h_stats.resize((size_t)n * 4);
+      HIP_TRY(hipMemcpyAsync(h_stats.data(), pl->hp_stats.p, (size_t)n * 4 * sizeof(double), hipMemcpyDeviceToHost, s));
+    }
+    // the signals: one copy when the caller's layout is the chunk's (packed clips in order), else one per clip
+    bool packed = true;
+    for (int q = 0; q < n && packed; ++q) packed = offsets[idx[q]] - offsets[idx[0]] == recs[q].y_off;
+    for (int which = 0; which < 2; ++which) {
+      float* dst = which ? out_perc : out_harm;
+      const float* src = which ? d_p : d_h;
+      if (!dst) continue;
+      if (packed) {
+        HIP_TRY(hipMemcpyAsync(dst + offsets[idx[0]], src, (size_t)ysz * sizeof(float), hipMemcpyDeviceToHost, s));
+      } else {
+        for (int q = 0; q < n; ++q)
+          HIP_TRY(hipMemcpyAsync(dst + offsets[idx[q]], src + recs[q].y_off, (size_t)recs[q].len * sizeof(float), hipMemcpyDeviceToHost, s));
+      }
+    }
+    if (sd)
+      for (int q = 0; q < n; ++q)
+        HIP_TRY(hipMemcpyAsync(out_spec + spec_off[idx[q]], (const float*)pl->hp_spec.p + recs[q].spec_off,
+                               (size_t)3 * kHpssBins * recs[q].T * sizeof(float), hipMemcpyDeviceToHost, s));
+    h_bad.resize(n);
+    HIP_TRY(hipMemcpyAsync(h_bad.data(), d_bad, n * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    for (int q = 0; q < n; ++q) {
+      const int i = idx[q];
+      out_status[i] = h_bad[q] ? AFX_CLIP_NONFINITE : AFX_CLIP_OK;
+      if (out_stats && !h_bad[q]) {
+        for (int k = 0; k < 4; ++k) out_stats[4 * i + k] = h_stats[4 * (size_t)q + k];
+        if (recs[q].len < 2) out_stats[4 * i + 2] = out_stats[4 * i + 3] = nan;   // k_frames3s skips clips of one sample
+      }
+    }
+    c0 = c1;
+  }
+  return AFX_OK;
+}

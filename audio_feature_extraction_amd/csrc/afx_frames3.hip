@@ -4,9 +4,10 @@
 //
 // Why a third frame kernel.  tools/micro/valu_rate.hip measured on MI355X that ONE wave issues a vector
 // instruction every ~8 cycles whatever the instruction, and that a SIMD only approaches its packed-f32 rate with
-// four waves resident (4.7 / 3.7 / 3.3 cycles per v_pk_fma_f32 at 2 / 3 / 4 waves).  k_frames2 runs two waves per
+// four waves resident (4.7 / 3.7 / 3.3 cycles per v_pk_fma_f32 at 2 / 3 / 4 waves).  k_frames2 (round 1's
+// 1024 / 256 kernel, since removed) ran two waves per
 // SIMD (204 VGPRs, 78 KB of LDS per 4-wave workgroup, two workgroup barriers per 16 frames) and was measured at
-// ~86 % of that two-wave issue limit: it cannot get faster without more waves or fewer instructions.  This kernel
+// ~86 % of that two-wave issue limit: it could not get faster without more waves or fewer instructions.  This kernel
 // does both:
 //   * every wave is autonomous -- it takes runs of 16-frame blocks (a contiguous share up front, then tickets:
 //     f3_runs_* in afx_frames3_dev.h), walks a block as 8 frame pairs, carries its rows from one block of a clip into

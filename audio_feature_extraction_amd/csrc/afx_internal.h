@@ -32,14 +32,6 @@ struct MelBlocks {
   std::vector<float> koff;      // per (group, row): kmin - kc  (k - kc = koff + 4*blk + q)
 };
 
-// Tap tables for k_frames2's mel stage: filters in groups of eight ("octs"), every filter of an oct padded
-// with zero weights to the oct's longest tap count (a multiple of 4).
-struct MelTaps {
-  std::vector<float> taps;        // per oct: 8 filters x (4 * n4) weights
-  std::vector<int32_t> meta;      // per filter: k0 | n4 << 10 | tap offset << 15
-  bool usable = false;            // false: the generic kernel is used instead
-};
-
 // ortho DCT-II rows as MFMA A-operand images: dctA[(c * (n_mels/4) + i) * 64 + l] =
 // D[16c + (l & 15)][4i + (l >> 4)], zero for coefficient rows >= n_mfcc.
 struct DctBlocks {
@@ -55,7 +47,6 @@ struct HostTables {
   std::vector<float> tw;          // n_fft/2 complex: exp(-2*pi*i*n/(n_fft/2))
   std::vector<float> post;        // n_fft/2 complex: exp(-2*pi*i*k/n_fft)
   MelBlocks mel;
-  MelTaps taps;
   DctBlocks dctb;
   HostF3Mel f3mel;
 };

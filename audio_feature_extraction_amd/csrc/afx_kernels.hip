@@ -1086,474 +1086,6 @@ __global__ __launch_bounds__(256, (NFFT >= 2048 ? 1 : 2)) void k_frames(const vo
   flush_logmel();
 }
 
-// Round 1's 4-wave kernel for 1024 / 256.  Since round 2 the wave-level k_frames3 serves that shape; this one is reachable only
-// through AFX_NO_FRAMES3 and is compiled only into the diagnostic library (make dbg: -DAFX_WITH_FRAMES2), not into libafx.so.
-#ifdef AFX_WITH_FRAMES2
-// ---------------------------------------------------------------------------
-// k_frames2: the n_fft = 1024 kernel.  Differences from the generic k_frames above:
-//   * two real frames ride one 1024-point complex FFT (z = xA + i*xB): X_A[k], X_B[k] follow from
-//     Z[k] and Z[N-k] by adds only -- no split twiddles, and no third ("mirror") exchange, because the
-//     last radix-8 pass gives each lane the butterflies j and 128-j, i.e. both Z[k] and Z[N-k];
-//   * schedule 16 x 8 x 8 on one wave (16 points per lane): two LDS exchanges of 8 KB per frame pair,
-//     image XOR-swizzled a ^ ((a>>4)&15) -> every ds_write_b64 / ds_read_b64 conflict-free;
-//   * no staging pass: a lane fetches 16-byte sample quads straight from global memory and re-cuts them into
-//     rows through the wave's idle exchange image (pre-emphasis with the predecessor read at offset -1 of the
-//     same image); the next block's quads fly under the second pair's FFT and the mel phase;
-//   * the window (x 0.5) sits in 16 registers per lane; the exchange-image slot bases are rebuilt per pair from
-//     an opaque copy of the lane id -- hoisted out of the block loop their XOR variants cost 30 registers, and
-//     the kernel's register budget decides whether the other streams' small kernels fit beside it;
-//   * mel: filters in octs, a lane walks one filter for the two frames of a pair (8-byte PB reads, packed FMAs).
-// LDS: exchange images 32 KB + power-spectrum buffer 36.3 KB + twiddle tables 4.5 KB + mel taps 5.1 KB = 78 KB.
-// ---------------------------------------------------------------------------
-constexpr int kPb2Stride = 18;  // k_frames2's power-spectrum rows: 8 frame pairs + 1 pad pair.  Even, so that a pair is one
-                                // aligned 8-byte access; 18 l mod 32 is a permutation of the even banks for 16 lanes
-struct Lds2 { int ex, pb, t2, t3, tp, total; };         // float offsets
-__host__ __device__ inline Lds2 lds2_layout(int ntaps) {
-  Lds2 L;
-  L.ex = 0;
-  L.pb = L.ex + kWaves * 1024 * 2;
-  L.t2 = L.pb + round4((513 + kPbPadRows) * kPb2Stride);    // pass-2 twiddles: 128 float2
-  L.t3 = L.t2 + 256;                        // last-pass twiddles of butterfly jb: 7 x 64 float2
-  L.tp = L.t3 + 7 * 64 * 2;                 // mel tap weights, oct-padded (sized by the plan's table)
-  L.total = L.tp + round4(ntaps);
-  return L;
-}
-size_t frames2_lds_bytes(int ntaps) { return (size_t)lds2_layout(ntaps).total * sizeof(float); }
-
-// radix-16 DFT in registers as 4 x 4 with the W16 twiddles as constants
-__device__ __forceinline__ void dft16(float2* x) {
-  const float c1 = 0.92387953251128675613f, s1 = 0.38268343236508977173f, h = 0.70710678118654752440f;
-  float2 t[4][4];                       // t[k1][n2]
-#pragma unroll
-  for (int n2 = 0; n2 < 4; ++n2) {
-    float2 a = x[n2], b = x[n2 + 4], c = x[n2 + 8], d = x[n2 + 12];
-    dft4(a, b, c, d);
-    t[0][n2] = a; t[1][n2] = b; t[2][n2] = c; t[3][n2] = d;
-  }
-  // t[k1][n2] *= W16^(n2*k1)
-  auto mulw = [&](float2 v, float wr, float wi) { return make_float2(v.x * wr - v.y * wi, v.x * wi + v.y * wr); };
-  t[1][1] = mulw(t[1][1], c1, -s1);                                   // W16^1
-  t[1][2] = make_float2((t[1][2].x + t[1][2].y) * h, (t[1][2].y - t[1][2].x) * h);   // W16^2 = W8^1
-  t[1][3] = mulw(t[1][3], s1, -c1);                                   // W16^3
-  t[2][1] = make_float2((t[2][1].x + t[2][1].y) * h, (t[2][1].y - t[2][1].x) * h);   // W16^2
-  t[2][2] = mul_mi(t[2][2]);                                          // W16^4 = -i
-  t[2][3] = make_float2((t[2][3].y - t[2][3].x) * h, (-t[2][3].x - t[2][3].y) * h);  // W16^6 = W8^3
-  t[3][1] = mulw(t[3][1], s1, -c1);                                   // W16^3
-  t[3][2] = make_float2((t[3][2].y - t[3][2].x) * h, (-t[3][2].x - t[3][2].y) * h);  // W16^6
-  t[3][3] = mulw(t[3][3], -c1, s1);                                   // W16^9 = -W16^1
-#pragma unroll
-  for (int k1 = 0; k1 < 4; ++k1) {
-    float2 a = t[k1][0], b = t[k1][1], c = t[k1][2], d = t[k1][3];
-    dft4(a, b, c, d);
-    x[k1] = a; x[k1 + 4] = b; x[k1 + 8] = c; x[k1 + 12] = d;
-  }
-}
-
-// DBG: the timing-only ablation switches (AFX_DEBUG_SKIP) are compiled in; the production instantiation does not
-// carry the flag word or its branches
-template <int FMT, bool STAMP, bool DBG>
-__global__ __launch_bounds__(256, 2) void k_frames2(const void* __restrict__ samples,
-                                                    ClipInfo* __restrict__ info,
-                                                    const BlockDesc* __restrict__ blocks, int nblocks,
-                                                    DevTables tb, KParams kp,
-                                                    float* __restrict__ logmel,
-                                                    float* __restrict__ rms_rows,
-                                                    unsigned long long* __restrict__ stamps) {
-  constexpr int N = 1024, NB = 513;
-  unsigned long long st_sum[ST_COUNT] = {}, st_prev = 0;
-  auto stamp = [&](int ph) {
-    if constexpr (STAMP) {
-      __builtin_amdgcn_sched_barrier(0);
-      const unsigned long long t = __builtin_amdgcn_s_memtime();
-      __builtin_amdgcn_s_waitcnt(0xC07F);
-      __builtin_amdgcn_sched_barrier(0);
-      if (ph >= 0) st_sum[ph] += t - st_prev;
-      st_prev = t;
-    }
-  };
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  const Lds2 L = lds2_layout(tb.mel_ntaps);
-  const int hop = kp.hop, M = kp.n_mels;
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  float2* const EX = reinterpret_cast<float2*>(smem + L.ex) + wave * 1024;
-  float* const PB = smem + L.pb;
-  float2* const T2 = reinterpret_cast<float2*>(smem + L.t2);
-  float2* const T3 = reinterpret_cast<float2*>(smem + L.t3);
-  float* const TP = smem + L.tp;
-
-  // ---- once per workgroup: tables -> LDS, per-lane twiddles -> registers
-  for (int i = tid; i < kPbPadRows * kPb2Stride; i += 256) PB[NB * kPb2Stride + i] = 0.f;
-  const float2* w1024 = reinterpret_cast<const float2*>(tb.post);      // exp(-2 pi i k / 1024), k < 512
-  auto W = [&](int m) {                                                  // W_1024^m, 0 <= m < 1024
-    const float2 v = w1024[m & 511];
-    return (m & 512) ? make_float2(-v.x, -v.y) : v;
-  };
-  if (tid < 128) T2[tid] = W(8 * (tid >> 4) * (tid & 15));              // pass-2 twiddles W_128^(c*r) at [r*16 + c]: a row per r,
-                                                                         // so the 16 distinct c of a wave read 128 contiguous bytes
-  float wreg[16];                          // this lane's 16 window values (w[n] = w[N - n]) x 0.5: the A/B split then needs no 1/2
-#pragma unroll
-  for (int u = 0; u < 16; ++u) wreg[u] = 0.5f * tb.window[u < 8 ? lane + 64 * u : (64 - lane) + 64 * (15 - u)];
-  const int ja = lane, jb = lane ? 128 - lane : 64;                      // last-pass butterflies of this lane
-  float2 tw3a[7];                                                        // butterfly ja: registers; jb: LDS table
-#pragma unroll
-  for (int r = 1; r < 8; ++r) tw3a[r - 1] = W(ja * r);
-  if (tid < 64) {
-#pragma unroll
-    for (int r = 1; r < 8; ++r) T3[(r - 1) * 64 + tid] = W(jb * r);
-  }
-  for (int i = tid; i < tb.mel_ntaps; i += 256) TP[i] = tb.mel_taps[i];
-  // exchange-image slots (see header): all per-lane bases
-
-  // mel octs (8 filters) of this wave: oct NO-1 - (4*it + (it odd ? 3 - wave : wave)), it = 0..3 -- a snake over the
-  // octs from the widest down, which balances the four waves because tap counts grow with the filter index.
-  // Computed where used from `wave` (never kept per oct: that would cost scalar registers).
-  constexpr int kOctsPerWave = kMelMaxOcts / 4;
-  const int NO = (M + 7) >> 3;
-  auto oct_of = [&](int wv, int it) { return NO - 1 - (4 * it + ((it & 1) ? 3 - wv : wv)); };
-  const bool pre = (kp.flags & AFX_FLAG_PREEMPH) != 0;
-  const float b1 = kp.preemph_b1;
-
-  auto fetch_desc = [&](int b) -> int {
-    const int bb = b < nblocks ? b : nblocks - 1;
-    return reinterpret_cast<const int*>(blocks + bb)[lane & 15];
-  };
-  auto resolve = [&](int w, int b) -> BlkCtx {
-    BlkCtx c;
-    auto rl = [&](int i) { return __builtin_amdgcn_readlane(w, i); };
-    auto rl64 = [&](int i) { return (int64_t)(((uint64_t)(uint32_t)rl(i + 1) << 32) | (uint32_t)rl(i)); };
-    c.sample_base = rl64(0); c.frame_slot = rl64(2); c.clip_off = rl64(4);
-    c.keep_lo = rl(6); c.keep_hi = rl(7); c.have_lo = rl(8); c.have_hi = rl(9);
-    c.clip = rl(10); c.t0 = 0; c.T = rl(12) - rl(11);     // only T - t0 (frames left from this block on) is used here
-    c.active = (b < nblocks) && rl(13) != 0;
-    c.interior = false;
-    return c;
-  };
-
-  // deferred log-mel stores (see k_frames)
-  float2 lmh[kOctsPerWave];                 // log-mel of this lane's filter for its two frames, per oct
-  bool pend = false;
-  float pend_lmax = -INFINITY;
-  int64_t pend_slot = 0;
-  int pend_t0 = 0, pend_T = 0, pend_clip = 0;
-  auto flush_logmel = [&]() {
-    if (!pend) return;
-    pend = false;
-    int lane_f = lane;
-    asm volatile("" : "+v"(lane_f));
-    const int fp2 = (lane_f & 7) * 2, j8 = lane_f >> 3;               // frames fp2, fp2 + 1; filter j8 of the oct
-    const bool v0 = (pend_t0 + fp2) < pend_T, v1 = (pend_t0 + fp2 + 1) < pend_T;
-    // tile layout [mel/4][frame][mel%4]
-    float* tile = logmel + pend_slot * (int64_t)M + (j8 >> 2) * 64 + fp2 * 4 + (j8 & 3);
-    int wv = wave;
-    asm volatile("" : "+s"(wv));
-#pragma unroll
-    for (int i = 0; i < kOctsPerWave; ++i) {
-      const int o = oct_of(wv, i);
-      if (o >= 0 && o * 8 + j8 < M) {
-        if (v0) tile[o * 128] = lmh[i].x;
-        if (v1) tile[o * 128 + 4] = lmh[i].y;
-      }
-    }
-    const float mx = wave_max(pend_lmax);
-    if (lane_f == 0 && mx > -INFINITY) atomicMax(&info[pend_clip].lmax_ord, f2ord(mx));
-  };
-
-  // ---- sample rows.  A lane holds samples l + 64u ("row" u).  hop = 256 = 4 rows, so frame B of a pair is
-  // frame A shifted by 4 rows and the wave's second pair starts 8 rows after the first: one window of
-  // 20 rows serves pair 0, 12 of them plus 8 new rows serve pair 1.  Rows are fetched raw (next block's
-  // 20 rows under the second pair's FFT and the mel phase; the 8 new rows under the first pair's FFT),
-  // pre-emphasised once in place, and shared by the two frames of a pair.
-  // Fetch: 16-byte loads (the texture-address unit charges per instruction, ~16 cycles per wave, whatever
-  // the width): lane l takes samples 4l..4l+3 of each 256-sample chunk -- 5 chunks for a 20-row window,
-  // 2 for the 8 new rows -- and the rows are re-cut through this wave's idle exchange image:
-  // written as 16-byte quads at float offset 4, read back as rows (offset 4) and as their left
-  // neighbours (offset 3; slot 3 holds the sample before the window).  S16 clips fetch 8 bytes per quad.
-  float rows[20], inc[8];
-  float4 qrows[5], qinc[2];
-  float np_rows = 0.f, np_inc = 0.f;
-  bool rows_raw = false, inc_raw = false;              // false: the pair is an edge pair (clamped path)
-  auto raw_ld = [&](int64_t idx) -> float {            // one converted sample (edge path, predecessors)
-    if constexpr (FMT == AFX_FMT_S16) return (float)((const int16_t*)samples)[idx] * (1.0f / 32768.0f);
-    else return ((const float*)samples)[idx];
-  };
-  auto quad_ld = [&](int64_t idx) -> float4 {          // 4 consecutive samples, idx % 4 == 0
-    if constexpr (FMT == AFX_FMT_S16) {
-      const int2 q = *reinterpret_cast<const int2*>((const int16_t*)samples + idx);
-      const float sc = 1.0f / 32768.0f;
-      return make_float4((float)(short)(q.x & 0xffff) * sc, (float)(short)(q.x >> 16) * sc,
-                         (float)(short)(q.y & 0xffff) * sc, (float)(short)(q.y >> 16) * sc);
-    } else return *reinterpret_cast<const float4*>((const float*)samples + idx);
-  };
-  auto pair_is_interior = [&](const BlkCtx& c, int fl) -> bool {       // both frames: all samples and their
-    const int j0 = fl * hop, j1 = j0 + hop + N;                        // predecessors exist and are kept,
-    return (j0 - 1 >= c.have_lo) && (j1 <= c.have_hi) && (j0 >= c.keep_lo) && (j1 <= c.keep_hi) &&
-           ((c.sample_base & 3) == 0);                                 // and the quads are aligned
-  };
-  auto issue_rows = [&](const BlkCtx& c) {             // first pair of block c: rows 0..19
-    rows_raw = c.active && pair_is_interior(c, wave * 4);
-    if (rows_raw && !(DBG && (kp.flags & 0x100))) {             // 0x100: timing-only ablation (stale registers)
-      const int64_t ba = c.sample_base + (int64_t)(wave * 4) * hop;
-#pragma unroll
-      for (int ch = 0; ch < 5; ++ch) qrows[ch] = quad_ld(ba + 4 * lane + 256 * ch);
-      np_rows = raw_ld(ba - 1);                        // wave-uniform address
-    }
-  };
-  auto issue_inc = [&](const BlkCtx& c) {              // second pair: its 8 new rows (20..27 of the window)
-    inc_raw = pair_is_interior(c, wave * 4 + 2);
-    if (inc_raw && !(DBG && (kp.flags & 0x100))) {
-      const int64_t ba = c.sample_base + (int64_t)(wave * 4) * hop + 64 * 20;
-#pragma unroll
-      for (int ch = 0; ch < 2; ++ch) qinc[ch] = quad_ld(ba + 4 * lane + 256 * ch);
-      np_inc = raw_ld(ba - 1);
-    }
-  };
-  float* const XB = reinterpret_cast<float*>(EX);
-  // quads q[0..NCH) + predecessor p0 -> rows r[0..4*NCH), pre-emphasised when `pre`
-  auto cut_rows = [&](const float4* q, float p0, float* r, auto NCHt) {
-    constexpr int NCH = decltype(NCHt)::value, NR = 4 * NCH;
-#pragma unroll
-    for (int ch = 0; ch < NCH; ++ch) *reinterpret_cast<float4*>(XB + 4 + 4 * lane + 256 * ch) = q[ch];
-    XB[3] = p0;
-    AFX_CBARRIER();
-    float prev[NR];
-#pragma unroll
-    for (int u = 0; u < NR; ++u) { r[u] = XB[4 + 64 * u + lane]; prev[u] = XB[3 + 64 * u + lane]; }
-    AFX_CBARRIER();
-    if (pre) {
-#pragma unroll
-      for (int u = 0; u < NR; ++u) r[u] = preemph1(r[u], prev[u], b1);
-    }
-  };
-  auto edge_sample = [&](const BlkCtx& c, int j) -> float {            // pre-emphasised, trim-masked sample j
-    const int lo = c.have_lo, hi = c.have_hi - 1;
-    const int jc = j < lo ? lo : (j > hi ? hi : j), jp = (j - 1) < lo ? lo : ((j - 1) > hi ? hi : (j - 1));
-    const float y = (jc == j) ? raw_ld(c.sample_base + jc) : 0.f;
-    const float yp = (jp == j - 1) ? raw_ld(c.sample_base + jp) : 0.f;
-    float v = y;
-    if (pre) {
-      v = preemph1(y, yp, b1);
-      if (j == lo) v = preemph0(raw_ld(c.clip_off), raw_ld(c.clip_off + 1));   // clip sample 0
-    }
-    return (j >= c.keep_lo && j < c.keep_hi) ? v : 0.f;
-  };
-
-  // ---- one pair: z = w*yA + i*w*yB -> 1024-point FFT -> |X_A|^2, |X_B|^2 into PB columns flA, flA+1
-  auto fft_pair = [&](float2 (&v)[16], int flA) {
-    stamp(ST_STAGE);
-    // exchange-image slots, rebuilt per pair from an opaque copy of the lane id: kept across the block loop they
-    // would hold five registers that the frame kernel's 224-register budget does not have
-    int ln = lane;
-    asm volatile("" : "+v"(ln));
-    const int sA1 = 16 * ln + (ln & 15);
-    const int sR1 = ln ^ (ln >> 4);
-    const int sW2a = 128 * (ln >> 4) + ((ln & 15) ^ (((ln >> 4) & 1) << 3));
-    const int jbl = ln ? 128 - ln : 64;
-    const int sRa = ln ^ ((ln >> 4) & 7), sRb = jbl ^ ((jbl >> 4) & 7);
-    // pass 1: radix 16 (no twiddles), exchange
-    dft16(v);
-#pragma unroll
-    for (int r = 0; r < 16; ++r) EX[sA1 ^ r] = v[r];
-    AFX_CBARRIER();
-#pragma unroll
-    for (int u = 0; u < 16; ++u) v[u] = EX[(sR1 ^ ((u & 3) << 2)) + 64 * u];
-    AFX_CBARRIER();
-    stamp(ST_BAR1);
-    // pass 2: radix 8 x 2 butterflies (j = lane, lane + 64): inputs u = i + 2r, twiddle W_128^((lane&15) r)
-    {
-      float2 t2v[8];
-#pragma unroll
-      for (int r = 1; r < 8; ++r) t2v[r] = T2[r * 16 + (lane & 15)];
-      float2 xa[8], xb[8];
-#pragma unroll
-      for (int r = 0; r < 8; ++r) { xa[r] = v[2 * r]; xb[r] = v[2 * r + 1]; }
-#pragma unroll
-      for (int r = 1; r < 8; ++r) { xa[r] = cmul(xa[r], t2v[r]); xb[r] = cmul(xb[r], t2v[r]); }
-      dft<8>(xa); dft<8>(xb);
-#pragma unroll
-      // butterfly j = lane + 64 sits 512 slots further (x = (lane >> 4) + 4, same parity; 17 r and sW2a are < 512)
-      for (int r = 0; r < 8; ++r) { EX[sW2a ^ (17 * r)] = xa[r]; EX[(sW2a ^ (17 * r)) + 512] = xb[r]; }
-    }
-    AFX_CBARRIER();
-    stamp(ST_PREFETCH);
-    // pass 3: radix 8, butterflies ja = lane and jb = 128 - lane (lane 0: 0 and 64)
-    float2 A[8], B[8];
-#pragma unroll
-    for (int r = 0; r < 8; ++r) {
-      A[r] = EX[(sRa ^ ((r & 1) << 3)) + 128 * r];
-      B[r] = EX[(sRb ^ ((r & 1) << 3)) + 128 * r];
-    }
-    AFX_CBARRIER();
-#pragma unroll
-    for (int r = 1; r < 8; ++r) { A[r] = cmul(A[r], tw3a[r - 1]); B[r] = cmul(B[r], T3[(r - 1) * 64 + lane]); }
-    dft<8>(A); dft<8>(B);
-    // A[r] = Z[lane + 128 r], B[r] = Z[128 - lane + 128 r]: pair s holds Z[k], Z[N-k] with k = lane + 128 s.
-    // Lane 0 owns the self-mirrored butterflies 0 and 64 and pairs inside them.
-    const bool l0 = lane == 0;
-    float* const pcol = PB + flA;
-    auto power = [&](float2 za, float2 zb, int bin) {
-      const float ar = za.x + zb.x, ai = za.y - zb.y, br = za.y + zb.y, bi = za.x - zb.x;
-      *reinterpret_cast<float2*>(pcol + bin * kPb2Stride) =        // |X_A[bin]|^2, |X_B[bin]|^2: flA is even
-          make_float2(ar * ar + ai * ai, br * br + bi * bi);
-    };
-    auto sel = [&](float2 a, float2 b) { return make_float2(l0 ? b.x : a.x, l0 ? b.y : a.y); };
-    power(sel(A[0], A[1]), sel(B[7], A[7]), l0 ? 128 : lane);
-    power(sel(A[1], A[2]), sel(B[6], A[6]), l0 ? 256 : lane + 128);
-    power(sel(A[2], A[3]), sel(B[5], A[5]), l0 ? 384 : lane + 256);
-    power(sel(A[3], B[0]), sel(B[4], B[7]), l0 ? 64 : lane + 384);
-    power(sel(A[4], B[1]), sel(B[3], B[6]), l0 ? 192 : 512 - lane);
-    power(sel(A[5], B[2]), sel(B[2], B[5]), l0 ? 320 : 384 - lane);
-    power(sel(A[6], B[3]), sel(B[1], B[4]), l0 ? 448 : 256 - lane);
-    power(sel(A[7], A[0]), sel(B[0], A[0]), l0 ? 0 : 128 - lane);
-    if (l0) {                                              // Nyquist bin from Z[512] = A[4]
-      *reinterpret_cast<float2*>(pcol + 512 * kPb2Stride) = make_float2(4.f * A[4].x * A[4].x, 4.f * A[4].y * A[4].y);
-    }
-    AFX_CBARRIER();
-    stamp(ST_FFT);
-  };
-  // window the pair whose frame A is rows y[0..15] and frame B rows y[4..19] (RMS rows come from k_trim_decide)
-  auto make_z = [&](const float (&y)[20], float2 (&v)[16], const BlkCtx& c, int flA) {
-#pragma unroll
-    for (int u = 0; u < 16; ++u) v[u] = make_float2(wreg[u] * y[u], wreg[u] * y[u + 4]);
-  };
-
-  // experiment (AFX_DEBUG_SKIP bits 0x1000 / 0x2000): start half of the workgroups ~half a block late
-  if (DBG && (((kp.flags & 0x1000) && blockIdx.x >= gridDim.x / 2) || ((kp.flags & 0x2000) && (blockIdx.x & 1)))) {
-    for (int i = 0; i < 2; ++i) __builtin_amdgcn_s_sleep(127);
-  }
-  BlkCtx cur = resolve(fetch_desc(blockIdx.x), blockIdx.x);
-  int dnext = fetch_desc(blockIdx.x + gridDim.x);
-  issue_rows(cur);
-  AFX_LDS_BARRIER();
-
-  for (int b = blockIdx.x; b < nblocks; b += gridDim.x) {
-    stamp(-1);
-    const BlkCtx nxt = resolve(dnext, b + gridDim.x);
-    dnext = fetch_desc(b + 2 * gridDim.x);
-
-    if (cur.active && !(DBG && (kp.flags & 0x200))) {
-      const int fl0 = wave * 4;
-      float2 v[16];
-      // ---- pair 0 (frames fl0, fl0+1): rows 0..19
-      if (rows_raw) {
-        cut_rows(qrows, np_rows, rows, std::integral_constant<int, 5>());
-      } else {
-        // edge pair (clip start/end, trimmed span): clamped loads in a rolled loop (low register
-        // pressure, rare), parked in the exchange image and read back with static row indices
-#pragma unroll 1
-        for (int u = 0; u < 20; ++u) XB[64 * u + lane] = edge_sample(cur, fl0 * hop + lane + 64 * u);
-        AFX_CBARRIER();
-#pragma unroll
-        for (int u = 0; u < 20; ++u) rows[u] = XB[64 * u + lane];
-        AFX_CBARRIER();
-      }
-      stamp(ST_X0);
-      make_z(rows, v, cur, fl0);
-      stamp(ST_X1);
-      flush_logmel();                        // older than every load issued from here on
-      stamp(ST_X2);
-      issue_inc(cur);
-      fft_pair(v, fl0);
-      // ---- pair 1 (frames fl0+2, fl0+3): rows 8..27 = 12 kept rows + the 8 fetched ones
-      float r1[20];
-#pragma unroll
-      for (int u = 0; u < 12; ++u) r1[u] = rows[u + 8];
-      if (inc_raw) {
-        cut_rows(qinc, np_inc, inc, std::integral_constant<int, 2>());
-#pragma unroll
-        for (int u = 0; u < 8; ++u) r1[12 + u] = inc[u];
-      } else {
-#pragma unroll 1
-        for (int u = 0; u < 20; ++u) XB[64 * u + lane] = edge_sample(cur, (fl0 + 2) * hop + lane + 64 * u);
-        AFX_CBARRIER();
-#pragma unroll
-        for (int u = 0; u < 20; ++u) r1[u] = XB[64 * u + lane];
-        AFX_CBARRIER();
-      }
-      stamp(ST_X0);
-      make_z(r1, v, cur, fl0 + 2);
-      stamp(ST_X1);
-      issue_rows(nxt);                       // next block's first pair lands under this FFT and the mel phase
-      fft_pair(v, fl0 + 2);
-    } else {
-      flush_logmel();
-      issue_rows(nxt);
-    }
-    stamp(ST_FFT);
-    AFX_LDS_BARRIER();
-    stamp(ST_BAR2);
-
-    // ---- mel filterbank + dB on the vector pipe.  A mel row touches only its own ~2..60 bins, so as a matrix
-    // product it is >85 % zeros even block-sparse; here every multiply is a real tap.  Filters are taken eight
-    // at a time (an oct): lane (pair fp, j) walks the taps of filter 8*oct + j for the frames 2fp and 2fp+1 -- one
-    // 8-byte P read (both frames), a quarter of a 16-byte weight read (shared by the oct's 8 lanes of that filter)
-    // and one packed FMA per tap.
-    const bool mel_on = cur.active && !(DBG && (kp.flags & 0x400));
-    if (mel_on) {
-      int lane_m = lane;
-      asm volatile("" : "+v"(lane_m));
-      const int fp2 = (lane_m & 7) * 2, j8 = lane_m >> 3;
-      const bool v0 = (cur.t0 + fp2) < cur.T, v1 = (cur.t0 + fp2 + 1) < cur.T;
-      float lmax = -INFINITY;
-      int wv = wave;
-      asm volatile("" : "+s"(wv));
-      int mw[kOctsPerWave];
-#pragma unroll
-      for (int it = 0; it < kOctsPerWave; ++it) { const int o = oct_of(wv, it); mw[it] = o >= 0 ? tb.mel_meta[8 * o + j8] : 0; }
-#pragma unroll
-      for (int it = 0; it < kOctsPerWave; ++it) {
-        const int o = oct_of(wv, it);
-        if (o >= 0) {
-          const int n4 = __builtin_amdgcn_readfirstlane(mw[it] >> 10) & 31;   // same for the eight filters of an oct, >= 1
-          const float* p = PB + (mw[it] & 1023) * kPb2Stride + fp2;
-          const float4* w = reinterpret_cast<const float4*>(TP + (mw[it] >> 15));
-          float2 a0 = make_float2(0.f, 0.f), a1 = make_float2(0.f, 0.f);
-          auto ld = [&](float2 (&xx)[4], float4& c, int bi) {
-#pragma unroll
-            for (int t = 0; t < 4; ++t) xx[t] = *reinterpret_cast<const float2*>(p + (4 * bi + t) * kPb2Stride);
-            c = w[bi];
-          };
-          auto fm = [&](const float2 (&xx)[4], const float4& c) {
-            a0.x = fmaf(c.x, xx[0].x, a0.x); a0.y = fmaf(c.x, xx[0].y, a0.y);
-            a1.x = fmaf(c.y, xx[1].x, a1.x); a1.y = fmaf(c.y, xx[1].y, a1.y);
-            a0.x = fmaf(c.z, xx[2].x, a0.x); a0.y = fmaf(c.z, xx[2].y, a0.y);
-            a1.x = fmaf(c.w, xx[3].x, a1.x); a1.y = fmaf(c.w, xx[3].y, a1.y);
-          };
-          float2 x0[4], x1[4];
-          float4 c0, c1;
-          ld(x0, c0, 0);
-          int bi = 1;
-          for (; bi + 1 < n4; bi += 2) {                    // two batches per turn, the next pair in flight
-            ld(x1, c1, bi);
-            fm(x0, c0);
-            ld(x0, c0, bi + 1);
-            fm(x1, c1);
-          }
-          if (bi < n4) { ld(x1, c1, bi); fm(x0, c0); fm(x1, c1); }
-          else fm(x0, c0);
-          const float L0 = 3.01029995663981195f * __builtin_amdgcn_logf(fmaxf(kp.amin, a0.x + a1.x));
-          const float L1 = 3.01029995663981195f * __builtin_amdgcn_logf(fmaxf(kp.amin, a0.y + a1.y));
-          lmh[it] = make_float2(L0, L1);
-          if (o * 8 + j8 < M) {
-            if (v0) lmax = fmaxf(lmax, L0);
-            if (v1) lmax = fmaxf(lmax, L1);
-          }
-        }
-      }
-      pend = true;
-      pend_lmax = lmax; pend_slot = cur.frame_slot; pend_t0 = cur.t0; pend_T = cur.T; pend_clip = cur.clip;
-    }
-    stamp(ST_MEL);
-    AFX_LDS_BARRIER();      // PB is free for the next block's spectra
-    stamp(ST_BAR3);
-    stamp(ST_MELFIN);
-    cur = nxt;
-  }
-  if constexpr (STAMP) { if (lane == 0) for (int i = 0; i < ST_COUNT; ++i) stamps[((size_t)blockIdx.x * kWaves + wave) * ST_COUNT + i] = st_sum[i]; }
-  flush_logmel();
-}
-#endif  // AFX_WITH_FRAMES2
-
 // ---------------------------------------------------------------------------
 // k_dct: clamp at (clip max - top_db), ortho DCT-II on the matrix pipe.
 // One wave per 16-frame log-mel tile: the tile's [mel][16 frames] layout is exactly the
@@ -1862,17 +1394,6 @@ hipError_t launch_trim_decide(hipStream_t s, const ClipDesc* clips, ClipInfo* in
   return hipGetLastError();
 }
 
-bool frames2_eligible(const KParams& kp, const DevTables& tb) {
-#ifndef AFX_WITH_FRAMES2
-  (void)kp; (void)tb;
-  return false;
-#else
-  const int per = kp.hop > 0 ? kp.trim_hop / kp.hop : 0;
-  return kp.n_fft == 1024 && kp.hop == 256 && tb.mel_ntaps > 0 && frames2_lds_bytes(tb.mel_ntaps) <= 80 * 1024 && kp.n_mels <= 128 &&
-         kp.trim_hop % kp.hop == 0 && per >= 1 && per <= 4 && !dev_env().generic_1024;
-#endif
-}
-
 template <int NFFT>
 static hipError_t launch_frames_t(hipStream_t s, const void* samples, ClipInfo* info,
                                   const BlockDesc* blocks, int nblocks, const DevTables& tb, const KParams& kp,
@@ -1900,43 +1421,9 @@ static hipError_t launch_frames_t(hipStream_t s, const void* samples, ClipInfo* 
   return hipGetLastError();
 }
 
-#ifdef AFX_WITH_FRAMES2
-template <int FMT, bool STAMP, bool DBG>
-static hipError_t launch_frames2_t(hipStream_t s, const void* samples, ClipInfo* info, const BlockDesc* blocks,
-                                   int nblocks, const DevTables& tb, const KParams& kp, float* logmel,
-                                   float* rms_rows, int grid, unsigned long long* stamps) {
-  static bool attr_set[64] = {};
-  int dev = 0;
-  hipError_t e = hipGetDevice(&dev);
-  if (e != hipSuccess) return e;
-  if (dev >= 0 && dev < 64 && !attr_set[dev]) {
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_frames2<FMT, STAMP, DBG>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) return e;
-    attr_set[dev] = true;
-  }
-  hipLaunchKernelGGL((k_frames2<FMT, STAMP, DBG>), dim3(grid), dim3(256), frames2_lds_bytes(tb.mel_ntaps), s, samples, info,
-                     blocks, nblocks, tb, kp, logmel, rms_rows, stamps);
-  return hipGetLastError();
-}
-
-#endif  // AFX_WITH_FRAMES2
-
 hipError_t launch_frames(hipStream_t s, const void* samples, ClipInfo* info,
                          const BlockDesc* blocks, int nblocks, const DevTables& tb, const KParams& kp,
                          float* logmel, float* rms_rows, int grid, unsigned long long* stamps) {
-#ifdef AFX_WITH_FRAMES2
-  if (frames2_eligible(kp, tb) && kp.rms_sub > 0) {
-    const bool dbg = (kp.flags & 0x7f00) != 0 || stamps != nullptr;     // ablation switches / stamps: diagnostic instantiations
-#define AFX_F2(FMT)                                                                                              \
-    (stamps ? launch_frames2_t<FMT, true, true>(s, samples, info, blocks, nblocks, tb, kp, logmel, rms_rows, grid, stamps)   \
-            : dbg ? launch_frames2_t<FMT, false, true>(s, samples, info, blocks, nblocks, tb, kp, logmel, rms_rows, grid, stamps)  \
-                  : launch_frames2_t<FMT, false, false>(s, samples, info, blocks, nblocks, tb, kp, logmel, rms_rows, grid, stamps))
-    if (kp.fmt == AFX_FMT_S16) return AFX_F2(AFX_FMT_S16);
-    return AFX_F2(AFX_FMT_F32);
-#undef AFX_F2
-  }
-#endif
   switch (kp.n_fft) {
     case 256:  return launch_frames_t<256>(s, samples, info, blocks, nblocks, tb, kp, logmel, rms_rows, grid, stamps);
     case 512:  return launch_frames_t<512>(s, samples, info, blocks, nblocks, tb, kp, logmel, rms_rows, grid, stamps);

@@ -1,0 +1,167 @@
+// The state behind the opaque handles of include/afx.h (afx_ctx, afx_plan) and the front end every batch entry point
+// shares: argument checks, sample staging, the preprocessing chain, per-frame output ranges.  Internal to libafx.so:
+// included by afx_api.cpp (which defines the helpers), afx_features.cpp and afx_ctx_ops.cpp.
+#pragma once
+#include <algorithm>
+#include <cstdint>
+#include <string>
+#include <utility>
+#include <vector>
+
+#include <hip/hip_runtime.h>
+
+#include "afx_device.h"
+#include "afx_f0.h"
+#include "afx_frames3.h"
+#include "afx_internal.h"
+#include "afx_resample.h"
+
+namespace afx {
+
+struct DevBuf {
+  void* p = nullptr;
+  size_t cap = 0;
+};
+
+}  // namespace afx
+
+using namespace afx;
+
+struct afx_ctx {
+  int device = 0;
+  hipStream_t stream = nullptr;
+  DevBuf dtw_raw, dtw_feats, dtw_norms, dtw_pairs, dtw_codes, dtw_rows, dtw_d, dtw_path, dtw_cost, dtw_status, dtw_len;   // afx_dtw_batch
+  // afx_resample_batch: the tables of the last rate pair (or caller-supplied filter) used, and the staging of host batches
+  struct {
+    bool valid = false, custom = false;
+    int up = 0, down = 0;
+    std::vector<double> taps;        // the caller's filter the tables were built from (custom only)
+    RsTables t;
+  } rs;
+  DevBuf rs_g, rs_tstart, rs_clips, rs_in, rs_out;
+};
+
+struct afx_plan {
+  afx_ctx* ctx = nullptr;
+  int device = 0;             // copy: the plan may be destroyed after its context by a garbage-collected binding
+  afx_params p{};
+  KParams kp{};
+  HostTables ht;
+  DevTables dt{};
+  F3Tables f3{};              // k_frames3 (n_fft 1024 / hop 256): mel schedule + twiddle source
+  bool use_f3 = false;
+  std::vector<void*> table_allocs;
+  DevBuf samples, clips, info, blocks, bsum, logmel, rms, mfcc, frames, frame_offs, stamps;     // statistics go straight to h_pin
+  DevBuf blocks_spec, blockmax, items, n_items;      // speculative pipeline (k_frames3 before the trim decision)
+  std::vector<BlockDesc> h_blocks;     // AFX_HOST_BLOCKS (A/B) only: the block list is built by k_build_blocks3
+  // pinned staging of the clip records: the upload is a true asynchronous copy, and the event tells when the
+  // staging may be rewritten (no stream synchronisation on a batch whose clip lengths are new)
+  ClipDesc* h_clips_pin = nullptr;
+  size_t h_clips_pin_cap = 0;
+  hipEvent_t clips_ev = nullptr;
+  bool clips_ev_pending = false;
+  // extract_f0 (pYIN): tables for the last (fmin, fmax) used and the stage's workspace
+  bool f0_ready = false;
+  double f0_fmin = 0.0, f0_fmax = 0.0;
+  HostF0Tables f0_ht;
+  F0Tables f0_dt{};
+  std::vector<void*> f0_allocs;
+  DevBuf f0_in, f0_ysig, f0_energy, f0_cnt, f0_vp, f0_bin, f0_prob, f0_lprob, f0_lu, f0_ptr, f0_best, f0_states, f0_stats, f0_out, f0_offs;
+  DevBuf hp_clips, hp_y, hp_h, hp_p, hp_x, hp_yh, hp_yp, hp_bad, hp_stats, hp_spec;   // afx_hpss_batch
+  // cached per-batch descriptors
+  std::vector<int64_t> c_off, c_len;
+  std::vector<ClipDesc> h_clips;
+  std::vector<int64_t> h_rebased;   // per-frame output offsets of the pending chunk (source of an asynchronous upload: lives until collect)
+  int nblocks = 0, max_tblocks = 0, max_tmax = 0;
+  int64_t total_tpad = 0, total_tblk = 0;
+  // pinned staging for the small per-call results (a device-to-pageable copy is staged and synchronous)
+  void* h_pin = nullptr;
+  void* h_pin_dev = nullptr;       // the same block as the device addresses it
+  size_t h_pin_cap = 0;
+  int info_clean_n = 0;            // leading clip records (and the counters) known to be zero on the stream
+  // a submitted, not yet collected chunk (afx_extract_submit / afx_extract_collect; afx_extract_batch = both, per chunk)
+  struct Pending {
+    bool active = false;
+    int n = 0;
+    size_t stats_bytes = 0;
+    float* out_stats = nullptr; int32_t* out_status = nullptr; int64_t* out_trim = nullptr; int32_t* out_nframes = nullptr;
+  } pend;
+  hipEvent_t done = nullptr;       // recorded behind the chunk's last copy: collect waits for this chunk, not for the stream
+  volatile unsigned* flag = nullptr;   // host word the device stores the chunk's sequence number to (behind the same copy)
+  unsigned* flag_dev = nullptr;
+  unsigned seq = 0;
+  // timing
+  bool timing = false;
+  bool timing_frames_only = false;   // afx_plan_set_timing(plan, 2): events around the frame kernel only
+  hipEvent_t ev[AFX_K_COUNT][2] = {};
+  bool ev_ready = false;
+  double ms_sum[AFX_K_COUNT] = {};
+  int32_t launches[AFX_K_COUNT] = {};
+  std::vector<std::pair<double, double>> spans[AFX_K_COUNT];   // (start, end) ms on the device's common clock, newest kMaxSpans
+  int n_cu = 256;
+};
+
+// everything below is internal to libafx.so: none of it is exported
+#pragma GCC visibility push(hidden)
+
+#define HIP_TRY(expr)                                                                  \
+  do {                                                                                 \
+    hipError_t e__ = (expr);                                                           \
+    if (e__ != hipSuccess) {                                                           \
+      set_error(std::string(#expr) + ": " + hipGetErrorString(e__));                   \
+      return AFX_ERR_HIP;                                                              \
+    }                                                                                  \
+  } while (0)
+
+inline int ensure(DevBuf& b, size_t bytes) {
+  if (bytes <= b.cap && b.p) return AFX_OK;
+  if (b.p) { (void)hipFree(b.p); b.p = nullptr; b.cap = 0; }
+  size_t want = std::max<size_t>(bytes + bytes / 8, 256);
+  hipError_t e = hipMalloc(&b.p, want);
+  if (e != hipSuccess) {
+    set_error(std::string("hipMalloc(") + std::to_string(want) + "): " + hipGetErrorString(e));
+    b.p = nullptr;
+    return e == hipErrorOutOfMemory ? AFX_ERR_NOMEM : AFX_ERR_HIP;
+  }
+  b.cap = want;
+  return AFX_OK;
+}
+
+inline void release(DevBuf& b) {
+  if (b.p) (void)hipFree(b.p);
+  b.p = nullptr; b.cap = 0;
+}
+
+// ---- the front end of the batch entry points (afx_api.cpp).  who: the entry point's name, in front of every error text ----
+int null_arg(const char* who);       // sets "who: null/invalid argument", returns AFX_ERR_INVALID
+int check_sample_format(const char* who, int sample_fmt, int mem_kind);
+// plan, clip arrays and sample format of a plan-based entry point (its own output pointers are the caller's to check);
+// empty_ok: a batch of no clips may come with null arrays
+int check_batch_args(const char* who, afx_plan* pl, const void* samples, int sample_fmt, int mem_kind,
+                     const int64_t* offsets, const int64_t* lengths, int n_clips, bool empty_ok = false);
+// offsets (and out_offsets, when given) in [0, max_off], lengths in [0, 2^31]
+int check_clip_ranges(const char* who, const int64_t* offsets, const int64_t* lengths, const int64_t* out_offsets, int n_clips,
+                      int64_t max_off);
+// clears a stale HIP error, selects the plan's device, refuses a plan whose submitted batch has not been collected
+int begin_plan_call(const char* who, afx_plan* pl);
+// *d_samples: the caller's buffer if it is device memory, else a copy of [0, highest sample of the batch) in buf
+int stage_samples(afx_plan* pl, DevBuf& buf, const void* samples, int sample_fmt, int mem_kind, const int64_t* offsets,
+                  const int64_t* lengths, int n, const void** d_samples);
+int prepare_descriptors(afx_plan* pl, const int64_t* offsets, const int64_t* lengths, int n);
+// the clips prepare_descriptors saw last: cleared clip records, k_trim_blocks, k_trim_decide and, with f0_prep, the
+// preprocessed signal in pl->f0_ysig
+int run_preprocess(afx_plan* pl, const void* d_samples, int n, const KParams& kp, bool f0_prep);
+// Per-frame output: the chunk's clips occupy [*lo, *hi) of the caller's buffer (per_frame elements per frame).  The device
+// copy holds exactly that range (rebased = offs - *lo), so that a later chunk never touches -- or copies stale device
+// memory over -- an earlier one's rows.  what names the offsets in the error text.
+int rebase_offsets(const afx_plan* pl, const char* what, const int64_t* offs, int n, int64_t per_frame,
+                   std::vector<int64_t>& rebased, int64_t* lo, int64_t* hi);
+// uploads n rebased offsets to d_offs and fills bytes of out with the byte fill
+int upload_frame_range(afx_plan* pl, const int64_t* rebased, int n, DevBuf& d_offs, DevBuf& out, size_t bytes, int fill);
+// k_frames3s<DESC> over a device signal: kSpecFloats per frame into pl->frames (count floats) at the n host offsets
+int run_spectral(afx_plan* pl, const void* d_signal, int n, const KParams& kp, const int64_t* h_offsets, size_t count,
+                 const SpecBands& sb);
+// downloads the clip records (synchronises the stream): AFX_CLIP_NONFINITE or AFX_CLIP_OK per clip
+int statuses_from_info(afx_plan* pl, int n, int32_t* out_status);
+
+#pragma GCC visibility pop

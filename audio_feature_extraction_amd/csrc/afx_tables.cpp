@@ -166,38 +166,6 @@ static void build_mel_blocks(const afx_params& p, const std::vector<float>& W,
   }
 }
 
-static void build_mel_taps(const afx_params& p, const std::vector<float>& W, MelTaps& t) {
-  // Filters are taken eight at a time (an "oct"): in k_frames2's mel walk lane (pair, j) accumulates filter
-  // 8 * oct + j for the two frames of a frame pair, so the eight filters of an oct are padded with zero weights
-  // to the oct's longest tap count (a multiple of 4).
-  const int M = p.n_mels, NB = p.n_fft / 2 + 1, NO = (M + 7) / 8;
-  t.usable = NO <= kMelMaxOcts;
-  t.taps.clear(); t.meta.assign((size_t)NO * 8, 0);
-  for (int o = 0; o < NO; ++o) {
-    int first[8], nnz[8], n4 = 1;                      // the kernel always accumulates the first batch
-    for (int j = 0; j < 8; ++j) {
-      const int m = 8 * o + j;
-      first[j] = 0; nnz[j] = 0;
-      if (m >= M) continue;
-      int f = -1, l = -1;
-      for (int k = 0; k < NB; ++k) if (W[(size_t)m * NB + k] != 0.f) { if (f < 0) f = k; l = k; }
-      if (f >= 0) { first[j] = f; nnz[j] = l - f + 1; }
-      n4 = std::max(n4, (nnz[j] + 3) / 4);
-    }
-    for (int j = 0; j < 8; ++j) {
-      // the padded taps of every filter must stay inside the spectrum buffer's pad rows
-      if (first[j] + 4 * n4 - 1 > NB + kPbPadRows - 1) t.usable = false;
-      const int m = 8 * o + j;
-      const int woff = (int)t.taps.size();
-      if (n4 > 31 || woff >= (1 << 16)) t.usable = false;
-      t.meta[m] = first[j] | (n4 << 10) | (woff << 15);
-      for (int i = 0; i < 4 * n4; ++i)
-        t.taps.push_back((m < M && i < nnz[j]) ? W[(size_t)m * NB + first[j] + i] : 0.f);
-    }
-  }
-  if (t.taps.empty()) t.taps.push_back(0.f);
-}
-
 
 // k_frames3's mel schedule (afx_frames3.h).  Filters sorted by tap count are cut into rounds of 64 / width filters;
 // a dynamic programme picks the widths: a round costs its batches (4 reads + 1 weight read + 4 packed FMAs each)
@@ -371,7 +339,6 @@ void build_host_tables(const afx_params& p, HostTables& t) {
   std::vector<double> mel_f;
   build_mel_dense(p, t.mel_dense, mel_f);
   build_mel_blocks(p, t.mel_dense, mel_f, t.mel);
-  build_mel_taps(p, t.mel_dense, t.taps);
   // wave-level frame kernels: 1024 -> one frame pair per wave (bins as (A, B) pairs), 2048 -> one frame per wave (bins
   // as floats), 512 -> two frame pairs per wave, one per half-wave with half the image each
   if (N == 1024) build_f3_mel(t.mel_dense, M, N / 2 + 1, kF3ExFloats / 2 - 1, 64, 2, t.f3mel);
