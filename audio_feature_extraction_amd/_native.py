@@ -206,6 +206,59 @@ def device_count() -> int:
     return int(lib().afx_device_count())
 
 
+# The front end every batch method shares.  The C side trusts what it is handed: these checks are the only ones.
+def _ptr(a):
+    """Address of an optional array (None: NULL)."""
+    return None if a is None else a.ctypes.data
+
+
+def packed_offsets(counts, align: int = 1) -> np.ndarray:
+    """Where each item starts when items of ``counts`` elements lie one after another, each rounded up to ``align``
+    elements: the exclusive cumulative sum, int64 (empty for no items)."""
+    counts = np.asarray(counts, np.int64).reshape(-1)
+    if align > 1:
+        counts = (counts + (align - 1)) // align * align
+    out = np.zeros(counts.shape[0], np.int64)
+    if counts.shape[0] > 1:
+        np.cumsum(counts[:-1], out=out[1:])
+    return out
+
+
+def _clip_arrays(offsets, lengths):
+    """-> (offsets, lengths, n): contiguous 1-D int64 (an array that already is one is not copied), one entry per clip."""
+    offsets = np.ascontiguousarray(offsets, np.int64).reshape(-1)
+    lengths = np.ascontiguousarray(lengths, np.int64).reshape(-1)
+    n = int(offsets.shape[0])
+    if lengths.shape[0] != n:
+        raise ValueError("offsets and lengths must have one entry per clip")
+    return offsets, lengths, n
+
+
+def _sample_fmt(samples, fmt):
+    """``fmt`` when the caller gave one; else what a numpy array's dtype says (resample_batch's convention)."""
+    if fmt is not None:
+        return fmt
+    if isinstance(samples, np.ndarray):
+        return FMT_S16 if samples.dtype == np.int16 else FMT_F32
+    raise ValueError("fmt is required for device-resident samples")
+
+
+def _sample_source(samples, fmt, offsets, lengths, mem=None):
+    """-> (pointer, MEM_HOST | MEM_DEVICE) of a batch's samples.  ``mem`` None: a numpy array is host memory, anything
+    else a DeviceBuffer or a device address; MEM_HOST / MEM_DEVICE: the caller says which, and only that is taken.
+    A host array must be C-contiguous, of ``fmt``'s dtype, and hold every clip of ``_clip_arrays``' offsets / lengths."""
+    if mem is None:
+        mem = MEM_HOST if isinstance(samples, np.ndarray) else MEM_DEVICE
+    if mem != MEM_HOST:
+        return (samples.ptr if isinstance(samples, DeviceBuffer) else int(samples)), MEM_DEVICE
+    want = np.int16 if fmt == FMT_S16 else np.float32
+    if not isinstance(samples, np.ndarray) or samples.dtype != want or not samples.flags.c_contiguous:
+        raise ValueError(f"samples must be a C-contiguous {want.__name__} array")
+    if offsets.shape[0] and int((offsets + lengths).max()) > samples.size:
+        raise ValueError("a clip extends past the sample buffer")
+    return samples.ctypes.data, MEM_HOST
+
+
 def make_params(sr=22050, n_fft=1024, hop=256, n_mfcc=13, n_mels=128, window="hamming",
                 preemph=0.97, fmin=0.0, fmax=None, htk=False, lifter=0.0) -> Params:
     p = Params()
@@ -243,7 +296,18 @@ def build_mel_schedule(p: Params) -> dict:
             "weights": w, "meta": meta.reshape(rounds, 64)}
 
 
-class DeviceBuffer:
+class _Owner:
+    """Base of the objects that own a native resource: ``close()`` when collected (a failure there, as at interpreter
+    shutdown, is ignored)."""
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class DeviceBuffer(_Owner):
     """HBM allocation owned by a Context (for device-resident batches)."""
 
     def __init__(self, ctx: "Context", nbytes: int):
@@ -262,14 +326,10 @@ class DeviceBuffer:
             lib().afx_free(self.ctx.handle, self.ptr)
             self.ptr = None
 
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
+    close = free
 
 
-class PinnedBuffer:
+class PinnedBuffer(_Owner):
     """Page-locked host memory owned by a Context: ``array(dtype, count)`` is a numpy view of its start.  Uploads from it
     are DMA at link rate (no staging copy by the runtime)."""
 
@@ -292,14 +352,10 @@ class PinnedBuffer:
             lib().afx_host_free(self.ctx.handle, self.ptr)
             self.ptr = None
 
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
+    close = free
 
 
-class Context:
+class Context(_Owner):
     """One HIP device + stream.  Not thread-safe: one per worker thread."""
 
     def __init__(self, device: int = 0):
@@ -314,12 +370,6 @@ class Context:
                 pl.close()
             lib().afx_destroy(self.handle)
             self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def dtw_batch(self, feats, x_off, x_len, y_off, y_len, band_r=None, metric: str = "euclidean",
                   backtrack: bool = True, store_d: bool = False) -> dict:
@@ -347,21 +397,16 @@ class Context:
         path = poff = plen = dmat = doff = None
         if backtrack:
             steps = xl + yl - 1
-            poff = np.zeros(n, np.int64)
-            if n:
-                poff[1:] = np.cumsum(steps)[:-1]
-            path = np.zeros((int(steps.sum()) if n else 0, 2), np.int32)
+            poff = packed_offsets(steps)
+            path = np.zeros((int(steps.sum()), 2), np.int32)
             plen = np.zeros(n, np.int32)
         if store_d:
             cells = xl * yl
-            doff = np.zeros(n, np.int64)
-            if n:
-                doff[1:] = np.cumsum(cells)[:-1]
-            dmat = np.empty(int(cells.sum()) if n else 0, np.float64)
-        ptr = (lambda a: None if a is None else a.ctypes.data)
+            doff = packed_offsets(cells)
+            dmat = np.empty(int(cells.sum()), np.float64)
         _check(lib().afx_dtw_batch(self.handle, feats.ctypes.data, dim, xo.ctypes.data, xl.ctypes.data, yo.ctypes.data,
-                                   yl.ctypes.data, ptr(br), n, DTW_METRICS[metric], flags, cost.ctypes.data,
-                                   status.ctypes.data, ptr(path), ptr(poff), ptr(plen), ptr(dmat), ptr(doff)),
+                                   yl.ctypes.data, _ptr(br), n, DTW_METRICS[metric], flags, cost.ctypes.data,
+                                   status.ctypes.data, _ptr(path), _ptr(poff), _ptr(plen), _ptr(dmat), _ptr(doff)),
                "afx_dtw_batch")
         out = {"cost": cost, "status": status}
         if backtrack:
@@ -378,31 +423,14 @@ class Context:
         ``samples``: numpy int16 / float32 array (host) or a DeviceBuffer / device pointer (then ``fmt`` says which).
         ``out``: None (a new host array), a float32 numpy array, or a DeviceBuffer the result stays in; ``out_offsets``:
         where each clip goes (default: packed with 4-element alignment, as parallel._pack).  Returns out, offsets, lengths."""
-        offsets = np.ascontiguousarray(offsets, np.int64).reshape(-1)
-        lengths = np.ascontiguousarray(lengths, np.int64).reshape(-1)
-        n = int(offsets.shape[0])
-        if lengths.shape[0] != n:
-            raise ValueError("offsets and lengths must have one entry per clip")
+        offsets, lengths, n = _clip_arrays(offsets, lengths)
         if int(sr_in) <= 0 or int(sr_out) <= 0:
             raise ValueError("sample rates must be positive")
-        if isinstance(samples, np.ndarray):
-            if fmt is None:
-                fmt = FMT_S16 if samples.dtype == np.int16 else FMT_F32
-            want = np.int16 if fmt == FMT_S16 else np.float32
-            if samples.dtype != want or not samples.flags.c_contiguous:
-                raise ValueError(f"samples must be C-contiguous {want.__name__}")
-            if n and lengths.min() >= 0 and int((offsets + lengths).max()) > samples.size:
-                raise ValueError("clip extends past the sample buffer")
-            sptr, kind = samples.ctypes.data, MEM_HOST
-        else:
-            if fmt is None:
-                raise ValueError("fmt is required for device-resident samples")
-            sptr, kind = (samples.ptr if isinstance(samples, DeviceBuffer) else int(samples)), MEM_DEVICE
+        fmt = _sample_fmt(samples, fmt)
+        sptr, kind = _sample_source(samples, fmt, offsets, lengths)
         olen = resample_lengths(np.maximum(lengths, 0), sr_in, sr_out)
         if out_offsets is None:
-            out_offsets = np.zeros(n, np.int64)
-            if n:
-                out_offsets[1:] = np.cumsum((olen + 3) // 4 * 4)[:-1]
+            out_offsets = packed_offsets(olen, 4)
         out_offsets = np.ascontiguousarray(out_offsets, np.int64).reshape(-1)
         if out_offsets.shape[0] != n:
             raise ValueError("out_offsets must have one entry per clip")
@@ -422,13 +450,13 @@ class Context:
         if not hasattr(lib(), "afx_resample_batch"):
             raise NotImplementedError("this libafx has no afx_resample_batch")
         _check(lib().afx_resample_batch(self.handle, sptr, int(fmt), kind, offsets.ctypes.data, lengths.ctypes.data, n,
-                                        int(sr_in), int(sr_out), None if tp is None else tp.ctypes.data,
+                                        int(sr_in), int(sr_out), _ptr(tp),
                                         0 if tp is None else int(tp.size), optr, okind, out_offsets.ctypes.data,
                                         got.ctypes.data), "afx_resample_batch")
         return {"out": out, "offsets": out_offsets, "lengths": got}
 
 
-class Plan:
+class Plan(_Owner):
     def __init__(self, ctx: Context, params: Params):
         self.ctx, self.params = ctx, params
         h = C.c_void_p()
@@ -436,17 +464,12 @@ class Plan:
         self.handle = h
         ctx._plans.add(self)
         self.n_stats = 4 * params.n_mfcc + 3
+        self._pending = None                   # (out, keep, want_frames) between extract_submit and extract_collect
 
     def close(self):
         if self.handle:
             lib().afx_plan_destroy(self.handle)
             self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def device_buffer(self, nbytes: int) -> "DeviceBuffer":
         """HBM allocation on this plan's device (the seam parallel.process_files uploads a window through)."""
@@ -479,10 +502,9 @@ class Plan:
         n = min(int(cnt.value), cap)
         return np.stack([st[:n], en[:n]], axis=1)
 
-    def _extract_args(self, samples, offsets, lengths, fmt, want_frames, out):
-        offsets = np.ascontiguousarray(offsets, np.int64)
-        lengths = np.ascontiguousarray(lengths, np.int64)
-        n = int(offsets.shape[0])
+    def _extract_args(self, samples, offsets, lengths, flags, fmt, want_frames, out):
+        offsets, lengths, n = _clip_arrays(offsets, lengths)
+        sptr, kind = _sample_source(samples, fmt, offsets, lengths)
         K, hop = self.params.n_mfcc, self.params.hop
         if out is None:
             out = {
@@ -491,29 +513,14 @@ class Plan:
                 "trim": np.zeros((n, 2), np.int64),
                 "nframes": np.zeros(n, np.int32),
             }
-        if isinstance(samples, np.ndarray):
-            want = np.int16 if fmt == FMT_S16 else np.float32
-            if samples.dtype != want or not samples.flags.c_contiguous:
-                raise ValueError(f"samples must be C-contiguous {want.__name__}")
-            if n and int((offsets + lengths).max()) > samples.size:
-                raise ValueError("clip extends past the sample buffer")
-            sptr, kind = samples.ctypes.data, MEM_HOST
-        else:
-            sptr = samples.ptr if isinstance(samples, DeviceBuffer) else int(samples)
-            kind = MEM_DEVICE
-        fptr = foffs_ptr = None
         frames = foffs = None
         if want_frames:
-            tmax = 1 + lengths // hop
-            rows = 3 * K + 1
-            foffs = np.zeros(n, np.int64)
-            if n:
-                foffs[1:] = np.cumsum(rows * tmax)[:-1]
-            frames = np.zeros(int((rows * tmax).sum()) if n else 0, np.float32)
-            fptr, foffs_ptr = frames.ctypes.data, foffs.ctypes.data
-        args = (self.handle, sptr, int(fmt), kind, offsets.ctypes.data, lengths.ctypes.data, n, int(self._flags),
+            cnt = (3 * K + 1) * (1 + lengths // hop)
+            foffs = packed_offsets(cnt)
+            frames = np.zeros(int(cnt.sum()), np.float32)
+        args = (self.handle, sptr, int(fmt), kind, offsets.ctypes.data, lengths.ctypes.data, n, int(flags),
                 out["stats"].ctypes.data, out["status"].ctypes.data, out["trim"].ctypes.data,
-                out["nframes"].ctypes.data, fptr, foffs_ptr)
+                out["nframes"].ctypes.data, _ptr(frames), _ptr(foffs))
         keep = (samples, offsets, lengths, frames, foffs)       # alive until the call (or the collect) is over
         return args, out, keep
 
@@ -534,8 +541,7 @@ class Plan:
                       fmt=FMT_F32, want_frames: bool = False, out=None):
         """samples: numpy array (host) or DeviceBuffer/int device pointer.  Returns a dict with
         stats [n, 4K+3], status [n], trim [n, 2], nframes [n] (and frames list when asked)."""
-        self._flags = flags
-        args, out, keep = self._extract_args(samples, offsets, lengths, fmt, want_frames, out)
+        args, out, keep = self._extract_args(samples, offsets, lengths, flags, fmt, want_frames, out)
         _check(lib().afx_extract_batch(*args), "afx_extract_batch")
         return self._frames_out(out, keep, want_frames)
 
@@ -544,13 +550,12 @@ class Plan:
         """First half of extract_batch: queues the batch on the context's stream and returns.  extract_collect() waits
         for it and returns the result dict.  Two plans of one context used alternately keep the device busy while
         the host takes one batch's results and submits the next."""
-        self._flags = flags
-        args, out, keep = self._extract_args(samples, offsets, lengths, fmt, want_frames, out)
+        args, out, keep = self._extract_args(samples, offsets, lengths, flags, fmt, want_frames, out)
         _check(lib().afx_extract_submit(*args), "afx_extract_submit")
         self._pending = (out, keep, want_frames)
 
     def extract_collect(self):
-        if getattr(self, "_pending", None) is None:
+        if self._pending is None:
             raise AfxError("extract_collect: nothing submitted")
         out, keep, want_frames = self._pending
         self._pending = None
@@ -561,32 +566,17 @@ class Plan:
                  flags=FLAG_PREEMPH | FLAG_TRIM, fmt=FMT_F32, want_frames: bool = False):
         """extract_f0 (pYIN) of a ragged batch.  Returns stats [n, 4] float64 (f0_mean, f0_std,
         f0_missing_rate, f0_quality), status [n] and, when asked, f0: list of per-frame arrays (NaN = unvoiced)."""
-        offsets = np.ascontiguousarray(offsets, np.int64)
-        lengths = np.ascontiguousarray(lengths, np.int64)
-        n = int(offsets.shape[0])
+        offsets, lengths, n = _clip_arrays(offsets, lengths)
+        sptr, kind = _sample_source(samples, fmt, offsets, lengths)
         out = {"stats": np.zeros((n, 4), np.float64), "status": np.zeros(n, np.int32)}
-        if isinstance(samples, np.ndarray):
-            want = np.int16 if fmt == FMT_S16 else np.float32
-            if samples.dtype != want or not samples.flags.c_contiguous:
-                raise ValueError(f"samples must be C-contiguous {want.__name__}")
-            if n and int((offsets + lengths).max()) > samples.size:
-                raise ValueError("clip extends past the sample buffer")
-            sptr, kind = samples.ctypes.data, MEM_HOST
-        else:
-            sptr = samples.ptr if isinstance(samples, DeviceBuffer) else int(samples)
-            kind = MEM_DEVICE
-        fptr = foffs_ptr = None
         f0 = foffs = None
         if want_frames:
             tmax = 1 + lengths // self.params.hop
-            foffs = np.zeros(n, np.int64)
-            if n:
-                foffs[1:] = np.cumsum(tmax)[:-1]
-            f0 = np.full(int(tmax.sum()) if n else 0, np.nan, np.float64)
-            fptr, foffs_ptr = f0.ctypes.data, foffs.ctypes.data
+            foffs = packed_offsets(tmax)
+            f0 = np.full(int(tmax.sum()), np.nan, np.float64)
         rc = lib().afx_f0_batch(
             self.handle, sptr, int(fmt), kind, offsets.ctypes.data, lengths.ctypes.data, n, int(flags),
-            C.c_double(fmin), C.c_double(fmax), out["stats"].ctypes.data, out["status"].ctypes.data, fptr, foffs_ptr)
+            C.c_double(fmin), C.c_double(fmax), out["stats"].ctypes.data, out["status"].ctypes.data, _ptr(f0), _ptr(foffs))
         _check(rc, "afx_f0_batch")
         if want_frames:
             out["f0_flat"], out["f0_offsets"] = f0, foffs
@@ -594,19 +584,13 @@ class Plan:
 
     def zcr_batch(self, samples, offsets, lengths, flags=FLAG_PREEMPH | FLAG_TRIM, fmt=FMT_F32):
         """Zero-crossing rate per frame (float64) of a ragged host batch: list of arrays, plus status."""
-        offsets = np.ascontiguousarray(offsets, np.int64)
-        lengths = np.ascontiguousarray(lengths, np.int64)
-        n = int(offsets.shape[0])
-        want = np.int16 if fmt == FMT_S16 else np.float32
-        if not isinstance(samples, np.ndarray) or samples.dtype != want or not samples.flags.c_contiguous:
-            raise ValueError(f"samples must be a C-contiguous {want.__name__} array")
+        offsets, lengths, n = _clip_arrays(offsets, lengths)
+        sptr, kind = _sample_source(samples, fmt, offsets, lengths, mem=MEM_HOST)
         tmax = 1 + lengths // self.params.hop
-        zoffs = np.zeros(n, np.int64)
-        if n:
-            zoffs[1:] = np.cumsum(tmax)[:-1]
-        z = np.zeros(int(tmax.sum()) if n else 0, np.float64)
+        zoffs = packed_offsets(tmax)
+        z = np.zeros(int(tmax.sum()), np.float64)
         status = np.zeros(n, np.int32)
-        _check(lib().afx_zcr_batch(self.handle, samples.ctypes.data, int(fmt), MEM_HOST, offsets.ctypes.data,
+        _check(lib().afx_zcr_batch(self.handle, sptr, int(fmt), kind, offsets.ctypes.data,
                                    lengths.ctypes.data, n, int(flags), z.ctypes.data, zoffs.ctypes.data,
                                    status.ctypes.data), "afx_zcr_batch")
         return {"zcr_flat": z, "zcr_offsets": zoffs, "status": status}
@@ -615,19 +599,13 @@ class Plan:
         """Frame-level spectral descriptors of a ragged host batch (plan: frame_length 2048, hop_length 512).  Returns per
         clip a dict: centroid / bandwidth / rolloff (T,) float32, valley / peak (7, T) float32 (spectral_contrast's band
         extremes before the dB difference)."""
-        offsets = np.ascontiguousarray(offsets, np.int64)
-        lengths = np.ascontiguousarray(lengths, np.int64)
-        n = int(offsets.shape[0])
-        want = np.int16 if fmt == FMT_S16 else np.float32
-        if not isinstance(samples, np.ndarray) or samples.dtype != want or not samples.flags.c_contiguous:
-            raise ValueError(f"samples must be a C-contiguous {want.__name__} array")
+        offsets, lengths, n = _clip_arrays(offsets, lengths)
+        sptr, kind = _sample_source(samples, fmt, offsets, lengths, mem=MEM_HOST)
         T = 1 + lengths // self.params.hop
-        doffs = np.zeros(n, np.int64)
-        if n:
-            doffs[1:] = np.cumsum(17 * T)[:-1]
-        d = np.zeros(int((17 * T).sum()) if n else 0, np.float32)
+        doffs = packed_offsets(17 * T)
+        d = np.zeros(int(17 * T.sum()), np.float32)
         status = np.zeros(n, np.int32)
-        _check(lib().afx_spectral_batch(self.handle, samples.ctypes.data, int(fmt), MEM_HOST, offsets.ctypes.data,
+        _check(lib().afx_spectral_batch(self.handle, sptr, int(fmt), kind, offsets.ctypes.data,
                                         lengths.ctypes.data, n, int(flags), d.ctypes.data, doffs.ctypes.data,
                                         status.ctypes.data), "afx_spectral_batch")
         out = []
@@ -643,20 +621,8 @@ class Plan:
         ``samples``: a C-contiguous host array, or with ``mem=MEM_DEVICE`` a device address (int) of ``fmt`` samples.
         Returns status [n] int32 and, as asked, ``harm`` / ``perc`` (lists of float32 arrays), ``stats`` [n, 4] float64
         (sum h^2, sum y^2, mean and std of h's spectral centroid) and ``spec`` (per clip S, Hm, Pm as [3, 1025, T])."""
-        offsets = np.ascontiguousarray(offsets, np.int64).reshape(-1)
-        lengths = np.ascontiguousarray(lengths, np.int64).reshape(-1)
-        n = int(offsets.shape[0])
-        if lengths.shape[0] != n:
-            raise ValueError("offsets and lengths must have one entry per clip")
-        if mem == MEM_HOST:
-            want = np.int16 if fmt == FMT_S16 else np.float32
-            if not isinstance(samples, np.ndarray) or samples.dtype != want or not samples.flags.c_contiguous:
-                raise ValueError(f"samples must be a C-contiguous {want.__name__} array")
-            if n and int((offsets + lengths).max()) > samples.size:
-                raise ValueError("a clip extends past the sample buffer")
-            sptr = samples.ctypes.data
-        else:
-            sptr = int(samples)
+        offsets, lengths, n = _clip_arrays(offsets, lengths)
+        sptr, kind = _sample_source(samples, fmt, offsets, lengths, mem=mem)
         total = int((offsets + lengths).max()) if n else 0
         harm = np.zeros(total, np.float32) if want_harm else None
         perc = np.zeros(total, np.float32) if want_perc else None
@@ -667,13 +633,10 @@ class Plan:
         if store_spec:
             flags |= HPSS_STORE_SPEC
             cnt = 3 * HPSS_BINS * T
-            soff = np.zeros(n, np.int64)
-            if n:
-                soff[1:] = np.cumsum(cnt)[:-1]
-            spec = np.zeros(int(cnt.sum()) if n else 0, np.float32)
-        ptr = (lambda a: None if a is None else a.ctypes.data)
-        _check(lib().afx_hpss_batch(self.handle, sptr, int(fmt), int(mem), offsets.ctypes.data, lengths.ctypes.data, n,
-                                    int(flags), ptr(harm), ptr(perc), ptr(stats), ptr(spec), ptr(soff),
+            soff = packed_offsets(cnt)
+            spec = np.zeros(int(cnt.sum()), np.float32)
+        _check(lib().afx_hpss_batch(self.handle, sptr, int(fmt), kind, offsets.ctypes.data, lengths.ctypes.data, n,
+                                    int(flags), _ptr(harm), _ptr(perc), _ptr(stats), _ptr(spec), _ptr(soff),
                                     status.ctypes.data), "afx_hpss_batch")
         out = {"status": status}
         if want_harm:

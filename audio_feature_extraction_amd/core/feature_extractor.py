@@ -28,6 +28,12 @@ _C7_HZ = 2093.004522404789
 
 
 
+def _one_clip(y: np.ndarray) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """(samples, offsets, lengths) of a batch that is the one clip ``y``, as contiguous float32."""
+    y = np.ascontiguousarray(y, dtype=np.float32)
+    return y, np.zeros(1, np.int64), np.array([y.size], np.int64)
+
+
 def _status_error(status: int, what: str, n_frames: int = 0) -> Exception:
     if status == _native.CLIP_NONFINITE:
         return ValueError("Audio buffer is not finite everywhere")
@@ -92,20 +98,22 @@ class AudioFeatureExtractor:
             return [self.device]
         return [int(d) for d in self.device]
 
+    def _cached_plan(self, device: int, key, make_params) -> _native.Plan:
+        """The plan (own context + stream) cached under (device, key), created from ``make_params()`` on first use."""
+        with self._plan_lock:
+            pl = self._plans.get((device, key))
+            if pl is None:
+                pl = self._plans[(device, key)] = _native.Plan(_native.Context(device), make_params())
+            return pl
+
     def _plan(self, device: Optional[int] = None, lane: int = 0) -> _native.Plan:
         """One plan (own context + stream) per (device, lane); lanes > 0 are the extra in-flight
         workers ``batch_process`` runs per GPU."""
         if device is None:
             device = self._devices()[0]
-        with self._plan_lock:
-            pl = self._plans.get((device, lane))
-            if pl is None:
-                params = _native.make_params(self.sr, self.frame_length, self.hop_length, self.n_mfcc,
-                                             self.n_mels, self.window, self.pre_emphasis,
-                                             self.fmin, self.fmax, self.htk, self.lifter)
-                pl = _native.Plan(_native.Context(device), params)
-                self._plans[(device, lane)] = pl
-            return pl
+        return self._cached_plan(device, lane, lambda: _native.make_params(
+            self.sr, self.frame_length, self.hop_length, self.n_mfcc, self.n_mels, self.window, self.pre_emphasis,
+            self.fmin, self.fmax, self.htk, self.lifter))
 
     def _uses_reference_stages(self) -> bool:
         """True when no stage method has been replaced on the instance or in a subclass
@@ -132,8 +140,7 @@ class AudioFeatureExtractor:
         return mfcc, energy
 
     def _run_one(self, y: np.ndarray, flags: int) -> np.ndarray:
-        y = np.ascontiguousarray(y, dtype=np.float32)
-        out = self._plan().extract_batch(y, np.zeros(1, np.int64), np.array([y.size], np.int64), flags=flags)
+        out = self._plan().extract_batch(*_one_clip(y), flags=flags)
         if out["status"][0] != _native.CLIP_OK:
             raise _status_error(int(out["status"][0]), "extract", int(out["nframes"][0]))
         return out["stats"][0]
@@ -171,9 +178,7 @@ class AudioFeatureExtractor:
         return "extract_f0" not in self.__dict__ and type(self).extract_f0 is AudioFeatureExtractor.extract_f0
 
     def _run_f0(self, y: np.ndarray, flags: int) -> np.ndarray:
-        y = np.ascontiguousarray(y, dtype=np.float32)
-        out = self._plan().f0_batch(y, np.zeros(1, np.int64), np.array([y.size], np.int64),
-                                    float(self.f0_min), float(self.f0_max), flags=flags)
+        out = self._plan().f0_batch(*_one_clip(y), float(self.f0_min), float(self.f0_max), flags=flags)
         if out["status"][0] != _native.CLIP_OK:
             raise _status_error(int(out["status"][0]), "extract_f0")
         return out["stats"][0]
@@ -195,8 +200,8 @@ class AudioFeatureExtractor:
         return self._energy_from(y, 0)
 
     def _energy_from(self, y: np.ndarray, flags: int) -> Dict[str, Any]:
-        y = np.ascontiguousarray(y, dtype=np.float32)
-        out = self._plan().extract_batch(y, np.zeros(1, np.int64), np.array([y.size], np.int64), flags=flags)
+        y, off, ln = _one_clip(y)
+        out = self._plan().extract_batch(y, off, ln, flags=flags)
         st = int(out["status"][0])
         # a TOO_SHORT clip with at least two samples has its RMS statistics on every shape (include/afx.h, out_stats)
         if st != _native.CLIP_OK and not (st == _native.CLIP_TOO_SHORT and y.size >= 2 and out["nframes"][0] >= 1):
@@ -253,10 +258,8 @@ class AudioFeatureExtractor:
         ``vstack([mfcc, delta, delta2])`` of shape (3*n_mfcc, T) float32, ``f0`` the pYIN track (T,)
         float64 with NaN on unvoiced frames, ``energy`` the RMS row (T,) float32, ``zcr`` the
         zero-crossing rate (T,) float64 -- all of the preprocessed signal, all computed on the GPU."""
-        y, _ = self.load_audio(audio_path)
-        y = np.ascontiguousarray(y, dtype=np.float32)
+        y, off, ln = _one_clip(self.load_audio(audio_path)[0])
         flags = _native.FLAG_PREEMPH | _native.FLAG_TRIM
-        off, ln = np.zeros(1, np.int64), np.array([y.size], np.int64)
         plan = self._plan()
         out = plan.extract_batch(y, off, ln, flags=flags, want_frames=True)
         if out["status"][0] != _native.CLIP_OK:
@@ -275,21 +278,15 @@ class AudioFeatureExtractor:
     # ------------------------------------------------------------------ sibling frame features
     def _spectral_plan(self) -> _native.Plan:
         """librosa's defaults for the spectral descriptors: n_fft 2048, hop 512, Hann -- a plan of its own."""
-        device = self._devices()[0]
-        with self._plan_lock:
-            pl = self._plans.get((device, "spectral"))
-            if pl is None:
-                pl = _native.Plan(_native.Context(device), _native.make_params(self.sr, 2048, 512, 13, 128, "hann", self.pre_emphasis))
-                self._plans[(device, "spectral")] = pl
-            return pl
+        return self._cached_plan(self._devices()[0], "spectral",
+                                 lambda: _native.make_params(self.sr, 2048, 512, 13, 128, "hann", self.pre_emphasis))
 
     def extract_spectral_frames(self, y: np.ndarray) -> Dict[str, np.ndarray]:
         """Frame-level ``librosa.feature.spectral_centroid / spectral_bandwidth / spectral_rolloff / spectral_contrast`` of
         a signal at librosa's defaults, as the reference's experiment extractor calls them
         (04_feature_extraction_experiment/feature_extractor.py:497-506): STFT, moments, roll-off search and the band
         extremes of the contrast on the GPU; the contrast's dB difference with its clip-global ``top_db`` on the host."""
-        y = np.ascontiguousarray(y, dtype=np.float32)
-        out = self._spectral_plan().spectral_batch(y, np.zeros(1, np.int64), np.array([y.size], np.int64))
+        out = self._spectral_plan().spectral_batch(*_one_clip(y))
         if out["status"][0] != _native.CLIP_OK:
             raise _status_error(int(out["status"][0]), "extract_spectral_features")
         d = out["clips"][0]
@@ -320,9 +317,7 @@ class AudioFeatureExtractor:
             if y.ndim != 1:
                 raise ValueError(f"signals must be 1-D (mono), got shape {y.shape}")
         lengths = np.array([y.size for y in ys], np.int64)
-        offsets = np.zeros(len(ys), np.int64)
-        offsets[1:] = np.cumsum(lengths)[:-1]
-        out = self._spectral_plan().hpss_batch(np.concatenate(ys), offsets, lengths, want_harm=False)
+        out = self._spectral_plan().hpss_batch(np.concatenate(ys), _native.packed_offsets(lengths), lengths, want_harm=False)
         res = []
         for i, st in enumerate(out["status"]):
             if st != _native.CLIP_OK:
@@ -359,9 +354,7 @@ class AudioFeatureExtractor:
         if wavs:
             ys = [np.ascontiguousarray(self.load_audio(p)[0], np.float32) for p in wavs]
             lengths = np.array([y.size for y in ys], np.int64)
-            offsets = np.zeros(len(ys), np.int64)
-            offsets[1:] = np.cumsum(lengths)[:-1]
-            res = self._plan().extract_batch(np.concatenate(ys), offsets, lengths,
+            res = self._plan().extract_batch(np.concatenate(ys), _native.packed_offsets(lengths), lengths,
                                              flags=_native.FLAG_PREEMPH | _native.FLAG_TRIM, want_frames=True)
             for i, p in enumerate(wavs):
                 st = int(res["status"][i])

@@ -49,9 +49,7 @@ def _as_signal(y, i=None) -> np.ndarray:
 
 def _run(signals: Sequence[np.ndarray], want_perc: bool, device: int) -> dict:
     lengths = np.array([s.size for s in signals], np.int64)
-    offsets = np.zeros(len(signals), np.int64)
-    offsets[1:] = np.cumsum(lengths)[:-1]
-    out = _plan(device).hpss_batch(np.concatenate(signals), offsets, lengths, want_perc=want_perc, want_stats=False)
+    out = _plan(device).hpss_batch(np.concatenate(signals), _native.packed_offsets(lengths), lengths, want_perc=want_perc, want_stats=False)
     bad = np.flatnonzero(out["status"] != _native.CLIP_OK)
     if bad.size:
         raise ValueError(f"hpss: clip {int(bad[0])} status {int(out['status'][bad[0]])}")

@@ -14,6 +14,7 @@ traffic.  Two deployment shapes share the partition/gather helpers here:
 """
 from __future__ import annotations
 
+import os
 import queue
 import sys
 import threading
@@ -24,6 +25,7 @@ from typing import Any, Dict, List, Sequence, Tuple
 import numpy as np
 
 from . import _native, wavio
+from .core.feature_extractor import AudioFeatureExtractor, _status_error
 from .hostinfo import usable_cpus
 
 
@@ -66,35 +68,32 @@ def gather_shards(local: np.ndarray, n_total: int, rank: int, world: int, group=
     return out
 
 
-def _decode(path: str, sr: int):
-    """-> ('s16'|'f32', mono array) ; PCM16 mono files at the target rate stay int16 so that
-    the upload is 2 bytes/sample and the /32768 happens on the GPU (bit-identical)."""
-    a, rate, kind = wavio.read_wav_raw(path)
-    if kind == "s16" and a.shape[1] == 1 and rate == sr:
-        return "s16", np.ascontiguousarray(a[:, 0])
-    y = wavio.to_mono(wavio.to_float32(a, kind))
-    if rate != sr:
-        y = wavio.resample(y, rate, sr)
-    return "f32", y
-
-
-def _decode_raw(path: str, sr: int):
-    """As _decode, but a file at another rate is left at its own rate for the device resampler:
-    -> ('s16'|'f32', mono array, file rate)."""
+def _decode(path: str, sr: int, keep_rate: bool = False):
+    """-> ('s16'|'f32', mono array, its rate) ; PCM16 mono files at the target rate stay int16 so that
+    the upload is 2 bytes/sample and the /32768 happens on the GPU (bit-identical).  A file at another rate is
+    resampled to ``sr`` on the host, or with ``keep_rate`` left at its own rate for the device resampler."""
     a, rate, kind = wavio.read_wav_raw(path)
     if kind == "s16" and a.shape[1] == 1 and rate == sr:
         return "s16", np.ascontiguousarray(a[:, 0]), rate
-    return "f32", wavio.to_mono(wavio.to_float32(a, kind)), rate
+    y = wavio.to_mono(wavio.to_float32(a, kind))
+    if rate != sr and not keep_rate:
+        y, rate = wavio.resample(y, rate, sr), sr
+    return "f32", y, rate
+
+
+_ALIGN = 4               # clips start on 4-element boundaries (enables the kernels' 16-byte loads)
+
+
+def _padded(n):
+    """A clip length, or an array of them, rounded up to the alignment."""
+    return (n + (_ALIGN - 1)) // _ALIGN * _ALIGN
 
 
 def _pack(clips: List[np.ndarray], dtype) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
-    """Packs clips with 4-element alignment (enables the kernels' 16-byte loads)."""
+    """Packs clips with 4-element alignment."""
     lengths = np.array([c.size for c in clips], np.int64)
-    padded = (lengths + 3) // 4 * 4
-    offsets = np.zeros(len(clips), np.int64)
-    if len(clips):
-        offsets[1:] = np.cumsum(padded)[:-1]
-    buf = np.zeros(int(padded.sum()), dtype)
+    offsets = _native.packed_offsets(lengths, _ALIGN)
+    buf = np.zeros(int(_padded(lengths).sum()), dtype)
     for c, o in zip(clips, offsets):
         buf[o:o + c.size] = c
     return buf, offsets, lengths
@@ -213,6 +212,333 @@ def normalize_features(features_to_extract) -> Tuple[str, ...]:
     return tuple(g for g in FEATURE_GROUPS if g in req)
 
 
+def _size_estimate(path) -> int:
+    """A file's sample count as its size says (a proxy for clip length that needs no decode)."""
+    try:
+        return max(1, os.path.getsize(str(path)) // 2)
+    except OSError:
+        return 1
+
+
+def _budget_runs(sizes: Sequence[int], budget: int, keys=None):
+    """Cuts items (in order) into runs (pos, end): a run holds at least one item, never exceeds ``budget`` with more than
+    one item, and with ``keys`` never mixes keys."""
+    pos, n = 0, len(sizes)
+    while pos < n:
+        tot, end = int(sizes[pos]), pos + 1
+        while end < n and (keys is None or keys[end] == keys[pos]) and tot + int(sizes[end]) <= budget:
+            tot += int(sizes[end])
+            end += 1
+        yield pos, end
+        pos = end
+
+
+def _lane_pool(extractor, attr: str, key, make):
+    """The pool ``key`` of the extractor's ``attr`` (_dev_pools / _pin_pools: kept with the extractor across calls)."""
+    pools = extractor.__dict__.setdefault(attr, {})
+    return pools.get(key) or pools.setdefault(key, make())
+
+
+class _Lane:
+    """What one (device, lane) worker drives: the MFCC / RMS plan and the pYIN plan (own context and stream each), its
+    pooled device buffers and, where the plan offers them, page-locked window buffers and the device resampler."""
+
+    def __init__(self, extractor, lane, want_f0: bool):
+        self.plan = extractor._plan(lane[0], lane[1])
+        self.plan_f0 = extractor._plan(lane[0], (lane[1], "f0")) if want_f0 else None
+        self.dev = _lane_pool(extractor, "_dev_pools", lane, lambda: _DevPool(self.plan))
+        self.can_rs = hasattr(self.plan, "resample_batch")
+        self.dev_in = self.pin = None
+        if self.can_rs:                                           # the resampler's input: a second pooled device buffer
+            self.dev_in = _lane_pool(extractor, "_dev_pools", (lane, "in"), lambda: _DevPool(self.plan))
+        if hasattr(self.plan, "pinned_buffer"):                   # page-locked window buffers, kept with the extractor
+            self.pin = _lane_pool(extractor, "_pin_pools", lane, lambda: _PinPool(self.plan))
+
+
+class _Job:
+    """The state of one process_files call: what its lane workers and the calling thread share."""
+
+    def __init__(self, extractor, files, budget, workers_per_gpu, features_to_extract):
+        self.ex, self.files, self.budget, self.log = extractor, files, budget, extractor.logger
+        n = len(files)
+        devices = extractor._devices()
+        self.t_start = time.perf_counter()
+        self.errors: List[Any] = [None] * n
+        K = self.K = extractor.n_mfcc
+        self.stats = np.zeros((n, 4 * K + 3), np.float32)
+        self.status = np.full(n, -1, np.int32)          # -1: not extracted (yet)
+        self.nframes = np.zeros(n, np.int32)
+        self.f0s = np.zeros((n, 4), np.float64)
+        self.f0_done = np.zeros(n, bool)
+        self.nsamp = np.zeros(n, np.int64)
+        self.lanes = [(d, w) for d in devices for w in range(max(1, int(workers_per_gpu)))]
+        if n < 4 * len(self.lanes):                             # small jobs: one worker per GPU
+            self.lanes = [(d, 0) for d in devices]
+        # shard by file size: longest-processing-time-first
+        self.sizes = [_size_estimate(f) for f in files]
+        self.parts = lpt_partition(self.sizes, len(self.lanes))
+        self.flags = _native.FLAG_PREEMPH | _native.FLAG_TRIM
+        self.want = normalize_features(features_to_extract)
+        self.want_f0, self.want_stats = "f0" in self.want, ("mfcc" in self.want or "energy" in self.want)
+        host_cpus = usable_cpus()                   # the job's share of the host, not os.cpu_count()
+        self.pool = ThreadPoolExecutor(max(1, min(host_cpus, DECODE_THREADS_PER_GPU * len(devices), n)))
+        self.native_threads = max(1, min(host_cpus, DECODE_THREADS_PER_GPU * len(devices)) // max(1, min(len(self.lanes), 4)))
+        self.win_pool = ThreadPoolExecutor(max(1, len(self.lanes)))
+        self.phase = {"decode_wait": 0.0, "device": 0.0}
+        self.phase_lock = threading.Lock()
+        self.timeline: List[Any] = []            # (lane, clips, t_begin, t_uploaded, t_f0_done, t_collected) per sub-batch
+        self.finished: Any = queue.SimpleQueue()  # index lists of sub-batches whose results are in the arrays
+        self.recs: List[Any] = [None] * n
+        # the result dicts are built here, in plain Python, while the extractor's own builders are the stock ones
+        self.stock = (getattr(type(extractor), "_stats_to_dicts", None) is AudioFeatureExtractor._stats_to_dicts and
+                      getattr(type(extractor), "_f0_to_dict", None) is AudioFeatureExtractor._f0_to_dict)
+
+    def now(self) -> float:
+        return time.perf_counter() - self.t_start
+
+    def decode(self, i: int, keep_rate: bool):
+        try:
+            return _decode(str(self.files[i]), self.ex.sr, keep_rate)
+        except Exception as e:          # load_audio: log + the file is dropped
+            self.log.error(f"載入音頻文件失敗: {str(e)}")
+            self.errors[i] = e
+            return None
+
+    def load_window(self, win, pin=None, can_rs=False):
+        """-> (packed 16-bit group or None, indices decoded by wavio, their decoded clips); pin: the worker's pool of
+        page-locked buffers (None: ordinary memory); can_rs: the plan resamples on the device, so 16-bit mono files of
+        any rate are read natively (laid out rate by rate, the extractor's own rate first) and decoded files keep theirs.
+
+        Files that need no conversion -- 16-bit PCM, mono, at the target rate: what a corpus of speech clips is -- never
+        pass through Python: libafx parses their headers and reads their samples straight into the packed int16 batch
+        buffer with native threads (afx_wav_probe / afx_wav_read_s16).  Everything else, and any file the native reader
+        cannot open or parse, goes through wavio (which also produces the error a bad file is logged with)."""
+        sr = self.ex.sr
+        rest = list(win)
+        packed = None
+        held = None
+        try:
+            paths = [str(self.files[i]) for i in win]
+            pr = _native.wav_probe(paths, self.native_threads)
+            ok = (pr["status"] == 0) & (pr["tag"] == 1) & (pr["bits"] == 16) & (pr["channels"] == 1)
+            ok &= (pr["rate"] > 0) if can_rs else (pr["rate"] == sr)
+            sel = np.nonzero(ok)[0]
+            if sel.size and (pr["rate"][sel] != sr).any():
+                sel = sel[np.lexsort((sel, pr["rate"][sel], pr["rate"][sel] != sr))]
+            if sel.size:
+                lens = pr["frames"][sel].astype(np.int64)
+                padded = _padded(lens)
+                offs = _native.packed_offsets(lens, _ALIGN)
+                nel = max(int(padded.sum()), 1)
+                if pin is not None:
+                    held = pin.get(nel * 2)
+                    buf = held.array(np.int16, nel)
+                else:
+                    buf = np.empty(nel, np.int16)
+                st = _native.wav_read_s16([paths[j] for j in sel], pr["data_off"][sel], lens, buf, offs, self.native_threads)
+                for o, ln, pd in zip(offs[padded > lens], lens[padded > lens], padded[padded > lens]):
+                    buf[o + ln: o + pd] = 0
+                good = st == 0
+                if good.any():
+                    packed = ([win[j] for j in sel[good]], buf, offs[good], lens[good], held,
+                              pr["rate"][sel[good]].astype(np.int64))
+                    held = None
+                    taken = set(packed[0])
+                    rest = [i for i in win if i not in taken]
+        except Exception:                                         # no native reader: the Python decoder takes the window
+            rest, packed = list(win), None
+        if held is not None:
+            pin.put(held)
+        decoded = list(self.pool.map(self.decode, rest, [can_rs] * len(rest))) if rest else []
+        return packed, rest, decoded
+
+    def resample_on_device(self, lane: _Lane, buf, offs, lens, fmt, rate: int):
+        """Clips at ``rate`` -> float32 clips at the extractor's rate in a pooled device buffer (4-aligned, as _pack):
+        (buffer, offsets, lengths), or None for a rate pair the device resampler does not hold.  The input buffer always
+        goes back to its pool (the resampler is synchronous: it is done with), the output buffer on every exit but the
+        first."""
+        sr = int(self.ex.sr)
+        olens = _native.resample_lengths(lens, rate, sr)             # known on the host: no read-back
+        ooffs = _native.packed_offsets(olens, _ALIGN)
+        din = lane.dev_in.get(max(buf.nbytes, 16))
+        dbuf = None
+        try:
+            din.upload(buf)
+            dbuf = lane.dev.get(max(4 * int(ooffs[-1] + _padded(olens[-1])), 16))
+            lane.plan.resample_batch(din, offs, lens, rate, sr, fmt=fmt, out=dbuf, out_offsets=ooffs)
+        except BaseException as e:
+            if dbuf is not None:
+                lane.dev.put(dbuf)
+            if isinstance(e, NotImplementedError):
+                return None
+            raise
+        finally:
+            lane.dev_in.put(din)
+        return dbuf, ooffs, olens
+
+    def resample_on_host(self, buf, offs, lens, fmt, rate: int):
+        """The fallback of resample_on_device: wavio.resample clip by clip -> packed float32 (buffer, offsets, lengths)."""
+        f = np.float32(1.0 / 32768.0) if fmt == _native.FMT_S16 else None
+        ys = [wavio.resample(buf[o:o + ln].astype(np.float32) * f if f is not None else buf[o:o + ln], rate, int(self.ex.sr))
+              for o, ln in zip(offs, lens)]
+        return _pack(ys, np.float32)
+
+    def run_group(self, lane: _Lane, cur, buf, offs, lens, fmt, rate: int):
+        """One sub-batch: upload, (resample on the device when ``rate`` is another rate than the extractor's,) both passes."""
+        tl = [None, len(cur), self.now(), 0.0, 0.0, 0.0]
+        dbuf = None
+        if rate != int(self.ex.sr):
+            res = self.resample_on_device(lane, buf, offs, lens, fmt, rate)
+            if res is not None:
+                dbuf, offs, lens = res
+            else:
+                buf, offs, lens = self.resample_on_host(buf, offs, lens, fmt, rate)
+            fmt = _native.FMT_F32
+        uploaded = dbuf is not None
+        if not uploaded:
+            dbuf = lane.dev.get(max(buf.nbytes, 16))                  # one PCIe copy for both passes
+        try:
+            if not uploaded:
+                dbuf.upload(buf)
+            tl[3] = self.now()
+            submitted = False
+            if self.want_stats:                                   # MFCC / RMS pass: queued, runs beside the pYIN pass below
+                lane.plan.extract_submit(dbuf, offs, lens, flags=self.flags, fmt=fmt)
+                submitted = True
+            out = f0 = None
+            try:
+                if self.want_f0:
+                    f0 = lane.plan_f0.f0_batch(dbuf, offs, lens, self.ex.f0_min, self.ex.f0_max, flags=self.flags, fmt=fmt)
+                tl[4] = self.now()
+            finally:
+                if submitted:                                     # always: the buffer must outlive the queued pass
+                    out = lane.plan.extract_collect()
+            tl[5] = self.now()
+            self.timeline.append(tl)
+            self.nsamp[cur] = lens
+            if out is not None:
+                self.stats[cur] = out["stats"]
+                self.nframes[cur] = out["nframes"]
+            if f0 is not None:
+                self.f0s[cur] = f0["stats"]
+            self.f0_done[cur] = True
+            # last: a file counts only with every requested pass done.  Without the MFCC / RMS pass the f0 pass's own
+            # status (non-finite input) decides
+            self.status[cur] = out["status"] if out is not None else f0["status"]
+            self.finished.put(list(cur))
+        finally:
+            lane.dev.put(dbuf)                                    # both passes are through (collect above): reusable
+
+    def run_window(self, lane: _Lane, packed, rest, decoded):
+        """The sub-batches of one loaded window: runs of one file rate and sample type, within the budget before and after
+        resampling (a window may still exceed the budget: its sizes were estimates)."""
+        sr = self.ex.sr
+        if packed is not None:                                    # the natively packed 16-bit clips
+            ids, buf, offs, lens, _held, rates = packed
+            olens = np.maximum(lens, _native.resample_lengths(lens, rates, sr))
+            for pos, end in _budget_runs(olens, self.budget, rates):
+                lo = int(offs[pos])
+                hi = int(offs[end - 1] + _padded(lens[end - 1]))
+                self.run_group(lane, ids[pos:end], buf[lo:hi], offs[pos:end] - lo, lens[pos:end], _native.FMT_S16,
+                               int(rates[pos]))
+        groups = sorted({(d[2] != sr, d[2], d[0] != "s16") for d in decoded if d is not None})
+        for _, rate, is_f32 in groups:
+            kind, fmt, dt = (("f32", _native.FMT_F32, np.float32) if is_f32 else ("s16", _native.FMT_S16, np.int16))
+            sel = [(i, d[1]) for i, d in zip(rest, decoded) if d is not None and d[0] == kind and d[2] == rate]
+            osz = [max(y.size, int(_native.resample_lengths(y.size, rate, sr))) for _, y in sel]
+            for pos, end in _budget_runs(osz, self.budget):
+                buf, offs, lens = _pack([y for _, y in sel[pos:end]], dt)
+                self.run_group(lane, [i for i, _ in sel[pos:end]], buf, offs, lens, fmt, int(rate))
+
+    def lane_worker(self, lane_id, idxs):
+        """One (device, lane): its files in windows; window k + 1 loads while window k is on the device."""
+        wins = _windows(self.sizes, idxs, self.budget)
+        try:
+            lane = _Lane(self.ex, lane_id, self.want_f0)
+        except Exception as e:                                    # no device for this lane: its files are dropped, the batch goes on
+            for i in idxs:
+                self.errors[i] = e
+            return
+        pending = self.win_pool.submit(self.load_window, wins[0], lane.pin, lane.can_rs) if wins else None
+        for k, win in enumerate(wins):
+            t0 = time.perf_counter()
+            packed, rest, decoded = pending.result()
+            # next window loads while this one is on the device
+            pending = self.win_pool.submit(self.load_window, wins[k + 1], lane.pin, lane.can_rs) if k + 1 < len(wins) else None
+            t1 = time.perf_counter()
+            try:
+                self.run_window(lane, packed, rest, decoded)
+            except Exception as e:          # a device-level failure drops the files of the sub-batch it hit, and the
+                for i in win:               # rest of this window; later windows are still attempted
+                    if self.errors[i] is None and not (self.status[i] >= 0 and self.f0_done[i]):
+                        self.errors[i] = e
+                        self.status[i] = -1
+            if packed is not None and packed[4] is not None:
+                lane.pin.put(packed[4])
+            del decoded, packed
+            with self.phase_lock:
+                self.phase["decode_wait"] += t1 - t0
+                self.phase["device"] += time.perf_counter() - t1
+
+    def delivered(self, i: int) -> bool:
+        # fewer than nine frames fails the MFCC group only (the width-9 delta); extract_energy has its statistics
+        st = self.status[i]
+        return st == _native.CLIP_OK or ("mfcc" not in self.want and st == _native.CLIP_TOO_SHORT and
+                                         self.nsamp[i] >= 2 and self.nframes[i] >= 1)
+
+    def record(self, i: int) -> Dict[str, Any]:
+        """The result dict of file i.  With the stock extractor: what _stats_to_dicts / _f0_to_dict build, key for key, in
+        plain Python from tolist() rows (cheap enough to run beside the workers); else through the extractor's own."""
+        want, rec = self.want, {"file_path": str(self.files[i])}
+        if not self.stock:
+            mfcc, energy = self.ex._stats_to_dicts(self.stats[i])
+            if self.want_f0:
+                rec.update(self.ex._f0_to_dict(self.f0s[i]))
+            if "mfcc" in want:
+                rec.update(mfcc)
+            if "energy" in want:
+                rec.update(energy)
+            return rec
+        K, K4, row = self.K, 4 * self.K, self.stats[i].tolist()
+        if self.want_f0:
+            q = self.f0s[i].tolist()
+            rec["f0_mean"], rec["f0_std"], rec["f0_missing_rate"], rec["f0_quality"] = q[0], q[1], q[2], q[3]
+        if "mfcc" in want:
+            rec["mfcc_mean"], rec["mfcc_std"] = row[0:K], row[K:2 * K]
+            rec["mfcc_delta_mean"], rec["mfcc_delta2_mean"] = row[2 * K:3 * K], row[3 * K:K4]
+        if "energy" in want:
+            rec["energy_mean"], rec["energy_std"], rec["energy_range"] = row[K4], row[K4 + 1], row[K4 + 2]
+        return rec
+
+    def drain(self, block: bool) -> bool:
+        """Takes one finished sub-batch off the queue and builds its files' dicts; False when there was none."""
+        try:
+            cur = self.finished.get(timeout=0.002) if block else self.finished.get_nowait()
+        except queue.Empty:
+            return False
+        if self.stock:
+            for i in cur:
+                if self.errors[i] is None and self.delivered(i):
+                    self.recs[i] = self.record(i)
+        return True
+
+    def results(self) -> List[Dict[str, Any]]:
+        """The dicts of the delivered files in input order; every other file is logged with the reference's messages."""
+        out: List[Dict[str, Any]] = []
+        for i, f in enumerate(self.files):
+            name = getattr(f, "name", str(f))
+            err = self.errors[i]
+            if err is None and not self.delivered(i):
+                err = _status_error(int(self.status[i]), "extract_features", int(self.nframes[i]))
+                self.log.error(f"特徵提取失敗: {str(err)}")
+            if err is not None:
+                self.log.error(f"處理文件 {name} 失敗: {str(err)}")
+                continue
+            out.append(self.recs[i] if self.recs[i] is not None else self.record(i))
+            self.log.info(f"成功處理文件: {name}")
+        return out
+
+
 def process_files(extractor, files: Sequence, max_batch_samples: int = 80 * 1024 * 1024,
                   workers_per_gpu: int = WORKERS_PER_GPU, features_to_extract=None) -> List[Dict[str, Any]]:
     """Shard over GPUs (and over a few workers per GPU) -> per worker a pipeline of bounded windows:
@@ -233,315 +559,31 @@ def process_files(extractor, files: Sequence, max_batch_samples: int = 80 * 1024
 
     Error behaviour is the reference's (feature_extractor.py:229-235): a file that cannot be loaded, a clip the
     kernels reject, or a device-level failure while its window is processed is logged and left out; the batch goes on."""
-    import os
-    log = extractor.logger
-    n = len(files)
-    if n == 0:
+    if len(files) == 0:
         return []
-    devices = extractor._devices()
-    t_start = time.perf_counter()
-    errors: List[Any] = [None] * n
-    K = extractor.n_mfcc
-    stats = np.zeros((n, 4 * K + 3), np.float32)
-    status = np.full(n, -1, np.int32)          # -1: not extracted (yet)
-    nframes = np.zeros(n, np.int32)
-    f0s = np.zeros((n, 4), np.float64)
-    f0_done = np.zeros(n, bool)
-    nsamp = np.zeros(n, np.int64)
-    lanes = [(d, w) for d in devices for w in range(max(1, int(workers_per_gpu)))]
-    if n < 4 * len(lanes):                             # small jobs: one worker per GPU
-        lanes = [(d, 0) for d in devices]
-    # shard by file size (a proxy for clip length that needs no decode): longest-processing-time-first
-    def fsize(f):
-        try:
-            return max(1, os.path.getsize(str(f)) // 2)
-        except OSError:
-            return 1
-    sizes = [fsize(f) for f in files]
-    parts = lpt_partition(sizes, len(lanes))
-    flags = _native.FLAG_PREEMPH | _native.FLAG_TRIM
-    want = normalize_features(features_to_extract)
-    want_f0, want_stats = "f0" in want, ("mfcc" in want or "energy" in want)
-    host_cpus = usable_cpus()                   # the job's share of the host, not os.cpu_count()
-    pool = ThreadPoolExecutor(max(1, min(host_cpus, DECODE_THREADS_PER_GPU * len(devices), n)))
-    phase = {"decode_wait": 0.0, "device": 0.0}
-    phase_lock = threading.Lock()
-
-    def dec(i, raw=False):
-        try:
-            if raw:                      # the device resamples: keep the file's rate
-                return _decode_raw(str(files[i]), extractor.sr)
-            return _decode(str(files[i]), extractor.sr) + (extractor.sr,)
-        except Exception as e:          # load_audio: log + the file is dropped
-            log.error(f"載入音頻文件失敗: {str(e)}")
-            errors[i] = e
-            return None
-
-    # Files that need no conversion -- 16-bit PCM, mono, at the target rate: what a corpus of speech clips is -- never
-    # pass through Python: libafx parses their headers and reads their samples straight into the packed int16 batch
-    # buffer with native threads (afx_wav_probe / afx_wav_read_s16).  Everything else, and any file the native reader
-    # cannot open or parse, goes through wavio as before (which also produces the error a bad file is logged with).
-    native_threads = max(1, min(host_cpus, DECODE_THREADS_PER_GPU * len(devices)) // max(1, min(len(lanes), 4)))
-    win_pool = ThreadPoolExecutor(max(1, len(lanes)))
-
-    def load_window(win, pin=None, can_rs=False):
-        """-> (packed 16-bit group or None, indices decoded by wavio, their decoded clips); pin: the worker's pool of
-        page-locked buffers (None: ordinary memory); can_rs: the plan resamples on the device, so 16-bit mono files of
-        any rate are read natively (laid out rate by rate, the extractor's own rate first) and decoded files keep theirs"""
-        rest = list(win)
-        packed = None
-        held = None
-        try:
-            paths = [str(files[i]) for i in win]
-            pr = _native.wav_probe(paths, native_threads)
-            ok = (pr["status"] == 0) & (pr["tag"] == 1) & (pr["bits"] == 16) & (pr["channels"] == 1)
-            ok &= (pr["rate"] > 0) if can_rs else (pr["rate"] == extractor.sr)
-            sel = np.nonzero(ok)[0]
-            if sel.size and (pr["rate"][sel] != extractor.sr).any():
-                sel = sel[np.lexsort((sel, pr["rate"][sel], pr["rate"][sel] != extractor.sr))]
-            if sel.size:
-                lens = pr["frames"][sel].astype(np.int64)
-                padded = (lens + 3) // 4 * 4                      # 4-element alignment, as _pack
-                offs = np.zeros(sel.size, np.int64)
-                offs[1:] = np.cumsum(padded)[:-1]
-                nel = max(int(padded.sum()), 1)
-                if pin is not None:
-                    held = pin.get(nel * 2)
-                    buf = held.array(np.int16, nel)
-                else:
-                    buf = np.empty(nel, np.int16)
-                st = _native.wav_read_s16([paths[j] for j in sel], pr["data_off"][sel], lens, buf, offs, native_threads)
-                for o, ln, pd in zip(offs[padded > lens], lens[padded > lens], padded[padded > lens]):
-                    buf[o + ln: o + pd] = 0
-                good = st == 0
-                if good.any():
-                    packed = ([win[j] for j in sel[good]], buf, offs[good], lens[good], held,
-                              pr["rate"][sel[good]].astype(np.int64))
-                    held = None
-                    taken = set(packed[0])
-                    rest = [i for i in win if i not in taken]
-        except Exception:                                         # no native reader: the Python decoder takes the window
-            rest, packed = list(win), None
-        if held is not None:
-            pin.put(held)
-        decoded = list(pool.map(lambda i: dec(i, can_rs), rest)) if rest else []
-        return packed, rest, decoded
-
-    timeline: List[Any] = []                                      # (lane, clips, t_begin, t_uploaded, t_f0_done, t_collected) per sub-batch
-    finished: Any = queue.SimpleQueue()                          # index lists of sub-batches whose results are in the arrays
-    recs: List[Any] = [None] * n
-
-    def run_group(plans, cur, buf, offs, lens, fmt, dev, rate=None, dev_in=None):
-        """One sub-batch: upload, (resample on the device when ``rate`` is another rate than the extractor's,) both passes."""
-        plan, plan_f0 = plans
-        tl = [None, len(cur), time.perf_counter() - t_start, 0.0, 0.0, 0.0]
-        sr = int(extractor.sr)
-        if rate is not None and int(rate) != sr:
-            olens = _native.resample_lengths(lens, int(rate), sr)         # known on the host: no read-back
-            ooffs = np.zeros(len(cur), np.int64)
-            ooffs[1:] = np.cumsum((olens + 3) // 4 * 4)[:-1]
-            din = dev_in.get(max(buf.nbytes, 16))
-            dbuf = None
-            try:
-                din.upload(buf)
-                dbuf = dev.get(max(4 * int(ooffs[-1] + (olens[-1] + 3) // 4 * 4), 16))
-                plan.resample_batch(din, offs, lens, int(rate), sr, fmt=fmt, out=dbuf, out_offsets=ooffs)
-            except NotImplementedError:                               # a rate pair the device resampler does not hold
-                if dbuf is not None:
-                    dev.put(dbuf)
-                dev_in.put(din)
-                f = np.float32(1.0 / 32768.0) if fmt == _native.FMT_S16 else None
-                ys = [wavio.resample(buf[o:o + ln].astype(np.float32) * f if f is not None else buf[o:o + ln], int(rate), sr)
-                      for o, ln in zip(offs, lens)]
-                hb, ho, hl = _pack(ys, np.float32)
-                return run_group(plans, cur, hb, ho, hl, _native.FMT_F32, dev)
-            except BaseException:
-                if dbuf is not None:
-                    dev.put(dbuf)
-                dev_in.put(din)
-                raise
-            dev_in.put(din)                                           # the resampler is synchronous: the input is done with
-            offs, lens, fmt = ooffs, olens, _native.FMT_F32
-        else:
-            dbuf = dev.get(max(buf.nbytes, 16))                       # one PCIe copy for both passes
-        try:
-            if rate is None or int(rate) == sr:
-                dbuf.upload(buf)
-            tl[3] = time.perf_counter() - t_start
-            submitted = False
-            if want_stats:                                        # MFCC / RMS pass: queued, runs beside the pYIN pass below
-                plan.extract_submit(dbuf, offs, lens, flags=flags, fmt=fmt)
-                submitted = True
-            out = f0 = None
-            try:
-                if want_f0:
-                    f0 = plan_f0.f0_batch(dbuf, offs, lens, extractor.f0_min, extractor.f0_max, flags=flags, fmt=fmt)
-                tl[4] = time.perf_counter() - t_start
-            finally:
-                if submitted:                                     # always: the buffer must outlive the queued pass
-                    out = plan.extract_collect()
-            tl[5] = time.perf_counter() - t_start
-            timeline.append(tl)
-            nsamp[cur] = lens
-            if out is not None:
-                stats[cur] = out["stats"]
-                nframes[cur] = out["nframes"]
-            if f0 is not None:
-                f0s[cur] = f0["stats"]
-            f0_done[cur] = True
-            # last: a file counts only with every requested pass done.  Without the MFCC / RMS pass the f0 pass's own
-            # status (non-finite input) decides
-            status[cur] = out["status"] if out is not None else f0["status"]
-            finished.put(list(cur))
-        finally:
-            dev.put(dbuf)                                         # both passes are through (collect above): reusable
-
-    def worker(lane, idxs):
-        wins = _windows(sizes, idxs, max_batch_samples)
-        plan = pin = dev = dev_in = None
-        can_rs = False
-        try:                                                      # (MFCC / RMS plan, pYIN plan): own context and stream each
-            plan = (extractor._plan(lane[0], lane[1]),
-                    extractor._plan(lane[0], (lane[1], "f0")) if want_f0 else None)
-            dpools = extractor.__dict__.setdefault("_dev_pools", {})
-            dev = dpools.get(lane) or dpools.setdefault(lane, _DevPool(plan[0]))
-            can_rs = hasattr(plan[0], "resample_batch")
-            if can_rs:                                            # the resampler's input: a second pooled device buffer
-                dev_in = dpools.get((lane, "in")) or dpools.setdefault((lane, "in"), _DevPool(plan[0]))
-            if hasattr(plan[0], "pinned_buffer"):                 # page-locked window buffers, kept with the extractor
-                pools = extractor.__dict__.setdefault("_pin_pools", {})
-                pin = pools.get(lane) or pools.setdefault(lane, _PinPool(plan[0]))
-        except Exception as e:                                    # no device for this lane: its files are dropped, the batch goes on
-            for i in idxs:
-                errors[i] = e
-            return
-        pending = win_pool.submit(load_window, wins[0], pin, can_rs) if wins else None
-        for k, win in enumerate(wins):
-            t0 = time.perf_counter()
-            packed, rest, decoded = pending.result()
-            # next window loads while this one is on the device
-            pending = win_pool.submit(load_window, wins[k + 1], pin, can_rs) if k + 1 < len(wins) else None
-            t1 = time.perf_counter()
-            try:
-                if packed is not None:                            # the natively packed 16-bit clips, in budget-sized runs
-                    ids, buf, offs, lens, _held, rates = packed
-                    olens = np.maximum(lens, _native.resample_lengths(lens, rates, extractor.sr))
-                    pos = 0
-                    while pos < len(ids):          # runs of one file rate, within the budget before and after resampling
-                        tot, end = 0, pos
-                        while end < len(ids) and (end == pos or (rates[end] == rates[pos] and
-                                                                 tot + int(olens[end]) <= max_batch_samples)):
-                            tot += int(olens[end])
-                            end += 1
-                        lo = int(offs[pos])
-                        hi = int(offs[end - 1] + (lens[end - 1] + 3) // 4 * 4)
-                        run_group(plan, ids[pos:end], buf[lo:hi], offs[pos:end] - lo, lens[pos:end], _native.FMT_S16, dev,
-                                  int(rates[pos]), dev_in)
-                        pos = end
-                groups = sorted({(d[2] != extractor.sr, d[2], d[0] != "s16") for d in decoded if d is not None})
-                for _, rate, is_f32 in groups:
-                    kind, fmt, dt = (("f32", _native.FMT_F32, np.float32) if is_f32 else ("s16", _native.FMT_S16, np.int16))
-                    sel = [(i, d[1]) for i, d in zip(rest, decoded) if d is not None and d[0] == kind and d[2] == rate]
-                    osz = [max(y.size, int(_native.resample_lengths(y.size, rate, extractor.sr))) for _, y in sel]
-                    pos = 0
-                    while pos < len(sel):          # a window may still exceed the budget (sizes were estimates)
-                        tot, end = 0, pos
-                        while end < len(sel) and (end == pos or tot + osz[end] <= max_batch_samples):
-                            tot += osz[end]
-                            end += 1
-                        buf, offs, lens = _pack([y for _, y in sel[pos:end]], dt)
-                        run_group(plan, [i for i, _ in sel[pos:end]], buf, offs, lens, fmt, dev, int(rate), dev_in)
-                        pos = end
-            except Exception as e:          # a device-level failure drops the files of the sub-batch it hit, and the
-                for i in win:               # rest of this window; later windows are still attempted
-                    if errors[i] is None and not (status[i] >= 0 and f0_done[i]):
-                        errors[i] = e
-                        status[i] = -1
-            if packed is not None and packed[4] is not None:
-                pin.put(packed[4])
-            del decoded, packed
-            with phase_lock:
-                phase["decode_wait"] += t1 - t0
-                phase["device"] += time.perf_counter() - t1
-
-    threads = [threading.Thread(target=worker, args=(ln, p)) for ln, p in zip(lanes, parts) if p]
+    job = _Job(extractor, files, max_batch_samples, workers_per_gpu, features_to_extract)
+    threads = [threading.Thread(target=job.lane_worker, args=(ln, p)) for ln, p in zip(job.lanes, job.parts) if p]
     # The calling thread builds the result dicts of finished sub-batches while the workers drive the device (55 Python floats
     # and four lists per file: 35-50 ms for 8192 files if left to the end).  The workers need the interpreter only for
     # microseconds between two native calls, but would wait a whole switch interval (5 ms) for it: shortened for the duration.
-    def delivered(i):
-        # fewer than nine frames fails the MFCC group only (the width-9 delta); extract_energy has its statistics
-        return status[i] == _native.CLIP_OK or ("mfcc" not in want and status[i] == _native.CLIP_TOO_SHORT and
-                                                 nsamp[i] >= 2 and nframes[i] >= 1)
-
-    from .core.feature_extractor import AudioFeatureExtractor as _Stock
-    stock = (getattr(type(extractor), "_stats_to_dicts", None) is _Stock._stats_to_dicts and
-             getattr(type(extractor), "_f0_to_dict", None) is _Stock._f0_to_dict)      # else: the extractor's own methods, at the end
-    K4 = 4 * K
-
-    def build(i):                                                     # what _stats_to_dicts / _f0_to_dict build, key for key
-        row, rec = stats[i].tolist(), {"file_path": str(files[i])}
-        if want_f0:
-            q = f0s[i].tolist()
-            rec["f0_mean"], rec["f0_std"], rec["f0_missing_rate"], rec["f0_quality"] = q[0], q[1], q[2], q[3]
-        if "mfcc" in want:
-            rec["mfcc_mean"], rec["mfcc_std"] = row[0:K], row[K:2 * K]
-            rec["mfcc_delta_mean"], rec["mfcc_delta2_mean"] = row[2 * K:3 * K], row[3 * K:K4]
-        if "energy" in want:
-            rec["energy_mean"], rec["energy_std"], rec["energy_range"] = row[K4], row[K4 + 1], row[K4 + 2]
-        return rec
-
-    def drain(block):
-        try:
-            cur = finished.get(timeout=0.002) if block else finished.get_nowait()
-        except queue.Empty:
-            return False
-        if stock:
-            for i in cur:
-                if errors[i] is None and delivered(i):
-                    recs[i] = build(i)
-        return True
-
     _fast_switch(True)
     try:
         for t in threads:
             t.start()
         while any(t.is_alive() for t in threads):
-            drain(True)
-        while drain(False):
+            job.drain(True)
+        while job.drain(False):
             pass
         for t in threads:
             t.join()
     finally:
         _fast_switch(False)
-    win_pool.shutdown()
-    pool.shutdown()
+    job.win_pool.shutdown()
+    job.pool.shutdown()
 
     t_gpu = time.perf_counter()
-    results: List[Dict[str, Any]] = []
-    from .core.feature_extractor import _status_error
-    for i, f in enumerate(files):
-        name = getattr(f, "name", str(f))
-        err = errors[i]
-        if err is None and not delivered(i):
-            err = _status_error(int(status[i]), "extract_features", int(nframes[i]))
-            log.error(f"特徵提取失敗: {str(err)}")
-        if err is not None:
-            log.error(f"處理文件 {name} 失敗: {str(err)}")
-            continue
-        if recs[i] is not None:
-            results.append(recs[i])
-            log.info(f"成功處理文件: {name}")
-            continue
-        mfcc, energy = extractor._stats_to_dicts(stats[i])
-        rec: Dict[str, Any] = {"file_path": str(f)}
-        if want_f0:
-            rec.update(extractor._f0_to_dict(f0s[i]))
-        if "mfcc" in want:
-            rec.update(mfcc)
-        if "energy" in want:
-            rec.update(energy)
-        results.append(rec)
-        log.info(f"成功處理文件: {name}")
-    LAST_TIMING.update(pipeline=t_gpu - t_start, decode_wait=phase["decode_wait"], device=phase["device"],
-                       dicts=time.perf_counter() - t_gpu, files=n, workers=len(threads), timeline=sorted(timeline, key=lambda r: r[2]))
+    results = job.results()
+    LAST_TIMING.update(pipeline=t_gpu - job.t_start, decode_wait=job.phase["decode_wait"], device=job.phase["device"],
+                       dicts=time.perf_counter() - t_gpu, files=len(files), workers=len(threads),
+                       timeline=sorted(job.timeline, key=lambda r: r[2]))
     return results

@@ -178,8 +178,7 @@ def resample_batch(clips, sr_in: int, sr_out: int, device=None):
             if not idx:
                 continue
             lens = np.array([clips[i].size for i in idx], np.int64)
-            offs = np.zeros(len(idx), np.int64)
-            offs[1:] = np.cumsum(lens)[:-1]
+            offs = _native.packed_offsets(lens)
             buf = np.concatenate([clips[i] for i in idx]) if lens.sum() else np.zeros(1, dt)
             try:
                 r = ctx.resample_batch(buf, offs, lens, sr_in, sr_out)
