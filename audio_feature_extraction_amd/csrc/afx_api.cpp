@@ -366,19 +366,15 @@ int prepare_descriptors(afx_plan* pl, const int64_t* offsets, const int64_t* len
       HIP_TRY(launch_build_blocks3(s, (const ClipDesc*)pl->clips.p, n, (int)nblk, (BlockDesc*)pl->blocks_spec.p, pl->kp));
     } else {                      // A/B: round 2's host-built list (3.5 MB for 1000 ten-second clips) and its synchronisation
       const int per = pl->kp.rms_sub, half = pl->p.n_fft / 2;
-      const int64_t lim = (int64_t)1 << 30;
       pl->h_blocks.resize(nb_alloc);
       for (int i = 0; i < n; ++i) {
         const ClipDesc& c = pl->h_clips[i];
         const int64_t ntb = (c.len + th - 1) / th;
         for (int b = 0; b < c.tpad / kFramesPerBlock; ++b) {
-          BlockDesc& d = pl->h_blocks[(size_t)c.blk_base + b];
           const int64_t gs = (int64_t)b * kFramesPerBlock * hop - half;       // clip sample of staged index 0
-          auto rel = [&](int64_t x) { const int64_t q = x - gs; return (int32_t)(q < -lim ? -lim : (q > lim ? lim : q)); };
-          d.sample_base = c.off + gs; d.frame_slot = c.frame_base + (int64_t)b * kFramesPerBlock; d.clip_off = c.off;
-          d.keep_lo = rel(0); d.keep_hi = rel(c.len); d.have_lo = rel(0); d.have_hi = rel(c.len);
-          d.clip = i; d.t0 = b * kFramesPerBlock; d.T = c.tmax; d.active = (c.len >= 2 && d.t0 < c.tmax) ? 1 : 0;
-          d.pad_[0] = (int32_t)(c.tblk_base * per); d.pad_[1] = (int32_t)(ntb * per);
+          const int t0 = b * kFramesPerBlock;
+          pl->h_blocks[(size_t)c.blk_base + b] = make_block(c, i, gs, t0, 0, c.len, c.len, t0, c.tmax, c.len >= 2 && t0 < c.tmax,
+                                                            (int32_t)(c.tblk_base * per), (int32_t)(ntb * per));
         }
       }
       HIP_TRY(hipMemcpyAsync(pl->blocks_spec.p, pl->h_blocks.data(), pl->h_blocks.size() * sizeof(BlockDesc), hipMemcpyHostToDevice, s));
@@ -582,16 +578,20 @@ static int chunk_enqueue(afx_plan* pl, const void* samples, int fmt, int mem_kin
   // (k_tail).  A batch of very few, very long clips keeps the many-workgroups-per-clip kernels.
   const bool fused_tail = f3 && pl->nblocks > 0 && !out_frames && !dev_env().no_fused_tail && tail_eligible(kp, pl->dt) &&
                           (n >= 32 || pl->max_tmax <= 2048);
+  const F3Launch f3l{s, d_samples, d_info, pl->f3, kp, (float*)pl->logmel.p, pl->n_cu};      // what every wave-level launch of the batch shares
   if (f3 && !no_spec && pl->nblocks > 0) {
     // the samples are read once: frames before the trim decision (which the same pass feeds), then the few frames a cut touches
     const int max_items = n * kF3ItemsPerClip;
-    TIMED(AFX_K_FRAMES, launch_frames3_any(s, d_samples, d_info, (const BlockDesc*)pl->blocks_spec.p, pl->nblocks, nullptr, pl->f3, kp,
-                                       (float*)pl->logmel.p, (float*)pl->blockmax.p, (float*)pl->bsum.p, true,
-                                       dev_env().no_tickets ? nullptr : (int*)pl->n_items.p + 1, pl->n_cu));
+    F3Launch spec = f3l;
+    spec.blocks = (const BlockDesc*)pl->blocks_spec.p; spec.nblocks = pl->nblocks; spec.spec = true;
+    spec.blockmax = (float*)pl->blockmax.p; spec.bsum = (float*)pl->bsum.p;
+    spec.work_ctr = dev_env().no_tickets ? nullptr : (int*)pl->n_items.p + 1;
+    TIMED(AFX_K_FRAMES, launch_frames3_any(spec));
     TIMED(AFX_K_TRIM_DECIDE, launch_trim_decide3(s, d_clips, d_info, (const float*)pl->bsum.p, (const float*)pl->blockmax.p,
                                                  (BlockDesc*)pl->items.p, (int*)pl->n_items.p, max_items, (float*)pl->rms.p, n, kp));
-    TIMED(AFX_K_TRIM_BLOCKS, launch_frames3_any(s, d_samples, d_info, (const BlockDesc*)pl->items.p, max_items, (const int*)pl->n_items.p,
-                                            pl->f3, kp, (float*)pl->logmel.p, nullptr, nullptr, false, nullptr, pl->n_cu));
+    F3Launch redo = f3l;
+    redo.blocks = (const BlockDesc*)pl->items.p; redo.nblocks = max_items; redo.nblocks_dev = (const int*)pl->n_items.p;
+    TIMED(AFX_K_TRIM_BLOCKS, launch_frames3_any(redo));
     if (!fused_tail)
       TIMED(AFX_K_DCT, launch_dct(s, d_clips, d_info, pl->dt, kp, (const float*)pl->logmel.p, (float*)pl->mfcc.p, n, pl->max_tmax, true, true));
   } else {
@@ -605,9 +605,11 @@ static int chunk_enqueue(afx_plan* pl, const void* samples, int fmt, int mem_kin
       d_stamps = (unsigned long long*)pl->stamps.p;
       HIP_TRY(hipMemsetAsync(d_stamps, 0, (size_t)grid * kWaves * kStampPhases * 8, s));
     }
-    if (f3)
-      TIMED(AFX_K_FRAMES, launch_frames3_any(s, d_samples, d_info, (const BlockDesc*)pl->blocks.p, pl->nblocks, nullptr, pl->f3, kp,
-                                         (float*)pl->logmel.p, nullptr, nullptr, false, nullptr, pl->n_cu));
+    if (f3) {
+      F3Launch all = f3l;
+      all.blocks = (const BlockDesc*)pl->blocks.p; all.nblocks = pl->nblocks;
+      TIMED(AFX_K_FRAMES, launch_frames3_any(all));
+    }
     else
       TIMED(AFX_K_FRAMES, launch_frames(s, d_samples, d_info, (const BlockDesc*)pl->blocks.p, pl->nblocks,
                                         pl->dt, kp, (float*)pl->logmel.p, (float*)pl->rms.p, grid, d_stamps));

@@ -1,5 +1,6 @@
 // Device-visible structures and kernel launcher prototypes (host callable).
 #pragma once
+#include <cstddef>
 #include <cstdint>
 
 #include <hip/hip_runtime_api.h>
@@ -24,19 +25,40 @@ struct ClipDesc {
   int32_t pad_;
 };
 
-// One per 16-frame block of k_frames, written by k_trim_decide once the kept span is known,
-// so that k_frames needs a single 64-byte fetch per block (no dependent clip lookups).
-// Staged index j (0 .. 15*hop + n_fft) is sample g0 + j of the clip, g0 = start + t0*hop - n_fft/2.
+// One per 16-frame block of a frame kernel, so that the kernel needs a single 64-byte fetch per block (no dependent clip
+// lookups).  Producers: k_trim_decide (every block of a clip, once the kept span is known), k_build_blocks3 or the
+// host-built list of AFX_HOST_BLOCKS (the speculative pass's absolute blocks, nothing trimmed yet: the only records with
+// bsum_base / bsum_n set) and k_trim_decide3 (the redo items around a cut).  All of them go through make_block.
+// Staged index j (0 .. 15*hop + n_fft) is sample gs + j of the clip, gs = first frame * hop - n_fft/2 (+ start once trimmed).
 struct BlockDesc {
-  int64_t sample_base;   // element index of staged sample 0 in the packed buffer (clip off + g0)
-  int64_t frame_slot;    // clip frame_base + t0
+  int64_t sample_base;   // element index of staged sample 0 in the packed buffer (clip off + gs)
+  int64_t frame_slot;    // clip frame_base + first frame
   int64_t clip_off;      // element index of the clip's sample 0
   int32_t keep_lo, keep_hi;   // j kept by trim iff keep_lo <= j < keep_hi (else staged as zero)
-  int32_t have_lo, have_hi;   // sample exists iff have_lo <= j < have_hi   (have_lo = -g0)
+  int32_t have_lo, have_hi;   // sample exists iff have_lo <= j < have_hi   (have_lo = -gs)
   int32_t clip, t0, T, active;
-  int32_t pad_[2];
+  int32_t bsum_base;     // speculative pass: slot of the clip's first sub-block sum in bsum (tblk_base * rms_sub) ...
+  int32_t bsum_n;        // ... and how many the clip has; the wave-level frame kernels store sum j of the clip iff j < bsum_n
 };
 static_assert(sizeof(BlockDesc) == 64, "BlockDesc must be 64 bytes");
+static_assert(offsetof(BlockDesc, bsum_base) == 56 && offsetof(BlockDesc, bsum_n) == 60, "BlockDesc: the frame kernels read it as 16 dwords");
+
+// The record of the block whose staged sample 0 is sample gs of clip `clip` (record cd, N samples, kept span [start, end))
+// and whose first frame is `frame` of the clip's padded frame slots.  Spans are relative to gs, saturated at +-2^30.
+__host__ __device__ inline BlockDesc make_block(const ClipDesc& cd, int clip, int64_t gs, int64_t frame, int64_t start,
+                                                int64_t end, int64_t N, int t0, int T, bool active, int32_t bsum_base,
+                                                int32_t bsum_n) {
+  const int64_t lim = (int64_t)1 << 30;
+  auto rel = [&](int64_t x) { const int64_t r = x - gs; return (int32_t)(r < -lim ? -lim : (r > lim ? lim : r)); };
+  BlockDesc d;
+  d.sample_base = cd.off + gs; d.frame_slot = cd.frame_base + frame; d.clip_off = cd.off;
+  d.keep_lo = rel(start); d.keep_hi = rel(end);
+  d.have_lo = rel(0); d.have_hi = rel(N);
+  d.clip = clip; d.t0 = t0; d.T = T;
+  d.active = active ? 1 : 0;
+  d.bsum_base = bsum_base; d.bsum_n = bsum_n;
+  return d;
+}
 
 // Device-written, per clip (k_trim_decide), read by every later kernel.
 struct ClipInfo {
@@ -74,6 +96,24 @@ struct KParams {
   int32_t rms_sub;       // > 0: k_trim_blocks keeps sums per hop-sized sub-block (rms_sub per trim block) and
                          // k_trim_decide derives the RMS rows from them (the wave-level frame kernels); 0: the frame kernel computes RMS
 };
+
+// Raises a kernel's dynamic-LDS limit to `bytes` (the runtime refuses more than 64 KB unasked) ...
+template <typename K>
+inline hipError_t set_lds_limit(K kernel, size_t bytes) {
+  return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+}
+// ... and the same asked once per device and kernel, for the whole 160 KB of a CU (the attribute is per device:
+// batch_process drives every visible GPU from one process)
+template <auto Kernel>
+inline hipError_t allow_lds_once() {
+  static bool done[64] = {};
+  int dev = 0;
+  hipError_t e = hipGetDevice(&dev);
+  if (e != hipSuccess) return e;
+  if (dev < 0 || dev >= 64 || done[dev]) return hipSuccess;
+  if ((e = set_lds_limit(Kernel, 160 * 1024)) == hipSuccess) done[dev] = true;
+  return e;
+}
 
 // dynamic LDS bytes k_frames needs for (n_fft, hop); 0 if n_fft unsupported
 size_t frames_lds_bytes(int n_fft, int hop);

@@ -24,6 +24,7 @@
 #include <type_traits>
 
 #include "afx_f0.h"
+#include "afx_wave.h"
 
 namespace afx {
 
@@ -51,11 +52,6 @@ __device__ __forceinline__ double shfl_xor_d(double v, int m) {
   lo = __shfl_xor(lo, m); hi = __shfl_xor(hi, m);
   return __hiloint2double(hi, lo);
 }
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v += shfl_xor_d(v, o);
-  return v;
-}
 __device__ __forceinline__ double wave_min_d(double v) {
 #pragma unroll
   for (int o = 32; o >= 1; o >>= 1) v = fmin(v, shfl_xor_d(v, o));
@@ -70,11 +66,9 @@ __device__ __forceinline__ int lanes_below(unsigned long long mask) {       // s
   return __builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0));
 }
 
-// quad_perm / row_mirror / row_half_mirror only: every lane has a source, so bound_ctrl changes nothing but spares the
-// v_mov_b32 that would otherwise initialise the destination with the `old` value
-#define F0_DPP_I(v, ctrl) __builtin_amdgcn_update_dpp(0, (v), (ctrl), 0xf, 0xf, true)
+// quad_perm / row_mirror / row_half_mirror only: every lane has a source, so the DPP moves here set bound_ctrl (afx_wave.h)
 template <int CTRL> __device__ __forceinline__ double dpp_dd(double v) {
-  return __hiloint2double(F0_DPP_I(__double2hiint(v), CTRL), F0_DPP_I(__double2loint(v), CTRL));
+  return __hiloint2double(AFX_DPP_I(__double2hiint(v), CTRL, true), AFX_DPP_I(__double2loint(v), CTRL, true));
 }
 // max of two doubles that are never NaN, as the one instruction it is: fmax() makes the compiler quiet a possible signalling
 // NaN in every operand whose origin it cannot see (a v_max_f64 x, x, x in front of the real one -- for values read from LDS,
@@ -95,10 +89,10 @@ __device__ __forceinline__ double wave_max_dpp(double v) {         // uniform re
   return fmax(fmax(rl(0), rl(16)), fmax(rl(32), rl(48)));
 }
 __device__ __forceinline__ int wave_min_dpp(int v) {               // uniform result
-  v = min(v, F0_DPP_I(v, 0xB1));
-  v = min(v, F0_DPP_I(v, 0x4E));
-  v = min(v, F0_DPP_I(v, 0x141));
-  v = min(v, F0_DPP_I(v, 0x140));
+  v = min(v, AFX_DPP_I(v, 0xB1, true));
+  v = min(v, AFX_DPP_I(v, 0x4E, true));
+  v = min(v, AFX_DPP_I(v, 0x141, true));
+  v = min(v, AFX_DPP_I(v, 0x140, true));
   return min(min(__builtin_amdgcn_readlane(v, 0), __builtin_amdgcn_readlane(v, 16)),
              min(__builtin_amdgcn_readlane(v, 32), __builtin_amdgcn_readlane(v, 48)));
 }
@@ -893,7 +887,7 @@ __global__ __launch_bounds__(kVitThreads, 8) void k_f0_viterbi(const ClipDesc* _
     if (__popcll(at) == 1) bi = __builtin_amdgcn_readlane(bi, (int)__builtin_ctzll(at));
     else {
       int x = bv == m ? bi : (1 << 30);
-      x = min(x, F0_DPP_I(x, 0xB1)); x = min(x, F0_DPP_I(x, 0x4E)); x = min(x, F0_DPP_I(x, 0x141)); x = min(x, F0_DPP_I(x, 0x140));
+      x = min(x, AFX_DPP_I(x, 0xB1, true)); x = min(x, AFX_DPP_I(x, 0x4E, true)); x = min(x, AFX_DPP_I(x, 0x141, true)); x = min(x, AFX_DPP_I(x, 0x140, true));
       bi = __builtin_amdgcn_readlane(x, 0);
     }
     bv = m;
@@ -1389,7 +1383,7 @@ hipError_t launch_zcr(hipStream_t s, const float* ysig, const ClipDesc* clips, c
 template <typename K>
 static hipError_t allow_lds(K kernel, size_t bytes) {
   if (bytes <= 64 * 1024) return hipSuccess;
-  return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+  return set_lds_limit(kernel, bytes);
 }
 
 hipError_t launch_f0_energy(hipStream_t s, const float* ysig, const ClipDesc* clips, const ClipInfo* info,

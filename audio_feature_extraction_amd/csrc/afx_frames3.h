@@ -1,4 +1,5 @@
-// k_frames3 (afx_frames3.hip): tables, LDS geometry and launcher.  Internal to libafx.so.
+// The wave-level frame kernels (afx_frames3*.hip) and the trim kernels that go with them (afx_trim.hip): tables, LDS
+// geometry and launchers.  Internal to libafx.so.
 #pragma once
 #include <cstdint>
 #include <vector>
@@ -50,23 +51,39 @@ void build_f3_mel(const std::vector<float>& mel_dense, int n_mels, int n_bins, i
 size_t frames3_lds_bytes(int waves, const F3Tables& ft);
 bool frames3_eligible(const KParams& kp, const F3Tables& ft);
 int frames3_waves(const F3Tables& ft);
-// spec = true: the speculative first launch over the host-built absolute blocks (emits bsum / blockmax);
-// spec = false: blocks come from a device-built list whose length is *nblocks_dev (nblocks = its capacity).
+// One launch of a wave-level frame kernel.  spec = true: the speculative first launch over every absolute block of every clip
+// (emits bsum / blockmax); spec = false: a list launch -- when nblocks_dev is set the blocks come from a device-built list
+// whose length is *nblocks_dev (nblocks = its capacity).
 // work_ctr: a zeroed device int -> the waves take the second half of the list by ticket (runs that shrink towards the
 // end) instead of equal shares; nullptr -> equal contiguous shares
-hipError_t launch_frames3(hipStream_t s, const void* samples, ClipInfo* info, const BlockDesc* blocks, int nblocks,
-                          const int* nblocks_dev, const F3Tables& ft, const KParams& kp, float* logmel,
-                          float* blockmax, float* bsum, bool spec, int* work_ctr, int n_cu);
-// the same for n_fft 2048 / hop 512 (afx_frames3s.hip: one frame per FFT, real-FFT split) and n_fft 512 / hop 128
-// (afx_frames3d.hip: two frame pairs per wave)
+struct F3Launch {
+  hipStream_t s;
+  const void* samples;
+  ClipInfo* info;
+  const F3Tables& ft;
+  const KParams& kp;
+  float* logmel;
+  int n_cu;
+  const BlockDesc* blocks = nullptr;
+  int nblocks = 0;
+  const int* nblocks_dev = nullptr;
+  float* blockmax = nullptr;
+  float* bsum = nullptr;
+  bool spec = false;
+  int* work_ctr = nullptr;
+};
+inline int f3_grid(const F3Launch& L, int waves) {      // one workgroup per CU at most, a block per wave at least
+  const int want = (L.nblocks + waves - 1) / waves;
+  return want < 1 ? 1 : (want < L.n_cu ? want : L.n_cu);
+}
+// n_fft 1024 / hop 256 (afx_frames3.hip), n_fft 2048 / hop 512 (afx_frames3s.hip: one frame per FFT, real-FFT split) and
+// n_fft 512 / hop 128 (afx_frames3d.hip: two frame pairs per wave); launch_frames3_any dispatches on kp.n_fft
 size_t frames3s_lds_bytes(int waves, const F3Tables& ft);
 size_t frames3d_lds_bytes(int waves, const F3Tables& ft);
-hipError_t launch_frames3s(hipStream_t s, const void* samples, ClipInfo* info, const BlockDesc* blocks, int nblocks,
-                           const int* nblocks_dev, const F3Tables& ft, const KParams& kp, float* logmel,
-                           float* blockmax, float* bsum, bool spec, int* work_ctr, int n_cu);
-hipError_t launch_frames3d(hipStream_t s, const void* samples, ClipInfo* info, const BlockDesc* blocks, int nblocks,
-                           const int* nblocks_dev, const F3Tables& ft, const KParams& kp, float* logmel,
-                           float* blockmax, float* bsum, bool spec, int* work_ctr, int n_cu);
+hipError_t launch_frames3(const F3Launch& L);
+hipError_t launch_frames3s(const F3Launch& L);
+hipError_t launch_frames3d(const F3Launch& L);
+hipError_t launch_frames3_any(const F3Launch& L);
 // spectral descriptors (k_frames3s<DESC>): librosa.feature.spectral_contrast's octave bands as bin ranges [lo, hi] of the
 // sub-band and the number of magnitudes averaged at either end
 struct SpecBands {
@@ -77,10 +94,6 @@ constexpr int kSpecFloats = 17;            // per frame: centroid, bandwidth, ro
 hipError_t launch_spectral(hipStream_t s, const void* samples, ClipInfo* info, const BlockDesc* blocks, int nblocks,
                            const F3Tables& ft, const KParams& kp, float* desc_out, const int64_t* desc_offs,
                            const SpecBands& sb, int n_cu);
-// dispatch on kp.n_fft
-hipError_t launch_frames3_any(hipStream_t s, const void* samples, ClipInfo* info, const BlockDesc* blocks, int nblocks,
-                              const int* nblocks_dev, const F3Tables& ft, const KParams& kp, float* logmel,
-                              float* blockmax, float* bsum, bool spec, int* work_ctr, int n_cu);
 // the speculative launch's block list (every absolute 16-frame block of every clip) from the clip records, on the device
 hipError_t launch_build_blocks3(hipStream_t s, const ClipDesc* clips, int n_clips, int nblocks, BlockDesc* blocks,
                                 const KParams& kp);

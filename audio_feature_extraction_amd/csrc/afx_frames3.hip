@@ -78,7 +78,7 @@ __global__ __launch_bounds__(WAVES * 64) void k_frames3(const void* __restrict__
                                                         int* __restrict__ work_ctr) {
   constexpr int N = 1024, HOP = 256;
   extern __shared__ __attribute__((aligned(16))) float smem[];
-  if (nblocks_dev) {                       // the list launch: an empty list (nothing was trimmed) costs no table set-up
+  if (nblocks_dev) {
     nblocks = *nblocks_dev;
     if (nblocks <= 0) return;
   }
@@ -146,16 +146,7 @@ __global__ __launch_bounds__(WAVES * 64) void k_frames3(const void* __restrict__
   v2* const ea = E + lane;                 // pass-3 reads of butterfly ja; power-spectrum bins lane + 128 s
   v2* const eb = E + jb;                   // butterfly jb; bins jb + 384 - 128 (s - 4)
 
-  auto raw_ld = [&](int64_t idx) -> float {
-    if constexpr (FMT == AFX_FMT_S16) return (float)((const int16_t*)samples)[idx] * (1.0f / 32768.0f);
-    else return ((const float*)samples)[idx];
-  };
-  // row loads of interior pairs: wave-uniform base pointer + 32-bit lane offset (global_load ... s[base] offset:imm)
-  typedef typename std::conditional<FMT == AFX_FMT_S16, int16_t, float>::type sample_t;
-  auto row_ld = [&](const sample_t* base, unsigned idx) -> float {
-    if constexpr (FMT == AFX_FMT_S16) return (float)base[idx] * (1.0f / 32768.0f);
-    else return base[idx];
-  };
+  using sample_t = sample_of<FMT>;
   const int n_rounds = mel_rounds;
   const int meta0 = MM[lane], meta1 = MM[64 + lane];       // straight-line schedule: the lane's two filters
   const unsigned mf0 = (meta0 >> 11) & 511, mf1 = (meta1 >> 11) & 511;
@@ -180,7 +171,7 @@ __global__ __launch_bounds__(WAVES * 64) void k_frames3(const void* __restrict__
   };
   auto sub_store = [&](const BlockDesc& bd) {
     const int j = bd.t0 + lane;
-    if (((bsmask >> lane) & 1) && j < bd.pad_[1]) bsum[bd.pad_[0] + j] = bs;
+    if (((bsmask >> lane) & 1) && j < bd.bsum_n) bsum[bd.bsum_base + j] = bs;
     bsmask = 0;
   };
 
@@ -227,12 +218,12 @@ __global__ __launch_bounds__(WAVES * 64) void k_frames3(const void* __restrict__
       const BlockDesc& bd = blocks[f3_opaque(b)];
       const int lo = bd.have_lo, hi = bd.have_hi - 1;
       const int jc = j < lo ? lo : (j > hi ? hi : j), jp = (j - 1) < lo ? lo : ((j - 1) > hi ? hi : (j - 1));
-      const float y = (jc == j) ? raw_ld(sbase + jc) : 0.f;
-      const float yp = (jp == j - 1) ? raw_ld(sbase + jp) : 0.f;
+      const float y = (jc == j) ? ld_raw<FMT>(samples, sbase + jc) : 0.f;
+      const float yp = (jp == j - 1) ? ld_raw<FMT>(samples, sbase + jp) : 0.f;
       float v = y;
       if (pre) {
-        v = f3_pre1(y, yp, b1);
-        if (j == lo) v = f3_pre0(raw_ld(bd.clip_off), raw_ld(bd.clip_off + 1));   // clip sample 0
+        v = preemph1(y, yp, b1);
+        if (j == lo) v = preemph0(ld_raw<FMT>(samples, bd.clip_off), ld_raw<FMT>(samples, bd.clip_off + 1));   // clip sample 0
       }
       return (j >= bd.keep_lo && j < bd.keep_hi) ? v : 0.f;
     };
@@ -243,9 +234,9 @@ __global__ __launch_bounds__(WAVES * 64) void k_frames3(const void* __restrict__
       if (interior(0, N + HOP)) {
         float y[20], yp[20];
 #pragma unroll
-        for (int u = 0; u < 20; ++u) { y[u] = row_ld(sp, 64 * u + lane); yp[u] = row_ld(sp - 1, 64 * u + lane); }
+        for (int u = 0; u < 20; ++u) { y[u] = ld_row<FMT>(sp, 64 * u + lane); yp[u] = ld_row<FMT>(sp - 1, 64 * u + lane); }
 #pragma unroll
-        for (int u = 0; u < 20; ++u) rows[u] = f3_pre1(y[u], yp[u], b1);
+        for (int u = 0; u < 20; ++u) rows[u] = preemph1(y[u], yp[u], b1);
       } else {
 #pragma unroll 1
         for (int u = 0; u < 20; ++u) XB[64 * u + lane] = edge_sample(64 * u + lane);
@@ -360,7 +351,7 @@ __global__ __launch_bounds__(WAVES * 64) void k_frames3(const void* __restrict__
       float ny[8], nyp[8];
       if (nint) {
 #pragma unroll
-        for (int u = 0; u < 8; ++u) { ny[u] = row_ld(sp + jn, 64 * u + lane); nyp[u] = row_ld(sp + jn - 1, 64 * u + lane); }
+        for (int u = 0; u < 8; ++u) { ny[u] = ld_row<FMT>(sp + jn, 64 * u + lane); nyp[u] = ld_row<FMT>(sp + jn - 1, 64 * u + lane); }
       }
       // ---- mel + dB
       // The kernel waits on the LDS pipe (SQ_WAIT_INST_LDS is a quarter of a wave's life); a wave in the mel phase -- 27 reads
@@ -434,9 +425,9 @@ __global__ __launch_bounds__(WAVES * 64) void k_frames3(const void* __restrict__
         F3_BATCH(0) F3_BATCH(1) F3_BATCH(2) F3_BATCH(3) F3_BATCH(4) F3_BATCH(5) F3_BATCH(6) F3_BATCH(7)
 #undef F3_BATCH
         v2 acc = a0 + a1;
-        if (wd >= 2) { acc.x += F3_DPP(acc.x, 0xB1); acc.y += F3_DPP(acc.y, 0xB1); }       // lane ^ 1
-        if (wd >= 4) { acc.x += F3_DPP(acc.x, 0x4E); acc.y += F3_DPP(acc.y, 0x4E); }       // lane ^ 2
-        if (wd >= 8) { acc.x += F3_DPP(acc.x, 0x141); acc.y += F3_DPP(acc.y, 0x141); }     // the other quad of 8
+        if (wd >= 2) { acc.x += AFX_DPP_F(acc.x, 0xB1, false); acc.y += AFX_DPP_F(acc.y, 0xB1, false); }       // lane ^ 1
+        if (wd >= 4) { acc.x += AFX_DPP_F(acc.x, 0x4E, false); acc.y += AFX_DPP_F(acc.y, 0x4E, false); }       // lane ^ 2
+        if (wd >= 8) { acc.x += AFX_DPP_F(acc.x, 0x141, false); acc.y += AFX_DPP_F(acc.y, 0x141, false); }     // the other quad of 8
         const float L0 = 3.01029995663981195f * __builtin_amdgcn_logf(f3_max(acc.x, amin));
         const float L1 = 3.01029995663981195f * __builtin_amdgcn_logf(f3_max(acc.y, amin));
         if (meta & (1 << 20)) {                               // this lane owns filter m
@@ -455,7 +446,7 @@ __global__ __launch_bounds__(WAVES * 64) void k_frames3(const void* __restrict__
         float n[8];
         if (nint) {
 #pragma unroll
-          for (int u = 0; u < 8; ++u) n[u] = f3_pre1(ny[u], nyp[u], b1);
+          for (int u = 0; u < 8; ++u) n[u] = preemph1(ny[u], nyp[u], b1);
         } else {
           // (the rare path: its sample indices are rebuilt from an opaque copy of jn, or the compiler carries three
           // lane-indexed induction registers through every pair for it)
@@ -486,15 +477,10 @@ __global__ __launch_bounds__(WAVES * 64) void k_frames3(const void* __restrict__
     }
     // ---- clip maximum of the log-mel (power_to_db's top_db reference)
     {
-      float v = lmax;
-      v = f3_max(v, F3_DPP(v, 0xB1)); v = f3_max(v, F3_DPP(v, 0x4E)); v = f3_max(v, F3_DPP(v, 0x141)); v = f3_max(v, F3_DPP(v, 0x140));
-      const int vi = __float_as_int(v);
-      const float r0 = __int_as_float(__builtin_amdgcn_readlane(vi, 0)), r1 = __int_as_float(__builtin_amdgcn_readlane(vi, 16));
-      const float r2 = __int_as_float(__builtin_amdgcn_readlane(vi, 32)), r3 = __int_as_float(__builtin_amdgcn_readlane(vi, 48));
-      const float mx = fmaxf(fmaxf(r0, r1), fmaxf(r2, r3));
+      const float mx = f3_wave_max(lmax);
       const BlockDesc& be = blocks[f3_opaque(b)];          // read again: see interior_r
       if constexpr (SPEC) { if (lane == 0) blockmax[b] = mx; sub_store(be); }
-      else { if (lane == 0 && mx > -INFINITY) atomicMax(&info[be.clip].lmax_ord, f3_ord(mx)); }
+      else { if (lane == 0 && mx > -INFINITY) atomicMax(&info[be.clip].lmax_ord, f2ord(mx)); }
     }
 #ifdef AFX_F3_DEBUG
     if (SPEC && lane == 0 && b < 65536) g_f3_blk[b] = wall_clock64();
@@ -524,180 +510,6 @@ extern "C" __attribute__((visibility("default"))) int afx_debug_f3_blocks(unsign
 }
 #endif
 
-
-// ---------------------------------------------------------------------------
-// k_trim_decide3: the trim decision AFTER the speculative frame pass.  One workgroup per clip:
-//   * librosa.effects.trim(top_db) on the sub-block sums k_frames3<SPEC> left in bsum (feature_extractor.py:72), exactly
-//     as k_trim_decide does it -> [start, end), T, status; RMS rows from the same sums (:164);
-//   * the clip's log-mel maximum (power_to_db's top_db reference) over the blocks the cut leaves untouched;
-//   * the frames the cut does touch -- the two frames whose window crosses `start`, the two that cross `end`, and
-//     the rest of their 16-frame blocks (a block maximum cannot be taken apart) -- as a list of up to-16-frame items
-//     for the second k_frames3 launch.
-// Frame t of the trimmed clip is absolute frame start / hop + t: later kernels read the spill at that offset.
-// ---------------------------------------------------------------------------
-__device__ __forceinline__ float td3_frame_rms(const float* bs, int64_t t, int64_t nb, int half, int per, float inv_n) {
-  float s = 0.f;
-  for (int64_t b = (t - half) * per; b < (t + half) * per; ++b)
-    if (b >= 0 && b < nb * per) s += bs[b];
-  return sqrtf(s * inv_n);
-}
-
-__global__ __launch_bounds__(256) void k_trim_decide3(const ClipDesc* __restrict__ clips, ClipInfo* __restrict__ info,
-                                                      const float* __restrict__ bsum, const float* __restrict__ blockmax,
-                                                      BlockDesc* __restrict__ items, int* __restrict__ n_items, int max_items,
-                                                      float* __restrict__ rms_rows, KParams kp) {
-  __shared__ float red_f[4];
-  __shared__ long long red_a[4], red_b[4];
-  const int clip = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const ClipDesc cd = clips[clip];
-  const int64_t N = cd.len;
-  const uint32_t nonfinite = info[clip].nonfinite;
-  int status = AFX_CLIP_OK;
-  if (N < 2) status = AFX_CLIP_TOO_SHORT;
-  else if (nonfinite) status = AFX_CLIP_NONFINITE;
-  int64_t start = 0, end = N;
-  const int per = kp.rms_sub;
-  auto wave_maxf = [&](float v) {
-    v = fmaxf(v, F3_DPP(v, 0xB1)); v = fmaxf(v, F3_DPP(v, 0x4E)); v = fmaxf(v, F3_DPP(v, 0x141)); v = fmaxf(v, F3_DPP(v, 0x140));
-    const int vi = __float_as_int(v);
-    return fmaxf(fmaxf(__int_as_float(__builtin_amdgcn_readlane(vi, 0)), __int_as_float(__builtin_amdgcn_readlane(vi, 16))),
-                 fmaxf(__int_as_float(__builtin_amdgcn_readlane(vi, 32)), __int_as_float(__builtin_amdgcn_readlane(vi, 48))));
-  };
-  if ((kp.flags & AFX_FLAG_TRIM) && status == AFX_CLIP_OK) {   // uniform per workgroup
-    const int th = kp.trim_hop, half = (kp.trim_frame / th) / 2;
-    const int64_t nb = (N + th - 1) / th, nt = 1 + N / th;
-    const float inv_n = 1.0f / (float)kp.trim_frame;
-    const float* bs = bsum + cd.tblk_base * per;
-    float mx = 0.f;
-    for (int64_t t = tid; t < nt; t += 256) mx = fmaxf(mx, td3_frame_rms(bs, t, nb, half, per, inv_n));
-    mx = wave_maxf(mx);
-    if (lane == 0) red_f[wave] = mx;
-    __syncthreads();
-    mx = fmaxf(fmaxf(red_f[0], red_f[1]), fmaxf(red_f[2], red_f[3]));
-    __syncthreads();
-    const float ref_db = 10.0f * log10f(fmaxf(1e-10f, mx * mx));      // amplitude_to_db(mse, ref=np.max, amin=1e-5, top_db=None)
-    long long first = (long long)1 << 62, last = -1;
-    for (int64_t t = tid; t < nt; t += 256) {
-      const float r = td3_frame_rms(bs, t, nb, half, per, inv_n);
-      const float db = 10.0f * log10f(fmaxf(1e-10f, r * r)) - ref_db;
-      if (db > -kp.trim_top_db) { if (t < first) first = t; if (t > last) last = t; }
-    }
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) {
-      const long long f2 = __shfl_xor(first, o), l2 = __shfl_xor(last, o);
-      first = f2 < first ? f2 : first; last = l2 > last ? l2 : last;
-    }
-    if (lane == 0) { red_a[wave] = first; red_b[wave] = last; }
-    __syncthreads();
-    first = red_a[0]; last = red_b[0];
-#pragma unroll
-    for (int w = 1; w < 4; ++w) { first = red_a[w] < first ? red_a[w] : first; last = red_b[w] > last ? red_b[w] : last; }
-    if (last >= 0) { start = first * th; end = (last + 1) * th < N ? (last + 1) * th : N; }
-    else { start = 0; end = 0; }
-  }
-  const int hop = kp.hop;
-  const int T = (int)(1 + (end - start) / hop);
-  if (status == AFX_CLIP_OK && T < 9) status = AFX_CLIP_TOO_SHORT;   // librosa.feature.delta width 9
-  // ---- which blocks of the speculative pass stand
-  const int g0 = (int)(start / hop), glast = g0 + T - 1;
-  const int nblk = cd.tpad / kFramesPerBlock;
-  const bool cutL = start > 0, cutR = end < N;
-  const int bLo = cutL ? (g0 + 2 + 15) >> 4 : 0;
-  const int bHi = cutR ? (glast >= 17 ? (glast - 17) >> 4 : -1) : nblk - 1;
-  float cm = -INFINITY;
-  if (status == AFX_CLIP_OK)
-    for (int b = bLo + tid; b <= bHi; b += 256) cm = fmaxf(cm, blockmax[cd.blk_base + b]);
-  cm = wave_maxf(cm);
-  if (lane == 0) red_f[wave] = cm;
-  __syncthreads();
-  cm = fmaxf(fmaxf(red_f[0], red_f[1]), fmaxf(red_f[2], red_f[3]));
-  if (tid == 0) {
-    ClipInfo ci;
-    ci.start = start; ci.end = end; ci.T = T; ci.status = status;
-    ci.lmax_ord = cm > -INFINITY ? f3_ord(cm) : 0u;
-    ci.nonfinite = nonfinite;
-    info[clip] = ci;
-    // ---- frames to redo: [g0, 16 bLo) on a cut left side, [16 (bHi + 1), glast] on a cut right side
-    if (status == AFX_CLIP_OK && (cutL || cutR)) {
-      int r0[2], r1[2], nr = 0;
-      if (bLo > bHi) { r0[0] = g0; r1[0] = glast + 1; nr = 1; }
-      else {
-        if (cutL && 16 * bLo > g0) { r0[nr] = g0; r1[nr] = 16 * bLo < glast + 1 ? 16 * bLo : glast + 1; ++nr; }
-        if (cutR && 16 * (bHi + 1) <= glast) { r0[nr] = 16 * (bHi + 1) > g0 ? 16 * (bHi + 1) : g0; r1[nr] = glast + 1; ++nr; }
-      }
-      int cnt = 0;
-      for (int r = 0; r < nr; ++r) cnt += (r1[r] - r0[r] + 15) / 16;
-      if (cnt > 0) {
-        const int at = atomicAdd(n_items, cnt);
-        int k = 0;
-        const int64_t lim = (int64_t)1 << 30;
-        for (int r = 0; r < nr; ++r)
-          for (int gf = r0[r]; gf < r1[r]; gf += 16, ++k) {
-            if (at + k >= max_items) break;                 // cannot happen: the list holds 6 items per clip
-            const int nfr = r1[r] - gf < 16 ? r1[r] - gf : 16;
-            const int64_t gs = (int64_t)gf * hop - kp.n_fft / 2;
-            auto rel = [&](int64_t x) { const int64_t q = x - gs; return (int32_t)(q < -lim ? -lim : (q > lim ? lim : q)); };
-            BlockDesc d;
-            d.sample_base = cd.off + gs; d.frame_slot = cd.frame_base + gf; d.clip_off = cd.off;
-            d.keep_lo = rel(start); d.keep_hi = rel(end); d.have_lo = rel(0); d.have_hi = rel(N);
-            d.clip = clip; d.t0 = 0; d.T = nfr; d.active = 1; d.pad_[0] = 0; d.pad_[1] = 0;
-            items[at + k] = d;
-          }
-      }
-    }
-  }
-  // ---- RMS rows from the sub-block sums (feature_extractor.py:164, librosa.feature.rms center=True), trimmed frame index
-  if (rms_rows && (status == AFX_CLIP_OK || (status == AFX_CLIP_TOO_SHORT && N >= 2))) {      // extract_energy needs no delta
-    const float* bs = bsum + cd.tblk_base * per;
-    const int64_t s_lo = start / hop, s_hi = (end + hop - 1) / hop;
-    const int nsb = kp.n_fft / hop, back = nsb / 2;
-    const float inv_n = 1.0f / (float)kp.n_fft;
-    for (int t = tid; t < T; t += 256) {
-      float sacc = 0.f;
-      for (int k = 0; k < nsb; ++k) {
-        const int64_t sb = s_lo + t - back + k;
-        if (sb >= s_lo && sb < s_hi) sacc += bs[sb];
-      }
-      rms_rows[cd.frame_base + t] = sqrtf(sacc * inv_n);
-    }
-  }
-}
-
-// ---------------------------------------------------------------------------
-// k_build_blocks3: the speculative launch's block list, built on the device from the batch's clip records.
-// reference call site: audio_feature_extraction_toolkit/core/feature_extractor.py:228-235 -- batch_process never sees the
-// same clip lengths twice, so nothing per batch may be built block by block on the host: the host uploads one 48-byte
-// ClipDesc per clip and this kernel writes the 64-byte record of every absolute 16-frame block (one wave per clip).  54 000 records (3.5 MB) for 1000 ten-second clips.
-// ---------------------------------------------------------------------------
-__global__ __launch_bounds__(64) void k_build_blocks3(const ClipDesc* __restrict__ clips, int n_clips,
-                                                      BlockDesc* __restrict__ blocks, int n_fft, int hop, int trim_hop, int per) {
-  // one wave per clip: its record is read once (scalar), its blocks written lane by lane -- no search for the clip of a block
-  const int clip = blockIdx.x;
-  if (clip >= n_clips) return;
-  const ClipDesc c = clips[clip];
-  const int nb = c.tpad / kFramesPerBlock;
-  const int64_t lim = (int64_t)1 << 30;
-  const int64_t ntb = (c.len + trim_hop - 1) / trim_hop;
-  for (int b = threadIdx.x; b < nb; b += 64) {
-    const int64_t gs = (int64_t)b * kFramesPerBlock * hop - n_fft / 2;       // clip sample of staged index 0
-    auto rel = [&](int64_t x) { const int64_t q = x - gs; return (int32_t)(q < -lim ? -lim : (q > lim ? lim : q)); };
-    BlockDesc d;
-    d.sample_base = c.off + gs; d.frame_slot = c.frame_base + (int64_t)b * kFramesPerBlock; d.clip_off = c.off;
-    d.keep_lo = rel(0); d.keep_hi = rel(c.len); d.have_lo = d.keep_lo; d.have_hi = d.keep_hi;
-    d.clip = clip; d.t0 = b * kFramesPerBlock; d.T = c.tmax; d.active = (c.len >= 2 && d.t0 < c.tmax) ? 1 : 0;
-    d.pad_[0] = (int32_t)(c.tblk_base * per); d.pad_[1] = (int32_t)(ntb * per);
-    blocks[c.blk_base + b] = d;
-  }
-}
-
-hipError_t launch_build_blocks3(hipStream_t s, const ClipDesc* clips, int n_clips, int nblocks, BlockDesc* blocks,
-                                const KParams& kp) {
-  if (nblocks <= 0 || n_clips <= 0) return hipSuccess;
-  hipLaunchKernelGGL(k_build_blocks3, dim3(n_clips), dim3(64), 0, s, clips, n_clips, blocks,
-                     kp.n_fft, kp.hop, kp.trim_hop, kp.rms_sub);
-  return hipGetLastError();
-}
-
 bool frames3_eligible(const KParams& kp, const F3Tables& ft) {
   const int per = kp.hop > 0 ? kp.trim_hop / kp.hop : 0;
   if (!(ft.mel_rounds > 0 && kp.n_mels <= 512 && kp.hop > 0 && kp.trim_hop % kp.hop == 0 && per >= 1 && per <= 4) ||
@@ -709,12 +521,10 @@ bool frames3_eligible(const KParams& kp, const F3Tables& ft) {
   return false;
 }
 
-hipError_t launch_frames3_any(hipStream_t s, const void* samples, ClipInfo* info, const BlockDesc* blocks, int nblocks,
-                              const int* nblocks_dev, const F3Tables& ft, const KParams& kp, float* logmel,
-                              float* blockmax, float* bsum, bool spec, int* work_ctr, int n_cu) {
-  if (kp.n_fft == 2048) return launch_frames3s(s, samples, info, blocks, nblocks, nblocks_dev, ft, kp, logmel, blockmax, bsum, spec, work_ctr, n_cu);
-  if (kp.n_fft == 512) return launch_frames3d(s, samples, info, blocks, nblocks, nblocks_dev, ft, kp, logmel, blockmax, bsum, spec, work_ctr, n_cu);
-  return launch_frames3(s, samples, info, blocks, nblocks, nblocks_dev, ft, kp, logmel, blockmax, bsum, spec, work_ctr, n_cu);
+hipError_t launch_frames3_any(const F3Launch& L) {
+  if (L.kp.n_fft == 2048) return launch_frames3s(L);
+  if (L.kp.n_fft == 512) return launch_frames3d(L);
+  return launch_frames3(L);
 }
 
 int frames3_waves(const F3Tables& ft) {
@@ -724,57 +534,33 @@ int frames3_waves(const F3Tables& ft) {
 }
 
 template <int FMT, int WAVES, int NB0, int NB1, bool SPEC>
-static hipError_t launch_frames3_t(hipStream_t s, const void* samples, ClipInfo* info, const BlockDesc* blocks,
-                                   int nblocks, const int* nblocks_dev, const F3Tables& ft, const KParams& kp,
-                                   float* logmel, float* blockmax, float* bsum, int* work_ctr, int n_cu) {
-  static bool attr_set[64] = {};
-  int dev = 0;
-  hipError_t e = hipGetDevice(&dev);
+static hipError_t launch_frames3_t(const F3Launch& L) {
+  const hipError_t e = allow_lds_once<k_frames3<FMT, WAVES, NB0, NB1, SPEC>>();
   if (e != hipSuccess) return e;
-  if (dev >= 0 && dev < 64 && !attr_set[dev]) {
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_frames3<FMT, WAVES, NB0, NB1, SPEC>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) return e;
-    attr_set[dev] = true;
-  }
-  const int grid = std::max(1, std::min(n_cu, (nblocks + WAVES - 1) / WAVES));
-  hipLaunchKernelGGL((k_frames3<FMT, WAVES, NB0, NB1, SPEC>), dim3(grid), dim3(WAVES * 64), frames3_lds_bytes(WAVES, ft), s,
-                     samples, info, blocks, nblocks, nblocks_dev, ft, kp, logmel, blockmax, bsum, work_ctr);
+  hipLaunchKernelGGL((k_frames3<FMT, WAVES, NB0, NB1, SPEC>), dim3(f3_grid(L, WAVES)), dim3(WAVES * 64), frames3_lds_bytes(WAVES, L.ft), L.s,
+                     L.samples, L.info, L.blocks, L.nblocks, L.nblocks_dev, L.ft, L.kp, L.logmel, L.blockmax, L.bsum, L.work_ctr);
   return hipGetLastError();
 }
 
 template <int FMT, int WAVES, bool SPEC>
-static hipError_t launch_frames3_w(hipStream_t s, const void* samples, ClipInfo* info, const BlockDesc* blocks,
-                                   int nblocks, const int* nblocks_dev, const F3Tables& ft, const KParams& kp,
-                                   float* logmel, float* blockmax, float* bsum, int* work_ctr, int n_cu) {
+static hipError_t launch_frames3_w(const F3Launch& L) {
+  const F3Tables& ft = L.ft;
   // straight-line mel schedules compiled in: two rounds of width 1
   const bool two = ft.mel_rounds == 2 && ((ft.mel_rp[0] >> 4) & 15) == 1 && ((ft.mel_rp[1] >> 4) & 15) == 1 && ft.mel_all_own &&
                    ft.mel_wfloats == (int)((ft.mel_rp[0] & 15) + (ft.mel_rp[1] & 15)) * 256 && (ft.mel_rp[1] >> 8) == (ft.mel_rp[0] & 15) * 256 &&
                    !dev_env().f3_generic_mel;
   const int nb0 = ft.mel_rp[0] & 15, nb1 = ft.mel_rp[1] & 15;
   if (two && nb0 == 2 && nb1 == 7)
-    return launch_frames3_t<FMT, WAVES, 2, 7, SPEC>(s, samples, info, blocks, nblocks, nblocks_dev, ft, kp, logmel, blockmax, bsum, work_ctr, n_cu);
-  return launch_frames3_t<FMT, WAVES, 0, 0, SPEC>(s, samples, info, blocks, nblocks, nblocks_dev, ft, kp, logmel, blockmax, bsum, work_ctr, n_cu);
+    return launch_frames3_t<FMT, WAVES, 2, 7, SPEC>(L);
+  return launch_frames3_t<FMT, WAVES, 0, 0, SPEC>(L);
 }
 
-// spec: the speculative first launch (host-built blocks; emits bsum / blockmax); otherwise the list launch
-hipError_t launch_frames3(hipStream_t s, const void* samples, ClipInfo* info, const BlockDesc* blocks, int nblocks,
-                          const int* nblocks_dev, const F3Tables& ft, const KParams& kp, float* logmel,
-                          float* blockmax, float* bsum, bool spec, int* work_ctr, int n_cu) {
-  const int waves = frames3_waves(ft);
-#define AFX_F3_GO(FMT, W)                                                                                                   \
-  (spec ? launch_frames3_w<FMT, W, true>(s, samples, info, blocks, nblocks, nblocks_dev, ft, kp, logmel, blockmax, bsum, work_ctr, n_cu) \
-        : launch_frames3_w<FMT, W, false>(s, samples, info, blocks, nblocks, nblocks_dev, ft, kp, logmel, blockmax, bsum, work_ctr, n_cu))
-  if (kp.fmt == AFX_FMT_S16) return waves == 16 ? AFX_F3_GO(AFX_FMT_S16, 16) : AFX_F3_GO(AFX_FMT_S16, 12);
+hipError_t launch_frames3(const F3Launch& L) {
+  const int waves = frames3_waves(L.ft);
+#define AFX_F3_GO(FMT, W) (L.spec ? launch_frames3_w<FMT, W, true>(L) : launch_frames3_w<FMT, W, false>(L))
+  if (L.kp.fmt == AFX_FMT_S16) return waves == 16 ? AFX_F3_GO(AFX_FMT_S16, 16) : AFX_F3_GO(AFX_FMT_S16, 12);
   return waves == 16 ? AFX_F3_GO(AFX_FMT_F32, 16) : AFX_F3_GO(AFX_FMT_F32, 12);
 #undef AFX_F3_GO
-}
-
-hipError_t launch_trim_decide3(hipStream_t s, const ClipDesc* clips, ClipInfo* info, const float* bsum, const float* blockmax,
-                               BlockDesc* items, int* n_items, int max_items, float* rms_rows, int n_clips, const KParams& kp) {
-  hipLaunchKernelGGL(k_trim_decide3, dim3(n_clips), dim3(256), 0, s, clips, info, bsum, blockmax, items, n_items, max_items,
-                     rms_rows, kp);
-  return hipGetLastError();
 }
 
 }  // namespace afx

@@ -1,10 +1,15 @@
 // Device-side building blocks shared by the wave-level frame kernels (afx_frames3*.hip): packed-f32 helpers with
-// VOP3P source modifiers, the radix-4 / 8 / 16 butterflies, pre-emphasis as scipy.signal.lfilter rounds it.
+// VOP3P source modifiers, the radix-4 / 8 / 16 butterflies, which blocks a wave works on, and the scaffolding the three
+// kernels have in common around their FFTs (edge samples, block maximum).
 // Include from .hip files only.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+
+#include "afx_device.h"
+#include "afx_frames3.h"
+#include "afx_wave.h"
 
 namespace afx {
 
@@ -161,21 +166,6 @@ __device__ __forceinline__ void f3_dft16(v2* x, const v2 H, const v2 W1, const v
   }
 }
 
-__device__ __forceinline__ float f3_pre1(float y, float prev, float b1) {     // as scipy.signal.lfilter rounds it
-#pragma clang fp contract(off)
-  const float p = b1 * prev;
-  return y + p;
-}
-__device__ __forceinline__ float f3_pre0(float y0, float y1) {                // librosa's zi = 2 y0 - y1
-#pragma clang fp contract(off)
-  const float t = 2.0f * y0;
-  const float zi = t - y1;
-  return zi + y0;
-}
-__device__ __forceinline__ uint32_t f3_ord(float f) {
-  const uint32_t u = __float_as_uint(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
 // a wave-uniform value the optimizer may not trace back to its definition (no strength reduction across loop trips)
 __device__ __forceinline__ int f3_opaque(int x) { asm volatile("" : "+s"(x)); return x; }
 // timing-only ablation switches (libafx built with -DAFX_F3_DEBUG, AFX_DEBUG_SKIP bits << 8 in kp.flags); results invalid
@@ -226,8 +216,6 @@ __device__ __forceinline__ bool f3_runs_next(F3Runs& r, int* work_ctr, int nbloc
   return true;
 }
 
-#define F3_DPP(v, ctrl) __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), (ctrl), 0xf, 0xf, false))
-
 // v[lane] + v[lane ^ 16] and v[lane] + v[lane ^ 32] by gfx950's row / half swaps (one swap + one add each)
 __device__ __forceinline__ float f3_add_xor16(float v) {
   const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
@@ -245,12 +233,33 @@ __device__ __forceinline__ float f3_sel(float a, float b, unsigned long long mas
 // Two wave-wide sums at once: returns a register whose odd lanes all hold sum(x) and whose even lanes all hold sum(y)
 // (x, y: one addend per lane).  Pairs first, then one register carries both parities through the remaining steps.
 __device__ __forceinline__ float f3_sum2(float x, float y) {
-  x += F3_DPP(x, 0xB1); y += F3_DPP(y, 0xB1);                   // lane ^ 1
+  x += AFX_DPP_F(x, 0xB1, false); y += AFX_DPP_F(y, 0xB1, false);   // lane ^ 1
   float m = f3_sel(y, x, 0xAAAAAAAAAAAAAAAAull);
-  m += F3_DPP(m, 0x4E);                                          // lane ^ 2
-  m += F3_DPP(m, 0x124); m += F3_DPP(m, 0x128);                  // row_ror 4, 8: the four quads of a row
+  m += AFX_DPP_F(m, 0x4E, false);   // lane ^ 2
+  m += AFX_DPP_F(m, 0x124, false); m += AFX_DPP_F(m, 0x128, false);   // row_ror 4, 8: the four quads of a row
   return f3_add_xor32(f3_add_xor16(m));
 }
 
+// ---- scaffolding of the three kernels -------------------------------------------------------------------------------
+// pre-emphasised, trim-masked staged sample j of a block at a clip edge or a cut (clamped loads); sbase = bd.sample_base
+template <int FMT>
+__device__ __forceinline__ float f3_edge_sample(const void* samples, const BlockDesc& bd, int64_t sbase, bool pre, float b1, int j) {
+  const int lo = bd.have_lo, hi = bd.have_hi - 1;
+  const int jc = j < lo ? lo : (j > hi ? hi : j), jp = (j - 1) < lo ? lo : ((j - 1) > hi ? hi : (j - 1));
+  const float y = (jc == j) ? ld_raw<FMT>(samples, sbase + jc) : 0.f;
+  const float yp = (jp == j - 1) ? ld_raw<FMT>(samples, sbase + jp) : 0.f;
+  float v = y;
+  if (pre) {
+    v = preemph1(y, yp, b1);
+    if (j == lo) v = preemph0(ld_raw<FMT>(samples, bd.clip_off), ld_raw<FMT>(samples, bd.clip_off + 1));   // clip sample 0
+  }
+  return (j >= bd.keep_lo && j < bd.keep_hi) ? v : 0.f;
+}
+// wave maximum of the block's log-mel values (f3_max inside the rows), uniform
+struct F3Max { __device__ float operator()(float a, float b) const { return f3_max(a, b); } };
+__device__ __forceinline__ float f3_wave_max(float v) {
+  v = row_reduce(v, F3Max());
+  return fmaxf(fmaxf(row_total(v, 0), row_total(v, 1)), fmaxf(row_total(v, 2), row_total(v, 3)));
+}
 
 }  // namespace afx

@@ -96,15 +96,7 @@ __global__ __launch_bounds__(WAVES * 64) void k_frames3d(const void* __restrict_
   const v2* const e1r = E + 34 * (lp & 15) + (lp >> 4);
   v2* const e2w = E + 128 * (lp >> 4) + (lp & 15);
 
-  auto raw_ld = [&](int64_t idx) -> float {
-    if constexpr (FMT == AFX_FMT_S16) return (float)((const int16_t*)samples)[idx] * (1.0f / 32768.0f);
-    else return ((const float*)samples)[idx];
-  };
-  typedef typename std::conditional<FMT == AFX_FMT_S16, int16_t, float>::type sample_t;
-  auto row_ld = [&](const sample_t* base, unsigned idx) -> float {
-    if constexpr (FMT == AFX_FMT_S16) return (float)base[idx] * (1.0f / 32768.0f);
-    else return base[idx];
-  };
+  using sample_t = sample_of<FMT>;
   const int n_rounds = ft.mel_rounds;
   const float amin = kp.amin;
 
@@ -112,14 +104,12 @@ __global__ __launch_bounds__(WAVES * 64) void k_frames3d(const void* __restrict_
   auto rowsum4 = [&](float r0, float r1, float r2, float r3, bool upper, bool& bad) -> float {
     float q = r0 * r0; q = fmaf(r1, r1, q); q = fmaf(r2, r2, q); q = fmaf(r3, r3, q);
     bad = !(isfinite(r0) && isfinite(r1) && isfinite(r2) && isfinite(r3));
-    q += F3_DPP(q, 0xB1); q += F3_DPP(q, 0x4E); q += F3_DPP(q, 0x141); q += F3_DPP(q, 0x140);
-    const int qi = __float_as_int(q);
-    return upper ? __int_as_float(__builtin_amdgcn_readlane(qi, 32)) + __int_as_float(__builtin_amdgcn_readlane(qi, 48))
-                 : __int_as_float(__builtin_amdgcn_readlane(qi, 0)) + __int_as_float(__builtin_amdgcn_readlane(qi, 16));
+    q = row_reduce(q, OpAdd());
+    return upper ? row_total(q, 2) + row_total(q, 3) : row_total(q, 0) + row_total(q, 1);
   };
   auto put_sum = [&](float t, bool bad, bool upper, const BlockDesc& bd, int j) {
-    if (j >= 0 && j < bd.pad_[1]) {
-      if (lane == 0) bsum[bd.pad_[0] + j] = t;
+    if (j >= 0 && j < bd.bsum_n) {
+      if (lane == 0) bsum[bd.bsum_base + j] = t;
       if (!(fabsf(t) < INFINITY)) {
         const bool mine = bad && ((lane >> 5) == (upper ? 1 : 0));
         if (__any(mine) && lane == 0) atomicOr(&info[bd.clip].nonfinite, 1u);
@@ -140,18 +130,7 @@ __global__ __launch_bounds__(WAVES * 64) void k_frames3d(const void* __restrict_
     auto interior = [&](int j0, int j1) -> bool {
       return (j0 - 1 >= bd.have_lo) && (j1 <= bd.have_hi) && (j0 >= bd.keep_lo) && (j1 <= bd.keep_hi);
     };
-    auto edge_sample = [&](int j) -> float {
-      const int lo = bd.have_lo, hi = bd.have_hi - 1;
-      const int jc = j < lo ? lo : (j > hi ? hi : j), jp = (j - 1) < lo ? lo : ((j - 1) > hi ? hi : (j - 1));
-      const float y = (jc == j) ? raw_ld(sbase + jc) : 0.f;
-      const float yp = (jp == j - 1) ? raw_ld(sbase + jp) : 0.f;
-      float v = y;
-      if (pre) {
-        v = f3_pre1(y, yp, b1);
-        if (j == lo) v = f3_pre0(raw_ld(bd.clip_off), raw_ld(bd.clip_off + 1));
-      }
-      return (j >= bd.keep_lo && j < bd.keep_hi) ? v : 0.f;
-    };
+    auto edge_sample = [&](int j) { return f3_edge_sample<FMT>(samples, bd, sbase, pre, b1, j); };
     float lmax = -INFINITY;
     float* const tile = logmel + bd.frame_slot * (int64_t)M;     // [frame][mel]
 
@@ -164,10 +143,10 @@ __global__ __launch_bounds__(WAVES * 64) void k_frames3d(const void* __restrict_
         float y[20], yp[20];
 #pragma unroll
         for (int u = 0; u < 20; ++u) {
-          y[u] = row_ld(sp + j0, 256 * half + 32 * u + lp); yp[u] = row_ld(sp + j0 - 1, 256 * half + 32 * u + lp);
+          y[u] = ld_row<FMT>(sp + j0, 256 * half + 32 * u + lp); yp[u] = ld_row<FMT>(sp + j0 - 1, 256 * half + 32 * u + lp);
         }
 #pragma unroll
-        for (int u = 0; u < 20; ++u) rows[u] = pre ? f3_pre1(y[u], yp[u], b1) : y[u];
+        for (int u = 0; u < 20; ++u) rows[u] = pre ? preemph1(y[u], yp[u], b1) : y[u];
       } else {
 #pragma unroll 1
         for (int u = 0; u < 20; ++u) XBw[640 * half + 32 * u + lp] = edge_sample(j0 + 256 * half + 32 * u + lp);
@@ -192,18 +171,18 @@ __global__ __launch_bounds__(WAVES * 64) void k_frames3d(const void* __restrict_
           q[k] = fmaf(rows[7 + 4 * k], rows[7 + 4 * k], q[k]);
         }
         const unsigned long long odd = 0xAAAAAAAAAAAAAAAAull, hi2 = 0xCCCCCCCCCCCCCCCCull;
-        float s01 = f3_sel(q[0], q[1], odd) + F3_DPP(f3_sel(q[1], q[0], odd), 0xB1);       // lane ^ 1
-        float s23 = f3_sel(q[2], q[3], odd) + F3_DPP(f3_sel(q[3], q[2], odd), 0xB1);
-        float sq = f3_sel(s01, s23, hi2) + F3_DPP(f3_sel(s23, s01, hi2), 0x4E);            // lane ^ 2
-        sq += F3_DPP(sq, 0x124); sq += F3_DPP(sq, 0x128);                                   // row_ror 4, 8: the four quads of a row
+        float s01 = f3_sel(q[0], q[1], odd) + AFX_DPP_F(f3_sel(q[1], q[0], odd), 0xB1, false);   // lane ^ 1
+        float s23 = f3_sel(q[2], q[3], odd) + AFX_DPP_F(f3_sel(q[3], q[2], odd), 0xB1, false);
+        float sq = f3_sel(s01, s23, hi2) + AFX_DPP_F(f3_sel(s23, s01, hi2), 0x4E, false);   // lane ^ 2
+        sq += AFX_DPP_F(sq, 0x124, false); sq += AFX_DPP_F(sq, 0x128, false);   // row_ror 4, 8: the four quads of a row
         sq = f3_add_xor16(sq);                                                              // the half's two rows
         const int jk = g + 1 + (lane & 3);
-        if (lane >= 32 && lane < 36 && jk < bd.pad_[1]) bsum[bd.pad_[0] + jk] = sq;
+        if (lane >= 32 && lane < 36 && jk < bd.bsum_n) bsum[bd.bsum_base + jk] = sq;
         if (__any(lane >= 32 && !(fabsf(sq) < INFINITY))) {       // rare: a sum that is not finite -- is it the samples?
 #pragma unroll
           for (int k = 0; k < 4; ++k) {
             const bool badk = !(isfinite(rows[4 + 4 * k]) && isfinite(rows[5 + 4 * k]) && isfinite(rows[6 + 4 * k]) && isfinite(rows[7 + 4 * k]));
-            if (g + 1 + k < bd.pad_[1] && __any(badk && lane >= 32) && lane == 0) atomicOr(&info[bd.clip].nonfinite, 1u);
+            if (g + 1 + k < bd.bsum_n && __any(badk && lane >= 32) && lane == 0) atomicOr(&info[bd.clip].nonfinite, 1u);
           }
         }
       }
@@ -323,9 +302,9 @@ __global__ __launch_bounds__(WAVES * 64) void k_frames3d(const void* __restrict_
         F3_BATCH(0) F3_BATCH(1) F3_BATCH(2) F3_BATCH(3) F3_BATCH(4) F3_BATCH(5) F3_BATCH(6) F3_BATCH(7)
 #undef F3_BATCH
         v2 acc = a0 + a1;
-        if (wd >= 2) { acc.x += F3_DPP(acc.x, 0xB1); acc.y += F3_DPP(acc.y, 0xB1); }
-        if (wd >= 4) { acc.x += F3_DPP(acc.x, 0x4E); acc.y += F3_DPP(acc.y, 0x4E); }
-        if (wd >= 8) { acc.x += F3_DPP(acc.x, 0x141); acc.y += F3_DPP(acc.y, 0x141); }
+        if (wd >= 2) { acc.x += AFX_DPP_F(acc.x, 0xB1, false); acc.y += AFX_DPP_F(acc.y, 0xB1, false); }
+        if (wd >= 4) { acc.x += AFX_DPP_F(acc.x, 0x4E, false); acc.y += AFX_DPP_F(acc.y, 0x4E, false); }
+        if (wd >= 8) { acc.x += AFX_DPP_F(acc.x, 0x141, false); acc.y += AFX_DPP_F(acc.y, 0x141, false); }
         const float L0 = 3.01029995663981195f * __builtin_amdgcn_logf(f3_max(acc.x, amin));
         const float L1 = 3.01029995663981195f * __builtin_amdgcn_logf(f3_max(acc.y, amin));
         if (meta & (1 << 20)) {
@@ -338,14 +317,9 @@ __global__ __launch_bounds__(WAVES * 64) void k_frames3d(const void* __restrict_
       __builtin_amdgcn_s_setprio(0);
     }
     {
-      float v = lmax;
-      v = f3_max(v, F3_DPP(v, 0xB1)); v = f3_max(v, F3_DPP(v, 0x4E)); v = f3_max(v, F3_DPP(v, 0x141)); v = f3_max(v, F3_DPP(v, 0x140));
-      const int vi = __float_as_int(v);
-      const float r0 = __int_as_float(__builtin_amdgcn_readlane(vi, 0)), r1 = __int_as_float(__builtin_amdgcn_readlane(vi, 16));
-      const float r2 = __int_as_float(__builtin_amdgcn_readlane(vi, 32)), r3 = __int_as_float(__builtin_amdgcn_readlane(vi, 48));
-      const float mx = fmaxf(fmaxf(r0, r1), fmaxf(r2, r3));
+      const float mx = f3_wave_max(lmax);
       if constexpr (SPEC) { if (lane == 0) blockmax[b] = mx; }
-      else { if (lane == 0 && mx > -INFINITY) atomicMax(&info[bd.clip].lmax_ord, f3_ord(mx)); }
+      else { if (lane == 0 && mx > -INFINITY) atomicMax(&info[bd.clip].lmax_ord, f2ord(mx)); }
     }
   }
   } while (f3_runs_next(runs, work_ctr, nblocks, (int)(gridDim.x * WAVES), lane));
@@ -358,28 +332,16 @@ int frames3d_waves(const F3Tables& ft) {
 }
 
 template <int FMT, int WAVES, bool SPEC, int NBS>
-static hipError_t launch_frames3d_t(hipStream_t s, const void* samples, ClipInfo* info, const BlockDesc* blocks,
-                                    int nblocks, const int* nblocks_dev, const F3Tables& ft, const KParams& kp,
-                                    float* logmel, float* blockmax, float* bsum, int* work_ctr, int n_cu) {
-  static bool attr_set[64] = {};
-  int dev = 0;
-  hipError_t e = hipGetDevice(&dev);
+static hipError_t launch_frames3d_t(const F3Launch& L) {
+  const hipError_t e = allow_lds_once<k_frames3d<FMT, WAVES, SPEC, NBS>>();
   if (e != hipSuccess) return e;
-  if (dev >= 0 && dev < 64 && !attr_set[dev]) {
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_frames3d<FMT, WAVES, SPEC, NBS>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) return e;
-    attr_set[dev] = true;
-  }
-  const int grid = std::max(1, std::min(n_cu, (nblocks + WAVES - 1) / WAVES));
-  hipLaunchKernelGGL((k_frames3d<FMT, WAVES, SPEC, NBS>), dim3(grid), dim3(WAVES * 64), frames3d_lds_bytes(WAVES, ft), s,
-                     samples, info, blocks, nblocks, nblocks_dev, ft, kp, logmel, blockmax, bsum, work_ctr);
+  hipLaunchKernelGGL((k_frames3d<FMT, WAVES, SPEC, NBS>), dim3(f3_grid(L, WAVES)), dim3(WAVES * 64), frames3d_lds_bytes(WAVES, L.ft), L.s,
+                     L.samples, L.info, L.blocks, L.nblocks, L.nblocks_dev, L.ft, L.kp, L.logmel, L.blockmax, L.bsum, L.work_ctr);
   return hipGetLastError();
 }
 
-hipError_t launch_frames3d(hipStream_t s, const void* samples, ClipInfo* info, const BlockDesc* blocks, int nblocks,
-                           const int* nblocks_dev, const F3Tables& ft, const KParams& kp, float* logmel,
-                           float* blockmax, float* bsum, bool spec, int* work_ctr, int n_cu) {
+hipError_t launch_frames3d(const F3Launch& L) {
+  const F3Tables& ft = L.ft;
   const int waves = frames3d_waves(ft);
   // the compiled-in schedule: rounds of width 1 with 1, 1, 2, 4 batches, every lane an owner, weights packed round after round
   bool fixed = ft.mel_rounds == 4 && ft.mel_all_own && !dev_env().f3_generic_mel;
@@ -389,11 +351,9 @@ hipError_t launch_frames3d(hipStream_t s, const void* samples, ClipInfo* info, c
     fixed = (int)(ft.mel_rp[r] & 15) == want_nb[r] && ((ft.mel_rp[r] >> 4) & 15) == 1 && (int)(ft.mel_rp[r] >> 8) == woff;
     woff += want_nb[r] * 256;
   }
-#define AFX_F3D_GO2(FMT, W, NBS)                                                                                                    \
-  (spec ? launch_frames3d_t<FMT, W, true, NBS>(s, samples, info, blocks, nblocks, nblocks_dev, ft, kp, logmel, blockmax, bsum, work_ctr, n_cu) \
-        : launch_frames3d_t<FMT, W, false, NBS>(s, samples, info, blocks, nblocks, nblocks_dev, ft, kp, logmel, blockmax, bsum, work_ctr, n_cu))
+#define AFX_F3D_GO2(FMT, W, NBS) (L.spec ? launch_frames3d_t<FMT, W, true, NBS>(L) : launch_frames3d_t<FMT, W, false, NBS>(L))
 #define AFX_F3D_GO(FMT, W) (fixed ? AFX_F3D_GO2(FMT, W, 0x4211) : AFX_F3D_GO2(FMT, W, 0))
-  if (kp.fmt == AFX_FMT_S16) return waves == 16 ? AFX_F3D_GO(AFX_FMT_S16, 16) : AFX_F3D_GO(AFX_FMT_S16, 12);
+  if (L.kp.fmt == AFX_FMT_S16) return waves == 16 ? AFX_F3D_GO(AFX_FMT_S16, 16) : AFX_F3D_GO(AFX_FMT_S16, 12);
   return waves == 16 ? AFX_F3D_GO(AFX_FMT_F32, 16) : AFX_F3D_GO(AFX_FMT_F32, 12);
 #undef AFX_F3D_GO
 #undef AFX_F3D_GO2

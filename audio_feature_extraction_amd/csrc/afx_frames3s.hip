@@ -112,28 +112,16 @@ __global__ __launch_bounds__(WAVES * 64) void k_frames3s(const void* __restrict_
   const v2* const ea = E + lane;
   const v2* const eb = E + jb;
 
-  auto raw_ld = [&](int64_t idx) -> float {
-    if constexpr (FMT == AFX_FMT_S16) return (float)((const int16_t*)samples)[idx] * (1.0f / 32768.0f);
-    else return ((const float*)samples)[idx];
-  };
-  typedef typename std::conditional<FMT == AFX_FMT_S16, int16_t, float>::type sample_t;
-  auto row_ld = [&](const sample_t* base, unsigned idx) -> float {
-    if constexpr (FMT == AFX_FMT_S16) return (float)base[idx] * (1.0f / 32768.0f);
-    else return base[idx];
-  };
+  using sample_t = sample_of<FMT>;
   const int n_rounds = ft.mel_rounds;
   const float amin = kp.amin;
 
   // sum of squares of four float2 rows (one 512-sample sub-block of the pre-emphasised signal), wave-wide
   auto subblock = [&](v2 r0, v2 r1, v2 r2, v2 r3, const BlockDesc& bd, int j) {
     v2 a = r0 * r0; a = r1 * r1 + a; a = r2 * r2 + a; a = r3 * r3 + a;
-    float q = a.x + a.y;
-    q += F3_DPP(q, 0xB1); q += F3_DPP(q, 0x4E); q += F3_DPP(q, 0x141); q += F3_DPP(q, 0x140);
-    const int qi = __float_as_int(q);
-    const float t = (__int_as_float(__builtin_amdgcn_readlane(qi, 0)) + __int_as_float(__builtin_amdgcn_readlane(qi, 16))) +
-                    (__int_as_float(__builtin_amdgcn_readlane(qi, 32)) + __int_as_float(__builtin_amdgcn_readlane(qi, 48)));
-    if (j >= 0 && j < bd.pad_[1]) {
-      if (lane == 0) bsum[bd.pad_[0] + j] = t;
+    const float t = wave_sum(a.x + a.y);
+    if (j >= 0 && j < bd.bsum_n) {
+      if (lane == 0) bsum[bd.bsum_base + j] = t;
       if (!(fabsf(t) < INFINITY)) {
         const bool bad = !(isfinite(r0.x) && isfinite(r0.y) && isfinite(r1.x) && isfinite(r1.y) &&
                            isfinite(r2.x) && isfinite(r2.y) && isfinite(r3.x) && isfinite(r3.y));
@@ -165,21 +153,10 @@ __global__ __launch_bounds__(WAVES * 64) void k_frames3s(const void* __restrict_
     auto interior = [&](int j0, int j1) -> bool {
       return (j0 - 1 >= bd.have_lo) && (j1 <= bd.have_hi) && (j0 >= bd.keep_lo) && (j1 <= bd.keep_hi);
     };
-    auto edge_sample = [&](int j) -> float {
-      const int lo = bd.have_lo, hi = bd.have_hi - 1;
-      const int jc = j < lo ? lo : (j > hi ? hi : j), jp = (j - 1) < lo ? lo : ((j - 1) > hi ? hi : (j - 1));
-      const float y = (jc == j) ? raw_ld(sbase + jc) : 0.f;
-      const float yp = (jp == j - 1) ? raw_ld(sbase + jp) : 0.f;
-      float v = y;
-      if (pre) {
-        v = f3_pre1(y, yp, b1);
-        if (j == lo) v = f3_pre0(raw_ld(bd.clip_off), raw_ld(bd.clip_off + 1));
-      }
-      return (j >= bd.keep_lo && j < bd.keep_hi) ? v : 0.f;
-    };
+    auto edge_sample = [&](int j) { return f3_edge_sample<FMT>(samples, bd, sbase, pre, b1, j); };
     // one float2 row: samples j0 + 2 lane, + 1 (pre-emphasised)
     auto pre_row = [&](float x0, float x1, float xp) -> v2 {
-      return pre ? v2{f3_pre1(x0, xp, b1), f3_pre1(x1, x0, b1)} : v2{x0, x1};
+      return pre ? v2{preemph1(x0, xp, b1), preemph1(x1, x0, b1)} : v2{x0, x1};
     };
 
     // ---- rows of the first frame: staged samples [0, 2048)
@@ -188,7 +165,7 @@ __global__ __launch_bounds__(WAVES * 64) void k_frames3s(const void* __restrict_
       float x0[16], x1[16], xp[16];
 #pragma unroll
       for (int u = 0; u < 16; ++u) {
-        x0[u] = row_ld(sp, 128 * u + 2 * lane); x1[u] = row_ld(sp, 128 * u + 2 * lane + 1); xp[u] = row_ld(sp - 1, 128 * u + 2 * lane);
+        x0[u] = ld_row<FMT>(sp, 128 * u + 2 * lane); x1[u] = ld_row<FMT>(sp, 128 * u + 2 * lane + 1); xp[u] = ld_row<FMT>(sp - 1, 128 * u + 2 * lane);
       }
 #pragma unroll
       for (int u = 0; u < 16; ++u) R[u] = pre_row(x0[u], x1[u], xp[u]);
@@ -273,7 +250,7 @@ __global__ __launch_bounds__(WAVES * 64) void k_frames3s(const void* __restrict_
       if (nint) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-          nx0[i] = row_ld(sp + jn, 128 * i + 2 * lane); nx1[i] = row_ld(sp + jn, 128 * i + 2 * lane + 1); nxp[i] = row_ld(sp + jn - 1, 128 * i + 2 * lane);
+          nx0[i] = ld_row<FMT>(sp + jn, 128 * i + 2 * lane); nx1[i] = ld_row<FMT>(sp + jn, 128 * i + 2 * lane + 1); nxp[i] = ld_row<FMT>(sp + jn - 1, 128 * i + 2 * lane);
         }
       }
       if constexpr (DESC) {
@@ -286,10 +263,8 @@ __global__ __launch_bounds__(WAVES * 64) void k_frames3s(const void* __restrict_
         }
         mg[16] = lane == 63 ? sqrtf(XB[1024]) : 0.f;
         auto wsum = [&](float q) -> float {
-          q += F3_DPP(q, 0xB1); q += F3_DPP(q, 0x4E); q += F3_DPP(q, 0x141); q += F3_DPP(q, 0x140);
-          const int qi = __float_as_int(q);
-          return (__int_as_float(__builtin_amdgcn_readlane(qi, 0)) + __int_as_float(__builtin_amdgcn_readlane(qi, 16))) +
-                 (__int_as_float(__builtin_amdgcn_readlane(qi, 32)) + __int_as_float(__builtin_amdgcn_readlane(qi, 48)));
+          q += AFX_DPP_F(q, 0xB1, false); q += AFX_DPP_F(q, 0x4E, false); q += AFX_DPP_F(q, 0x141, false); q += AFX_DPP_F(q, 0x140, false);
+          return (row_total(q, 0) + row_total(q, 1)) + (row_total(q, 2) + row_total(q, 3));
         };
         const float hz = sb.hz_per_bin, k0f = (float)(16 * lane);
         float s0 = 0.f, s1 = 0.f;
@@ -340,11 +315,9 @@ __global__ __launch_bounds__(WAVES * 64) void k_frames3s(const void* __restrict_
                 m = better ? mg[j] : m; jm = better ? j : jm;
               }
               float w = m;
-              if (side) { w = fmaxf(w, F3_DPP(w, 0xB1)); w = fmaxf(w, F3_DPP(w, 0x4E)); w = fmaxf(w, F3_DPP(w, 0x141)); w = fmaxf(w, F3_DPP(w, 0x140)); }
-              else { w = fminf(w, F3_DPP(w, 0xB1)); w = fminf(w, F3_DPP(w, 0x4E)); w = fminf(w, F3_DPP(w, 0x141)); w = fminf(w, F3_DPP(w, 0x140)); }
-              const int wi = __float_as_int(w);
-              const float r0 = __int_as_float(__builtin_amdgcn_readlane(wi, 0)), r1 = __int_as_float(__builtin_amdgcn_readlane(wi, 16));
-              const float r2 = __int_as_float(__builtin_amdgcn_readlane(wi, 32)), r3 = __int_as_float(__builtin_amdgcn_readlane(wi, 48));
+              if (side) { w = fmaxf(w, AFX_DPP_F(w, 0xB1, false)); w = fmaxf(w, AFX_DPP_F(w, 0x4E, false)); w = fmaxf(w, AFX_DPP_F(w, 0x141, false)); w = fmaxf(w, AFX_DPP_F(w, 0x140, false)); }
+              else { w = fminf(w, AFX_DPP_F(w, 0xB1, false)); w = fminf(w, AFX_DPP_F(w, 0x4E, false)); w = fminf(w, AFX_DPP_F(w, 0x141, false)); w = fminf(w, AFX_DPP_F(w, 0x140, false)); }
+              const float r0 = row_total(w, 0), r1 = row_total(w, 1), r2 = row_total(w, 2), r3 = row_total(w, 3);
               const float best = side ? fmaxf(fmaxf(r0, r1), fmaxf(r2, r3)) : fminf(fminf(r0, r1), fminf(r2, r3));
               const bool have = side ? m >= 0.f : m < INFINITY;      // the lane still had a candidate
               const unsigned long long holders = __ballot(have && m == best);
@@ -383,9 +356,9 @@ __global__ __launch_bounds__(WAVES * 64) void k_frames3s(const void* __restrict_
           }
           const v2 a = a0 + a1;
           float acc = a.x + a.y;
-          if (wd >= 2) acc += F3_DPP(acc, 0xB1);
-          if (wd >= 4) acc += F3_DPP(acc, 0x4E);
-          if (wd >= 8) acc += F3_DPP(acc, 0x141);
+          if (wd >= 2) acc += AFX_DPP_F(acc, 0xB1, false);
+          if (wd >= 4) acc += AFX_DPP_F(acc, 0x4E, false);
+          if (wd >= 8) acc += AFX_DPP_F(acc, 0x141, false);
           const float L = 3.01029995663981195f * __builtin_amdgcn_logf(f3_max(acc, amin));
           if (wd == 1 || (meta & (1 << 20))) {              // width 1: every lane owns its filter (launch_frames3s checks)
             const unsigned m = (meta >> 11) & 511;
@@ -411,9 +384,9 @@ __global__ __launch_bounds__(WAVES * 64) void k_frames3s(const void* __restrict_
 #undef F3_BATCH
         const v2 a = a0 + a1;
         float acc = a.x + a.y;
-        if (wd >= 2) acc += F3_DPP(acc, 0xB1);
-        if (wd >= 4) acc += F3_DPP(acc, 0x4E);
-        if (wd >= 8) acc += F3_DPP(acc, 0x141);
+        if (wd >= 2) acc += AFX_DPP_F(acc, 0xB1, false);
+        if (wd >= 4) acc += AFX_DPP_F(acc, 0x4E, false);
+        if (wd >= 8) acc += AFX_DPP_F(acc, 0x141, false);
         const float L = 3.01029995663981195f * __builtin_amdgcn_logf(f3_max(acc, amin));
         if (meta & (1 << 20)) {
           const unsigned m = (meta >> 11) & 511;
@@ -442,15 +415,10 @@ __global__ __launch_bounds__(WAVES * 64) void k_frames3s(const void* __restrict_
       }
     }
     {
-      float v = lmax;
-      v = f3_max(v, F3_DPP(v, 0xB1)); v = f3_max(v, F3_DPP(v, 0x4E)); v = f3_max(v, F3_DPP(v, 0x141)); v = f3_max(v, F3_DPP(v, 0x140));
-      const int vi = __float_as_int(v);
-      const float r0 = __int_as_float(__builtin_amdgcn_readlane(vi, 0)), r1 = __int_as_float(__builtin_amdgcn_readlane(vi, 16));
-      const float r2 = __int_as_float(__builtin_amdgcn_readlane(vi, 32)), r3 = __int_as_float(__builtin_amdgcn_readlane(vi, 48));
-      const float mx = fmaxf(fmaxf(r0, r1), fmaxf(r2, r3));
+      const float mx = f3_wave_max(lmax);
       if constexpr (DESC) { (void)mx; }
       else if constexpr (SPEC) { if (lane == 0) blockmax[b] = mx; }
-      else { if (lane == 0 && mx > -INFINITY) atomicMax(&info[bd.clip].lmax_ord, f3_ord(mx)); }
+      else { if (lane == 0 && mx > -INFINITY) atomicMax(&info[bd.clip].lmax_ord, f2ord(mx)); }
     }
     if (!chain) break;
     first = false;
@@ -468,22 +436,11 @@ int frames3s_waves(const F3Tables& ft) {
 }
 
 template <int FMT, int WAVES, bool SPEC, int NBS, int WDS>
-static hipError_t launch_frames3s_t(hipStream_t s, const void* samples, ClipInfo* info, const BlockDesc* blocks,
-                                    int nblocks, const int* nblocks_dev, const F3Tables& ft, const KParams& kp,
-                                    float* logmel, float* blockmax, float* bsum, int* work_ctr, int n_cu) {
-  static bool attr_set[64] = {};
-  int dev = 0;
-  hipError_t e = hipGetDevice(&dev);
+static hipError_t launch_frames3s_t(const F3Launch& L) {
+  const hipError_t e = allow_lds_once<k_frames3s<FMT, WAVES, SPEC, false, NBS, WDS>>();
   if (e != hipSuccess) return e;
-  if (dev >= 0 && dev < 64 && !attr_set[dev]) {
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_frames3s<FMT, WAVES, SPEC, false, NBS, WDS>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) return e;
-    attr_set[dev] = true;
-  }
-  const int grid = std::max(1, std::min(n_cu, (nblocks + WAVES - 1) / WAVES));
-  hipLaunchKernelGGL((k_frames3s<FMT, WAVES, SPEC, false, NBS, WDS>), dim3(grid), dim3(WAVES * 64), frames3s_lds_bytes(WAVES, ft), s,
-                     samples, info, blocks, nblocks, nblocks_dev, ft, kp, logmel, blockmax, bsum, nullptr, nullptr, SpecBands{}, work_ctr);
+  hipLaunchKernelGGL((k_frames3s<FMT, WAVES, SPEC, false, NBS, WDS>), dim3(f3_grid(L, WAVES)), dim3(WAVES * 64), frames3s_lds_bytes(WAVES, L.ft), L.s,
+                     L.samples, L.info, L.blocks, L.nblocks, L.nblocks_dev, L.ft, L.kp, L.logmel, L.blockmax, L.bsum, nullptr, nullptr, SpecBands{}, L.work_ctr);
   return hipGetLastError();
 }
 
@@ -491,16 +448,8 @@ template <int FMT>
 static hipError_t launch_spectral_t(hipStream_t s, const void* samples, ClipInfo* info, const BlockDesc* blocks, int nblocks,
                                     const F3Tables& ft, const KParams& kp, float* desc_out, const int64_t* desc_offs,
                                     const SpecBands& sb, int n_cu) {
-  static bool attr_set[64] = {};
-  int dev = 0;
-  hipError_t e = hipGetDevice(&dev);
+  const hipError_t e = allow_lds_once<k_frames3s<FMT, 12, false, true>>();
   if (e != hipSuccess) return e;
-  if (dev >= 0 && dev < 64 && !attr_set[dev]) {
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_frames3s<FMT, 12, false, true>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) return e;
-    attr_set[dev] = true;
-  }
   const int grid = std::max(1, std::min(n_cu, (nblocks + 11) / 12));
   hipLaunchKernelGGL((k_frames3s<FMT, 12, false, true>), dim3(grid), dim3(12 * 64), frames3s_lds_bytes(12, ft), s,
                      samples, info, blocks, nblocks, nullptr, ft, kp, nullptr, nullptr, nullptr, desc_out, desc_offs, sb, nullptr);
@@ -514,9 +463,8 @@ hipError_t launch_spectral(hipStream_t s, const void* samples, ClipInfo* info, c
   return launch_spectral_t<AFX_FMT_F32>(s, samples, info, blocks, nblocks, ft, kp, desc_out, desc_offs, sb, n_cu);
 }
 
-hipError_t launch_frames3s(hipStream_t s, const void* samples, ClipInfo* info, const BlockDesc* blocks, int nblocks,
-                           const int* nblocks_dev, const F3Tables& ft, const KParams& kp, float* logmel,
-                           float* blockmax, float* bsum, bool spec, int* work_ctr, int n_cu) {
+hipError_t launch_frames3s(const F3Launch& L) {
+  const F3Tables& ft = L.ft;
   const int waves = frames3s_waves(ft);
   // the compiled-in schedule: batches 3, 1, 5, 5 at widths 1, 4, 2, 4, weights packed round after round; in a width-1 round
   // every lane must own a filter (the straight-line code stores without an owner test there)
@@ -528,11 +476,9 @@ hipError_t launch_frames3s(hipStream_t s, const void* samples, ClipInfo* info, c
     woff += want_nb[r] * 256;
   }
   fixed = fixed && (ft.mel_own_w1 != 0);
-#define AFX_F3S_GO2(FMT, W, NBS, WDS)                                                                                                    \
-  (spec ? launch_frames3s_t<FMT, W, true, NBS, WDS>(s, samples, info, blocks, nblocks, nblocks_dev, ft, kp, logmel, blockmax, bsum, work_ctr, n_cu) \
-        : launch_frames3s_t<FMT, W, false, NBS, WDS>(s, samples, info, blocks, nblocks, nblocks_dev, ft, kp, logmel, blockmax, bsum, work_ctr, n_cu))
+#define AFX_F3S_GO2(FMT, W, NBS, WDS) (L.spec ? launch_frames3s_t<FMT, W, true, NBS, WDS>(L) : launch_frames3s_t<FMT, W, false, NBS, WDS>(L))
 #define AFX_F3S_GO(FMT, W) (fixed ? AFX_F3S_GO2(FMT, W, 0x5513, 0x4241) : AFX_F3S_GO2(FMT, W, 0, 0))
-  if (kp.fmt == AFX_FMT_S16) return waves == 16 ? AFX_F3S_GO(AFX_FMT_S16, 16) : AFX_F3S_GO(AFX_FMT_S16, 12);
+  if (L.kp.fmt == AFX_FMT_S16) return waves == 16 ? AFX_F3S_GO(AFX_FMT_S16, 16) : AFX_F3S_GO(AFX_FMT_S16, 12);
   return waves == 16 ? AFX_F3S_GO(AFX_FMT_F32, 16) : AFX_F3S_GO(AFX_FMT_F32, 12);
 #undef AFX_F3S_GO
 #undef AFX_F3S_GO2

@@ -26,11 +26,6 @@ namespace {
 constexpr int kSP = 95;                    // LDS pitch of the |X| tile (94 x 94 cells; odd: the transposed walk is conflict-free)
 constexpr int kHP = 64;                    // LDS pitch of the harmonic-median tile
 
-__device__ __forceinline__ float hp_ld(const void* in, int fmt, int64_t i) {
-  if (fmt == AFX_FMT_S16) return (float)((const int16_t*)in)[i] * (1.0f / 32768.0f);
-  return ((const float*)in)[i];
-}
-
 // |x| as one fixed sequence of roundings (the tile load and the mask stage must agree bit for bit)
 __device__ __forceinline__ float hp_abs(v2 x) {
 #pragma clang fp contract(off)
@@ -143,12 +138,12 @@ __global__ __launch_bounds__(256) void k_hpss_prep(const void* __restrict__ in, 
     for (int u = 0; u < 4; ++u) {
       const int64_t i = i0 + u * 256 + threadIdx.x;
       if (i >= c.len) break;
-      const float v = hp_ld(in, fmt, c.in_off + i);
+      const float v = ld_sample(in, fmt, c.in_off + i);
       nf |= !isfinite(v);
       float o = v;
       if (pre) {
-        if (i == 0) o = c.len > 1 ? f3_pre0(v, hp_ld(in, fmt, c.in_off + 1)) : v;
-        else o = f3_pre1(v, hp_ld(in, fmt, c.in_off + i - 1), b1);
+        if (i == 0) o = c.len > 1 ? preemph0(v, ld_sample(in, fmt, c.in_off + 1)) : v;
+        else o = preemph1(v, ld_sample(in, fmt, c.in_off + i - 1), b1);
       }
       y[c.y_off + i] = o;
     }

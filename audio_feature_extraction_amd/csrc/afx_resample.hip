@@ -3,7 +3,9 @@
 #include <hip/hip_runtime.h>
 
 #include "afx.h"
+#include "afx_device.h"
 #include "afx_resample.h"
+#include "afx_wave.h"
 
 namespace afx {
 
@@ -32,12 +34,6 @@ __device__ __forceinline__ RsClip rs_clip(rs_const<RsClip> clips, int c) {
 }
 
 template <int FMT>
-__device__ __forceinline__ float rs_load(const void* __restrict__ in, int64_t i) {
-  if (FMT == AFX_FMT_S16) return (float)((const int16_t*)in)[i] * (1.0f / 32768.0f);
-  return ((const float*)in)[i];
-}
-
-template <int FMT>
 __global__ void __launch_bounds__(1024) k_resample(const void* __restrict__ in, float* __restrict__ out,
                                                    const RsClip* __restrict__ clips, int n_clips,
                                                    const double* __restrict__ G, const int32_t* __restrict__ tstart,
@@ -53,7 +49,7 @@ __global__ void __launch_bounds__(1024) k_resample(const void* __restrict__ in, 
     const unsigned row = e / (unsigned)p.rw, col = e - row * (unsigned)p.rw;
     const int64_t i = x0 + e;
     // samples outside the clip are zero: a neighbour in the packed buffer is never read
-    xs[row * p.stride + col] = (i >= 0 && i < cl.in_len) ? rs_load<FMT>(in, cl.in_off + i) : 0.0f;
+    xs[row * p.stride + col] = (i >= 0 && i < cl.in_len) ? ld_raw<FMT>(in, cl.in_off + i) : 0.0f;
   }
   __syncthreads();
 
@@ -105,7 +101,7 @@ __global__ void __launch_bounds__(256) k_resample_copy(const void* __restrict__ 
   const int64_t i0 = (int64_t)(b - cl.first_block) * kRsCopyChunk;
   for (int e = threadIdx.x; e < kRsCopyChunk; e += 256) {
     const int64_t i = i0 + e;
-    if (i < cl.in_len) out[cl.out_off + i] = rs_load<FMT>(in, cl.in_off + i);
+    if (i < cl.in_len) out[cl.out_off + i] = ld_raw<FMT>(in, cl.in_off + i);
   }
 }
 
@@ -114,7 +110,7 @@ hipError_t launch_resample(hipStream_t s, const void* in, int fmt, float* out, c
   if (n_blocks <= 0) return hipSuccess;
   const size_t lds = (size_t)p.rows * p.stride * sizeof(float);
   auto kern = fmt == AFX_FMT_S16 ? k_resample<AFX_FMT_S16> : k_resample<AFX_FMT_F32>;
-  hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  hipError_t e = set_lds_limit(kern, lds);      // every launch: the bytes follow the resampling ratio
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(kern, dim3(n_blocks), dim3(64 * p.n_waves), lds, s, in, out, clips, n_clips, G, tstart, p);
   return hipGetLastError();

@@ -21,26 +21,22 @@
 
 #include "afx_device.h"
 #include "afx_devenv.h"
+#include "afx_wave.h"
 
 namespace afx {
 
 typedef float tl_f32x4 __attribute__((ext_vector_type(4)));
 
-__device__ __forceinline__ float tl_ord2f(uint32_t o) {
-  const uint32_t u = (o & 0x80000000u) ? (o & 0x7fffffffu) : ~o;
-  return __uint_as_float(u);
-}
 // sum over the 16 lanes of a row (all lanes of the row end with the total).  The two dwords of a double go through DPP moves
 // (__shfl_xor lowers to ds_bpermute round trips: 24 sums x 4 steps of those were 10 us per clip and wave)
-#define TL_DPP(x, ctrl) __builtin_amdgcn_update_dpp(0, (x), (ctrl), 0xf, 0xf, false)
 __device__ __forceinline__ double tl_dpp_d(double v, const int ctrl_sel) {
   const long long b = __double_as_longlong(v);
   int lo = (int)b, hi = (int)(b >> 32);
   switch (ctrl_sel) {
-    case 0: lo = TL_DPP(lo, 0xB1); hi = TL_DPP(hi, 0xB1); break;       // quad_perm [1,0,3,2]
-    case 1: lo = TL_DPP(lo, 0x4E); hi = TL_DPP(hi, 0x4E); break;       // quad_perm [2,3,0,1]
-    case 2: lo = TL_DPP(lo, 0x141); hi = TL_DPP(hi, 0x141); break;     // row_half_mirror
-    default: lo = TL_DPP(lo, 0x140); hi = TL_DPP(hi, 0x140); break;    // row_mirror
+    case 0: lo = AFX_DPP_I(lo, 0xB1, false); hi = AFX_DPP_I(hi, 0xB1, false); break;       // quad_perm [1,0,3,2]
+    case 1: lo = AFX_DPP_I(lo, 0x4E, false); hi = AFX_DPP_I(hi, 0x4E, false); break;       // quad_perm [2,3,0,1]
+    case 2: lo = AFX_DPP_I(lo, 0x141, false); hi = AFX_DPP_I(hi, 0x141, false); break;     // row_half_mirror
+    default: lo = AFX_DPP_I(lo, 0x140, false); hi = AFX_DPP_I(hi, 0x140, false); break;    // row_mirror
   }
   return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
 }
@@ -48,12 +44,6 @@ __device__ __forceinline__ double tl_row_sum(double v) {
   v += tl_dpp_d(v, 0); v += tl_dpp_d(v, 1); v += tl_dpp_d(v, 2); v += tl_dpp_d(v, 3);
   return v;
 }
-__device__ __forceinline__ double tl_wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-
 
 // SYM: the DCT-II rows are symmetric (even k) or antisymmetric (odd k) about the middle of the mel axis,
 // d_k(M - 1 - m) = (-1)^k d_k(m), so the contraction folds to M / 2 terms over L_m + L_{M-1-m} (even rows) or L_m - L_{M-1-m}
@@ -113,7 +103,7 @@ __global__ __launch_bounds__(WAVES * 64, ((NG == 1 && WAVES == 4 && RING == 0) ?
   const double invT = 1.0 / (double)T;
 
   if (ci.status == AFX_CLIP_OK) {
-    const float theta = tl_ord2f(ci.lmax_ord) - kp.top_db;
+    const float theta = ord2f(ci.lmax_ord) - kp.top_db;
     const int f = lane & 15, q = lane >> 4;
     const int ntiles = (T + 15) >> 4;
     // spec: the spill holds absolute frames (the frame kernel ran before the trim decision); trimmed frame t is frame start / hop + t
@@ -309,7 +299,7 @@ __global__ __launch_bounds__(WAVES * 64, ((NG == 1 && WAVES == 4 && RING == 0) ?
       const float v = r[t];
       s += (double)v; mx = fmaxf(mx, v); mn = fminf(mn, v);
     }
-    s = tl_wave_sum(s);
+    s = wave_sum_d(s);
     double dmx = (double)mx, dmn = (double)mn;
 #pragma unroll
     for (int o = 32; o >= 1; o >>= 1) { dmx = fmax(dmx, __shfl_xor(dmx, o)); dmn = fmin(dmn, __shfl_xor(dmn, o)); }
@@ -321,7 +311,7 @@ __global__ __launch_bounds__(WAVES * 64, ((NG == 1 && WAVES == 4 && RING == 0) ?
     const float meanf = (float)(tot * invT);
     double s2 = 0.0;
     for (int t = tid; t < T; t += kTailWaves * 64) { const float d = r[t] - meanf; s2 += (double)d * (double)d; }
-    s2 = tl_wave_sum(s2);
+    s2 = wave_sum_d(s2);
     if (lane == 0) red[wave * 4 + 3] = s2;
     __syncthreads();
     if (tid == 0) {
@@ -368,7 +358,7 @@ static hipError_t launch_tail_t(hipStream_t s, const ClipDesc* clips, const Clip
   if (per_cu_dev[dev] == 0) {
     const void* fn = reinterpret_cast<const void*>(&k_tail<NG, SYM, WAVES, RING>);
     if (lds > 48 * 1024) {
-      hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+      hipError_t e = allow_lds_once<k_tail<NG, SYM, WAVES, RING>>();
       if (e != hipSuccess) return e;
     }
     int nb = 0;
