@@ -35,7 +35,7 @@ SYMBOLS = (
     "afx_default_params", "afx_plan_create", "afx_plan_destroy", "afx_build_tables", "afx_build_mel_schedule",
     "afx_extract_batch", "afx_extract_submit", "afx_extract_collect", "afx_f0_batch", "afx_zcr_batch", "afx_spectral_batch", "afx_f0_build_tables", "afx_preprocess", "afx_plan_set_timing", "afx_plan_get_timings", "afx_plan_get_intervals",
     "afx_wav_probe", "afx_wav_read_s16", "afx_batch_geometry", "afx_dtw_batch", "afx_hpss_batch",
-    "afx_resample_design", "afx_resample_batch",
+    "afx_resample_design", "afx_resample_batch", "afx_rfft_host",
 )
 
 
@@ -108,6 +108,8 @@ def lib() -> C.CDLL:
         if hasattr(L, "afx_resample_batch"):                 # absent from a library older than version 107
             L.afx_resample_design.argtypes = [i32, i32, vp, vp]
             L.afx_resample_batch.argtypes = [vp, vp, i32, i32, vp, vp, i32, i32, i32, vp, i32, vp, i32, vp, vp]
+        if hasattr(L, "afx_rfft_host"):                      # absent from a library built before the mixed-radix lengths
+            L.afx_rfft_host.argtypes = [i32, vp, vp]
         _lib = L
     return _lib
 
@@ -182,6 +184,14 @@ def resample_design(sr_in: int, sr_out: int) -> dict:
     taps = np.zeros(int(info[2]), np.float64)
     _check(lib().afx_resample_design(int(sr_in), int(sr_out), info.ctypes.data, taps.ctypes.data), "afx_resample_design")
     return {"up": int(info[0]), "down": int(info[1]), "n_taps": int(info[2]), "half": int(info[3]), "taps": taps}
+
+
+def rfft_host(x) -> np.ndarray:
+    """Host-only: the frame kernel's mixed-radix real FFT of one frame, in float32 on the CPU (complex64, n/2 + 1 bins)."""
+    x = np.ascontiguousarray(x, np.float32).reshape(-1)
+    out = np.zeros(2 * (x.size // 2 + 1), np.float32)
+    _check(lib().afx_rfft_host(int(x.size), x.ctypes.data, out.ctypes.data), "afx_rfft_host")
+    return out.view(np.complex64)
 
 
 def resample_lengths(lengths, sr_in: int, sr_out: int) -> np.ndarray:

@@ -156,7 +156,7 @@ extern "C" int afx_plan_create(afx_ctx* ctx, const afx_params* p, afx_plan** out
   afx_plan* pl = new afx_plan();
   pl->ctx = ctx; pl->device = ctx->device; pl->p = *p;
   build_host_tables(*p, pl->ht);
-  const size_t lds = frames_lds_bytes(p->n_fft, p->hop);
+  const size_t lds = frames_mr_shape(p->n_fft) ? frames_mr_lds_bytes(p->n_fft, p->hop) : frames_lds_bytes(p->n_fft, p->hop);
   if (lds == 0 || lds > 160 * 1024) {
     delete pl;
     set_error("frame_length/hop_length combination needs more than 160 KiB of LDS per workgroup (hop too large)");
@@ -567,7 +567,7 @@ static int chunk_enqueue(afx_plan* pl, const void* samples, int fmt, int mem_kin
     HIP_TRY(hipMemsetAsync(pl->n_items.p, 0, 16, s));
   }
   pl->info_clean_n = 0;
-  const bool want_stamps = dev_env().stamps;     // diagnostic build of k_frames
+  const bool want_stamps = dev_env().stamps && !frames_mr_shape(kp.n_fft);     // diagnostic build of k_frames (k_frames_mr has none)
   const bool f3 = pl->use_f3 && !want_stamps && (!(kp.flags & 0x7f00) || dev_env().f3_debug);
   bool no_spec = dev_env().no_spec;             // A/B: the two-pass pipeline with k_frames3
   // k_trim_blocks sums 256-sample runs: it has the hop-sized sub-block sums the wave-level kernels' RMS rows need only
@@ -610,6 +610,9 @@ static int chunk_enqueue(afx_plan* pl, const void* samples, int fmt, int mem_kin
       all.blocks = (const BlockDesc*)pl->blocks.p; all.nblocks = pl->nblocks;
       TIMED(AFX_K_FRAMES, launch_frames3_any(all));
     }
+    else if (frames_mr_shape(kp.n_fft))       // not a power of two: the mixed-radix kernel
+      TIMED(AFX_K_FRAMES, launch_frames_mr(s, d_samples, d_info, (const BlockDesc*)pl->blocks.p, pl->nblocks,
+                                           pl->dt, kp, (float*)pl->logmel.p, (float*)pl->rms.p, grid));
     else
       TIMED(AFX_K_FRAMES, launch_frames(s, d_samples, d_info, (const BlockDesc*)pl->blocks.p, pl->nblocks,
                                         pl->dt, kp, (float*)pl->logmel.p, (float*)pl->rms.p, grid, d_stamps));

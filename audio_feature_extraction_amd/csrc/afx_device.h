@@ -129,6 +129,12 @@ hipError_t launch_frames(hipStream_t s, const void* samples, ClipInfo* info,
                          const BlockDesc* blocks, int nblocks, const DevTables& tb, const KParams& kp,
                          float* logmel, float* rms_rows, int grid, unsigned long long* stamps = nullptr);
 constexpr int kStampPhases = 12;
+// afx_frames_mr.hip: the frame kernel of the lengths that are not powers of two (afx_mr.h: multiples of 16 in [256, 2048]
+// with prime factors 2, 3, 5), same contract as launch_frames; 0 bytes = not one of its lengths
+bool frames_mr_shape(int n_fft);
+size_t frames_mr_lds_bytes(int n_fft, int hop);
+hipError_t launch_frames_mr(hipStream_t s, const void* samples, ClipInfo* info, const BlockDesc* blocks, int nblocks,
+                            const DevTables& tb, const KParams& kp, float* logmel, float* rms_rows, int grid);
 hipError_t launch_dct(hipStream_t s, const ClipDesc* clips, const ClipInfo* info, const DevTables& tb,
                       const KParams& kp, const float* logmel, float* mfcc, int n_clips, int max_tmax,
                       bool frame_major = false, bool spec = false);

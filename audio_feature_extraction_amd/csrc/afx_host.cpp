@@ -9,6 +9,7 @@
 #include "afx_device.h"
 #include "afx_f0.h"
 #include "afx_internal.h"
+#include "afx_mr.h"
 
 namespace afx {
 
@@ -47,9 +48,56 @@ bool build_clip_descs(int hop, int trim_hop, const int64_t* offsets, const int64
   return true;
 }
 
+// One Stockham pass of radix R over N2 points, butterfly by butterfly as k_frames_mr's lanes take them.
+template <int R>
+static void mr_host_pass(const mrc* in, mrc* out, const mrc* tw, int N2, int NS) {
+  const int nbf = N2 / R, step = N2 / (NS * R);
+  for (int j = 0; j < nbf; ++j) {
+    mrc x[R];
+    for (int r = 0; r < R; ++r) x[r] = in[j + r * nbf];
+    const int jm = j % NS;
+    mr_butterfly<R>(x, tw, jm, step, NS == 1);
+    for (int r = 0; r < R; ++r) out[(j - jm) * R + jm + r * NS] = x[r];
+  }
+}
+
 }  // namespace afx
 
 using namespace afx;
+
+// The kernel's real FFT on the CPU, float32 throughout: z[n] = x[2n] + i x[2n+1], the schedule's passes, the split.
+extern "C" int afx_rfft_host(int n_fft, const float* x, float* out) {
+  if (!x || !out) { set_error("afx_rfft_host: null argument"); return AFX_ERR_INVALID; }
+  if (!mr_supported(n_fft)) {
+    set_error("afx_rfft_host: frame_length must be a multiple of 16 in [256, 2048] with no prime factor other than 2, 3 and 5");
+    return AFX_ERR_UNSUPPORTED;
+  }
+  const int N2 = n_fft / 2;
+  std::vector<float> twf, postf;
+  build_fft_tables(n_fft, twf, postf);
+  const mrc* tw = reinterpret_cast<const mrc*>(twf.data());
+  const mrc* post = reinterpret_cast<const mrc*>(postf.data());
+  std::vector<mrc> a((size_t)N2), b((size_t)N2);
+  for (int n = 0; n < N2; ++n) a[n] = mr_mk(x[2 * n], x[2 * n + 1]);
+  const MrSchedule sc = mr_schedule(N2);
+  int NS = 1;
+  for (int p = 0; p < sc.n; ++p) {
+    switch (sc.radix(p)) {
+      case 3: mr_host_pass<3>(a.data(), b.data(), tw, N2, NS); break;
+      case 4: mr_host_pass<4>(a.data(), b.data(), tw, N2, NS); break;
+      case 5: mr_host_pass<5>(a.data(), b.data(), tw, N2, NS); break;
+      default: mr_host_pass<8>(a.data(), b.data(), tw, N2, NS); break;
+    }
+    NS *= sc.radix(p);
+    a.swap(b);
+  }
+  for (int k = 0; k < N2; ++k) {
+    const mrc X2 = mr_split2(a[k], a[(N2 - k) % N2], post[k]);
+    out[2 * k] = 0.5f * X2.x; out[2 * k + 1] = 0.5f * X2.y;
+  }
+  out[2 * N2] = a[0].x - a[0].y; out[2 * N2 + 1] = 0.f;
+  return AFX_OK;
+}
 
 extern "C" int afx_version(void) { return AFX_VERSION; }
 

@@ -54,6 +54,7 @@ struct HostTables {
 // returns AFX_OK or a negative status; msg set on failure
 int validate_params(const afx_params& p, std::string& msg);
 void build_host_tables(const afx_params& p, HostTables& t);
+void build_fft_tables(int n_fft, std::vector<float>& tw, std::vector<float>& post);   // HostTables::tw / post alone
 
 void set_error(const std::string& s);
 

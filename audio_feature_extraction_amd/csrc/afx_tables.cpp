@@ -11,6 +11,7 @@
 
 #include "afx_internal.h"
 #include "afx_frames3.h"
+#include "afx_mr.h"
 
 namespace afx {
 
@@ -33,9 +34,9 @@ int validate_params(const afx_params& p, std::string& msg) {
   if (!(p.fmin >= 0.f) || (p.fmax != 0.f && !(p.fmax > p.fmin)) || p.fmax > 0.5f * (float)p.sr + 1e-3f)
     return bad("need 0 <= fmin < fmax <= sr / 2 (fmax = 0 means sr / 2)");
   if (!(p.lifter >= 0.f)) return bad("lifter must be >= 0");
-  bool pow2 = p.n_fft > 0 && (p.n_fft & (p.n_fft - 1)) == 0;
-  if (!pow2 || p.n_fft < 256 || p.n_fft > 4096) {
-    msg = "frame_length must be a power of two in [256, 4096]";
+  // 4096 passes the table builders (afx_plan_create refuses it: the FFT is LDS-resident); the rest is mr_supported's set
+  if (p.n_fft != 4096 && !mr_supported(p.n_fft)) {
+    msg = "frame_length must be a multiple of 16 in [256, 2048] with no prime factor other than 2, 3 and 5";
     return (int)AFX_ERR_UNSUPPORTED;
   }
   return AFX_OK;
@@ -330,7 +331,7 @@ static void build_dct_blocks(const afx_params& p, const std::vector<float>& D, D
 }
 
 void build_host_tables(const afx_params& p, HostTables& t) {
-  const int N = p.n_fft, N2 = N / 2, M = p.n_mels, K = p.n_mfcc;
+  const int N = p.n_fft, M = p.n_mels, K = p.n_mfcc;
   t.window.resize(N);
   for (int n = 0; n < N; ++n) {
     const double c = std::cos(2.0 * kPi * (double)n / (double)N);
@@ -356,12 +357,19 @@ void build_host_tables(const afx_params& p, HostTables& t) {
     }
   }
   build_dct_blocks(p, t.dct, t.dctb);
-  t.tw.resize((size_t)2 * N2); t.post.resize((size_t)2 * N2);
+  build_fft_tables(N, t.tw, t.post);
+}
+
+// tw[n] = exp(-2 pi i n / N2), post[n] = exp(-2 pi i n / n_fft), n < N2 = n_fft / 2: evaluated in double, rounded once.
+// Any even n_fft: the pass twiddles of every radix schedule (afx_mr.h) are entries of tw.
+void build_fft_tables(int n_fft, std::vector<float>& tw, std::vector<float>& post) {
+  const int N = n_fft, N2 = N / 2;
+  tw.resize((size_t)2 * N2); post.resize((size_t)2 * N2);
   for (int n = 0; n < N2; ++n) {
     const double a = -2.0 * kPi * (double)n / (double)N2;
-    t.tw[2 * n] = (float)std::cos(a); t.tw[2 * n + 1] = (float)std::sin(a);
+    tw[2 * n] = (float)std::cos(a); tw[2 * n + 1] = (float)std::sin(a);
     const double b = -2.0 * kPi * (double)n / (double)N;
-    t.post[2 * n] = (float)std::cos(b); t.post[2 * n + 1] = (float)std::sin(b);
+    post[2 * n] = (float)std::cos(b); post[2 * n + 1] = (float)std::sin(b);
   }
 }
 

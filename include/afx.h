@@ -38,7 +38,7 @@ typedef enum afx_status {
   AFX_ERR_NO_DEVICE = -2,   /* no usable HIP device */
   AFX_ERR_HIP = -3,         /* a HIP runtime call or kernel launch failed */
   AFX_ERR_NOMEM = -4,
-  AFX_ERR_UNSUPPORTED = -5  /* e.g. n_fft not a power of two in [256, 2048] */
+  AFX_ERR_UNSUPPORTED = -5  /* e.g. n_fft outside the supported set (see afx_rfft_host) */
 } afx_status;
 
 /* per-clip status written to out_status[] */
@@ -344,6 +344,14 @@ int afx_resample_batch(afx_ctx* ctx, const void* samples, int sample_fmt, int me
                        const int64_t* offsets, const int64_t* lengths, int n_clips, int sr_in, int sr_out,
                        const double* taps, int n_taps, float* out, int out_mem_kind,
                        const int64_t* out_offsets, int64_t* out_lengths);
+
+/* Host-only (no device needed): the real FFT the frame kernel of the frame lengths that are not powers of two runs
+ * (k_frames_mr), executed in float32 on the CPU with the same radix schedule, twiddle tables and operation order:
+ * n_fft / 2 complex points through Stockham passes of radix 3, 5, 4, 8, then the real-FFT split.  out holds the
+ * n_fft / 2 + 1 bins as (re, im) pairs.  For tests of the schedule and for bisecting a device mismatch.
+ * AFX_ERR_UNSUPPORTED unless n_fft is a multiple of 16 in [256, 2048] with no prime factor other than 2, 3 and 5
+ * (the set afx_plan_create accepts). */
+int afx_rfft_host(int n_fft, const float* x /*[n_fft]*/, float* out /*[2 * (n_fft / 2 + 1)]*/);
 
 /* preprocess_audio(y) (F:58-74): pre-emphasis + trim of ONE host clip.
  * out_y receives the n pre-emphasised samples (host, n floats); the kept span
