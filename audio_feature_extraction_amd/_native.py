@@ -25,6 +25,11 @@ DTW_BACKTRACK, DTW_STORE_D = 1, 2
 DTW_MAX_DIM = 128
 HPSS_STORE_SPEC = 4
 HPSS_BINS = 1025
+SMP_U8, SMP_S16, SMP_S24, SMP_S32, SMP_F32, SMP_F64 = range(6)
+SMP_KINDS = {"u8": SMP_U8, "s16": SMP_S16, "s24": SMP_S24, "s32": SMP_S32, "f32": SMP_F32, "f64": SMP_F64}     # wavio's kind names
+SMP_BYTES = np.array([1, 2, 3, 4, 4, 8], np.int64)
+SMP_OF_WAV = {(1, 8): SMP_U8, (1, 16): SMP_S16, (1, 24): SMP_S24, (1, 32): SMP_S32, (3, 32): SMP_F32, (3, 64): SMP_F64}   # (tag, bits)
+DECODE_MAX_CHANNELS = 7
 K_NAMES = ("trim_blocks", "trim_decide", "frames", "dct", "stats")
 K_FRAMES = 2
 
@@ -35,7 +40,7 @@ SYMBOLS = (
     "afx_default_params", "afx_plan_create", "afx_plan_destroy", "afx_build_tables", "afx_build_mel_schedule",
     "afx_extract_batch", "afx_extract_submit", "afx_extract_collect", "afx_f0_batch", "afx_zcr_batch", "afx_spectral_batch", "afx_f0_build_tables", "afx_preprocess", "afx_plan_set_timing", "afx_plan_get_timings", "afx_plan_get_intervals",
     "afx_wav_probe", "afx_wav_read_s16", "afx_batch_geometry", "afx_dtw_batch", "afx_hpss_batch",
-    "afx_resample_design", "afx_resample_batch", "afx_rfft_host",
+    "afx_resample_design", "afx_resample_batch", "afx_rfft_host", "afx_wav_read_raw", "afx_decode_batch",
 )
 
 
@@ -108,6 +113,9 @@ def lib() -> C.CDLL:
         if hasattr(L, "afx_resample_batch"):                 # absent from a library older than version 107
             L.afx_resample_design.argtypes = [i32, i32, vp, vp]
             L.afx_resample_batch.argtypes = [vp, vp, i32, i32, vp, vp, i32, i32, i32, vp, i32, vp, i32, vp, vp]
+        if hasattr(L, "afx_decode_batch"):                   # newer than version 107 says: found by their presence
+            L.afx_wav_read_raw.argtypes = [vp, i32, i32, vp, vp, vp, C.c_int64, vp, vp]
+            L.afx_decode_batch.argtypes = [vp, vp, i32, vp, vp, vp, vp, i32, vp, i32, vp]
         if hasattr(L, "afx_rfft_host"):                      # absent from a library built before the mixed-radix lengths
             L.afx_rfft_host.argtypes = [i32, vp, vp]
         _lib = L
@@ -148,6 +156,38 @@ def wav_read_s16(paths, data_off, frames, out: np.ndarray, offsets, threads: int
         _check(lib().afx_wav_read_s16(arr, n, int(threads), data_off.ctypes.data, frames.ctypes.data, out.ctypes.data,
                                       int(out.size), offsets.ctypes.data, status.ctypes.data), "afx_wav_read_s16")
     return status
+
+
+def wav_read_raw(paths, data_off, nbytes, out: np.ndarray, offsets, threads: int = 16) -> np.ndarray:
+    """Host-only: ``nbytes[i]`` bytes of file i from ``data_off[i]`` straight into ``out`` (uint8, C-contiguous) at byte
+    ``offsets[i]``; -> status per file (0 read, 2 cannot be opened / read).  ValueError, with ``out`` untouched, when a
+    clip does not fit ``out``."""
+    n = len(paths)
+    status = np.zeros(n, np.int32)
+    if not hasattr(lib(), "afx_wav_read_raw"):
+        raise NotImplementedError("this libafx has no afx_wav_read_raw")
+    if n:
+        if out.dtype != np.uint8 or not out.flags.c_contiguous:
+            raise ValueError("out must be C-contiguous uint8")
+        data_off = np.ascontiguousarray(data_off, np.int64)
+        nbytes = np.ascontiguousarray(nbytes, np.int64)
+        offsets = np.ascontiguousarray(offsets, np.int64)
+        if not (data_off.shape[0] == nbytes.shape[0] == offsets.shape[0] == n):
+            raise ValueError("data_off, nbytes and offsets must have one entry per file")
+        arr = _path_array(paths)
+        _check(lib().afx_wav_read_raw(arr, n, int(threads), data_off.ctypes.data, nbytes.ctypes.data, out.ctypes.data,
+                                      int(out.size), offsets.ctypes.data, status.ctypes.data), "afx_wav_read_raw")
+    return status
+
+
+def wav_sample_kinds(probe: dict) -> np.ndarray:
+    """Per probed file the SMP_* kind afx_decode_batch takes it as, or -1: status 0, a (tag, bits) pair of SMP_OF_WAV,
+    1 .. DECODE_MAX_CHANNELS channels and a positive rate."""
+    kinds = np.full(probe["status"].shape[0], -1, np.int32)
+    for (tag, bits), k in SMP_OF_WAV.items():
+        kinds[(probe["tag"] == tag) & (probe["bits"] == bits)] = k
+    kinds[(probe["status"] != 0) | (probe["channels"] < 1) | (probe["channels"] > DECODE_MAX_CHANNELS) | (probe["rate"] <= 0)] = -1
+    return kinds
 
 
 def batch_geometry(p: "Params", offsets, lengths) -> dict:
@@ -331,6 +371,11 @@ class DeviceBuffer(_Owner):
         assert byte_offset + arr.nbytes <= self.nbytes
         _check(lib().afx_memcpy_h2d(self.ctx.handle, self.ptr + byte_offset, arr.ctypes.data, arr.nbytes), "afx_memcpy_h2d")
 
+    def download(self, arr: np.ndarray, byte_offset: int = 0):
+        """Fills the C-contiguous array ``arr`` from the buffer (synchronous)."""
+        assert arr.flags.c_contiguous and byte_offset + arr.nbytes <= self.nbytes
+        _check(lib().afx_memcpy_d2h(self.ctx.handle, arr.ctypes.data, self.ptr + byte_offset, arr.nbytes), "afx_memcpy_d2h")
+
     def free(self):
         if self.ptr:
             lib().afx_free(self.ctx.handle, self.ptr)
@@ -465,6 +510,52 @@ class Context(_Owner):
                                         got.ctypes.data), "afx_resample_batch")
         return {"out": out, "offsets": out_offsets, "lengths": got}
 
+    def decode_batch(self, raw, byte_offsets, frames, kinds, channels, out=None, out_offsets=None) -> dict:
+        """afx_decode_batch: raw WAVE data -> mono float32, bit for bit wavio.to_mono(wavio.to_float32(...)).  Clip i is
+        ``frames[i]`` interleaved frames of ``channels[i]`` (1 .. 7) channels of kind ``kinds[i]`` (SMP_*) from byte
+        ``byte_offsets[i]`` (a multiple of 16) of ``raw``: a uint8 numpy array (host) or a DeviceBuffer / device pointer.
+        ``out``: None (a new host array), a float32 numpy array, or a DeviceBuffer the result stays in; ``out_offsets``:
+        where each clip goes (multiples of 4; default: packed with 4-element alignment, as parallel._pack).  The elements
+        from a clip's end to the next multiple of 4 are zeroed.  Returns out, offsets, lengths."""
+        byte_offsets, frames, n = _clip_arrays(byte_offsets, frames)
+        kinds = np.ascontiguousarray(kinds, np.int32).reshape(-1)
+        channels = np.ascontiguousarray(channels, np.int32).reshape(-1)
+        if kinds.shape[0] != n or channels.shape[0] != n:
+            raise ValueError("kinds and channels must have one entry per clip")
+        if not hasattr(lib(), "afx_decode_batch"):
+            raise NotImplementedError("this libafx has no afx_decode_batch")
+        flen = np.maximum(frames, 0)
+        if isinstance(raw, np.ndarray):
+            if raw.dtype != np.uint8 or not raw.flags.c_contiguous:
+                raise ValueError("raw must be a C-contiguous uint8 array")
+            known = (kinds >= 0) & (kinds < 6)
+            nbytes = flen * SMP_BYTES[np.where(known, kinds, 0)] * np.maximum(channels, 0)
+            if n and int((byte_offsets + np.where(known, nbytes, 0)).max()) > raw.size:
+                raise ValueError("a clip extends past the raw buffer")
+            rptr, rkind = raw.ctypes.data, MEM_HOST
+        else:
+            rptr, rkind = (raw.ptr if isinstance(raw, DeviceBuffer) else int(raw)), MEM_DEVICE
+        if out_offsets is None:
+            out_offsets = packed_offsets(flen, 4)
+        out_offsets = np.ascontiguousarray(out_offsets, np.int64).reshape(-1)
+        if out_offsets.shape[0] != n:
+            raise ValueError("out_offsets must have one entry per clip")
+        need = int((out_offsets + (flen + 3) // 4 * 4).max()) if n else 0
+        if out is None:
+            out = np.zeros(need, np.float32)
+        if isinstance(out, np.ndarray):
+            if out.dtype != np.float32 or not out.flags.c_contiguous or out.size < need:
+                raise ValueError("out must be a C-contiguous float32 array that holds every clip, padded to 4 elements")
+            optr, okind = out.ctypes.data, MEM_HOST
+        else:
+            if isinstance(out, DeviceBuffer) and out.nbytes < 4 * need:
+                raise ValueError("the output DeviceBuffer is too small")
+            optr, okind = (out.ptr if isinstance(out, DeviceBuffer) else int(out)), MEM_DEVICE
+        _check(lib().afx_decode_batch(self.handle, rptr, rkind, byte_offsets.ctypes.data, frames.ctypes.data,
+                                      kinds.ctypes.data, channels.ctypes.data, n, optr, okind, out_offsets.ctypes.data),
+               "afx_decode_batch")
+        return {"out": out, "offsets": out_offsets, "lengths": frames}
+
 
 class Plan(_Owner):
     def __init__(self, ctx: Context, params: Params):
@@ -492,6 +583,10 @@ class Plan(_Owner):
     def resample_batch(self, samples, offsets, lengths, sr_in: int, sr_out: int, **kw) -> dict:
         """Context.resample_batch on this plan's context (synchronous on return: any plan may read the result)."""
         return self.ctx.resample_batch(samples, offsets, lengths, sr_in, sr_out, **kw)
+
+    def decode_batch(self, raw, byte_offsets, frames, kinds, channels, **kw) -> dict:
+        """Context.decode_batch on this plan's context (synchronous on return: any plan may read the result)."""
+        return self.ctx.decode_batch(raw, byte_offsets, frames, kinds, channels, **kw)
 
     def set_timing(self, on, frames_only: bool = False):
         """HIP events around every kernel of a batch (or, frames_only, around the frame kernel alone)."""

@@ -72,7 +72,7 @@ extern "C" void afx_destroy(afx_ctx* ctx) {
   (void)hipSetDevice(ctx->device);
   for (DevBuf* b : {&ctx->dtw_raw, &ctx->dtw_feats, &ctx->dtw_norms, &ctx->dtw_pairs, &ctx->dtw_codes, &ctx->dtw_rows, &ctx->dtw_d,
                     &ctx->dtw_path, &ctx->dtw_cost, &ctx->dtw_status, &ctx->dtw_len, &ctx->rs_g, &ctx->rs_tstart, &ctx->rs_clips,
-                    &ctx->rs_in, &ctx->rs_out})
+                    &ctx->rs_in, &ctx->rs_out, &ctx->dc_clips, &ctx->dc_in, &ctx->dc_out})
     release(*b);
   if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
   delete ctx;

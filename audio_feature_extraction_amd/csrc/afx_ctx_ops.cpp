@@ -1,4 +1,5 @@
-// The entry points of libafx.so that work on a context, not a plan: batched DTW and batched polyphase resampling.
+// The entry points of libafx.so that work on a context, not a plan: batched DTW, batched polyphase resampling, and the
+// conversion / mix-down of raw WAVE data.
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -9,6 +10,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include "afx_decode.h"
 #include "afx_devenv.h"
 #include "afx_dtw.h"
 #include "afx_internal.h"
@@ -250,6 +252,93 @@ extern "C" int afx_resample_batch(afx_ctx* ctx, const void* samples, int sample_
     HIP_TRY(hipStreamSynchronize(s));
     for (int i = 0; i < n_clips; ++i)
       if (recs[i].out_len) std::memcpy(out + out_offsets[i], h_out.data() + recs[i].out_off, (size_t)recs[i].out_len * sizeof(float));
+  } else {
+    HIP_TRY(hipStreamSynchronize(s));
+  }
+  return AFX_OK;
+}
+
+// ---- raw WAVE data -> mono float32 (wavio.to_float32 + wavio.to_mono: the decode half of librosa.load) -------------------
+extern "C" int afx_decode_batch(afx_ctx* ctx, const void* raw, int mem_kind, const int64_t* byte_offsets, const int64_t* frames,
+                                const int32_t* kinds, const int32_t* channels, int n_clips,
+                                float* out, int out_mem_kind, const int64_t* out_offsets) {
+  const std::string who = "afx_decode_batch";
+  if (!ctx || n_clips < 0 || (n_clips > 0 && (!byte_offsets || !frames || !kinds || !channels || !out_offsets))) {
+    set_error(who + ": null/invalid argument");
+    return AFX_ERR_INVALID;
+  }
+  int rc;
+  if ((rc = check_sample_format(who.c_str(), AFX_FMT_F32, mem_kind)) != AFX_OK) return rc;
+  if ((rc = check_sample_format(who.c_str(), AFX_FMT_F32, out_mem_kind)) != AFX_OK) return rc;
+  // clip records; host batches are staged packed (16-byte / 4-element alignment), so only the clips themselves cross the link
+  std::vector<DcClip> recs((size_t)n_clips);
+  std::vector<int> order;
+  int64_t n_blocks = 0, in_pos = 0, out_pos = 0;
+  for (int i = 0; i < n_clips; ++i) {
+    const auto clip = [&]() { return who + ": clip " + std::to_string(i); };      // error paths only
+    if (byte_offsets[i] < 0 || out_offsets[i] < 0 || frames[i] < 0 || byte_offsets[i] > INT64_MAX / 8 || out_offsets[i] > INT64_MAX / 8) {
+      set_error(clip() + ": offsets and frame counts must be >= 0");
+      return AFX_ERR_INVALID;
+    }
+    if (frames[i] > ((int64_t)1 << 31)) { set_error(clip() + ": more than 2^31 sample frames is not supported"); return AFX_ERR_UNSUPPORTED; }
+    const int sb = decode_sample_bytes(kinds[i]);
+    if (!sb) { set_error(clip() + ": unknown sample kind"); return AFX_ERR_INVALID; }
+    if (channels[i] < 1) { set_error(clip() + ": fewer than one channel"); return AFX_ERR_INVALID; }
+    if (channels[i] > kDcMaxChannels) { set_error(clip() + ": more than 7 channels is not supported"); return AFX_ERR_UNSUPPORTED; }
+    if ((byte_offsets[i] & 15) || (out_offsets[i] & 3)) {
+      set_error(clip() + ": byte_offsets must be multiples of 16 and out_offsets multiples of 4");
+      return AFX_ERR_INVALID;
+    }
+    DcClip& r = recs[i];
+    r.frames = frames[i]; r.kind = kinds[i]; r.channels = channels[i];
+    r.in_off = mem_kind == AFX_MEM_HOST ? in_pos : byte_offsets[i];
+    r.out_off = out_mem_kind == AFX_MEM_HOST ? out_pos : out_offsets[i];
+    r.first_block = (int32_t)n_blocks; r.pad_ = 0;
+    in_pos += (frames[i] * sb * channels[i] + 15) / 16 * 16;
+    out_pos += (frames[i] + 3) / 4 * 4;
+    n_blocks += (frames[i] + kDcFrames - 1) / kDcFrames;
+    if (n_blocks > INT32_MAX / 2) { set_error(who + ": batch too large for one launch"); return AFX_ERR_UNSUPPORTED; }
+    if (frames[i] > 0) order.push_back(i);
+  }
+  // every output element has one writer: the slots (4-element padding included) must not overlap
+  std::sort(order.begin(), order.end(), [&](int a, int b) { return out_offsets[a] < out_offsets[b]; });
+  for (size_t k = 1; k < order.size(); ++k) {
+    const int a = order[k - 1], b = order[k];
+    if (out_offsets[a] + (frames[a] + 3) / 4 * 4 > out_offsets[b]) {
+      set_error(who + ": the output slots of clips " + std::to_string(a) + " and " + std::to_string(b) + " overlap");
+      return AFX_ERR_INVALID;
+    }
+  }
+  if (order.empty()) return AFX_OK;
+  if (!raw || !out) { set_error(who + ": null raw / out"); return AFX_ERR_INVALID; }
+  (void)hipGetLastError();
+  HIP_TRY(hipSetDevice(ctx->device));
+  hipStream_t s = ctx->stream;
+  const void* d_in = raw;
+  std::vector<uint8_t> h_in;
+  if (mem_kind == AFX_MEM_HOST) {
+    h_in.assign((size_t)in_pos, 0);
+    for (int i : order)
+      std::memcpy(h_in.data() + recs[i].in_off, (const uint8_t*)raw + byte_offsets[i],
+                  (size_t)(frames[i] * decode_sample_bytes(kinds[i]) * channels[i]));
+    if ((rc = ensure(ctx->dc_in, h_in.size())) != AFX_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(ctx->dc_in.p, h_in.data(), h_in.size(), hipMemcpyHostToDevice, s));
+    d_in = ctx->dc_in.p;
+  }
+  float* d_out = out;
+  if (out_mem_kind == AFX_MEM_HOST) {
+    if ((rc = ensure(ctx->dc_out, (size_t)out_pos * sizeof(float))) != AFX_OK) return rc;
+    d_out = (float*)ctx->dc_out.p;
+  }
+  if ((rc = ensure(ctx->dc_clips, recs.size() * sizeof(DcClip))) != AFX_OK) return rc;
+  HIP_TRY(hipMemcpyAsync(ctx->dc_clips.p, recs.data(), recs.size() * sizeof(DcClip), hipMemcpyHostToDevice, s));
+  HIP_TRY(launch_decode(s, d_in, d_out, (const DcClip*)ctx->dc_clips.p, n_clips, (int)n_blocks));
+  if (out_mem_kind == AFX_MEM_HOST) {
+    std::vector<float> h_out((size_t)out_pos);
+    HIP_TRY(hipMemcpyAsync(h_out.data(), d_out, (size_t)out_pos * sizeof(float), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    for (int i : order)
+      std::memcpy(out + out_offsets[i], h_out.data() + recs[i].out_off, (size_t)((frames[i] + 3) / 4 * 4) * sizeof(float));
   } else {
     HIP_TRY(hipStreamSynchronize(s));
   }

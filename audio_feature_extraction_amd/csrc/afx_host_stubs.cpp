@@ -53,4 +53,8 @@ int afx_resample_batch(afx_ctx*, const void*, int, int, const int64_t*, const in
                        int, const int64_t*, int64_t*) {
   return no_device("afx_resample_batch");
 }
+int afx_decode_batch(afx_ctx*, const void*, int, const int64_t*, const int64_t*, const int32_t*, const int32_t*, int, float*, int,
+                     const int64_t*) {
+  return no_device("afx_decode_batch");
+}
 }

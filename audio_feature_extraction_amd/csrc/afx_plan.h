@@ -10,6 +10,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include "afx_decode.h"
 #include "afx_device.h"
 #include "afx_f0.h"
 #include "afx_frames3.h"
@@ -39,6 +40,7 @@ struct afx_ctx {
     RsTables t;
   } rs;
   DevBuf rs_g, rs_tstart, rs_clips, rs_in, rs_out;
+  DevBuf dc_clips, dc_in, dc_out;      // afx_decode_batch: clip records, staging of host batches
 };
 
 struct afx_plan {

@@ -1,5 +1,6 @@
 // Host-side ingest for batch_process: RIFF/WAVE headers of many files parsed, and the samples of the files that need
-// no conversion (16-bit PCM) read straight into the caller's packed batch buffer, by native threads.
+// no conversion (16-bit PCM) read straight into the caller's packed batch buffer, by native threads; the data chunk of every
+// other layout read as bytes for the device decoder (afx_decode_batch).
 // (reference: AudioFeatureExtractor.load_audio, core/feature_extractor.py:52 -> librosa.load -> soundfile; the chunk walk
 // and its error cases are those of audio_feature_extraction_amd/wavio.py: _parse / read_wav_raw, which remains the
 // decoder of every other sample type and of files these entry points reject.)
@@ -130,6 +131,27 @@ extern "C" int afx_wav_read_s16(const char* const* paths, int n, int threads, co
     const int fd = paths[i] ? ::open(paths[i], O_RDONLY | O_CLOEXEC) : -1;
     if (fd < 0) return;
     if (frames[i] == 0 || pread_all(fd, out + offsets[i], (size_t)frames[i] * sizeof(int16_t), data_off[i])) status[i] = 0;
+    ::close(fd);
+  });
+  return AFX_OK;
+}
+
+extern "C" int afx_wav_read_raw(const char* const* paths, int n, int threads, const int64_t* data_off, const int64_t* nbytes,
+                                uint8_t* out, int64_t out_len, const int64_t* offsets, int32_t* status) {
+  if (n < 0 || out_len < 0 || (n > 0 && (!paths || !data_off || !nbytes || !out || !offsets || !status))) {
+    afx::set_error("afx_wav_read_raw: null/invalid argument");
+    return AFX_ERR_INVALID;
+  }
+  for (int i = 0; i < n; ++i)
+    if (nbytes[i] < 0 || offsets[i] < 0 || data_off[i] < 0 || nbytes[i] > out_len || offsets[i] > out_len - nbytes[i]) {   // no signed overflow
+      afx::set_error("afx_wav_read_raw: a clip does not fit the output buffer");
+      return AFX_ERR_INVALID;
+    }
+  run_threads(n, threads, [&](int i) {
+    status[i] = 2;
+    const int fd = paths[i] ? ::open(paths[i], O_RDONLY | O_CLOEXEC) : -1;
+    if (fd < 0) return;
+    if (nbytes[i] == 0 || pread_all(fd, out + offsets[i], (size_t)nbytes[i], data_off[i])) status[i] = 0;
     ::close(fd);
   });
   return AFX_OK;

@@ -82,6 +82,12 @@ def _decode(path: str, sr: int, keep_rate: bool = False):
 
 
 _ALIGN = 4               # clips start on 4-element boundaries (enables the kernels' 16-byte loads)
+_RAW_ALIGN = 16          # raw WAVE data: clips start on 16-byte boundaries (afx_decode_batch)
+
+
+def _raw_padded(nbytes):
+    """A clip's byte count, or an array of them, rounded up to the raw alignment."""
+    return (nbytes + (_RAW_ALIGN - 1)) // _RAW_ALIGN * _RAW_ALIGN
 
 
 def _padded(n):
@@ -213,7 +219,10 @@ def normalize_features(features_to_extract) -> Tuple[str, ...]:
 
 
 def _size_estimate(path) -> int:
-    """A file's sample count as its size says (a proxy for clip length that needs no decode)."""
+    """A file's sample count as its size says (a proxy for clip length that needs no decode, not even a header read: exact
+    for 16-bit mono; a stereo or wider file counts for more than its mono samples, so its windows -- which bound the
+    page-locked host memory, two per worker -- come out smaller than the device budget allows; the sub-batches themselves
+    are cut from the frame counts the probe reports)."""
     try:
         return max(1, os.path.getsize(str(path)) // 2)
     except OSError:
@@ -241,18 +250,25 @@ def _lane_pool(extractor, attr: str, key, make):
 
 class _Lane:
     """What one (device, lane) worker drives: the MFCC / RMS plan and the pYIN plan (own context and stream each), its
-    pooled device buffers and, where the plan offers them, page-locked window buffers and the device resampler."""
+    pooled device buffers and, where the plan offers them, page-locked window buffers, the device resampler and the device
+    decoder."""
 
     def __init__(self, extractor, lane, want_f0: bool):
         self.plan = extractor._plan(lane[0], lane[1])
         self.plan_f0 = extractor._plan(lane[0], (lane[1], "f0")) if want_f0 else None
         self.dev = _lane_pool(extractor, "_dev_pools", lane, lambda: _DevPool(self.plan))
         self.can_rs = hasattr(self.plan, "resample_batch")
-        self.dev_in = self.pin = None
-        if self.can_rs:                                           # the resampler's input: a second pooled device buffer
+        self.can_dec = hasattr(self.plan, "decode_batch")          # raw WAVE data is converted and mixed down on the device
+        self.dev_in = self.dev_raw = self.pin = None
+        if self.can_rs or self.can_dec:                           # the resampler's input: a second pooled device buffer
             self.dev_in = _lane_pool(extractor, "_dev_pools", (lane, "in"), lambda: _DevPool(self.plan))
-        if hasattr(self.plan, "pinned_buffer"):                   # page-locked window buffers, kept with the extractor
-            self.pin = _lane_pool(extractor, "_pin_pools", lane, lambda: _PinPool(self.plan))
+        if self.can_dec:                                          # the decoder's input: the raw bytes of a sub-batch
+            self.dev_raw = _lane_pool(extractor, "_dev_pools", (lane, "raw"), lambda: _DevPool(self.plan))
+        self.pin_raw = None
+        if hasattr(self.plan, "pinned_buffer"):                   # page-locked window buffers, kept with the extractor:
+            self.pin = _lane_pool(extractor, "_pin_pools", lane, lambda: _PinPool(self.plan))     # int16 windows
+            if self.can_dec:                                      # raw byte windows, of other sizes: a pool of their own
+                self.pin_raw = _lane_pool(extractor, "_pin_pools", (lane, "raw"), lambda: _PinPool(self.plan))
 
 
 class _Job:
@@ -285,6 +301,9 @@ class _Job:
         self.native_threads = max(1, min(host_cpus, DECODE_THREADS_PER_GPU * len(devices)) // max(1, min(len(self.lanes), 4)))
         self.win_pool = ThreadPoolExecutor(max(1, len(self.lanes)))
         self.phase = {"decode_wait": 0.0, "device": 0.0}
+        # files by the ingest path that took them: native_s16 / native_raw count files the native readers delivered to a
+        # device pass, python the files handed to the Python decoder (those it rejects included)
+        self.ingest = {"native_s16": 0, "native_raw": 0, "python": 0}
         self.phase_lock = threading.Lock()
         self.timeline: List[Any] = []            # (lane, clips, t_begin, t_uploaded, t_f0_done, t_collected) per sub-batch
         self.finished: Any = queue.SimpleQueue()  # index lists of sub-batches whose results are in the arrays
@@ -304,18 +323,21 @@ class _Job:
             self.errors[i] = e
             return None
 
-    def load_window(self, win, pin=None, can_rs=False):
-        """-> (packed 16-bit group or None, indices decoded by wavio, their decoded clips); pin: the worker's pool of
-        page-locked buffers (None: ordinary memory); can_rs: the plan resamples on the device, so 16-bit mono files of
-        any rate are read natively (laid out rate by rate, the extractor's own rate first) and decoded files keep theirs.
+    def load_window(self, win, pin=None, can_rs=False, can_dec=False, pin_raw=None):
+        """-> (packed 16-bit group or None, packed raw group or None, indices decoded by wavio, their decoded clips);
+        pin / pin_raw: the worker's pools of page-locked int16 / byte buffers (None: ordinary memory); can_rs: the plan resamples on the device, so
+        16-bit mono files of any rate are read natively (laid out rate by rate, the extractor's own rate first) and
+        decoded files keep theirs; can_dec: the plan converts and mixes down raw WAVE data on the device.
 
         Files that need no conversion -- 16-bit PCM, mono, at the target rate: what a corpus of speech clips is -- never
         pass through Python: libafx parses their headers and reads their samples straight into the packed int16 batch
-        buffer with native threads (afx_wav_probe / afx_wav_read_s16).  Everything else, and any file the native reader
-        cannot open or parse, goes through wavio (which also produces the error a bad file is logged with)."""
+        buffer with native threads (afx_wav_probe / afx_wav_read_s16).  With can_dec, the data chunk of every other file
+        afx_decode_batch takes (PCM 8 / 16 / 24 / 32 bit, float 32 / 64 bit, 1 to 7 channels, any rate) is read as it is
+        into a byte window, each clip at a 16-byte boundary (afx_wav_read_raw).  Everything else, and any file the native
+        readers cannot open or parse, goes through wavio (which also produces the error a bad file is logged with)."""
         sr = self.ex.sr
         rest = list(win)
-        packed = None
+        packed = rawpack = None
         held = None
         try:
             paths = [str(self.files[i]) for i in win]
@@ -345,25 +367,67 @@ class _Job:
                     held = None
                     taken = set(packed[0])
                     rest = [i for i in win if i not in taken]
+            if can_dec:
+                rawpack = self.load_raw(win, paths, pr, ~ok, pin_raw)
+                if rawpack is not None:
+                    taken = set(rawpack[0])
+                    rest = [i for i in rest if i not in taken]
         except Exception:                                         # no native reader: the Python decoder takes the window
-            rest, packed = list(win), None
+            for pool, held_by in ((pin, packed and packed[4]), (pin_raw, rawpack and rawpack[7])):
+                if held_by is not None:
+                    pool.put(held_by)
+            rest, packed, rawpack = list(win), None, None
         if held is not None:
             pin.put(held)
         decoded = list(self.pool.map(self.decode, rest, [can_rs] * len(rest))) if rest else []
-        return packed, rest, decoded
+        return packed, rawpack, rest, decoded
 
-    def resample_on_device(self, lane: _Lane, buf, offs, lens, fmt, rate: int):
+    def load_raw(self, win, paths, pr, free, pin):
+        """The raw group of a window: of the probed files ``free`` marks (not taken as 16-bit mono), those the device
+        decoder takes, their data chunks read into one byte window (page-locked with ``pin``) rate by rate, the extractor's
+        own rate first -> (file indices, bytes, byte offsets, frames, kinds, channels, rates, held buffer) or None.  A file
+        whose read fails is left to the Python decoder."""
+        kinds = _native.wav_sample_kinds(pr)
+        sel = np.nonzero(free & (kinds >= 0))[0]
+        if not sel.size:
+            return None
+        sr = self.ex.sr
+        sel = sel[np.lexsort((sel, pr["rate"][sel], pr["rate"][sel] != sr))]
+        frames = pr["frames"][sel].astype(np.int64)
+        chans = pr["channels"][sel].astype(np.int32)
+        nbytes = frames * _native.SMP_BYTES[kinds[sel]] * chans
+        boffs = _native.packed_offsets(nbytes, _RAW_ALIGN)
+        total = max(int(boffs[-1] + _raw_padded(nbytes[-1])), _RAW_ALIGN)
+        held = pin.get(total) if pin is not None else None
+        good = None
+        try:
+            buf = held.array(np.uint8, total) if held is not None else np.empty(total, np.uint8)
+            st = _native.wav_read_raw([paths[j] for j in sel], pr["data_off"][sel], nbytes, buf, boffs, self.native_threads)
+            good = st == 0
+        finally:
+            if held is not None and (good is None or not good.any()):
+                pin.put(held)
+        if not good.any():
+            return None
+        return ([win[j] for j in sel[good]], buf, boffs[good], frames[good], kinds[sel[good]], chans[good],
+                pr["rate"][sel[good]].astype(np.int64), held)
+
+    def resample_on_device(self, lane: _Lane, buf, offs, lens, fmt, rate: int, din=None):
         """Clips at ``rate`` -> float32 clips at the extractor's rate in a pooled device buffer (4-aligned, as _pack):
-        (buffer, offsets, lengths), or None for a rate pair the device resampler does not hold.  The input buffer always
-        goes back to its pool (the resampler is synchronous: it is done with), the output buffer on every exit but the
-        first."""
+        (buffer, offsets, lengths), or None for a rate pair the device resampler does not hold.  ``buf``: the clips in host
+        memory, uploaded to a pooled input buffer that always goes back to its pool (the resampler is synchronous: it is
+        done with); or ``din``: a device buffer that holds them already and stays the caller's.  The output buffer goes
+        back to its pool on every exit but the first."""
         sr = int(self.ex.sr)
         olens = _native.resample_lengths(lens, rate, sr)             # known on the host: no read-back
         ooffs = _native.packed_offsets(olens, _ALIGN)
-        din = lane.dev_in.get(max(buf.nbytes, 16))
+        own = din is None
+        if own:
+            din = lane.dev_in.get(max(buf.nbytes, 16))
         dbuf = None
         try:
-            din.upload(buf)
+            if own:
+                din.upload(buf)
             dbuf = lane.dev.get(max(4 * int(ooffs[-1] + _padded(olens[-1])), 16))
             lane.plan.resample_batch(din, offs, lens, rate, sr, fmt=fmt, out=dbuf, out_offsets=ooffs)
         except BaseException as e:
@@ -373,7 +437,8 @@ class _Job:
                 return None
             raise
         finally:
-            lane.dev_in.put(din)
+            if own:
+                lane.dev_in.put(din)
         return dbuf, ooffs, olens
 
     def resample_on_host(self, buf, offs, lens, fmt, rate: int):
@@ -394,12 +459,56 @@ class _Job:
             else:
                 buf, offs, lens = self.resample_on_host(buf, offs, lens, fmt, rate)
             fmt = _native.FMT_F32
-        uploaded = dbuf is not None
-        if not uploaded:
+        if dbuf is None:
             dbuf = lane.dev.get(max(buf.nbytes, 16))                  # one PCIe copy for both passes
-        try:
-            if not uploaded:
+            try:
                 dbuf.upload(buf)
+            except BaseException:
+                lane.dev.put(dbuf)
+                raise
+        self.run_passes(lane, cur, dbuf, offs, lens, fmt, tl)
+
+    def run_raw_group(self, lane: _Lane, cur, raw, boffs, frames, kinds, chans, rate: int):
+        """One sub-batch of raw WAVE data: one upload of the bytes as they are, conversion and mix-down on the device
+        (afx_decode_batch) into a pooled float32 buffer (4-aligned, as _pack) that the passes read -- or, at another rate
+        than the extractor's, that the device resampler reads.  Every buffer goes back to its pool on every exit path."""
+        tl = [None, len(cur), self.now(), 0.0, 0.0, 0.0]
+        sr = int(self.ex.sr)
+        offs = _native.packed_offsets(frames, _ALIGN)
+        lens = frames
+        pool = lane.dev if rate == sr else lane.dev_in
+        dbuf = pool.get(max(4 * int(offs[-1] + _padded(frames[-1])), 16))
+        try:
+            draw = lane.dev_raw.get(max(raw.nbytes, 16))
+            try:
+                draw.upload(raw)
+                lane.plan.decode_batch(draw, boffs, frames, kinds, chans, out=dbuf, out_offsets=offs)
+            finally:
+                lane.dev_raw.put(draw)                            # the decoder is synchronous: it is done with
+            if rate != sr:
+                res = self.resample_on_device(lane, None, offs, lens, _native.FMT_F32, rate, din=dbuf) if lane.can_rs else None
+                host = None
+                if res is None:                                   # no device table: the decoded samples copied back
+                    host = np.empty(int(offs[-1] + _padded(frames[-1])), np.float32)
+                    dbuf.download(host)
+                pool.put(dbuf)
+                dbuf = None
+                if res is not None:
+                    dbuf, offs, lens = res
+                else:
+                    buf, offs, lens = self.resample_on_host(host, offs, lens, _native.FMT_F32, rate)
+                    dbuf = lane.dev.get(max(buf.nbytes, 16))
+                    pool = lane.dev
+                    dbuf.upload(buf)
+        except BaseException:
+            if dbuf is not None:
+                pool.put(dbuf)
+            raise
+        self.run_passes(lane, cur, dbuf, offs, lens, _native.FMT_F32, tl)
+
+    def run_passes(self, lane: _Lane, cur, dbuf, offs, lens, fmt, tl):
+        """Both passes over the clips of a sub-batch in ``dbuf``, a buffer of lane.dev's that goes back to that pool."""
+        try:
             tl[3] = self.now()
             submitted = False
             if self.want_stats:                                   # MFCC / RMS pass: queued, runs beside the pYIN pass below
@@ -429,18 +538,33 @@ class _Job:
         finally:
             lane.dev.put(dbuf)                                    # both passes are through (collect above): reusable
 
-    def run_window(self, lane: _Lane, packed, rest, decoded):
+    def count(self, path: str, n: int):
+        with self.phase_lock:
+            self.ingest[path] += n
+
+    def run_window(self, lane: _Lane, packed, rawpack, rest, decoded):
         """The sub-batches of one loaded window: runs of one file rate and sample type, within the budget before and after
-        resampling (a window may still exceed the budget: its sizes were estimates)."""
+        resampling, counted in mono samples (a window may still exceed the budget: its sizes were estimates)."""
         sr = self.ex.sr
+        self.count("python", len(rest))
         if packed is not None:                                    # the natively packed 16-bit clips
             ids, buf, offs, lens, _held, rates = packed
             olens = np.maximum(lens, _native.resample_lengths(lens, rates, sr))
             for pos, end in _budget_runs(olens, self.budget, rates):
                 lo = int(offs[pos])
                 hi = int(offs[end - 1] + _padded(lens[end - 1]))
+                self.count("native_s16", end - pos)
                 self.run_group(lane, ids[pos:end], buf[lo:hi], offs[pos:end] - lo, lens[pos:end], _native.FMT_S16,
                                int(rates[pos]))
+        if rawpack is not None:                                   # the raw data chunks the device decodes
+            ids, raw, boffs, frames, kinds, chans, rates, _held = rawpack
+            olens = np.maximum(frames, _native.resample_lengths(frames, rates, sr))
+            for pos, end in _budget_runs(olens, self.budget, rates):
+                lo = int(boffs[pos])
+                hi = int(boffs[end - 1] + _raw_padded(frames[end - 1] * _native.SMP_BYTES[kinds[end - 1]] * chans[end - 1]))
+                self.count("native_raw", end - pos)
+                self.run_raw_group(lane, ids[pos:end], raw[lo:hi], boffs[pos:end] - lo, frames[pos:end], kinds[pos:end],
+                                   chans[pos:end], int(rates[pos]))
         groups = sorted({(d[2] != sr, d[2], d[0] != "s16") for d in decoded if d is not None})
         for _, rate, is_f32 in groups:
             kind, fmt, dt = (("f32", _native.FMT_F32, np.float32) if is_f32 else ("s16", _native.FMT_S16, np.int16))
@@ -459,15 +583,16 @@ class _Job:
             for i in idxs:
                 self.errors[i] = e
             return
-        pending = self.win_pool.submit(self.load_window, wins[0], lane.pin, lane.can_rs) if wins else None
+        load = lambda w: self.win_pool.submit(self.load_window, w, lane.pin, lane.can_rs, lane.can_dec, lane.pin_raw)
+        pending = load(wins[0]) if wins else None
         for k, win in enumerate(wins):
             t0 = time.perf_counter()
-            packed, rest, decoded = pending.result()
+            packed, rawpack, rest, decoded = pending.result()
             # next window loads while this one is on the device
-            pending = self.win_pool.submit(self.load_window, wins[k + 1], lane.pin, lane.can_rs) if k + 1 < len(wins) else None
+            pending = load(wins[k + 1]) if k + 1 < len(wins) else None
             t1 = time.perf_counter()
             try:
-                self.run_window(lane, packed, rest, decoded)
+                self.run_window(lane, packed, rawpack, rest, decoded)
             except Exception as e:          # a device-level failure drops the files of the sub-batch it hit, and the
                 for i in win:               # rest of this window; later windows are still attempted
                     if self.errors[i] is None and not (self.status[i] >= 0 and self.f0_done[i]):
@@ -475,7 +600,9 @@ class _Job:
                         self.status[i] = -1
             if packed is not None and packed[4] is not None:
                 lane.pin.put(packed[4])
-            del decoded, packed
+            if rawpack is not None and rawpack[7] is not None:
+                lane.pin_raw.put(rawpack[7])
+            del decoded, packed, rawpack
             with self.phase_lock:
                 self.phase["decode_wait"] += t1 - t0
                 self.phase["device"] += time.perf_counter() - t1
@@ -545,6 +672,12 @@ def process_files(extractor, files: Sequence, max_batch_samples: int = 80 * 1024
     decode window k + 1 on the shared host pool while window k is packed, uploaded and extracted ->
     dicts in input (glob) order.  Host memory holds at most two windows per worker, not the directory.
 
+    16-bit PCM mono files are read natively and uploaded as int16.  Every other layout the device decoder takes (PCM 8 /
+    16 / 24 / 32 bit, float 32 / 64 bit, up to 7 channels) is read natively as raw bytes, uploaded once and converted and
+    mixed down on the device (afx_decode_batch, bit for bit wavio.to_float32 + wavio.to_mono) into the buffer the passes --
+    or the device resampler -- read; a plan without ``decode_batch`` leaves those files, like files of 8 or more channels
+    and other sample widths, to the Python decoder.  LAST_TIMING["ingest"] counts the files by the path that took them.
+
     Files at another sample rate than the extractor's are resampled on the device (afx_resample_batch, the arithmetic of
     wavio.resample): 16-bit PCM mono ones are read natively like the rest and uploaded as int16, files Python decodes are
     uploaded as float32 at their own rate; a sub-batch holds one file rate, its resampled clips go to a second pooled device
@@ -584,6 +717,6 @@ def process_files(extractor, files: Sequence, max_batch_samples: int = 80 * 1024
     t_gpu = time.perf_counter()
     results = job.results()
     LAST_TIMING.update(pipeline=t_gpu - job.t_start, decode_wait=job.phase["decode_wait"], device=job.phase["device"],
-                       dicts=time.perf_counter() - t_gpu, files=len(files), workers=len(threads),
+                       dicts=time.perf_counter() - t_gpu, files=len(files), workers=len(threads), ingest=dict(job.ingest),
                        timeline=sorted(job.timeline, key=lambda r: r[2]))
     return results

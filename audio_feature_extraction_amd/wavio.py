@@ -143,7 +143,7 @@ def resample(y: np.ndarray, sr_in: int, sr_out: int) -> np.ndarray:
     return out.astype(np.float32)
 
 
-_BATCH_CTX = {}          # device -> (lock, _native.Context) of resample_batch
+_BATCH_CTX = {}          # device -> (lock, _native.Context) of resample_batch and load_batch
 
 
 def resample_batch(clips, sr_in: int, sr_out: int, device=None):
@@ -189,6 +189,81 @@ def resample_batch(clips, sr_in: int, sr_out: int, device=None):
             for k, i in enumerate(idx):
                 o, n = int(r["offsets"][k]), int(r["lengths"][k])
                 out[i] = r["out"][o:o + n].copy()
+    return out
+
+
+_LOAD_BATCH_BYTES = 1 << 28     # raw bytes per device round trip of load_batch
+
+
+def load_batch(paths, sr: int | None = None, device=None):
+    """``load`` of many files -> list of (float32 mono samples, rate).  With a GPU visible, libafx parses the headers and
+    reads the data chunks natively (afx_wav_probe / afx_wav_read_raw), the bytes are converted and mixed down on ``device``
+    (default 0; afx_decode_batch, bit for bit ``to_mono(to_float32(...))``) and, where ``sr`` differs from a file's rate and
+    the device resampler holds the rate pair, resampled there (within one float32 ulp of ``resample``).  With ``sr`` None or
+    equal to the file's rate the samples are bit-identical to ``load``.  A file the native path does not take (8 or more
+    channels, other sample widths or format tags), a file it cannot read, and every file when no GPU is visible goes through
+    ``load`` -- which also raises what a bad file raises.  The bytes pass through ordinary (pageable) host memory here and
+    are staged once more inside afx_decode_batch; the page-locked, uploaded-once path is batch_process's."""
+    import threading
+    from . import _native
+    paths = [str(p) for p in paths]
+    out = [None] * len(paths)
+    try:
+        on_gpu = _native.device_count() > 0 and hasattr(_native.lib(), "afx_decode_batch")
+    except (_native.AfxError, OSError):
+        on_gpu = False
+    todo = np.zeros(0, np.int64)
+    if on_gpu and paths:
+        pr = _native.wav_probe(paths)
+        kinds = _native.wav_sample_kinds(pr)
+        todo = np.nonzero(kinds >= 0)[0]
+        nbytes = pr["frames"] * _native.SMP_BYTES[np.maximum(kinds, 0)] * pr["channels"]
+        dev = int(device or 0)
+        if dev not in _BATCH_CTX:
+            _BATCH_CTX[dev] = (threading.Lock(), _native.Context(dev))
+        lock, ctx = _BATCH_CTX[dev]
+    pos = 0
+    while pos < todo.size:                                   # chunks of bounded size, each a run of whole files
+        end, tot = pos + 1, int(nbytes[todo[pos]])
+        while end < todo.size and tot + int(nbytes[todo[end]]) <= _LOAD_BATCH_BYTES:
+            tot += int(nbytes[todo[end]])
+            end += 1
+        sel, pos = todo[pos:end], end
+        boffs = _native.packed_offsets(nbytes[sel], 16)
+        raw = np.empty(max(int(boffs[-1] + nbytes[sel[-1]]), 1), np.uint8)
+        st = _native.wav_read_raw([paths[j] for j in sel], pr["data_off"][sel], nbytes[sel], raw, boffs)
+        good = st == 0
+        sel, boffs = sel[good], boffs[good]
+        if not sel.size:
+            continue
+        frames, rates = pr["frames"][sel].astype(np.int64), pr["rate"][sel]
+        offs = _native.packed_offsets(frames, 4)
+        total = int(offs[-1] + (frames[-1] + 3) // 4 * 4)
+        with lock:
+            dbuf = _native.DeviceBuffer(ctx, max(4 * total, 16))
+            try:
+                ctx.decode_batch(raw, boffs, frames, kinds[sel], pr["channels"][sel], out=dbuf, out_offsets=offs)
+                y = np.empty(total, np.float32)
+                dbuf.download(y)
+                for k, j in enumerate(sel):
+                    if sr is None or int(rates[k]) == int(sr):
+                        out[j] = (y[offs[k]:offs[k] + frames[k]].copy(), int(rates[k]))
+                for rate in [] if sr is None else sorted({int(r) for r in rates} - {int(sr)}):
+                    ks = np.nonzero(rates == rate)[0]
+                    try:
+                        r = ctx.resample_batch(dbuf, offs[ks], frames[ks], rate, int(sr), fmt=_native.FMT_F32)
+                    except NotImplementedError:                  # no device table for this rate pair
+                        for k in ks:
+                            out[sel[k]] = (resample(y[offs[k]:offs[k] + frames[k]], rate, int(sr)), int(sr))
+                        continue
+                    for q, k in enumerate(ks):
+                        o, n = int(r["offsets"][q]), int(r["lengths"][q])
+                        out[sel[k]] = (r["out"][o:o + n].copy(), int(sr))
+            finally:
+                dbuf.free()
+    for j, p in enumerate(paths):
+        if out[j] is None:
+            out[j] = load(p, sr)
     return out
 
 

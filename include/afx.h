@@ -311,11 +311,39 @@ int afx_f0_build_tables(int sr, int n_fft, int hop, double fmin, double fmax, in
  * of the data chunk (cut at the file's end); status[i] = 0 ok, 1 not a usable RIFF/WAVE file, 2 cannot be opened / read.
  * afx_wav_read_s16 copies frames[i] 16-bit samples of file i from data_off[i] to out[offsets[i] ..] (for files the probe
  * found to be 16-bit PCM mono: a batch packed in place, uploaded as AFX_FMT_S16); status[i] = 0 or 2.  Every other sample
- * type, channel count or rate goes through the caller's own decoder. */
+ * type or channel count goes through afx_wav_read_raw / afx_decode_batch below, or the caller's own decoder. */
 int afx_wav_probe(const char* const* paths, int n, int threads, int32_t* info /*[4n]*/, int64_t* frames,
                   int64_t* data_off, int32_t* status);
 int afx_wav_read_s16(const char* const* paths, int n, int threads, const int64_t* data_off, const int64_t* frames,
                      int16_t* out, int64_t out_len, const int64_t* offsets, int32_t* status);
+
+/* Every other WAVE layout of load_audio (F:52 -> librosa.load -> soundfile, mono=True): the raw data chunk is read as
+ * bytes, uploaded as it is, and converted and mixed down on the device.  Both symbols are newer than AFX_VERSION 107 says:
+ * a binding detects them by their presence.
+ *
+ * afx_wav_read_raw (host-only) is afx_wav_read_s16 in bytes: nbytes[i] bytes of file i from data_off[i] go to
+ * out[offsets[i] ..]; status[i] = 0 or 2.  AFX_ERR_INVALID, with nothing read, when a clip does not fit out_len bytes.
+ *
+ * afx_decode_batch: clip i is frames[i] interleaved sample frames of channels[i] channels of sample kind kinds[i]
+ * (little-endian, as in the file) from byte byte_offsets[i] of raw (host or device memory); its mono float32 signal goes to
+ * out[out_offsets[i] .. + frames[i]) in host or device memory (out_mem_kind), the elements from there to the next multiple
+ * of 4 are written as 0, nothing else is written.  byte_offsets must be multiples of 16, out_offsets multiples of 4
+ * (AFX_ERR_INVALID otherwise; device pointers are taken to be 16-byte aligned); device-resident raw is read in whole
+ * 4-byte words, so the buffer must reach the next multiple of 4 behind the last clip.  A batch may mix kinds and channel
+ * counts; a clip of 0 frames writes nothing.  Host-resident raw / out are staged through pageable copies inside the call (as
+ * afx_resample_batch stages them): the path that uploads a page-locked window once is device memory on both sides.
+ *   u8   float32(v - 128) * 2^-7        s16  float32(v) * 2^-15        s24  float32(v) * 2^-23 (sign-extended)
+ *   s32  float32(v), rounded to nearest even, * 2^-31      f32  the bits as they are      f64  rounded to nearest even
+ * (libsndfile's scaling, wavio.to_float32); 2 to 7 channels: the float32 sum in channel order ((c0 + c1) + c2) ... divided
+ * by float32(channels) (numpy's mean over the channel axis for fewer than 8 channels, wavio.to_mono).  Denormals are kept.
+ * No atomics: results are bit-reproducible.  AFX_ERR_UNSUPPORTED for more than 7 channels; AFX_ERR_INVALID, before anything
+ * is uploaded, for negative offsets or sizes, an unknown kind, fewer than 1 channel, or clips whose output slots overlap. */
+enum { AFX_SMP_U8 = 0, AFX_SMP_S16 = 1, AFX_SMP_S24 = 2, AFX_SMP_S32 = 3, AFX_SMP_F32 = 4, AFX_SMP_F64 = 5 };
+int afx_wav_read_raw(const char* const* paths, int n, int threads, const int64_t* data_off, const int64_t* nbytes,
+                     uint8_t* out, int64_t out_len, const int64_t* offsets /*bytes*/, int32_t* status);
+int afx_decode_batch(afx_ctx* ctx, const void* raw, int mem_kind, const int64_t* byte_offsets, const int64_t* frames,
+                     const int32_t* kinds, const int32_t* channels, int n_clips,
+                     float* out, int out_mem_kind, const int64_t* out_offsets);
 
 /* Resampling to the extractor's rate, the other half of load_audio (F:52: librosa.load(path, sr=self.sr)).  The filter is
  * the engine's own (parity with librosa's soxr_hq is not claimed): a linear-phase Kaiser-windowed sinc, 125 dB, transition
