@@ -38,7 +38,7 @@ SYMBOLS = (
     "afx_version", "afx_device_count", "afx_last_error", "afx_init", "afx_destroy",
     "afx_malloc", "afx_free", "afx_host_alloc", "afx_host_free", "afx_memcpy_h2d", "afx_memcpy_d2h", "afx_synchronize",
     "afx_default_params", "afx_plan_create", "afx_plan_destroy", "afx_build_tables", "afx_build_mel_schedule",
-    "afx_extract_batch", "afx_extract_submit", "afx_extract_collect", "afx_f0_batch", "afx_zcr_batch", "afx_spectral_batch", "afx_f0_build_tables", "afx_preprocess", "afx_plan_set_timing", "afx_plan_get_timings", "afx_plan_get_intervals",
+    "afx_extract_batch", "afx_extract_submit", "afx_extract_collect", "afx_f0_batch", "afx_zcr_batch", "afx_spectral_batch", "afx_f0_build_tables", "afx_f0_dispatch", "afx_preprocess", "afx_plan_set_timing", "afx_plan_get_timings", "afx_plan_get_intervals",
     "afx_wav_probe", "afx_wav_read_s16", "afx_batch_geometry", "afx_dtw_batch", "afx_hpss_batch",
     "afx_resample_design", "afx_resample_batch", "afx_rfft_host", "afx_wav_read_raw", "afx_decode_batch",
 )
@@ -101,6 +101,7 @@ def lib() -> C.CDLL:
         L.afx_zcr_batch.argtypes = [vp, vp, i32, i32, vp, vp, i32, i32, vp, vp, vp]
         L.afx_spectral_batch.argtypes = [vp, vp, i32, i32, vp, vp, i32, i32, vp, vp, vp]
         L.afx_f0_build_tables.argtypes = [i32, i32, i32, C.c_double, C.c_double, vp, vp, vp, vp]
+        L.afx_f0_dispatch.argtypes = [i32, i32, i32, C.c_double, C.c_double, vp]
         L.afx_preprocess.argtypes = [vp, vp, C.c_int64, vp, i64p, i64p, i32p]
         L.afx_plan_set_timing.argtypes = [vp, i32]
         L.afx_plan_get_timings.argtypes = [vp, vp, vp, i32]
@@ -215,6 +216,20 @@ def f0_build_tables(sr: int, n_fft: int, hop: int, fmin: float, fmax: float) -> 
                                      freqs.ctypes.data), "afx_f0_build_tables")
     keys = ("min_period", "max_period", "n_bins", "band", "cap", "n_lag", "R", "slots")
     return {**{k: int(v) for k, v in zip(keys, info)}, "beta": beta, "lt": lt.reshape(2, w, w), "freqs": freqs}
+
+
+F0_DISPATCH_KEYS = ("energy_lpw", "epb", "yin_n", "yin_fpb", "yin_sh", "vit_nbt", "vit_bandt", "vit_tpt", "bt_depth",
+                    "band", "n_bins", "yin_lds")
+
+
+def f0_dispatch(sr: int, n_fft: int, hop: int, fmin: float, fmax: float) -> dict:
+    """Host-only: the kernel instantiations afx_f0_batch launches for a configuration (what its launchers switch on):
+    k_f0_energy (energy_lpw 0) or k_f0_energy2<energy_lpw> with epb frames per workgroup, k_f0_yin<yin_n, yin_n, yin_fpb,
+    yin_sh>, k_f0_viterbi<0, vit_nbt, vit_bandt> (0 / 0: generic) with vit_tpt targets per thread, k_f0_backtrack<bt_depth>.
+    NotImplementedError, with afx_f0_batch's reason, for a configuration extract_f0 refuses."""
+    out = np.zeros(len(F0_DISPATCH_KEYS), np.int32)
+    _check(lib().afx_f0_dispatch(int(sr), int(n_fft), int(hop), float(fmin), float(fmax), out.ctypes.data), "afx_f0_dispatch")
+    return {k: int(v) for k, v in zip(F0_DISPATCH_KEYS, out)}
 
 
 def resample_design(sr_in: int, sr_out: int) -> dict:

@@ -125,13 +125,6 @@ __device__ __forceinline__ float sq_acc(float e, float y) {
   return e + q;
 }
 
-size_t f0_energy_lds_bytes(const F0Params& fp) {
-  const size_t span = (size_t)(fp.epb - 1) * fp.hop + fp.W + fp.n_tau;
-  return (span + span / fp.hop + 8) * 4 + (size_t)fp.n_tau * (fp.epb + 1) * 4;
-}
-
-constexpr int kEnergyWaves = 4;       // waves per workgroup of k_f0_energy
-
 __global__ __launch_bounds__(64 * kEnergyWaves) void k_f0_energy(const float* __restrict__ ysig,
                                                                  const ClipDesc* __restrict__ clips,
                                                                  const ClipInfo* __restrict__ info,
@@ -232,15 +225,6 @@ __global__ __launch_bounds__(64 * kEnergyWaves) void k_f0_energy(const float* __
 // [frame][32 lags] tile: every 32 lags the wave's 64 lanes write its frames' pieces of the rows, 128 bytes each.
 // Needs W % hop == 0 (the pads of the two index streams then coincide); anything else takes k_f0_energy.
 // ---------------------------------------------------------------------------------------------
-constexpr int kE2Tile = 32;
-__host__ __device__ inline size_t f0_energy2_span(const F0Params& fp, int lpw) {
-  return (size_t)(kEnergyWaves * lpw - 1) * fp.hop + fp.W + fp.n_tau;
-}
-size_t f0_energy2_lds_bytes(const F0Params& fp, int lpw) {
-  const size_t span = f0_energy2_span(fp, lpw);
-  return (span + span / fp.hop + 8 + (size_t)kEnergyWaves * lpw * (kE2Tile + 1)) * 4;
-}
-
 template <int LPW>
 __global__ __launch_bounds__(64 * kEnergyWaves) void k_f0_energy2(const float* __restrict__ ysig,
                                                                   const ClipDesc* __restrict__ clips,
@@ -338,61 +322,13 @@ __global__ __launch_bounds__(64 * kEnergyWaves) void k_f0_energy2(const float* _
 // k_f0_yin
 // ---------------------------------------------------------------------------------------------
 
-struct YinLds { size_t span, per_wave, tables, total; };
-// compact (the REF instantiation): the trough / candidate arrays CP, CB live in the D row behind its 64 event flags -- D is
-// idle once the normalised difference is formed -- and the two tables that are only read with uniform indices (beta,
-// cumbeta) come through the scalar cache: 39.7 KB per workgroup, a fourth workgroup per CU
-__host__ __device__ inline YinLds yin_lds_i(int hop_, int n_fft_, int n_tau_pad_, int slots_, int cap_, int fpb, bool yf, bool compact = false) {
-  YinLds L;
-  L.span = (size_t)(fpb - 1) * hop_ + n_fft_ + 64;
-  // per wave (doubles): D[n_tau_pad] | X[slots*64 + 2] | CP[cap] | CB[cap] (ints, cap/2 doubles)
-  L.per_wave = (size_t)n_tau_pad_ + (size_t)slots_ * 64 + 2 + cap_ + (cap_ + 1) / 2;
-  // shared tables: thr[101] | beta[100] | cumbeta[101] | bfact[cap+1] | bexp[cap+1]
-  L.tables = 101 + 100 + 101 + 2 * ((size_t)cap_ + 1);
-  // the staged signal is kept as the float32 it is (converted on read: half the bytes of the autocorrelation's LDS reads and
-  // 20 KB less per workgroup); span is rounded up to an even count so that the double arrays behind it stay 8-byte aligned
-  // (yf: the instantiations with at most 6 lags per lane; the lag-heavy ones re-read the signal 11..16 times per step and keep it
-  // as float64 -- a conversion per read costs them more than the bytes)
-  L.span = (L.span + 1) & ~(size_t)1;
-  if (compact) {
-    L.per_wave = (size_t)n_tau_pad_ + (size_t)slots_ * 64 + 2;
-    L.tables = 101 + 2 * ((size_t)cap_ + 1);
-  }
-  L.total = L.span * (yf ? sizeof(float) : sizeof(double)) + (4 * L.per_wave + L.tables) * sizeof(double);
-  return L;
-}
-__host__ __device__ inline YinLds yin_lds(const F0Params& fp, int fpb, bool yf) {
-  return yin_lds_i(fp.hop, fp.n_fft, fp.n_tau_pad, fp.slots, fp.cap, fpb, yf);
-}
-// frames one workgroup owns: 16, or 8 where that (and only that) lets a third workgroup onto the CU -- the kernel is bound by
-// how often a wave gets to issue, and the lag-heavy instantiations (more than 6 lags per lane) cannot use a third wave anyway
-int f0_yin_frames_per_block(const F0Params& fp) {
-  const int need = fp.R > fp.slots ? fp.R : fp.slots;
-  const size_t third = 160 * 1024 / 3;
-  return (need <= 6 && yin_lds(fp, 16, true).total > third && yin_lds(fp, 8, true).total <= third) ? 8 : 16;
-}
-size_t f0_yin_lds_bytes(const F0Params& fp) {
-  const int need = fp.R > fp.slots ? fp.R : fp.slots;
-  return yin_lds(fp, f0_yin_frames_per_block(fp), need <= 6).total;
-}
-
+// (the LDS layout yin_lds_i, the frames per block and the compiled-in shapes YinShape<SH> are in afx_f0.h: the dispatch reads them)
 // RR >= lags per lane (fp.R), SS >= trough slots per lane (fp.slots): per-lane arrays are sized by them
 // REF: the reference's shape (22050 Hz, frame_length 1024, C2..C7) compiled in -- periods 10..338, 339 lags in rows of 384,
 // 329 kept, 168 candidates at most, 601 pitch bins: the kernel is short of scalar registers, and offsets become immediates.
 // SH: 0 any shape (from the parameters); 1 the reference's (above; compact LDS layout); 2 the same pitch range at 16 kHz,
 // frame_length 512 (BASELINE configs[2]): periods 7..245, 246 lags in rows of 256, 239 kept, 128 candidates; 3 the same at
 // 44.1 kHz, frame_length 2048 (configs[4]): periods 21..675, 676 lags in rows of 704, 655 kept, 336 candidates.
-template <int SH> struct YinShape { static constexpr int hop = 0, W = 0, n_fft = 0, R = 0, slots = 0, n_lag = 0, n_tau = 0, n_tau_pad = 0, min_period = 0, max_period = 0, cap = 0, n_bins = 0; };
-template <> struct YinShape<1> { static constexpr int hop = 256, W = 512, n_fft = 1024, R = 6, slots = 6, n_lag = 329, n_tau = 339, n_tau_pad = 384, min_period = 10, max_period = 338, cap = 168, n_bins = 601; };
-template <> struct YinShape<2> { static constexpr int hop = 128, W = 256, n_fft = 512, R = 4, slots = 4, n_lag = 239, n_tau = 246, n_tau_pad = 256, min_period = 7, max_period = 245, cap = 128, n_bins = 601; };
-template <> struct YinShape<3> { static constexpr int hop = 512, W = 1024, n_fft = 2048, R = 11, slots = 11, n_lag = 655, n_tau = 676, n_tau_pad = 704, min_period = 21, max_period = 675, cap = 336, n_bins = 601; };
-template <int SH>
-static bool yin_shape_is(const F0Params& fp) {
-  typedef YinShape<SH> Y;
-  return fp.hop == Y::hop && fp.W == Y::W && fp.n_fft == Y::n_fft && fp.R == Y::R && fp.slots == Y::slots && fp.n_lag == Y::n_lag &&
-         fp.n_tau == Y::n_tau && fp.n_tau_pad == Y::n_tau_pad && fp.min_period == Y::min_period && fp.max_period == Y::max_period &&
-         fp.cap == Y::cap && fp.n_bins == Y::n_bins;
-}
 template <int RR, int SS, int FPB, int SH>
 __global__ __launch_bounds__(256, ((SH == 1 || SH == 2) ? 4 : RR <= 6 ? 3 : 1)) void k_f0_yin(const float* __restrict__ ysig,
                                                 const ClipDesc* __restrict__ clips,
@@ -785,26 +721,11 @@ __global__ __launch_bounds__(256, ((SH == 1 || SH == 2) ? 4 : RR <= 6 ? 3 : 1)) 
 // recomputes, for the one state on the path, the same sums in the same order and takes their first maximum
 // (numpy's argmax rule) -- bit-identical to forming all pointers up front.
 // ---------------------------------------------------------------------------------------------
-constexpr int kVitThreads = 640;
 __device__ __forceinline__ int vit_role(int hw) {       // hardware wave -> the block of 64 targets it owns (a permutation)
   if (kVitThreads != 640) return hw;
   const unsigned long long roles = 0x1876549032ull;    // hw 0..9 -> 2 3 0 9 4 5 6 7 8 1 (nibble per wave, low first)
   return (int)((roles >> (4 * hw)) & 15);
 }
-
-struct VitLds { size_t v, olp, lt, red, edge, total; };
-__host__ __device__ inline VitLds vit_lds(int n_bins, int band_) {
-  const size_t S = 2 * (size_t)n_bins, width = 2 * (size_t)band_ + 1;
-  VitLds L;
-  L.v = 0;                                   // two value columns of 2 (n_bins + 2 band) + 4 band doubles
-  L.olp = 2 * (S + 8 * band_);               // 3 n_bins doubles
-  L.lt = L.olp + 3 * n_bins;                 // width * width doubles: the `stay` rows (k_f0_backtrack holds both tables)
-  L.red = L.lt + width * width;              // 32 doubles + 32 ints (16 doubles): two sets of per-wave partials
-  L.edge = L.red + 48;                       // per wave 4 x 2 band doubles (its best edge-class move per range-end target); 2 counters
-  L.total = (L.edge + (size_t)(kVitThreads / 64) * 8 * band_ + 2) * sizeof(double);
-  return L;
-}
-size_t f0_viterbi_lds_bytes(const F0Params& fp) { return vit_lds(fp.n_bins, fp.band).total; }
 
 // MODE 0: production; 1: the timing-only ablation bits of AFX_F0_DEBUG honoured; 2: per-phase cycle stamps as well.
 // NBT / BANDT: n_bins and band compiled in (0: taken from the parameters) -- the step loop is short of scalar registers,
@@ -1141,13 +1062,6 @@ __global__ __launch_bounds__(kVitThreads, 8) void k_f0_viterbi(const ClipDesc* _
 // access and no other memory instruction: the per-column (max, arg-max) records and the states travel 64 steps at a
 // time through the lanes' registers.
 // ---------------------------------------------------------------------------------------------
-constexpr int kBtWaves = 4;
-constexpr int kBtWin = 256;                       // doubles per half column in a ring slot: two 1 KB DMA instructions
-__host__ __device__ inline int f0_bt_depth(int band) { return 2 * band * 5 + 2 <= kBtWin ? 6 : 5; }
-size_t f0_backtrack_lds_bytes(const F0Params& fp) {
-  const size_t width = 2 * (size_t)fp.band + 1;
-  return (2 * width * width + 2 + (size_t)kBtWaves * (f0_bt_depth(fp.band) + 1) * 2 * kBtWin) * sizeof(double);
-}
 __device__ __forceinline__ unsigned lds_addr(const void* p) {
 #pragma clang diagnostic push
 #pragma clang diagnostic ignored "-Wold-style-cast"
@@ -1386,66 +1300,61 @@ static hipError_t allow_lds(K kernel, size_t bytes) {
   return set_lds_limit(kernel, bytes);
 }
 
+// Each launcher switches on f0_dispatch(fp) (afx_f0.h): the instantiation is chosen there and nowhere else, and a
+// choice no case below knows is an error, never another kernel.
 hipError_t launch_f0_energy(hipStream_t s, const float* ysig, const ClipDesc* clips, const ClipInfo* info,
                             float* energy, int n_clips, int max_tmax, const F0Params& fp) {
+  const F0Dispatch d = f0_dispatch(fp);
   hipError_t e;
-  if (fp.W % fp.hop == 0 && fp.n_tau <= fp.W) {
-    // lanes per wave: 8, or 4 for the long hops, if that keeps the workgroup's samples within a quarter of the CU's LDS
-    // (four workgroups per CU)
-#define AFX_E2_LAUNCH(LPW)                                                                                               \
-    do {                                                                                                                 \
-      const size_t lds2 = f0_energy2_lds_bytes(fp, LPW);                                                                 \
-      if (lds2 <= 40 * 1024) {                                                                                           \
-        dim3 grid2((max_tmax + kEnergyWaves * LPW - 1) / (kEnergyWaves * LPW), n_clips);                                 \
-        hipLaunchKernelGGL(k_f0_energy2<LPW>, grid2, dim3(64 * kEnergyWaves), lds2, s, ysig, clips, info, energy, fp);   \
-        return hipGetLastError();                                                                                        \
-      }                                                                                                                  \
-    } while (0)
+  dim3 grid((max_tmax + d.epb - 1) / d.epb, n_clips);
+  switch (d.energy_lpw) {
+#define AFX_E2_LAUNCH(LPW)                                                                                                 \
+    case LPW:                                                                                                              \
+      hipLaunchKernelGGL(k_f0_energy2<LPW>, grid, dim3(64 * kEnergyWaves), f0_energy2_lds_bytes(fp, LPW), s, ysig, clips,  \
+                         info, energy, fp);                                                                                \
+      return hipGetLastError()
     AFX_E2_LAUNCH(8);
     AFX_E2_LAUNCH(4);
 #undef AFX_E2_LAUNCH
+    case 0: {
+      const size_t lds = f0_energy_lds_bytes(fp);
+      if ((e = allow_lds(k_f0_energy, lds)) != hipSuccess) return e;
+      hipLaunchKernelGGL(k_f0_energy, grid, dim3(64 * kEnergyWaves), lds, s, ysig, clips, info, energy, fp);
+      return hipGetLastError();
+    }
   }
-  const size_t lds = f0_energy_lds_bytes(fp);
-  if ((e = allow_lds(k_f0_energy, lds)) != hipSuccess) return e;
-  dim3 grid((max_tmax + fp.epb - 1) / fp.epb, n_clips);
-  hipLaunchKernelGGL(k_f0_energy, grid, dim3(64 * kEnergyWaves), lds, s, ysig, clips, info, energy, fp);
-  return hipGetLastError();
+  return hipErrorInvalidValue;
 }
 
 hipError_t launch_f0_yin(hipStream_t s, const float* ysig, const ClipDesc* clips, const ClipInfo* info,
                          const float* energy, const F0Tables& tb, const F0Params& fp,
                          int32_t* cand_cnt, double* cand_vp, int16_t* cand_bin, double* cand_prob,
                          double* cand_lp, double* cand_lu, int n_clips, int max_tmax) {
-  const size_t lds = f0_yin_lds_bytes(fp);
-  const int fpb = f0_yin_frames_per_block(fp);
-  dim3 grid((max_tmax + fpb - 1) / fpb, n_clips);
-  const int need = fp.R > fp.slots ? fp.R : fp.slots;
-#define AFX_YIN_LAUNCH_FR(N, F, SH)                                                                             \
-  do {                                                                                                         \
+  const F0Dispatch d = f0_dispatch(fp);
+  const size_t lds = (size_t)d.yin_lds;
+  dim3 grid((max_tmax + d.yin_fpb - 1) / d.yin_fpb, n_clips);
+#define AFX_YIN_CASE(N, F, SH)                                                                                  \
+  if (d.yin_n == N && d.yin_fpb == F && d.yin_sh == SH) {                                                      \
     hipError_t e2 = allow_lds(k_f0_yin<N, N, F, SH>, lds);                                                     \
     if (e2 != hipSuccess) return e2;                                                                           \
     hipLaunchKernelGGL((k_f0_yin<N, N, F, SH>), grid, dim3(256), lds, s, ysig, clips, info, energy, tb, fp, cand_cnt, \
                        cand_vp, cand_bin, cand_prob, cand_lp, cand_lu);                                        \
-  } while (0)
-#define AFX_YIN_LAUNCH_F(N, F) AFX_YIN_LAUNCH_FR(N, F, 0)
-  if (yin_shape_is<1>(fp) && fpb == 8) {
-    const size_t lds_ref = yin_lds_i(fp.hop, fp.n_fft, fp.n_tau_pad, fp.slots, fp.cap, 8, true, true).total;
-    hipLaunchKernelGGL((k_f0_yin<6, 6, 8, 1>), grid, dim3(256), lds_ref, s, ysig, clips, info, energy, tb, fp, cand_cnt,
-                       cand_vp, cand_bin, cand_prob, cand_lp, cand_lu);
-    return hipGetLastError();
+    return hipGetLastError();                                                                                  \
   }
-  if (yin_shape_is<2>(fp) && fpb == 16) { AFX_YIN_LAUNCH_FR(4, 16, 2); return hipGetLastError(); }
-  if (yin_shape_is<3>(fp) && fpb == 16) { AFX_YIN_LAUNCH_FR(11, 16, 3); return hipGetLastError(); }
-#define AFX_YIN_LAUNCH(N) do { if (fpb == 8) AFX_YIN_LAUNCH_F(N, 8); else AFX_YIN_LAUNCH_F(N, 16); } while (0)
-  if (need <= 4) AFX_YIN_LAUNCH(4);
-  else if (need <= 6) AFX_YIN_LAUNCH(6);
-  else if (need <= 8) AFX_YIN_LAUNCH_F(8, 16);
-  else if (need <= 11) AFX_YIN_LAUNCH_F(11, 16);
-  else AFX_YIN_LAUNCH_F(16, 16);
-#undef AFX_YIN_LAUNCH
-#undef AFX_YIN_LAUNCH_F
-#undef AFX_YIN_LAUNCH_FR
-  return hipGetLastError();
+  AFX_YIN_CASE(6, 8, 1)
+  AFX_YIN_CASE(4, 16, 2)
+  AFX_YIN_CASE(11, 16, 3)
+  // <4, 4, 8, 0> is reached only where hop_length is about the frame length (16 frames then pass a third of the LDS with at most
+  // 4 lags per lane, i.e. frame_length <= 512) and the band still fits, sr >= 32 kHz: 48000 / 480 / 480 is the shape tested
+  AFX_YIN_CASE(4, 8, 0)
+  AFX_YIN_CASE(4, 16, 0)
+  AFX_YIN_CASE(6, 8, 0)
+  AFX_YIN_CASE(6, 16, 0)
+  AFX_YIN_CASE(8, 16, 0)
+  AFX_YIN_CASE(11, 16, 0)
+  AFX_YIN_CASE(16, 16, 0)
+#undef AFX_YIN_CASE
+  return hipErrorInvalidValue;
 }
 
 static hipError_t launch_f0_backtrack(hipStream_t s, const ClipDesc* clips, const ClipInfo* info, const F0Tables& tb,
@@ -1454,16 +1363,18 @@ static hipError_t launch_f0_backtrack(hipStream_t s, const ClipDesc* clips, cons
   const size_t lds = f0_backtrack_lds_bytes(fp);
   const dim3 grid((n_clips + kBtWaves - 1) / kBtWaves), block(64 * kBtWaves);
   hipError_t e;
-  if (f0_bt_depth(fp.band) == 6) {
-    if ((e = allow_lds(k_f0_backtrack<6>, lds)) != hipSuccess) return e;
-    hipLaunchKernelGGL(k_f0_backtrack<6>, grid, block, lds, s, clips, info, tb, fp, vrows, vbest, states, out_stats, out_f0,
-                       f0_offsets, n_clips);
-  } else {
-    if ((e = allow_lds(k_f0_backtrack<5>, lds)) != hipSuccess) return e;
-    hipLaunchKernelGGL(k_f0_backtrack<5>, grid, block, lds, s, clips, info, tb, fp, vrows, vbest, states, out_stats, out_f0,
-                       f0_offsets, n_clips);
+  switch (f0_dispatch(fp).bt_depth) {
+#define AFX_BT_LAUNCH(D)                                                                                                \
+    case D:                                                                                                             \
+      if ((e = allow_lds(k_f0_backtrack<D>, lds)) != hipSuccess) return e;                                              \
+      hipLaunchKernelGGL(k_f0_backtrack<D>, grid, block, lds, s, clips, info, tb, fp, vrows, vbest, states, out_stats,  \
+                         out_f0, f0_offsets, n_clips);                                                                  \
+      return hipGetLastError()
+    AFX_BT_LAUNCH(6);
+    AFX_BT_LAUNCH(5);
+#undef AFX_BT_LAUNCH
   }
-  return hipGetLastError();
+  return hipErrorInvalidValue;
 }
 
 hipError_t launch_f0_viterbi(hipStream_t s, const ClipDesc* clips, const ClipInfo* info, const F0Tables& tb,
@@ -1472,6 +1383,7 @@ hipError_t launch_f0_viterbi(hipStream_t s, const ClipDesc* clips, const ClipInf
                              double* vrows, VitBest* vbest,
                              uint16_t* states, double* out_stats, double* out_f0, const int64_t* f0_offsets,
                              int n_clips) {
+  const F0Dispatch d = f0_dispatch(fp);
   const size_t lds = f0_viterbi_lds_bytes(fp);
   hipError_t e;
 #define AFX_VIT_LAUNCH(MODE, NBT, BANDT)                                                                              \
@@ -1480,15 +1392,16 @@ hipError_t launch_f0_viterbi(hipStream_t s, const ClipDesc* clips, const ClipInf
     hipLaunchKernelGGL((k_f0_viterbi<MODE, NBT, BANDT>), dim3(n_clips), dim3(kVitThreads), lds, s, clips, info, tb, fp, \
                        cand_cnt, cand_bin, cand_lp, cand_lu, vrows, vbest);                                          \
   } while (0)
-  const bool ref_shape = fp.n_bins == 601 && fp.band == 25;       // fmin / fmax of the reference at hop / sr = 256 / 22050, 512 / 44100
+  const bool ref_shape = d.vit_nbt == 601 && d.vit_bandt == 25;
 #if AFX_F0_DEBUG_BUILD
   if (fp.debug & 16) AFX_VIT_LAUNCH(2, 0, 0);
   else if (fp.debug) { if (ref_shape) AFX_VIT_LAUNCH(1, 601, 25); else AFX_VIT_LAUNCH(1, 0, 0); }
   else
 #endif
   if (ref_shape) AFX_VIT_LAUNCH(0, 601, 25);
-  else if (fp.n_bins == 601 && fp.band == 15) AFX_VIT_LAUNCH(0, 601, 15);       // the same pitch range at hop / sr = 128 / 16000
-  else AFX_VIT_LAUNCH(0, 0, 0);
+  else if (d.vit_nbt == 601 && d.vit_bandt == 15) AFX_VIT_LAUNCH(0, 601, 15);
+  else if (d.vit_nbt == 0 && d.vit_bandt == 0) AFX_VIT_LAUNCH(0, 0, 0);
+  else return hipErrorInvalidValue;
 #undef AFX_VIT_LAUNCH
   if ((e = hipGetLastError()) != hipSuccess) return e;
   return launch_f0_backtrack(s, clips, info, tb, fp, vrows, vbest, states, out_stats, out_f0, f0_offsets, n_clips);

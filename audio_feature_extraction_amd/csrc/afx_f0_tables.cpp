@@ -96,4 +96,24 @@ bool build_f0_tables(int sr, int n_fft, int hop, double fmin, double fmax, HostF
   return true;
 }
 
+bool f0_plan(int sr, int n_fft, int hop, double fmin, double fmax, HostF0Tables& t, F0Dispatch& d, std::string& why) {
+  if (!build_f0_tables(sr, n_fft, hop, fmin, fmax, t, why)) return false;
+  const F0Params& p = t.p;
+  // k_f0_backtrack gives every source of the band a lane: the band grows with hop_length / sr (band = 5 round(431.04 hop / sr))
+  if (2 * p.band + 1 > 64) {
+    why = "transition band of " + std::to_string(2 * p.band + 1) + " bins (2 * band + 1, band " + std::to_string(p.band) +
+          ") is wider than the 64 lanes of k_f0_backtrack: hop_length / sr is too large";
+    return false;
+  }
+  const struct { const char* kernel; size_t bytes; } lds[4] = {{"k_f0_energy", f0_energy_lds_bytes(p)}, {"k_f0_yin", f0_yin_lds_bytes(p)},
+                                                               {"k_f0_viterbi", f0_viterbi_lds_bytes(p)}, {"k_f0_backtrack", f0_backtrack_lds_bytes(p)}};
+  for (const auto& k : lds)
+    if (k.bytes > kF0LdsLimit) {
+      why = std::string("frame_length / hop_length / f0 range needs more than 160 KiB of LDS (") + k.kernel + ": " + std::to_string(k.bytes) + " bytes)";
+      return false;
+    }
+  d = f0_dispatch(p);
+  return true;
+}
+
 }  // namespace afx

@@ -23,13 +23,10 @@ static int f0_setup(afx_plan* pl, double fmin, double fmax) {
   if (pl->f0_ready && pl->f0_fmin == fmin && pl->f0_fmax == fmax) return AFX_OK;
   std::string why;
   HostF0Tables ht;
-  if (!build_f0_tables(pl->p.sr, pl->p.n_fft, pl->p.hop, fmin, fmax, ht, why)) {
+  F0Dispatch disp;
+  // a refusal leaves the tables of the last accepted range installed (f0_ready, f0_fmin / f0_fmax untouched)
+  if (!f0_plan(pl->p.sr, pl->p.n_fft, pl->p.hop, fmin, fmax, ht, disp, why)) {
     set_error("afx_f0_batch: " + why);
-    return AFX_ERR_UNSUPPORTED;
-  }
-  if (f0_energy_lds_bytes(ht.p) > 160 * 1024 || f0_yin_lds_bytes(ht.p) > 160 * 1024 ||
-      f0_viterbi_lds_bytes(ht.p) > 160 * 1024 || f0_backtrack_lds_bytes(ht.p) > 160 * 1024 || 2 * ht.p.band + 1 > 64) {
-    set_error("afx_f0_batch: frame_length / f0 range needs more than 160 KiB of LDS");
     return AFX_ERR_UNSUPPORTED;
   }
   for (void* q : pl->f0_allocs) (void)hipFree(q);

@@ -1,5 +1,5 @@
 // Host-only part of libafx.so: the error string, the version, and the builders that need no device -- the clip records of
-// a batch (what prepare_descriptors uploads) and the pYIN tables.  Together with afx_tables.cpp, afx_f0_tables.cpp and
+// a batch (what prepare_descriptors uploads), the pYIN tables and the pYIN kernel dispatch (afx_f0_dispatch).  Together with afx_tables.cpp, afx_f0_tables.cpp and
 // afx_wav.cpp this is everything that parses caller- or file-supplied data on the host; `make asan` builds exactly these
 // files (plus afx_host_stubs.cpp) with g++ -fsanitize=address,undefined as libafx_host_asan.so.
 #include <algorithm>
@@ -136,3 +136,16 @@ extern "C" int afx_f0_build_tables(int sr, int n_fft, int hop, double fmin, doub
   return AFX_OK;
 }
 
+
+extern "C" int afx_f0_dispatch(int sr, int n_fft, int hop, double fmin, double fmax, int32_t* out) {
+  if (!out) { set_error("afx_f0_dispatch: null argument"); return AFX_ERR_INVALID; }
+  if (sr <= 0 || hop <= 0 || n_fft < 2 || n_fft > 4096) { set_error("afx_f0_dispatch: sr, hop_length must be positive and frame_length in [2, 4096]"); return AFX_ERR_INVALID; }
+  HostF0Tables t;
+  F0Dispatch d;
+  std::string why;
+  if (!f0_plan(sr, n_fft, hop, fmin, fmax, t, d, why)) { set_error("afx_f0_dispatch: " + why); return AFX_ERR_UNSUPPORTED; }
+  const int32_t v[12] = {d.energy_lpw, d.epb, d.yin_n, d.yin_fpb, d.yin_sh, d.vit_nbt, d.vit_bandt, d.vit_tpt, d.bt_depth,
+                         t.p.band, t.p.n_bins, d.yin_lds};
+  std::memcpy(out, v, sizeof(v));
+  return AFX_OK;
+}

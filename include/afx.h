@@ -305,6 +305,13 @@ int afx_hpss_batch(afx_plan* plan, const void* samples, int sample_fmt, int mem_
 int afx_f0_build_tables(int sr, int n_fft, int hop, double fmin, double fmax, int32_t* info,
                         double* beta, double* lt, double* freqs);
 
+/* Host-only: which instantiation of each pYIN kernel afx_f0_batch launches for a configuration -- the launchers switch on
+ * the same record.  out[12] = energy kernel (0 k_f0_energy, otherwise the LPW of k_f0_energy2), its frames per workgroup;
+ * k_f0_yin's N, FPB, SH; k_f0_viterbi's NBT, BANDT (0, 0: generic); Viterbi targets per thread; k_f0_backtrack's ring depth;
+ * then band, n_pitch_bins and the LDS bytes of the k_f0_yin launch.  AFX_ERR_UNSUPPORTED, with the reason afx_f0_batch
+ * gives, for a configuration extract_f0 refuses (transition band wider than 64 bins, more than 160 KiB of LDS). */
+int afx_f0_dispatch(int sr, int n_fft, int hop, double fmin, double fmax, int32_t* out);
+
 /* Host-only ingest for batch_process (load_audio, F:52 -> librosa.load -> soundfile), by `threads` native threads.
  * afx_wav_probe walks the RIFF chunks of n files: info[4 i ..] = format tag (1 PCM, 3 IEEE float; the sub-format of
  * WAVE_FORMAT_EXTENSIBLE), channels, sample rate, bits per sample; frames[i], data_off[i] = sample frames and byte offset

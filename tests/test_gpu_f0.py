@@ -6,6 +6,7 @@ from audio_feature_extraction_amd import _native as N
 from audio_feature_extraction_amd.synth import make_clip
 from oracle import cpu_ref as R
 from oracle import pyin_ref as P
+from tests import f0_shapes
 
 pytestmark = pytest.mark.gpu
 
@@ -34,13 +35,7 @@ def run(plan, clips, flags):
 
 
 def voiced_tone(freq, seconds, vib=0.0, seed=0):
-    rng = np.random.default_rng(seed)
-    t = np.arange(int(SR * seconds)) / SR
-    f = freq * (1 + vib * np.sin(2 * np.pi * 5 * t))
-    ph = 2 * np.pi * np.cumsum(f) / SR
-    y = 0.3 * np.sin(ph) + 0.1 * np.sin(2 * ph + 0.3) + 0.05 * np.sin(3 * ph + 1.0)
-    y += 0.005 * rng.standard_normal(t.size)
-    return y.astype(np.float32)
+    return f0_shapes.voiced_tone(SR, freq, seconds, vib=vib, seed=seed)
 
 
 NON_IDENTICAL = {}      # tag -> (frames that differ from the oracle's track, frames): printed by the last test of the module

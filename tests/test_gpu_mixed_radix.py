@@ -9,6 +9,7 @@ from audio_feature_extraction_amd import wavio
 from audio_feature_extraction_amd.synth import make_clip
 from oracle import cpu_ref as R
 from oracle import pyin_ref as P
+from tests.f0_shapes import voiced_tone
 from tests.parity import check_frames, check_stats
 
 pytestmark = pytest.mark.gpu
@@ -193,16 +194,6 @@ def test_ragged_mixed_format_batch_equals_single_clips(plans):
     for i in (0, 1):
         ref = oracle(qf[i], "400-40")
         check_stats(f32["stats"][i], ref, K, f"ragged{i}")
-
-
-def voiced_tone(sr, freq, seconds, vib=0.0, seed=0):
-    rng = np.random.default_rng(seed)
-    t = np.arange(int(sr * seconds)) / sr
-    f = freq * (1 + vib * np.sin(2 * np.pi * 5 * t))
-    ph = 2 * np.pi * np.cumsum(f) / sr
-    y = 0.3 * np.sin(ph) + 0.1 * np.sin(2 * ph + 0.3) + 0.05 * np.sin(3 * ph + 1.0)
-    y += 0.005 * rng.standard_normal(t.size)
-    return y.astype(np.float32)
 
 
 def test_extract_frame_features_at_400_160(tmp_path):
