@@ -61,8 +61,21 @@ __device__ __forceinline__ double tl_row_sum(double v) {
 // per SIMD and reads the spill at 2.9 TB/s.  The LDS image is lane-linear (the DMA's rule), so the bank swizzle is applied on
 // the SOURCE side: 16-byte chunk j of row f is stored at chunk position j ^ f of row f, and lane (f, q) reads chunk 4 s + q
 // of its row conflict-free.  RING = 0: the register path above (any n_mels that is a multiple of 16).
-template <int NG, bool SYM, int WAVES, int RING>
-__global__ __launch_bounds__(WAVES * 64, ((NG == 1 && WAVES == 4 && RING == 0) ? 4 : 1)) void k_tail(const ClipDesc* __restrict__ clips,
+//
+// RING = 1 (NG = 1, plain, four waves: up to 16 coefficients of 128 filters): four waves per SIMD instead of two, and a tile
+// in flight per wave across the whole of its compute phase.  The ring forms above run two waves per SIMD (the DCT images
+// and RING slots per wave fill the LDS), and a wave there waits for its DMA more than half its life with one partner to
+// cover it.  Here the images are not in LDS: each lane keeps the 32 image values it feeds the matrix pipe in registers
+// (loaded once per workgroup), which leaves 34 KB of LDS per workgroup -- one 8 KB slot per wave, the edge table, the
+// partials -- and, at no more than 128 registers, four workgroups per CU.  A wave waits for its one outstanding DMA,
+// empties the slot into registers (eight ds_read_b128, lgkmcnt(0)), issues the next tile's DMA into the same slot at once
+// and only then computes: the slot is read only behind the wait that retires its DMA and overwritten only after its
+// reads have returned, and the loop body touches LDS nowhere else (edge tiles apart), so nothing drains the next tile
+// before its turn.  16 waves x 8 KB = 128 KB in flight per CU.  Tile -> wave assignment, MFMA order and the float64 sums
+// are those of the ring forms: the statistics are the same bits.  AUX is the cache policy of its DMA pieces (0 default, 2 nt:
+// the spill is written once and read once per step and is larger than the Infinity Cache).
+template <int NG, bool SYM, int WAVES, int RING, int AUX = 0>
+__global__ __launch_bounds__(WAVES * 64, ((NG == 1 && WAVES == 4 && RING <= 1) ? 4 : 1)) void k_tail(const ClipDesc* __restrict__ clips,
                                                           const ClipInfo* __restrict__ info,
                                                           const float* __restrict__ dctP, KParams kp,
                                                           const float* __restrict__ logmel,
@@ -70,24 +83,45 @@ __global__ __launch_bounds__(WAVES * 64, ((NG == 1 && WAVES == 4 && RING == 0) ?
                                                           float* __restrict__ stats,
                                                           ClipInfo* __restrict__ info_out, int spec, int n_clips) {
   extern __shared__ float tl_smem[];
+#ifdef AFX_TAIL_DEBUG
+  // timing-only ablations of the one-slot form (libafx_dbg.so, AFX_TAIL_SKIP; results invalid): 1 no clamp / MFMA / sums behind a
+  // tile's reads, 2 no DMA (the slot is read as it lies), 4 nothing behind the tile loop (reductions, statistics, RMS pass)
+  const int dbg_skip = spec >> 8;
+  spec &= 255;
+#else
+  constexpr int dbg_skip = 0;
+#endif
   constexpr int NCG = NG;                                  // rows of coefficients handled: 16 NG
   constexpr int GH = SYM ? NG / 2 : NG;
+  constexpr bool ONE = RING == 1;                          // one slot per wave, the images in registers
+  static_assert(!ONE || (NG == 1 && !SYM && WAVES == 4), "the one-slot form is built for up to 16 coefficients, unfolded");
   const int M = kp.n_mels, K = kp.n_mfcc, S = M >> 4;     // S <= 8
   const int KS = SYM ? S >> 1 : S;                         // 16-filter segments the contraction runs over
   float* const dct_tab = tl_smem;                          // [(g KS + s) 4 + c][64 lanes]
-  float* const edge = dct_tab + NCG * KS * 4 * 64;         // [k < 16 NG][18]: frames 0..8, T-9..T-1 of row k
+  float* const edge = dct_tab + (ONE ? 0 : NCG * KS * 4 * 64);         // [k < 16 NG][18]: frames 0..8, T-9..T-1 of row k
   double* const part = reinterpret_cast<double*>(edge + NCG * 16 * 18 + (((NCG * 16 * 18) & 1) ? 1 : 0));   // [wave][k][2]
   double* const red = part + WAVES * NCG * 16 * 2;        // block reductions of the RMS row: [wave][4]
   float* const ring = reinterpret_cast<float*>(red + WAVES * 4);      // RING > 0: [wave][RING][16 rows x 128 floats], 16-byte aligned
   constexpr int kTailWaves = WAVES;
   // coefficient of row i of group g: consecutive, or (SYM) even coefficients in the first GH groups, odd ones in the rest
   auto coef = [&](int g, int i) -> int { return SYM ? 2 * (16 * (g % GH) + i) + g / GH : 16 * g + i; };
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   // a workgroup walks clips blockIdx.x, + gridDim.x, ...: the DCT images are copied to LDS once per workgroup, not per clip
-  for (int i = tid * 4; i < NCG * KS * 4 * 64; i += kTailWaves * 64 * 4)
+  float img[32];                                           // ONE: image value (s, c) of this lane, [s 4 + c]
+  if constexpr (ONE) {
+#pragma unroll
+    for (int i = 0; i < 32; ++i) img[i] = dctP[i * 64 + (threadIdx.x & 63)];
+  } else {
+  for (int i = threadIdx.x * 4; i < NCG * KS * 4 * 64; i += kTailWaves * 64 * 4)
     *reinterpret_cast<float4*>(dct_tab + i) = *reinterpret_cast<const float4*>(dctP + i);
+  }
   for (int clip = blockIdx.x; clip < n_clips; clip += gridDim.x) {
   __syncthreads();                                         // the previous clip's readers of edge / part / red are done (and the table is there)
+  // ONE: the thread's number is taken afresh per clip, so that what is worked out from it (LDS and piece offsets, a few
+  // instructions each) is worked out per clip: hoisted out of the clip loop those values live across the tile loop beside the
+  // 32 images, and are spilled
+  int tid_ = threadIdx.x;
+  if constexpr (ONE) asm volatile("" : "+v"(tid_));
+  const int tid = tid_, wave = tid >> 6, lane = tid & 63;
   const ClipInfo ci = info[clip];
   const ClipDesc cd = clips[clip];
   if (info_out && tid == 0) info_out[clip] = ci;           // the caller's copy (host memory the device can write)
@@ -142,6 +176,65 @@ __global__ __launch_bounds__(WAVES * 64, ((NG == 1 && WAVES == 4 && RING == 0) ?
       for (int r = 0; r < 4; ++r) { sm[g][r] = 0.0; sq[g][r] = 0.0; }
     float4 xc[8];
     int tile = wave;
+    if constexpr (ONE) {
+      // the wave's number as the scalar it is: tile numbers, tile bases and the slot's address stay out of the vector registers
+      // (a DMA piece is then a scalar base + one 32-bit lane offset; as vectors the eight 64-bit addresses alone spill)
+      tile = __builtin_amdgcn_readfirstlane(wave);
+      float* const slot1 = ring + tile * 2048;
+      const float* const clip_rows = logmel + (cd.frame_base + g0) * (int64_t)M;
+      auto dma1 = [&](int tl) {                            // dma_tile's image: position p = 64 i + lane <- chunk (p & 31) ^ f of row f = p >> 5
+        const float* tb = clip_rows + tl * 2048;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+          const unsigned fr = 2 * i + (lane >> 5), j = (lane & 31) ^ fr;
+          __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(tb + (fr * 128u + j * 4u)),
+                                           (__attribute__((address_space(3))) void*)(slot1 + i * 256), 16, 0, AUX);
+        }
+      };
+      if (tile < ntiles && !(dbg_skip & 2)) dma1(tile);
+      for (; tile < ntiles; tile += kTailWaves) {
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the one DMA outstanding: this tile
+        tl_f32x4 x[8];
+#pragma unroll
+        for (int s = 0; s < 8; ++s) x[s] = *reinterpret_cast<const tl_f32x4*>(slot1 + (f * 32 + ((4 * s + q) ^ f)) * 4);
+        // the slot is in registers before its refill is issued (the operands tie the wait behind the eight reads)
+        asm volatile("s_waitcnt lgkmcnt(0)"
+                     : "+v"(x[0]), "+v"(x[1]), "+v"(x[2]), "+v"(x[3]), "+v"(x[4]), "+v"(x[5]), "+v"(x[6]), "+v"(x[7])::"memory");
+        if (tile + kTailWaves < ntiles && !(dbg_skip & 2)) dma1(tile + kTailWaves);
+        __builtin_amdgcn_sched_barrier(0);                 // the refill goes out ahead of the arithmetic, not behind it
+        if (dbg_skip & 1) continue;
+        tl_f32x4 acc[NCG][2] = {{tl_f32x4{0.f, 0.f, 0.f, 0.f}, tl_f32x4{0.f, 0.f, 0.f, 0.f}}};
+#pragma unroll
+        for (int s = 0; s < 8; ++s) {
+          const float b0 = fmaxf(x[s][0], theta), b1 = fmaxf(x[s][1], theta);
+          const float b2 = fmaxf(x[s][2], theta), b3 = fmaxf(x[s][3], theta);
+          acc[0][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(img[4 * s], b0, acc[0][0], 0, 0, 0);
+          acc[0][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(img[4 * s + 1], b1, acc[0][1], 0, 0, 0);
+          acc[0][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(img[4 * s + 2], b2, acc[0][0], 0, 0, 0);
+          acc[0][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(img[4 * s + 3], b3, acc[0][1], 0, 0, 0);
+        }
+        const int t = tile * 16 + f;
+        const bool live = t < T;
+        const bool edge_tile = tile * 16 < 9 || tile * 16 + 16 > T - 9;      // wave-uniform: holds one of the 18 end frames
+#pragma unroll
+        for (int g = 0; g < NCG; ++g) {
+          const tl_f32x4 r4 = acc[g][0] + acc[g][1];       // the same two-accumulator sum as k_dct16 / k_dct16l: identical rows
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const double v = live ? (double)r4[r] : 0.0;
+            sm[g][r] += v; sq[g][r] = fma(v, v, sq[g][r]);
+          }
+          if (edge_tile && live) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+              const int k = coef(g, q * 4 + r);
+              if (t < 9) edge[k * 18 + t] = r4[r];
+              if (t >= T - 9) edge[k * 18 + 9 + (t - (T - 9))] = r4[r];
+            }
+          }
+        }
+      }
+    } else {
     if constexpr (RING > 0) {
 #pragma unroll
       for (int r = 0; r < RING; ++r) if (tile + r * kTailWaves < ntiles) dma_tile(tile + r * kTailWaves, r);
@@ -226,6 +319,8 @@ __global__ __launch_bounds__(WAVES * 64, ((NG == 1 && WAVES == 4 && RING == 0) ?
         }
       }
     }
+    }
+    if (dbg_skip & 4) continue;                            // uniform
     // ---- per wave: totals of the 16 frame lanes of each coefficient row
 #pragma unroll
     for (int g = 0; g < NCG; ++g)
@@ -338,12 +433,12 @@ int tail_sym_groups(const KParams& kp, const DevTables& tb) {
 }
 
 static size_t tail_lds_bytes(int ng, int ks, int waves, int ring) {
-  const size_t tab = (size_t)ng * ks * 4 * 64, edge = (size_t)ng * 16 * 18 + (((ng * 16 * 18) & 1) ? 1 : 0);
+  const size_t tab = ring == 1 ? 0 : (size_t)ng * ks * 4 * 64, edge = (size_t)ng * 16 * 18 + (((ng * 16 * 18) & 1) ? 1 : 0);
   return (tab + edge) * sizeof(float) + ((size_t)waves * ng * 16 * 2 + waves * 4) * sizeof(double) +
          (size_t)waves * ring * 2048 * sizeof(float) + 16;
 }
 
-template <int NG, bool SYM, int WAVES, int RING>
+template <int NG, bool SYM, int WAVES, int RING, int AUX = 0>
 static hipError_t launch_tail_t(hipStream_t s, const ClipDesc* clips, const ClipInfo* info, const float* table, const KParams& kp,
                                 const float* logmel, const float* rms_rows, float* stats, ClipInfo* info_out, int n_clips,
                                 int spec, int n_cu) {
@@ -356,9 +451,9 @@ static hipError_t launch_tail_t(hipStream_t s, const ClipDesc* clips, const Clip
   if (e0 != hipSuccess) return e0;
   if (dev < 0 || dev >= 64) return hipErrorInvalidDevice;
   if (per_cu_dev[dev] == 0) {
-    const void* fn = reinterpret_cast<const void*>(&k_tail<NG, SYM, WAVES, RING>);
+    const void* fn = reinterpret_cast<const void*>(&k_tail<NG, SYM, WAVES, RING, AUX>);
     if (lds > 48 * 1024) {
-      hipError_t e = allow_lds_once<k_tail<NG, SYM, WAVES, RING>>();
+      hipError_t e = allow_lds_once<k_tail<NG, SYM, WAVES, RING, AUX>>();
       if (e != hipSuccess) return e;
     }
     int nb = 0;
@@ -367,21 +462,31 @@ static hipError_t launch_tail_t(hipStream_t s, const ClipDesc* clips, const Clip
   }
   const int per_cu = per_cu_dev[dev];
   dim3 grid(std::max(1, std::min(n_clips, n_cu * per_cu))), block(WAVES * 64);
-  hipLaunchKernelGGL((k_tail<NG, SYM, WAVES, RING>), grid, block, lds, s, clips, info, table, kp, logmel, rms_rows, stats, info_out, spec, n_clips);
+#ifdef AFX_TAIL_DEBUG
+  if (RING == 1) spec |= dev_env().tail_skip << 8;
+#endif
+  hipLaunchKernelGGL((k_tail<NG, SYM, WAVES, RING, AUX>), grid, block, lds, s, clips, info, table, kp, logmel, rms_rows, stats, info_out, spec, n_clips);
   return hipGetLastError();
 }
+
+constexpr int kTailDefault16 = 6;     // the shipped mode for up to 16 coefficients of 128 filters (4 until the one-slot form)
 
 hipError_t launch_tail(hipStream_t s, const ClipDesc* clips, const ClipInfo* info, const DevTables& tb, const KParams& kp,
                        const float* logmel, const float* rms_rows, float* stats, ClipInfo* info_out, int n_clips, int spec,
                        int n_cu) {
   const int gh = tail_sym_groups(kp, tb);
   // mode: 0 the shipped choice; 1 registers; LDS-DMA ring of 2: 4 waves x 4 tiles, 3: 8 waves x 2 tiles, 4: 4 waves x 2 tiles with two
-  // workgroups per CU (A/B: AFX_TAIL_MODE).  Shipped: 3, and 4 for up to 16 coefficients -- a clip is only 54 tiles, and with two
-  // clips per CU the reductions and the RMS pass at the end of one run beside the tiles of the other (cfg 2 step 0.686 -> 0.679 ms;
-  // with 40 coefficients the wider kernel loses 7 % that way, with 20 it makes no difference)
+  // workgroups per CU; 5: one slot per wave, the images in registers, four workgroups per CU, 6: the same with nt DMA pieces --
+  // these two for up to 16 coefficients only, 3 elsewhere (A/B: AFX_TAIL_MODE).  Shipped: 3, and 6 for up to 16 coefficients:
+  // k_tail per launch 112 us (mode 4, shipped before) -> 98 (5) -> 81 (6), cfg 2 step 0.665 -> 0.644 ms; with 40 coefficients
+  // the forms with several workgroups per CU do not fit (registers, LDS) and 4 waves x 2 tiles loses 7 % to 3
   int mode = dev_env().tail_mode;
+  const bool upto16 = gh == 0 && kp.n_mfcc <= 16;
   if (kp.n_mels != 128) mode = 1;                          // the ring's image is laid out for 512-byte rows
-  else if (mode == 0) mode = (gh == 0 && kp.n_mfcc <= 16) ? 4 : 3;
+  else if (mode == 0) mode = upto16 ? kTailDefault16 : 3;
+  else if ((mode == 5 || mode == 6) && !upto16) mode = 3;
+  if (mode == 6) return launch_tail_t<1, false, 4, 1, 2>(s, clips, info, tb.dctP, kp, logmel, rms_rows, stats, info_out, n_clips, spec, n_cu);
+  if (mode == 5) return launch_tail_t<1, false, 4, 1>(s, clips, info, tb.dctP, kp, logmel, rms_rows, stats, info_out, n_clips, spec, n_cu);
 #define AFX_TAIL_W(NG, SYM, TAB, W, R) launch_tail_t<NG, SYM, W, R>(s, clips, info, TAB, kp, logmel, rms_rows, stats, info_out, n_clips, spec, n_cu)
 #define AFX_TAIL(NG, SYM, TAB) (mode == 2 ? AFX_TAIL_W(NG, SYM, TAB, 4, 4) : mode == 3 ? AFX_TAIL_W(NG, SYM, TAB, 8, 2) : mode == 4 ? AFX_TAIL_W(NG, SYM, TAB, 4, 2) : AFX_TAIL_W(NG, SYM, TAB, 4, 0))
   if (gh == 1) return AFX_TAIL(2, true, tb.dctS);
