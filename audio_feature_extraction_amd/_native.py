@@ -25,6 +25,8 @@ DTW_BACKTRACK, DTW_STORE_D = 1, 2
 DTW_MAX_DIM = 128
 HPSS_STORE_SPEC = 4
 HPSS_BINS = 1025
+CHROMA_STORE_HIST = 8
+CHROMA_HIST = 102            # per clip: peaks, kept, counts[100]
 SMP_U8, SMP_S16, SMP_S24, SMP_S32, SMP_F32, SMP_F64 = range(6)
 SMP_KINDS = {"u8": SMP_U8, "s16": SMP_S16, "s24": SMP_S24, "s32": SMP_S32, "f32": SMP_F32, "f64": SMP_F64}     # wavio's kind names
 SMP_BYTES = np.array([1, 2, 3, 4, 4, 8], np.int64)
@@ -41,6 +43,7 @@ SYMBOLS = (
     "afx_extract_batch", "afx_extract_submit", "afx_extract_collect", "afx_f0_batch", "afx_zcr_batch", "afx_spectral_batch", "afx_f0_build_tables", "afx_f0_dispatch", "afx_preprocess", "afx_plan_set_timing", "afx_plan_get_timings", "afx_plan_get_intervals",
     "afx_wav_probe", "afx_wav_read_s16", "afx_batch_geometry", "afx_dtw_batch", "afx_hpss_batch",
     "afx_resample_design", "afx_resample_batch", "afx_rfft_host", "afx_wav_read_raw", "afx_decode_batch",
+    "afx_chroma_batch", "afx_chroma_filters",
 )
 
 
@@ -117,6 +120,9 @@ def lib() -> C.CDLL:
         if hasattr(L, "afx_decode_batch"):                   # newer than version 107 says: found by their presence
             L.afx_wav_read_raw.argtypes = [vp, i32, i32, vp, vp, vp, C.c_int64, vp, vp]
             L.afx_decode_batch.argtypes = [vp, vp, i32, vp, vp, vp, vp, i32, vp, i32, vp]
+        if hasattr(L, "afx_chroma_batch"):                   # newer than version 107 says: found by their presence
+            L.afx_chroma_batch.argtypes = [vp, vp, i32, i32, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+            L.afx_chroma_filters.argtypes = [i32, C.c_double, vp]
         if hasattr(L, "afx_rfft_host"):                      # absent from a library built before the mixed-radix lengths
             L.afx_rfft_host.argtypes = [i32, vp, vp]
         _lib = L
@@ -247,6 +253,15 @@ def rfft_host(x) -> np.ndarray:
     out = np.zeros(2 * (x.size // 2 + 1), np.float32)
     _check(lib().afx_rfft_host(int(x.size), x.ctypes.data, out.ctypes.data), "afx_rfft_host")
     return out.view(np.complex64)
+
+
+def chroma_filters(sr: int, tuning: float = 0.0) -> np.ndarray:
+    """Host-only: librosa.filters.chroma(sr, 2048, tuning) at its defaults, [12, 1025] float32 (what afx_chroma_batch uploads)."""
+    if not hasattr(lib(), "afx_chroma_filters"):
+        raise NotImplementedError("this libafx has no afx_chroma_filters")
+    out = np.zeros((12, HPSS_BINS), np.float32)
+    _check(lib().afx_chroma_filters(int(sr), float(tuning), out.ctypes.data), "afx_chroma_filters")
+    return out
 
 
 def resample_lengths(lengths, sr_in: int, sr_out: int) -> np.ndarray:
@@ -767,6 +782,44 @@ class Plan(_Owner):
             out["stats"] = stats
         if store_spec:
             out["spec"] = [spec[soff[i]:soff[i] + 3 * HPSS_BINS * T[i]].reshape(3, HPSS_BINS, int(T[i])) for i in range(n)]
+        return out
+
+    def chroma_batch(self, samples, offsets, lengths, flags=0, fmt=FMT_F32, mem=MEM_HOST, tuning=None,
+                     want_chroma: bool = True, want_mel: bool = False, want_stats: bool = True, store_hist: bool = False) -> dict:
+        """afx_chroma_batch: librosa.feature.chroma_stft / melspectrogram of a ragged batch (plan: frame_length 2048,
+        hop_length 512, Hann).  ``tuning``: None (estimated per clip on the device), a scalar, or one value per clip.
+        Returns status [n] int32, ``tuning`` [n] float64 (the tuning used) and, as asked, ``chroma`` (list of [12, T]
+        float32), ``mel`` (list of [n_mels, T] float32 power), ``stats`` [n, 4] float64 (mel mean, std, chroma mean, std)
+        and ``hist`` [n, 102] int32 (peaks, kept, the 100 residual counts)."""
+        if not hasattr(lib(), "afx_chroma_batch"):
+            raise NotImplementedError("this libafx has no afx_chroma_batch")
+        offsets, lengths, n = _clip_arrays(offsets, lengths)
+        sptr, kind = _sample_source(samples, fmt, offsets, lengths, mem=mem)
+        T = 1 + lengths // self.params.hop
+        M = int(self.params.n_mels)
+        tin = None
+        if tuning is not None:
+            tin = np.ascontiguousarray(np.broadcast_to(np.asarray(tuning, np.float64), (n,)))
+        coff, moff = packed_offsets(12 * T), packed_offsets(M * T)
+        chroma = np.zeros(int(12 * T.sum()), np.float32) if want_chroma else None
+        mel = np.zeros(int(M * T.sum()), np.float32) if want_mel else None
+        stats = np.zeros((n, 4), np.float64) if want_stats else None
+        hist = np.zeros((n, CHROMA_HIST), np.int32) if store_hist else None
+        tout, status = np.zeros(n, np.float64), np.zeros(n, np.int32)
+        if store_hist:
+            flags |= CHROMA_STORE_HIST
+        _check(lib().afx_chroma_batch(self.handle, sptr, int(fmt), kind, offsets.ctypes.data, lengths.ctypes.data, n,
+                                      int(flags), _ptr(tin), _ptr(chroma), coff.ctypes.data, _ptr(mel), moff.ctypes.data,
+                                      tout.ctypes.data, _ptr(stats), _ptr(hist), status.ctypes.data), "afx_chroma_batch")
+        out = {"status": status, "tuning": tout}
+        if want_chroma:
+            out["chroma"] = [chroma[coff[i]:coff[i] + 12 * T[i]].reshape(12, int(T[i])) for i in range(n)]
+        if want_mel:
+            out["mel"] = [mel[moff[i]:moff[i] + M * T[i]].reshape(M, int(T[i])) for i in range(n)]
+        if want_stats:
+            out["stats"] = stats
+        if store_hist:
+            out["hist"] = hist
         return out
 
     def preprocess(self, y: np.ndarray):

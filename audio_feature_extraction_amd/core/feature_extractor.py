@@ -332,6 +332,46 @@ class AudioFeatureExtractor:
         spectral centroid, all on the GPU."""
         return self.extract_harmonic_features_batch([y])[0]
 
+    _TIMBRE_KEYS = ("mel_energy_mean", "mel_energy_std", "chroma_mean", "chroma_std", "mfcc_mean", "mfcc_std")
+
+    def extract_timbre_features_batch(self, signals: Sequence[np.ndarray]) -> List[Dict[str, Any]]:
+        """``extract_timbre_features`` of many signals in two device passes (a failing clip raises)."""
+        ys = [np.ascontiguousarray(y, dtype=np.float32) for y in signals]
+        if not ys:
+            return []
+        for y in ys:
+            if y.ndim != 1:
+                raise ValueError(f"signals must be 1-D (mono), got shape {y.shape}")
+            if y.size < 4096:
+                raise ValueError(f"extract_timbre_features needs at least 4096 samples (nine frames), got {y.size}")
+        lengths = np.array([y.size for y in ys], np.int64)
+        packed, offsets = np.concatenate(ys), _native.packed_offsets(lengths)
+        plan = self._spectral_plan()
+        out = plan.chroma_batch(packed, offsets, lengths, want_chroma=False)
+        mf = plan.extract_batch(packed, offsets, lengths, flags=0)
+        K = 13
+        res = []
+        for i in range(len(ys)):
+            for st in (out["status"][i], mf["status"][i]):
+                if st != _native.CLIP_OK:
+                    raise _status_error(int(st), "extract_timbre_features", int(mf["nframes"][i]))
+            # the MFCC rows share T: the matrix mean is the mean of the row means, its variance the mean of the rows'
+            # second moments less that mean squared
+            m, sd = mf["stats"][i][:K].astype(np.float64), mf["stats"][i][K:2 * K].astype(np.float64)
+            mean = float(np.mean(m))
+            var = float(np.mean(sd * sd + m * m)) - mean * mean
+            vals = [float(v) for v in out["stats"][i]] + [mean, float(np.sqrt(max(var, 0.0)))]
+            res.append(dict(zip(self._TIMBRE_KEYS, vals)))
+        return res
+
+    def extract_timbre_features(self, y: np.ndarray) -> Dict[str, Any]:
+        """提取音色特徵 (04_feature_extraction_experiment/feature_extractor.py:558-590): mean and std of
+        ``librosa.feature.melspectrogram``, of ``librosa.feature.chroma_stft`` (tuning estimated, as librosa does) and of
+        ``librosa.feature.mfcc(n_mfcc=13)``, all at librosa's defaults and on the GPU; the signal is taken as given.  The
+        MFCC statistics come from the extract pass, which needs nine frames: a signal under 4096 samples raises
+        ``ValueError`` (``feature.chroma_stft`` / ``feature.melspectrogram`` work from one sample up)."""
+        return self.extract_timbre_features_batch([y])[0]
+
     @staticmethod
     def save_frame_features(features: Dict[str, np.ndarray], npz_path: str) -> None:
         """``np.savez(npz_path, **features)`` -- the reference's on-disk schema for frame-level features."""

@@ -42,6 +42,7 @@ DevEnv::DevEnv() {
   if (const char* v = getenv("AFX_TEST_F0_CHUNK_FRAMES")) f0_chunk_frames = std::max<int64_t>(64, atoll(v));
   if (const char* v = getenv("AFX_TEST_DTW_BUDGET")) dtw_budget = std::max<int64_t>(1, atoll(v));
   if (const char* v = getenv("AFX_TEST_HPSS_BUDGET")) hpss_budget = std::max<int64_t>(1, atoll(v));
+  if (const char* v = getenv("AFX_TEST_CHROMA_BUDGET")) chroma_budget = std::max<int64_t>(1, atoll(v));
   f0_dump = getenv("AFX_F0_DUMP");
 }
 const DevEnv& dev_env() { static const DevEnv e; return e; }
@@ -251,7 +252,9 @@ extern "C" void afx_plan_destroy(afx_plan* pl) {
   release(pl->logmel); release(pl->rms); release(pl->mfcc); release(pl->frames);
   release(pl->frame_offs); release(pl->stamps);
   release(pl->blocks_spec); release(pl->blockmax); release(pl->items); release(pl->n_items);
-  for (DevBuf* b : {&pl->hp_clips, &pl->hp_y, &pl->hp_h, &pl->hp_p, &pl->hp_x, &pl->hp_yh, &pl->hp_yp, &pl->hp_bad, &pl->hp_stats, &pl->hp_spec})
+  for (DevBuf* b : {&pl->hp_clips, &pl->hp_y, &pl->hp_h, &pl->hp_p, &pl->hp_x, &pl->hp_yh, &pl->hp_yp, &pl->hp_bad, &pl->hp_stats, &pl->hp_spec,
+                    &pl->ch_grid, &pl->ch_extra, &pl->ch_mel, &pl->ch_s, &pl->ch_mag, &pl->ch_bin, &pl->ch_slot, &pl->ch_hist, &pl->ch_chroma,
+                    &pl->ch_melout, &pl->ch_parts})
     release(*b);
   if (pl->h_pin) (void)hipHostFree(pl->h_pin);
   if (pl->h_clips_pin) (void)hipHostFree(pl->h_clips_pin);

@@ -1,5 +1,5 @@
 // The plan-based feature entry points of libafx.so beside the MFCC / RMS pipeline (afx_api.cpp): pYIN f0, zero-crossing
-// rate, the spectral descriptors, preprocess_audio and harmonic-percussive separation.  Each reads: check -> begin ->
+// rate, the spectral descriptors, preprocess_audio, harmonic-percussive separation and chroma / tuning / mel power.  Each reads: check -> begin ->
 // stage -> its own work -> finish, on the front end of afx_plan.h.
 #include <algorithm>
 #include <cmath>
@@ -402,6 +402,240 @@ extern "C" int afx_hpss_batch(afx_plan* pl, const void* samples, int sample_fmt,
         for (int k = 0; k < 4; ++k) out_stats[4 * i + k] = h_stats[4 * (size_t)q + k];
         if (recs[q].len < 2) out_stats[4 * i + 2] = out_stats[4 * i + 3] = nan;   // k_frames3s skips clips of one sample
       }
+    }
+    c0 = c1;
+  }
+  return AFX_OK;
+}
+
+// ---- chroma_stft / estimate_tuning / melspectrogram (04_feature_extraction_experiment/feature_extractor.py:558-590) ------
+// a 12 x 1025 filterbank (afx_chroma_filters) as the A images k_chroma_apply reads (afx_chroma.h)
+static void chroma_images(const float* w, int rows, const float* dense, int row0, int s0, int s1, float* img) {
+  for (int s = s0; s < s1; ++s)
+    for (int c = 0; c < 4; ++c)
+      for (int l = 0; l < 64; ++l) {
+        const int r = row0 + (l & 15), b = 16 * s + 4 * (l >> 4) + c;
+        img[((size_t)(s - s0) * 4 + c) * 64 + l] = (r < rows && b < kHpssBins) ? (w ? w : dense)[(size_t)r * kHpssBins + b] : 0.f;
+      }
+}
+
+// the plan's tables, at first use: every tuning of estimate_tuning's grid, and the mel bank cut to the steps each group of
+// 16 filters touches
+static int chroma_setup(afx_plan* pl) {
+  if (pl->ch_grid.p) return AFX_OK;
+  const int M = pl->p.n_mels;
+  if (pl->ht.mel_dense.size() != (size_t)M * kHpssBins) { set_error("afx_chroma_batch: the plan has no mel table"); return AFX_ERR_INVALID; }
+  int rc;
+  ChromaMel mr{};
+  mr.n_mels = M; mr.n_groups = (M + 15) / 16;
+  std::vector<float> mimg;
+  for (int g = 0; g < mr.n_groups; ++g) {
+    int lo = kHpssBins, hi = -1;
+    for (int r = 16 * g; r < std::min(M, 16 * g + 16); ++r)
+      for (int b = 0; b < kHpssBins; ++b)
+        if (pl->ht.mel_dense[(size_t)r * kHpssBins + b] != 0.f) { lo = std::min(lo, b); hi = std::max(hi, b); }
+    mr.s0[g] = hi < 0 ? 0 : lo / 16; mr.s1[g] = hi < 0 ? 0 : hi / 16 + 1; mr.off[g] = (int32_t)(mimg.size() / 256);
+    mimg.resize(mimg.size() + (size_t)(mr.s1[g] - mr.s0[g]) * 256);
+    chroma_images(nullptr, M, pl->ht.mel_dense.data(), 16 * g, mr.s0[g], mr.s1[g], mimg.data() + (size_t)mr.off[g] * 256);
+  }
+  if ((rc = ensure(pl->ch_mel, std::max<size_t>(mimg.size(), 1) * sizeof(float))) != AFX_OK) return rc;
+  if (!mimg.empty()) HIP_TRY(hipMemcpy(pl->ch_mel.p, mimg.data(), mimg.size() * sizeof(float), hipMemcpyHostToDevice));
+  mr.img = (const float*)pl->ch_mel.p;
+  pl->ch_melrec = mr;
+  std::vector<float> w(12 * kHpssBins), img((size_t)kChromaGrid * kChromaImg);
+  for (int k = 0; k < kChromaGrid; ++k) {
+    if ((rc = afx_chroma_filters(pl->p.sr, (double)k * 0.01 + -0.5, w.data())) != AFX_OK) return rc;
+    chroma_images(w.data(), 12, nullptr, 0, 0, kChromaSteps, img.data() + (size_t)k * kChromaImg);
+  }
+  DevBuf gbuf;
+  if ((rc = ensure(gbuf, img.size() * sizeof(float))) != AFX_OK) return rc;
+  hipError_t e = hipMemcpy(gbuf.p, img.data(), img.size() * sizeof(float), hipMemcpyHostToDevice);
+  if (e != hipSuccess) { release(gbuf); set_error(std::string("afx_chroma_batch: table upload: ") + hipGetErrorString(e)); return AFX_ERR_HIP; }
+  pl->ch_grid = gbuf;                                  // set last: its presence marks the tables as ready
+  return AFX_OK;
+}
+
+extern "C" int afx_chroma_batch(afx_plan* pl, const void* samples, int sample_fmt, int mem_kind,
+                                const int64_t* offsets, const int64_t* lengths, int n_clips, int flags,
+                                const double* tuning_in, float* out_chroma, const int64_t* chroma_off,
+                                float* out_mel, const int64_t* mel_off, double* out_tuning, double* out_stats,
+                                int32_t* out_hist, int32_t* out_status) {
+  const char* who = "afx_chroma_batch";
+  const bool sh = (flags & AFX_CHROMA_STORE_HIST) != 0;
+  if (n_clips > 0 && !out_status) return null_arg(who);
+  int rc = check_batch_args(who, pl, samples, sample_fmt, mem_kind, offsets, lengths, n_clips, true);
+  if (rc != AFX_OK) return rc;
+  if (pl->p.n_fft != 2048 || pl->p.hop != 512 || pl->p.window != AFX_WINDOW_HANN || !pl->use_f3) {
+    set_error("afx_chroma_batch: the plan must have frame_length 2048, hop_length 512 and the Hann window (librosa's defaults)");
+    return AFX_ERR_UNSUPPORTED;
+  }
+  if (pl->p.n_mels > 16 * kChromaMelGroups) { set_error("afx_chroma_batch: at most 128 mel bands"); return AFX_ERR_UNSUPPORTED; }
+  if (flags & AFX_FLAG_TRIM) { set_error("afx_chroma_batch: trim is not applied here; pass the preprocessed signal"); return AFX_ERR_UNSUPPORTED; }
+  if (flags & ~(AFX_FLAG_PREEMPH | AFX_FLAG_TRIM | AFX_CHROMA_STORE_HIST)) { set_error("afx_chroma_batch: unknown flag"); return AFX_ERR_INVALID; }
+  if (n_clips > 0 && ((out_chroma && !chroma_off) || (out_mel && !mel_off) || (sh && !out_hist))) {
+    set_error("afx_chroma_batch: out_chroma needs chroma_off, out_mel needs mel_off, AFX_CHROMA_STORE_HIST needs out_hist");
+    return AFX_ERR_INVALID;
+  }
+  if ((rc = check_clip_ranges(who, offsets, lengths, out_chroma ? chroma_off : nullptr, n_clips, INT64_MAX / 4)) != AFX_OK) return rc;
+  if ((rc = check_clip_ranges(who, offsets, lengths, out_mel ? mel_off : nullptr, n_clips, INT64_MAX / 4)) != AFX_OK) return rc;
+  const int M = pl->p.n_mels;
+  const double nan = std::nan("");
+  for (int i = 0; i < n_clips; ++i) {
+    if (tuning_in && !std::isfinite(tuning_in[i])) { set_error("afx_chroma_batch: tuning_in must be finite"); return AFX_ERR_INVALID; }
+    out_status[i] = lengths[i] == 0 ? AFX_CLIP_TOO_SHORT : AFX_CLIP_OK;
+    if (out_stats) for (int k = 0; k < 4; ++k) out_stats[4 * i + k] = nan;
+    if (out_tuning) out_tuning[i] = tuning_in ? tuning_in[i] : 0.0;
+    if (sh) std::fill(out_hist + (size_t)kChromaHist * i, out_hist + (size_t)kChromaHist * (i + 1), 0);
+    if (lengths[i] == 0) {                              // one all-zero frame
+      if (out_chroma) std::fill(out_chroma + chroma_off[i], out_chroma + chroma_off[i] + 12, 0.f);
+      if (out_mel) std::fill(out_mel + mel_off[i], out_mel + mel_off[i] + M, 0.f);
+    }
+  }
+  if (n_clips == 0) return AFX_OK;
+  if ((rc = begin_plan_call(who, pl)) != AFX_OK) return rc;
+  if ((rc = chroma_setup(pl)) != AFX_OK) return rc;
+  hipStream_t s = pl->ctx->stream;
+  // piptrack's band, with the spec's own comparisons: 150 <= k sr / 2048 < min(4000, sr / 2), inside bins 1 .. 1023
+  ChromaBand band{1, 0, (float)((double)pl->p.sr / 2048.0)};
+  {
+    const double df = (double)pl->p.sr / 2048.0, fmax = std::min(4000.0, 0.5 * pl->p.sr);
+    int k0 = -1, k1 = -1;
+    for (int k = 1; k < 1024; ++k)
+      if ((double)k * df >= 150.0 && (double)k * df < fmax) { if (k0 < 0) k0 = k; k1 = k; }
+    if (k0 > 0) { band.kmin = k0; band.nr = k1 - k0 + 1; }
+  }
+  const bool est = tuning_in == nullptr, want_mel = out_mel || out_stats;
+  const size_t esz = sample_fmt == AFX_FMT_S16 ? 2 : 4;
+  const int64_t budget = dev_env().chroma_budget;
+  const HpssTabs tb{pl->f3.window, pl->f3.w1024, pl->f3.w2048};
+  std::vector<HpssClip> recs;
+  std::vector<int> idx;
+  std::vector<uint32_t> h_bad;
+  std::vector<int32_t> h_slot, h_hist;
+  std::vector<double> h_stats, extra_t;
+  std::vector<float> w(12 * kHpssBins), eimg;
+  for (int c0 = 0; c0 < n_clips;) {
+    // one chunk: as many clips as the workspace budget holds (at least one); zero-length clips take no work
+    recs.clear(); idx.clear();
+    int64_t frames = 0, ysz = 0, bytes = 0, lo = INT64_MAX, hi = 0, max_len = 0;
+    int tiles = 0;
+    int c1 = c0;
+    for (; c1 < n_clips && (int)recs.size() < 32768; ++c1) {
+      const int64_t L = lengths[c1];
+      if (L == 0) continue;
+      const int64_t T = 1 + L / 512, nt = (T + 15) / 16;
+      const int64_t pb = T * (kHpssPowPitch * 4 + (est ? band.nr * 5 : 0) + 12 * 4 + (want_mel ? M * 4 : 0) + 32) + L * 4 +
+                         (mem_kind == AFX_MEM_HOST ? L * (int64_t)esz : 0) + kChromaHist * 4 + 128;
+      if (!recs.empty() && (bytes + pb > budget || (int64_t)tiles + nt > INT32_MAX / 2)) break;
+      HpssClip r{};
+      r.in_off = offsets[c1]; r.y_off = ysz; r.len = L; r.frame_base = frames; r.T = (int32_t)T; r.tile_base = tiles;
+      recs.push_back(r); idx.push_back(c1);
+      frames += T; ysz += L; tiles += (int)nt; bytes += pb;
+      lo = std::min(lo, offsets[c1]); hi = std::max(hi, offsets[c1] + L); max_len = std::max(max_len, L);
+    }
+    const int n = (int)recs.size();
+    if (n == 0) { c0 = c1; continue; }
+    const void* d_in = samples;
+    if (mem_kind == AFX_MEM_HOST) {
+      if ((rc = ensure(pl->samples, (size_t)(hi - lo) * esz + 16)) != AFX_OK) return rc;
+      HIP_TRY(hipMemcpyAsync(pl->samples.p, (const char*)samples + (size_t)lo * esz, (size_t)(hi - lo) * esz, hipMemcpyHostToDevice, s));
+      for (HpssClip& r : recs) r.in_off -= lo;
+      d_in = pl->samples.p;
+    }
+    if ((rc = ensure(pl->hp_clips, n * sizeof(HpssClip))) != AFX_OK) return rc;
+    if ((rc = ensure(pl->hp_bad, n * sizeof(uint32_t))) != AFX_OK) return rc;
+    if ((rc = ensure(pl->hp_y, (size_t)ysz * sizeof(float) + 64)) != AFX_OK) return rc;
+    if ((rc = ensure(pl->ch_s, (size_t)frames * kHpssPowPitch * sizeof(float))) != AFX_OK) return rc;
+    if ((rc = ensure(pl->ch_slot, n * sizeof(int32_t))) != AFX_OK) return rc;
+    if ((rc = ensure(pl->ch_hist, (size_t)n * kChromaHist * sizeof(int32_t))) != AFX_OK) return rc;
+    if ((rc = ensure(pl->ch_chroma, (size_t)frames * 12 * sizeof(float))) != AFX_OK) return rc;
+    if (est && band.nr > 0) {
+      if ((rc = ensure(pl->ch_mag, (size_t)frames * band.nr * sizeof(float))) != AFX_OK) return rc;
+      if ((rc = ensure(pl->ch_bin, (size_t)frames * band.nr)) != AFX_OK) return rc;
+    }
+    if (out_mel && (rc = ensure(pl->ch_melout, (size_t)frames * M * sizeof(float))) != AFX_OK) return rc;
+    if (out_stats) {
+      if ((rc = ensure(pl->ch_parts, (size_t)frames * 4 * sizeof(double))) != AFX_OK) return rc;
+      if ((rc = ensure(pl->hp_stats, (size_t)n * 4 * sizeof(double))) != AFX_OK) return rc;
+    }
+    const HpssClip* d_clips = (const HpssClip*)pl->hp_clips.p;
+    uint32_t* d_bad = (uint32_t*)pl->hp_bad.p;
+    float* d_y = (float*)pl->hp_y.p;
+    float* d_S = (float*)pl->ch_s.p;
+    int32_t* d_slot = (int32_t*)pl->ch_slot.p;
+    float* d_mel = out_mel ? (float*)pl->ch_melout.p : nullptr;
+    double* d_parts = out_stats ? (double*)pl->ch_parts.p : nullptr;
+    HIP_TRY(hipMemcpyAsync(pl->hp_clips.p, recs.data(), n * sizeof(HpssClip), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemsetAsync(d_bad, 0, n * sizeof(uint32_t), s));
+    HIP_TRY(launch_hpss_prep(s, d_in, sample_fmt, flags & AFX_FLAG_PREEMPH, pl->kp.preemph_b1, d_clips, n, max_len, d_y, d_bad));
+    HIP_TRY(launch_hpss_stft_power(s, d_y, d_clips, d_bad, n, frames, tb, d_S));
+    if (est) {
+      if (band.nr > 0) HIP_TRY(launch_chroma_peaks(s, d_S, frames, band, (float*)pl->ch_mag.p, (uint8_t*)pl->ch_bin.p));
+      HIP_TRY(launch_chroma_tuning(s, d_clips, n, band, (const float*)pl->ch_mag.p, (const uint8_t*)pl->ch_bin.p, d_slot,
+                                   (int32_t*)pl->ch_hist.p));
+    } else {
+      // a tuning on estimate_tuning's grid reads the plan's table; every other distinct value gets images of its own
+      h_slot.resize(n); extra_t.clear();
+      for (int q = 0; q < n; ++q) {
+        const double t = tuning_in[idx[q]];
+        const long k = std::lround((t + 0.5) * 100.0);
+        if (k >= 0 && k < kChromaGrid && (double)k * 0.01 + -0.5 == t) { h_slot[q] = (int32_t)k; continue; }
+        size_t j = std::find(extra_t.begin(), extra_t.end(), t) - extra_t.begin();
+        if (j == extra_t.size()) extra_t.push_back(t);
+        h_slot[q] = kChromaGrid + (int32_t)j;
+      }
+      if (!extra_t.empty()) {
+        eimg.resize(extra_t.size() * kChromaImg);
+        for (size_t j = 0; j < extra_t.size(); ++j) {
+          if ((rc = afx_chroma_filters(pl->p.sr, extra_t[j], w.data())) != AFX_OK) return rc;
+          chroma_images(w.data(), 12, nullptr, 0, 0, kChromaSteps, eimg.data() + j * kChromaImg);
+        }
+        if ((rc = ensure(pl->ch_extra, eimg.size() * sizeof(float))) != AFX_OK) return rc;
+        HIP_TRY(hipMemcpyAsync(pl->ch_extra.p, eimg.data(), eimg.size() * sizeof(float), hipMemcpyHostToDevice, s));
+      }
+      HIP_TRY(hipMemcpyAsync(d_slot, h_slot.data(), n * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    }
+    HIP_TRY(launch_chroma_apply(s, d_S, d_clips, n, tiles, d_slot, (const float*)pl->ch_grid.p, (const float*)pl->ch_extra.p,
+                                pl->ch_melrec, want_mel, (float*)pl->ch_chroma.p, d_mel, d_parts));
+    if (out_stats) {
+      HIP_TRY(launch_chroma_stats(s, d_clips, n, M, d_parts, (double*)pl->hp_stats.p));
+      h_stats.resize((size_t)n * 4);
+      HIP_TRY(hipMemcpyAsync(h_stats.data(), pl->hp_stats.p, (size_t)n * 4 * sizeof(double), hipMemcpyDeviceToHost, s));
+    }
+    // the matrices: one copy when the caller's layout is the chunk's (packed clips in order), else one per clip
+    for (int which = 0; which < 2; ++which) {
+      float* dst = which ? out_mel : out_chroma;
+      const int64_t* off = which ? mel_off : chroma_off;
+      const float* src = which ? d_mel : (const float*)pl->ch_chroma.p;
+      const int64_t rows = which ? M : 12;
+      if (!dst) continue;
+      bool packed = true;
+      for (int q = 0; q < n && packed; ++q) packed = off[idx[q]] - off[idx[0]] == rows * recs[q].frame_base;
+      if (packed) {
+        HIP_TRY(hipMemcpyAsync(dst + off[idx[0]], src, (size_t)(rows * frames) * sizeof(float), hipMemcpyDeviceToHost, s));
+      } else {
+        for (int q = 0; q < n; ++q)
+          HIP_TRY(hipMemcpyAsync(dst + off[idx[q]], src + rows * recs[q].frame_base, (size_t)(rows * recs[q].T) * sizeof(float), hipMemcpyDeviceToHost, s));
+      }
+    }
+    if (est) {
+      h_slot.resize(n);
+      HIP_TRY(hipMemcpyAsync(h_slot.data(), d_slot, n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+      if (sh) {
+        h_hist.resize((size_t)n * kChromaHist);
+        HIP_TRY(hipMemcpyAsync(h_hist.data(), pl->ch_hist.p, h_hist.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+      }
+    }
+    h_bad.resize(n);
+    HIP_TRY(hipMemcpyAsync(h_bad.data(), d_bad, n * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    for (int q = 0; q < n; ++q) {
+      const int i = idx[q];
+      out_status[i] = h_bad[q] ? AFX_CLIP_NONFINITE : AFX_CLIP_OK;
+      if (est && out_tuning) out_tuning[i] = (double)h_slot[q] * 0.01 + -0.5;
+      if (est && sh) std::copy(h_hist.begin() + (size_t)q * kChromaHist, h_hist.begin() + (size_t)(q + 1) * kChromaHist, out_hist + (size_t)kChromaHist * i);
+      if (out_stats && !h_bad[q])
+        for (int k = 0; k < 4; ++k) out_stats[4 * i + k] = h_stats[4 * (size_t)q + k];
     }
     c0 = c1;
   }

@@ -1,8 +1,10 @@
 // Host-only part of libafx.so: the error string, the version, and the builders that need no device -- the clip records of
-// a batch (what prepare_descriptors uploads), the pYIN tables and the pYIN kernel dispatch (afx_f0_dispatch).  Together with afx_tables.cpp, afx_f0_tables.cpp and
+// a batch (what prepare_descriptors uploads), the pYIN tables, the pYIN kernel dispatch (afx_f0_dispatch) and the chroma filterbank (afx_chroma_filters).  Together with afx_tables.cpp, afx_f0_tables.cpp and
 // afx_wav.cpp this is everything that parses caller- or file-supplied data on the host; `make asan` builds exactly these
 // files (plus afx_host_stubs.cpp) with g++ -fsanitize=address,undefined as libafx_host_asan.so.
 #include <algorithm>
+#include <cfloat>
+#include <cmath>
 #include <cstring>
 #include <string>
 
@@ -147,5 +149,30 @@ extern "C" int afx_f0_dispatch(int sr, int n_fft, int hop, double fmin, double f
   const int32_t v[12] = {d.energy_lpw, d.epb, d.yin_n, d.yin_fpb, d.yin_sh, d.vit_nbt, d.vit_bandt, d.vit_tpt, d.bt_depth,
                          t.p.band, t.p.n_bins, d.yin_lds};
   std::memcpy(out, v, sizeof(v));
+  return AFX_OK;
+}
+
+// librosa.filters.chroma(sr, 2048, tuning, n_chroma=12, ctroct=5, octwidth=2, norm=2, base_c=True): float64 throughout, one
+// rounding to float32 (tests/chroma_ref.py chroma_filters is the spec).  Column j's width needs q[j + 1] only, and the norm
+// is per column, so the 1025 columns kept are all that is computed.
+extern "C" int afx_chroma_filters(int sr, double tuning, float* out) {
+  if (!out) { set_error("afx_chroma_filters: null argument"); return AFX_ERR_INVALID; }
+  if (sr <= 0 || !std::isfinite(tuning)) { set_error("afx_chroma_filters: sr must be positive and tuning finite"); return AFX_ERR_INVALID; }
+  constexpr int NB = 1025;
+  const double a440 = 440.0 * std::pow(2.0, tuning / 12.0) / 16.0, step = (double)sr / 2048.0;
+  double q[NB + 1];
+  for (int j = 1; j <= NB; ++j) q[j] = 12.0 * std::log2(((double)j * step) / a440);
+  q[0] = q[1] - 18.0;
+  for (int j = 0; j < NB; ++j) {
+    const double bw = std::max(q[j + 1] - q[j], 1.0);
+    double w[12], ss = 0.0;
+    for (int c = 0; c < 12; ++c) {
+      const double d = std::fmod(q[j] - (double)c + 6.0 + 120.0, 12.0) - 6.0, e = 2.0 * d / bw;
+      w[c] = std::exp(-0.5 * (e * e));
+      ss += w[c] * w[c];
+    }
+    const double norm = std::max(std::sqrt(ss), DBL_MIN), o = (q[j] / 12.0 - 5.0) / 2.0, oct = std::exp(-0.5 * (o * o));
+    for (int c = 0; c < 12; ++c) out[c * NB + j] = (float)(w[(c + 3) % 12] / norm * oct);     // roll(-3): row c is pitch class c + 3
+  }
   return AFX_OK;
 }

@@ -49,6 +49,10 @@ int afx_hpss_batch(afx_plan*, const void*, int, int, const int64_t*, const int64
                    const int64_t*, int32_t*) {
   return no_device("afx_hpss_batch");
 }
+int afx_chroma_batch(afx_plan*, const void*, int, int, const int64_t*, const int64_t*, int, int, const double*, float*,
+                     const int64_t*, float*, const int64_t*, double*, double*, int32_t*, int32_t*) {
+  return no_device("afx_chroma_batch");
+}
 int afx_resample_batch(afx_ctx*, const void*, int, int, const int64_t*, const int64_t*, int, int, int, const double*, int, float*,
                        int, const int64_t*, int64_t*) {
   return no_device("afx_resample_batch");

@@ -9,6 +9,7 @@ namespace afx {
 
 constexpr int kHpssBins = 1025;            // n_fft / 2 + 1
 constexpr int kHpssPitch = 1032;           // complex64 per frame row of the spectrum workspace (8256 B, 64-byte aligned rows)
+constexpr int kHpssPowPitch = 1040;        // float32 per frame row of the power spectrum (launch_hpss_stft_power): 65 x 16 bins, 4160 B
 constexpr int kHpssTile = 64;              // k_hpss_mask: 64 frames x 64 bins per workgroup
 constexpr int kHpssBinTiles = 17;          // ceil(1025 / 64)
 constexpr int kHpssHalo = 15;              // kernel_size 31
@@ -30,12 +31,28 @@ struct HpssTabs {
   const float* w2048;   // exp(-2 pi i k / 2048), k < 1024, float2
 };
 
+#ifdef __HIPCC__
+// clip of a row / tile index: the last record whose base is <= g (wave-uniform binary search)
+template <typename F>
+__device__ __forceinline__ int hp_find(int n, int64_t g, F base) {
+  int lo = 0, hi = n - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (base(mid) <= g) lo = mid; else hi = mid - 1;
+  }
+  return lo;
+}
+#endif
+
 // y[y_off + i] = sample i (pre-emphasised when flags has AFX_FLAG_PREEMPH); bad[c] = 1 when clip c holds a NaN / inf
 hipError_t launch_hpss_prep(hipStream_t s, const void* in, int fmt, int flags, float preemph_b1, const HpssClip* clips,
                             int n, int64_t max_len, float* y, uint32_t* bad);
 // the complex spectrum of every frame into rows of X (zeros for a bad clip)
 hipError_t launch_hpss_stft(hipStream_t s, const float* y, const HpssClip* clips, const uint32_t* bad, int n,
                             int64_t n_frames, HpssTabs tb, float2* X);
+// |X|^2 of every frame as float32 rows of kHpssPowPitch, entries 1025 .. 1039 zero (zeros for a bad clip)
+hipError_t launch_hpss_stft_power(hipStream_t s, const float* y, const HpssClip* clips, const uint32_t* bad, int n,
+                                  int64_t n_frames, HpssTabs tb, float* S);
 // both medians of |X|, the soft masks, Yh = X mh and (Yp != nullptr) Yp = X mp; spec != nullptr: S, Hm, Pm as well
 hipError_t launch_hpss_mask(hipStream_t s, const float2* X, const HpssClip* clips, int n, int n_tiles, float2* Yh,
                             float2* Yp, float* spec);

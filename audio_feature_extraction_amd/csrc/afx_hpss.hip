@@ -2,6 +2,7 @@
 // power 2, margin 1) on the 2048 / 512 periodic-Hann STFT, centred with zero padding.  Five kernels on one stream:
 //   k_hpss_prep   the chunk's clips as float32 (S16 / pre-emphasis applied), one NaN / inf flag per clip
 //   k_hpss_stft   one wave per frame: window, 1024-point complex FFT (radix-4 Stockham in LDS), real-FFT split
+//                 (its power-output instantiation is the front end of afx_chroma.hip)
 //   k_hpss_mask   64 x 64 cells per workgroup: |X| with a 15-cell halo in LDS, the two medians of 31 as sorted sliding
 //                 windows per lane, the soft masks, Yh = X mh (and Yp = X mp)
 //   k_hpss_irfft  one wave per frame, in place: irfft x window
@@ -40,17 +41,6 @@ __device__ __forceinline__ int hp_refl(int i, int n) {
   int m = i % p;
   if (m < 0) m += p;
   return m < n ? m : p - 1 - m;
-}
-
-// clip of a row / tile index: the last record whose base is <= g (wave-uniform binary search)
-template <typename F>
-__device__ __forceinline__ int hp_find(int n, int64_t g, F base) {
-  int lo = 0, hi = n - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (base(mid) <= g) lo = mid; else hi = mid - 1;
-  }
-  return lo;
 }
 
 // librosa.util.softmask(H, P, power=2, split_zeros=True) and softmask(P, H, ...), in librosa's float32 order
@@ -151,9 +141,11 @@ __global__ __launch_bounds__(256) void k_hpss_prep(const void* __restrict__ in, 
   if (nf) atomicOr(&bad[blockIdx.y], 1u);
 }
 
+// POW: |X|^2 as float32 rows of kHpssPowPitch (the pad behind bin 1024 zeroed) instead of the complex rows
+template <bool POW>
 __global__ __launch_bounds__(256) void k_hpss_stft(const float* __restrict__ y, const HpssClip* __restrict__ clips,
                                                    const uint32_t* __restrict__ bad, int n, int64_t n_frames, HpssTabs tb,
-                                                   v2* __restrict__ X) {
+                                                   void* __restrict__ out) {
   __shared__ v2 lds[4][1024];
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int64_t g = (int64_t)blockIdx.x * 4 + wave;
@@ -175,7 +167,8 @@ __global__ __launch_bounds__(256) void k_hpss_stft(const float* __restrict__ y, 
   hp_fft1024(buf, (const v2*)tb.w1024, lane);
   // real-FFT split: X[k] = (Z[k] + conj Z[N-k]) / 2 - i W2048^k (Z[k] - conj Z[N-k]) / 2
   const v2* W = (const v2*)tb.w2048;
-  v2* row = X + gg * kHpssPitch;
+  v2* row = (v2*)out + gg * kHpssPitch;
+  float* prow = (float*)out + gg * kHpssPowPitch;
 #pragma unroll 4
   for (int q = 0; q < 16; ++q) {
     const int k = lane + 64 * q;
@@ -185,9 +178,16 @@ __global__ __launch_bounds__(256) void k_hpss_stft(const float* __restrict__ y, 
     const v2 wb = hp_cmul(W[k], B);
     v2 xk = v2{A.x + wb.y, A.y - wb.x};
     if (zero) xk = v2{0.f, 0.f};
-    if (live) row[k] = xk;
+    if (POW) { if (live) prow[k] = xk.x * xk.x + xk.y * xk.y; }
+    else if (live) row[k] = xk;
   }
-  if (live && lane == 0) {
+  if (POW) {
+    if (live && lane < kHpssPowPitch - 1024) {
+      const v2 z0 = buf[0];
+      const float ny = z0.x - z0.y;
+      prow[1024 + lane] = (zero || lane > 0) ? 0.f : ny * ny;
+    }
+  } else if (live && lane == 0) {
     const v2 z0 = buf[0];
     row[1024] = zero ? v2{0.f, 0.f} : v2{z0.x - z0.y, 0.f};
   }
@@ -345,8 +345,15 @@ hipError_t launch_hpss_prep(hipStream_t s, const void* in, int fmt, int flags, f
 
 hipError_t launch_hpss_stft(hipStream_t s, const float* y, const HpssClip* clips, const uint32_t* bad, int n,
                             int64_t n_frames, HpssTabs tb, float2* X) {
-  hipLaunchKernelGGL(k_hpss_stft, dim3((unsigned)((n_frames + 3) / 4)), dim3(256), 0, s, y, clips, bad, n, n_frames, tb,
-                     (v2*)X);
+  hipLaunchKernelGGL(k_hpss_stft<false>, dim3((unsigned)((n_frames + 3) / 4)), dim3(256), 0, s, y, clips, bad, n, n_frames,
+                     tb, (void*)X);
+  return hipGetLastError();
+}
+
+hipError_t launch_hpss_stft_power(hipStream_t s, const float* y, const HpssClip* clips, const uint32_t* bad, int n,
+                                  int64_t n_frames, HpssTabs tb, float* S) {
+  hipLaunchKernelGGL(k_hpss_stft<true>, dim3((unsigned)((n_frames + 3) / 4)), dim3(256), 0, s, y, clips, bad, n, n_frames,
+                     tb, (void*)S);
   return hipGetLastError();
 }
 

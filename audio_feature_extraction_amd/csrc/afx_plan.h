@@ -10,6 +10,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include "afx_chroma.h"
 #include "afx_decode.h"
 #include "afx_device.h"
 #include "afx_f0.h"
@@ -70,6 +71,10 @@ struct afx_plan {
   std::vector<void*> f0_allocs;
   DevBuf f0_in, f0_ysig, f0_energy, f0_cnt, f0_vp, f0_bin, f0_prob, f0_lprob, f0_lu, f0_ptr, f0_best, f0_states, f0_stats, f0_out, f0_offs;
   DevBuf hp_clips, hp_y, hp_h, hp_p, hp_x, hp_yh, hp_yp, hp_bad, hp_stats, hp_spec;   // afx_hpss_batch
+  // afx_chroma_batch (with hp_clips, hp_y, hp_bad, hp_stats): the 100-tuning filterbank and the mel bank as MFMA images
+  // (built at first use), a chunk's off-grid filterbanks, the power rows, the peak records and the results
+  DevBuf ch_grid, ch_extra, ch_mel, ch_s, ch_mag, ch_bin, ch_slot, ch_hist, ch_chroma, ch_melout, ch_parts;
+  ChromaMel ch_melrec{};
   // cached per-batch descriptors
   std::vector<int64_t> c_off, c_len;
   std::vector<ClipDesc> h_clips;

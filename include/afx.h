@@ -296,6 +296,38 @@ int afx_hpss_batch(afx_plan* plan, const void* samples, int sample_fmt, int mem_
                    float* out_harm, float* out_perc, double* out_stats,
                    float* out_spec, const int64_t* spec_off, int32_t* out_status);
 
+/* The timbre group of 04_feature_extraction_experiment/feature_extractor.py:558-590: librosa.feature.chroma_stft (with
+ * librosa.estimate_tuning when no tuning is given) and librosa.feature.melspectrogram at librosa's defaults (n_fft 2048,
+ * hop 512, centred, periodic Hann, power 2; piptrack fmin 150 / fmax 4000 / threshold 0.1, tuning resolution 0.01, 12
+ * chroma, ctroct 5, octwidth 2, norm 2 / inf, base_c), as tests/chroma_ref.py restates them.  Both symbols are newer than
+ * AFX_VERSION 107 says: a binding detects them by their presence.  The plan must be n_fft 2048 / hop 512 with
+ * AFX_WINDOW_HANN and at most 128 mel bands (AFX_ERR_UNSUPPORTED otherwise); sr and the mel bank are the plan's.
+ *   flags       AFX_FLAG_PREEMPH or 0, plus AFX_CHROMA_STORE_HIST (AFX_FLAG_TRIM is unsupported)
+ *   tuning_in   NULL: the tuning of every clip is estimated on the device; else n_clips values (fractions of a semitone)
+ *   out_chroma, chroma_off   NULL or host float: clip i's 12 x T_i matrix, row-major, at out_chroma[chroma_off[i] ..],
+ *               T_i = 1 + lengths[i] / 512; every frame divided by its maximum (a frame below FLT_MIN stays zero)
+ *   out_mel, mel_off         NULL or host float: n_mels x T_i mel power at out_mel[mel_off[i] ..]
+ *   out_tuning  NULL or host double[n_clips]: the tuning used (an estimate is one of -0.5 + 0.01 k, k < 100; 0 when the
+ *               clip has no pitch peak)
+ *   out_stats   NULL or host double[4 n_clips]: mean and std (ddof 0) of the mel matrix, then of the chroma matrix;
+ *               NaN for a failed clip
+ *   out_hist    AFX_CHROMA_STORE_HIST only (no performance requirement; zeros where tuning_in is given): int32[102
+ *               n_clips]: pitch peaks, peaks at or above the median magnitude, their 100 residual counts
+ *   out_status  AFX_CLIP_TOO_SHORT for length 0, AFX_CLIP_NONFINITE for a NaN / inf sample; a failed clip's matrices are
+ *               zero and it never affects the other clips
+ * No float atomics: results are bit-reproducible and independent of what else is in the batch.  The batch runs in chunks
+ * whose device workspace stays within 2 GiB; a clip larger than that runs alone.
+ *
+ * afx_chroma_filters (host-only): librosa.filters.chroma(sr, 2048, tuning) as 12 x 1025 float32, row-major. */
+enum { AFX_CHROMA_STORE_HIST = 8 };
+int afx_chroma_batch(afx_plan* plan, const void* samples, int sample_fmt, int mem_kind,
+                     const int64_t* offsets, const int64_t* lengths, int n_clips, int flags,
+                     const double* tuning_in,
+                     float* out_chroma, const int64_t* chroma_off,
+                     float* out_mel, const int64_t* mel_off,
+                     double* out_tuning, double* out_stats, int32_t* out_hist, int32_t* out_status);
+int afx_chroma_filters(int sr, double tuning, float* out /*[12 * 1025]*/);
+
 /* Host-only (no device needed): the tables afx_f0_batch uploads, for inspection and tests.
  * info[8] = min_period, max_period, n_pitch_bins, band (transition half-width), candidate
  * capacity, lags kept, lags per lane, trough slots per lane.  beta[100] = Beta(2,18) mass of
