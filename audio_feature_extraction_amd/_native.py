@@ -27,6 +27,7 @@ HPSS_STORE_SPEC = 4
 HPSS_BINS = 1025
 CHROMA_STORE_HIST = 8
 CHROMA_HIST = 102            # per clip: peaks, kept, counts[100]
+TEMPO_MAX_WIN = 768          # lags of the tempogram window afx_rhythm_batch holds (sr <= 49215 at hop 512)
 SMP_U8, SMP_S16, SMP_S24, SMP_S32, SMP_F32, SMP_F64 = range(6)
 SMP_KINDS = {"u8": SMP_U8, "s16": SMP_S16, "s24": SMP_S24, "s32": SMP_S32, "f32": SMP_F32, "f64": SMP_F64}     # wavio's kind names
 SMP_BYTES = np.array([1, 2, 3, 4, 4, 8], np.int64)
@@ -43,7 +44,7 @@ SYMBOLS = (
     "afx_extract_batch", "afx_extract_submit", "afx_extract_collect", "afx_f0_batch", "afx_zcr_batch", "afx_spectral_batch", "afx_f0_build_tables", "afx_f0_dispatch", "afx_preprocess", "afx_plan_set_timing", "afx_plan_get_timings", "afx_plan_get_intervals",
     "afx_wav_probe", "afx_wav_read_s16", "afx_batch_geometry", "afx_dtw_batch", "afx_hpss_batch",
     "afx_resample_design", "afx_resample_batch", "afx_rfft_host", "afx_wav_read_raw", "afx_decode_batch",
-    "afx_chroma_batch", "afx_chroma_filters",
+    "afx_chroma_batch", "afx_chroma_filters", "afx_rhythm_batch", "afx_tempo_table",
 )
 
 
@@ -123,6 +124,9 @@ def lib() -> C.CDLL:
         if hasattr(L, "afx_chroma_batch"):                   # newer than version 107 says: found by their presence
             L.afx_chroma_batch.argtypes = [vp, vp, i32, i32, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
             L.afx_chroma_filters.argtypes = [i32, C.c_double, vp]
+        if hasattr(L, "afx_rhythm_batch"):                   # newer than version 107 says: found by their presence
+            L.afx_rhythm_batch.argtypes = [vp, vp, i32, i32, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+            L.afx_tempo_table.argtypes = [i32, i32p, i32p, vp, vp]
         if hasattr(L, "afx_rfft_host"):                      # absent from a library built before the mixed-radix lengths
             L.afx_rfft_host.argtypes = [i32, vp, vp]
         _lib = L
@@ -262,6 +266,19 @@ def chroma_filters(sr: int, tuning: float = 0.0) -> np.ndarray:
     out = np.zeros((12, HPSS_BINS), np.float32)
     _check(lib().afx_chroma_filters(int(sr), float(tuning), out.ctypes.data), "afx_chroma_filters")
     return out
+
+
+def tempo_table(sr: int) -> dict:
+    """Host-only: what afx_rhythm_batch decides the tempo with at a sample rate (hop 512): ``win`` = int(8 sr) // 512 lags,
+    ``kmin`` (the first lag slower than 320 bpm), ``bpm`` [win] (bpm[0] = inf) and ``logprior`` [win] (-inf below kmin), float64.
+    NotImplementedError when win is not in 2 .. 768 (sr above 49215)."""
+    if not hasattr(lib(), "afx_tempo_table"):
+        raise NotImplementedError("this libafx has no afx_tempo_table")
+    win, kmin = C.c_int32(), C.c_int32()
+    _check(lib().afx_tempo_table(int(sr), C.byref(win), C.byref(kmin), None, None), "afx_tempo_table")
+    bpm, logprior = np.zeros(win.value, np.float64), np.zeros(win.value, np.float64)
+    _check(lib().afx_tempo_table(int(sr), C.byref(win), C.byref(kmin), bpm.ctypes.data, logprior.ctypes.data), "afx_tempo_table")
+    return {"win": int(win.value), "kmin": int(kmin.value), "bpm": bpm, "logprior": logprior}
 
 
 def resample_lengths(lengths, sr_in: int, sr_out: int) -> np.ndarray:
@@ -820,6 +837,38 @@ class Plan(_Owner):
             out["stats"] = stats
         if store_hist:
             out["hist"] = hist
+        return out
+
+    def rhythm_batch(self, samples, offsets, lengths, flags=0, fmt=FMT_F32, mem=MEM_HOST, want_env: bool = True,
+                     want_tempogram: bool = False, want_acmean: bool = False, want_stats: bool = True) -> dict:
+        """afx_rhythm_batch: librosa.onset.onset_strength, the tempogram and tempo of librosa.beat.beat_track of a ragged
+        batch (plan: frame_length 2048, hop_length 512, Hann; sr <= 49215).  Returns status [n] int32, ``tempo`` [n] float64
+        (0.0 for an all-zero envelope, NaN for a failed clip), ``lag`` [n] int32 and, as asked, ``env`` (list of (T,) float32),
+        ``tempogram`` (list of [win, T] float32), ``acmean`` [n, win] float64 and ``stats`` [n, 2] float64 (mean, std of env)."""
+        if not hasattr(lib(), "afx_rhythm_batch"):
+            raise NotImplementedError("this libafx has no afx_rhythm_batch")
+        offsets, lengths, n = _clip_arrays(offsets, lengths)
+        sptr, kind = _sample_source(samples, fmt, offsets, lengths, mem=mem)
+        T = 1 + lengths // self.params.hop
+        win = (8 * int(self.params.sr)) // 512
+        eoff, toff = packed_offsets(T), packed_offsets(win * T)
+        env = np.zeros(int(T.sum()), np.float32) if want_env else None
+        tg = np.zeros(int(win * T.sum()), np.float32) if want_tempogram else None
+        acmean = np.zeros((n, win), np.float64) if want_acmean else None
+        stats = np.zeros((n, 2), np.float64) if want_stats else None
+        tempo, lag, status = np.zeros(n, np.float64), np.zeros(n, np.int32), np.zeros(n, np.int32)
+        _check(lib().afx_rhythm_batch(self.handle, sptr, int(fmt), kind, offsets.ctypes.data, lengths.ctypes.data, n,
+                                      int(flags), _ptr(env), eoff.ctypes.data, _ptr(tg), toff.ctypes.data, _ptr(acmean),
+                                      tempo.ctypes.data, lag.ctypes.data, _ptr(stats), status.ctypes.data), "afx_rhythm_batch")
+        out = {"status": status, "tempo": tempo, "lag": lag}
+        if want_env:
+            out["env"] = [env[eoff[i]:eoff[i] + T[i]] for i in range(n)]
+        if want_tempogram:
+            out["tempogram"] = [tg[toff[i]:toff[i] + win * T[i]].reshape(win, int(T[i])) for i in range(n)]
+        if want_acmean:
+            out["acmean"] = acmean
+        if want_stats:
+            out["stats"] = stats
         return out
 
     def preprocess(self, y: np.ndarray):

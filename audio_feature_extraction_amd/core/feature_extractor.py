@@ -372,6 +372,33 @@ class AudioFeatureExtractor:
         ``ValueError`` (``feature.chroma_stft`` / ``feature.melspectrogram`` work from one sample up)."""
         return self.extract_timbre_features_batch([y])[0]
 
+    _RHYTHM_KEYS = ("tempo", "rhythm_regularity", "onset_strength_mean", "onset_strength_std")
+
+    def extract_rhythm_features_batch(self, signals: Sequence[np.ndarray]) -> List[Dict[str, Any]]:
+        """``extract_rhythm_features`` of many signals in one device pass (a failing clip raises)."""
+        ys = [np.ascontiguousarray(y, dtype=np.float32) for y in signals]
+        if not ys:
+            return []
+        for y in ys:
+            if y.ndim != 1:
+                raise ValueError(f"signals must be 1-D (mono), got shape {y.shape}")
+        lengths = np.array([y.size for y in ys], np.int64)
+        out = self._spectral_plan().rhythm_batch(np.concatenate(ys), _native.packed_offsets(lengths), lengths, want_env=False)
+        res = []
+        for i, st in enumerate(out["status"]):
+            if st != _native.CLIP_OK:
+                raise _status_error(int(st), "extract_rhythm_features")
+            mean, std = (float(v) for v in out["stats"][i])
+            res.append(dict(zip(self._RHYTHM_KEYS, (float(out["tempo"][i]), std / (mean + 1e-8), mean, std))))
+        return res
+
+    def extract_rhythm_features(self, y: np.ndarray) -> Dict[str, Any]:
+        """提取節奏特徵 (04_feature_extraction_experiment/feature_extractor.py:592-622): the tempo
+        ``librosa.beat.beat_track`` reports for ``librosa.onset.onset_strength(y)`` (the beat positions, which the reference
+        discards, are not computed), the mean and std of that envelope and their ratio, all at librosa's defaults and on
+        the GPU; the signal is taken as given and may be as short as one sample (tempo 0.0 up to three frames)."""
+        return self.extract_rhythm_features_batch([y])[0]
+
     @staticmethod
     def save_frame_features(features: Dict[str, np.ndarray], npz_path: str) -> None:
         """``np.savez(npz_path, **features)`` -- the reference's on-disk schema for frame-level features."""

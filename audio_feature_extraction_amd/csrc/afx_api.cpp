@@ -43,6 +43,7 @@ DevEnv::DevEnv() {
   if (const char* v = getenv("AFX_TEST_DTW_BUDGET")) dtw_budget = std::max<int64_t>(1, atoll(v));
   if (const char* v = getenv("AFX_TEST_HPSS_BUDGET")) hpss_budget = std::max<int64_t>(1, atoll(v));
   if (const char* v = getenv("AFX_TEST_CHROMA_BUDGET")) chroma_budget = std::max<int64_t>(1, atoll(v));
+  if (const char* v = getenv("AFX_TEST_RHYTHM_BUDGET")) rhythm_budget = std::max<int64_t>(1, atoll(v));
   f0_dump = getenv("AFX_F0_DUMP");
 }
 const DevEnv& dev_env() { static const DevEnv e; return e; }
@@ -254,7 +255,8 @@ extern "C" void afx_plan_destroy(afx_plan* pl) {
   release(pl->blocks_spec); release(pl->blockmax); release(pl->items); release(pl->n_items);
   for (DevBuf* b : {&pl->hp_clips, &pl->hp_y, &pl->hp_h, &pl->hp_p, &pl->hp_x, &pl->hp_yh, &pl->hp_yp, &pl->hp_bad, &pl->hp_stats, &pl->hp_spec,
                     &pl->ch_grid, &pl->ch_extra, &pl->ch_mel, &pl->ch_s, &pl->ch_mag, &pl->ch_bin, &pl->ch_slot, &pl->ch_hist, &pl->ch_chroma,
-                    &pl->ch_melout, &pl->ch_parts})
+                    &pl->ch_melout, &pl->ch_parts,
+                    &pl->rh_tab, &pl->rh_db, &pl->rh_max, &pl->rh_env, &pl->rh_parts, &pl->rh_tg, &pl->rh_acmean, &pl->rh_res})
     release(*b);
   if (pl->h_pin) (void)hipHostFree(pl->h_pin);
   if (pl->h_clips_pin) (void)hipHostFree(pl->h_clips_pin);

@@ -1,5 +1,5 @@
 // The plan-based feature entry points of libafx.so beside the MFCC / RMS pipeline (afx_api.cpp): pYIN f0, zero-crossing
-// rate, the spectral descriptors, preprocess_audio, harmonic-percussive separation and chroma / tuning / mel power.  Each reads: check -> begin ->
+// rate, the spectral descriptors, preprocess_audio, harmonic-percussive separation, chroma / tuning / mel power and onset strength / tempogram / tempo.  Each reads: check -> begin ->
 // stage -> its own work -> finish, on the front end of afx_plan.h.
 #include <algorithm>
 #include <cmath>
@@ -419,12 +419,11 @@ static void chroma_images(const float* w, int rows, const float* dense, int row0
       }
 }
 
-// the plan's tables, at first use: every tuning of estimate_tuning's grid, and the mel bank cut to the steps each group of
-// 16 filters touches
-static int chroma_setup(afx_plan* pl) {
-  if (pl->ch_grid.p) return AFX_OK;
+// the mel bank cut to the steps each group of 16 filters touches, at first use (afx_chroma_batch and afx_rhythm_batch)
+static int mel_images_setup(afx_plan* pl, const char* who) {
+  if (pl->ch_melrec.img) return AFX_OK;
   const int M = pl->p.n_mels;
-  if (pl->ht.mel_dense.size() != (size_t)M * kHpssBins) { set_error("afx_chroma_batch: the plan has no mel table"); return AFX_ERR_INVALID; }
+  if (pl->ht.mel_dense.size() != (size_t)M * kHpssBins) { set_error(std::string(who) + ": the plan has no mel table"); return AFX_ERR_INVALID; }
   int rc;
   ChromaMel mr{};
   mr.n_mels = M; mr.n_groups = (M + 15) / 16;
@@ -441,7 +440,15 @@ static int chroma_setup(afx_plan* pl) {
   if ((rc = ensure(pl->ch_mel, std::max<size_t>(mimg.size(), 1) * sizeof(float))) != AFX_OK) return rc;
   if (!mimg.empty()) HIP_TRY(hipMemcpy(pl->ch_mel.p, mimg.data(), mimg.size() * sizeof(float), hipMemcpyHostToDevice));
   mr.img = (const float*)pl->ch_mel.p;
-  pl->ch_melrec = mr;
+  pl->ch_melrec = mr;                                  // set last: its image pointer marks the bank as ready
+  return AFX_OK;
+}
+
+// the plan's tables, at first use: every tuning of estimate_tuning's grid, and the mel bank
+static int chroma_setup(afx_plan* pl) {
+  if (pl->ch_grid.p) return AFX_OK;
+  int rc;
+  if ((rc = mel_images_setup(pl, "afx_chroma_batch")) != AFX_OK) return rc;
   std::vector<float> w(12 * kHpssBins), img((size_t)kChromaGrid * kChromaImg);
   for (int k = 0; k < kChromaGrid; ++k) {
     if ((rc = afx_chroma_filters(pl->p.sr, (double)k * 0.01 + -0.5, w.data())) != AFX_OK) return rc;
@@ -636,6 +643,178 @@ extern "C" int afx_chroma_batch(afx_plan* pl, const void* samples, int sample_fm
       if (est && sh) std::copy(h_hist.begin() + (size_t)q * kChromaHist, h_hist.begin() + (size_t)(q + 1) * kChromaHist, out_hist + (size_t)kChromaHist * i);
       if (out_stats && !h_bad[q])
         for (int k = 0; k < 4; ++k) out_stats[4 * i + k] = h_stats[4 * (size_t)q + k];
+    }
+    c0 = c1;
+  }
+  return AFX_OK;
+}
+
+// ---- onset_strength / tempogram / tempo (04_feature_extraction_experiment/feature_extractor.py:592-622) -----------------
+// the plan's table, at first use: bpm and logprior (afx_tempo_table), then the periodic Hann window of win lags as float32
+static int rhythm_setup(afx_plan* pl) {
+  if (pl->rh_tabrec.window) return AFX_OK;
+  int32_t win = 0, kmin = 0;
+  int rc = afx_tempo_table(pl->p.sr, &win, &kmin, nullptr, nullptr);
+  if (rc != AFX_OK) { set_error("afx_rhythm_batch: the 8 s tempogram window must hold 2 .. 768 frames (128 <= sr <= 49215)"); return rc; }
+  if ((rc = mel_images_setup(pl, "afx_rhythm_batch")) != AFX_OK) return rc;
+  std::vector<double> tab((size_t)2 * win);            // bpm, logprior; the window as float32 behind them
+  if ((rc = afx_tempo_table(pl->p.sr, &win, &kmin, tab.data(), tab.data() + win)) != AFX_OK) return rc;
+  std::vector<float> hw(win);
+  for (int i = 0; i < win; ++i) hw[i] = (float)(0.5 - 0.5 * std::cos(2.0 * M_PI * (double)i / (double)win));
+  const size_t tab_bytes = tab.size() * sizeof(double);
+  if ((rc = ensure(pl->rh_tab, tab_bytes + hw.size() * sizeof(float))) != AFX_OK) return rc;
+  HIP_TRY(hipMemcpy(pl->rh_tab.p, tab.data(), tab_bytes, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy((char*)pl->rh_tab.p + tab_bytes, hw.data(), hw.size() * sizeof(float), hipMemcpyHostToDevice));
+  RhythmTab t{};
+  t.bpm = (const double*)pl->rh_tab.p; t.logprior = t.bpm + win; t.win = win;
+  t.window = (const float*)((const char*)pl->rh_tab.p + tab_bytes);
+  pl->rh_tabrec = t;                                   // set last: its window pointer marks the table as ready
+  return AFX_OK;
+}
+
+extern "C" int afx_rhythm_batch(afx_plan* pl, const void* samples, int sample_fmt, int mem_kind,
+                                const int64_t* offsets, const int64_t* lengths, int n_clips, int flags,
+                                float* out_env, const int64_t* env_off, float* out_tempogram, const int64_t* tg_off,
+                                double* out_acmean, double* out_tempo, int32_t* out_lag, double* out_stats,
+                                int32_t* out_status) {
+  const char* who = "afx_rhythm_batch";
+  if (n_clips > 0 && (!out_status || !out_tempo || !out_lag)) return null_arg(who);
+  int rc = check_batch_args(who, pl, samples, sample_fmt, mem_kind, offsets, lengths, n_clips, true);
+  if (rc != AFX_OK) return rc;
+  if (pl->p.n_fft != 2048 || pl->p.hop != 512 || pl->p.window != AFX_WINDOW_HANN || !pl->use_f3) {
+    set_error("afx_rhythm_batch: the plan must have frame_length 2048, hop_length 512 and the Hann window (librosa's defaults)");
+    return AFX_ERR_UNSUPPORTED;
+  }
+  if (pl->p.n_mels > 16 * kChromaMelGroups) { set_error("afx_rhythm_batch: at most 128 mel bands"); return AFX_ERR_UNSUPPORTED; }
+  if (flags & AFX_FLAG_TRIM) { set_error("afx_rhythm_batch: trim is not applied here; pass the preprocessed signal"); return AFX_ERR_UNSUPPORTED; }
+  if (flags & ~(AFX_FLAG_PREEMPH | AFX_FLAG_TRIM)) { set_error("afx_rhythm_batch: unknown flag"); return AFX_ERR_INVALID; }
+  int32_t win = 0;
+  if (afx_tempo_table(pl->p.sr, &win, nullptr, nullptr, nullptr) != AFX_OK) {
+    set_error("afx_rhythm_batch: the 8 s tempogram window must hold 2 .. 768 frames (128 <= sr <= 49215)");
+    return AFX_ERR_UNSUPPORTED;
+  }
+  if (n_clips > 0 && ((out_env && !env_off) || (out_tempogram && !tg_off))) {
+    set_error("afx_rhythm_batch: out_env needs env_off, out_tempogram needs tg_off");
+    return AFX_ERR_INVALID;
+  }
+  if ((rc = check_clip_ranges(who, offsets, lengths, out_env ? env_off : nullptr, n_clips, INT64_MAX / 4)) != AFX_OK) return rc;
+  if ((rc = check_clip_ranges(who, offsets, lengths, out_tempogram ? tg_off : nullptr, n_clips, INT64_MAX / 4)) != AFX_OK) return rc;
+  const int M = pl->p.n_mels;
+  const double nan = std::nan("");
+  for (int i = 0; i < n_clips; ++i) {
+    out_status[i] = lengths[i] == 0 ? AFX_CLIP_TOO_SHORT : AFX_CLIP_OK;
+    out_tempo[i] = nan; out_lag[i] = 0;
+    if (out_stats) out_stats[2 * i] = out_stats[2 * i + 1] = nan;
+    if (out_acmean) std::fill(out_acmean + (size_t)win * i, out_acmean + (size_t)win * (i + 1), 0.0);
+    if (lengths[i] == 0) {                              // one all-zero frame
+      if (out_env) out_env[env_off[i]] = 0.f;
+      if (out_tempogram) std::fill(out_tempogram + tg_off[i], out_tempogram + tg_off[i] + win, 0.f);
+    }
+  }
+  if (n_clips == 0) return AFX_OK;
+  if ((rc = begin_plan_call(who, pl)) != AFX_OK) return rc;
+  if ((rc = rhythm_setup(pl)) != AFX_OK) return rc;
+  hipStream_t s = pl->ctx->stream;
+  const RhythmTab tab = pl->rh_tabrec;
+  const bool want_tg = out_tempogram != nullptr;
+  const size_t esz = sample_fmt == AFX_FMT_S16 ? 2 : 4;
+  const int64_t budget = dev_env().rhythm_budget;
+  const HpssTabs tb{pl->f3.window, pl->f3.w1024, pl->f3.w2048};
+  std::vector<HpssClip> recs;
+  std::vector<int> idx;
+  std::vector<uint32_t> h_bad;
+  std::vector<double> h_res;
+  for (int c0 = 0; c0 < n_clips;) {
+    // one chunk: as many clips as the workspace budget holds (at least one); zero-length clips take no work
+    recs.clear(); idx.clear();
+    int64_t frames = 0, ysz = 0, bytes = 0, lo = INT64_MAX, hi = 0, max_len = 0;
+    int tiles = 0;
+    int c1 = c0;
+    for (; c1 < n_clips && (int)recs.size() < 32768; ++c1) {
+      const int64_t L = lengths[c1];
+      if (L == 0) continue;
+      const int64_t T = 1 + L / 512, nt = (T + kRhTile - 1) / kRhTile;
+      const int64_t pb = T * (kHpssPowPitch * 4 + kRhMels * 4 + 4 + (want_tg ? win * 4 : 0)) + nt * win * 8 + L * 4 +
+                         (mem_kind == AFX_MEM_HOST ? L * (int64_t)esz : 0) + win * 8 + 128;
+      if (!recs.empty() && (bytes + pb > budget || (int64_t)tiles + nt > INT32_MAX / 2)) break;
+      HpssClip r{};
+      r.in_off = offsets[c1]; r.y_off = ysz; r.len = L; r.frame_base = frames; r.T = (int32_t)T; r.tile_base = tiles;
+      recs.push_back(r); idx.push_back(c1);
+      frames += T; ysz += L; tiles += (int)nt; bytes += pb;
+      lo = std::min(lo, offsets[c1]); hi = std::max(hi, offsets[c1] + L); max_len = std::max(max_len, L);
+    }
+    const int n = (int)recs.size();
+    if (n == 0) { c0 = c1; continue; }
+    const void* d_in = samples;
+    if (mem_kind == AFX_MEM_HOST) {
+      if ((rc = ensure(pl->samples, (size_t)(hi - lo) * esz + 16)) != AFX_OK) return rc;
+      HIP_TRY(hipMemcpyAsync(pl->samples.p, (const char*)samples + (size_t)lo * esz, (size_t)(hi - lo) * esz, hipMemcpyHostToDevice, s));
+      for (HpssClip& r : recs) r.in_off -= lo;
+      d_in = pl->samples.p;
+    }
+    if ((rc = ensure(pl->hp_clips, n * sizeof(HpssClip))) != AFX_OK) return rc;
+    if ((rc = ensure(pl->hp_bad, n * sizeof(uint32_t))) != AFX_OK) return rc;
+    if ((rc = ensure(pl->hp_y, (size_t)ysz * sizeof(float) + 64)) != AFX_OK) return rc;
+    if ((rc = ensure(pl->ch_s, (size_t)frames * kHpssPowPitch * sizeof(float))) != AFX_OK) return rc;
+    if ((rc = ensure(pl->rh_db, (size_t)frames * kRhMels * sizeof(float))) != AFX_OK) return rc;
+    if ((rc = ensure(pl->rh_max, n * sizeof(uint32_t))) != AFX_OK) return rc;
+    if ((rc = ensure(pl->rh_env, (size_t)frames * sizeof(float))) != AFX_OK) return rc;
+    if ((rc = ensure(pl->rh_parts, (size_t)tiles * win * sizeof(double))) != AFX_OK) return rc;
+    if (want_tg && (rc = ensure(pl->rh_tg, (size_t)frames * win * sizeof(float))) != AFX_OK) return rc;
+    if ((rc = ensure(pl->rh_acmean, (size_t)n * win * sizeof(double))) != AFX_OK) return rc;
+    if ((rc = ensure(pl->rh_res, (size_t)n * 4 * sizeof(double))) != AFX_OK) return rc;
+    const HpssClip* d_clips = (const HpssClip*)pl->hp_clips.p;
+    uint32_t* d_bad = (uint32_t*)pl->hp_bad.p;
+    float* d_y = (float*)pl->hp_y.p;
+    float* d_S = (float*)pl->ch_s.p;
+    float* d_env = (float*)pl->rh_env.p;
+    float* d_tg = want_tg ? (float*)pl->rh_tg.p : nullptr;
+    HIP_TRY(hipMemcpyAsync(pl->hp_clips.p, recs.data(), n * sizeof(HpssClip), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemsetAsync(d_bad, 0, n * sizeof(uint32_t), s));
+    HIP_TRY(hipMemsetAsync(pl->rh_max.p, 0, n * sizeof(uint32_t), s));
+    HIP_TRY(launch_hpss_prep(s, d_in, sample_fmt, flags & AFX_FLAG_PREEMPH, pl->kp.preemph_b1, d_clips, n, max_len, d_y, d_bad));
+    HIP_TRY(launch_hpss_stft_power(s, d_y, d_clips, d_bad, n, frames, tb, d_S));
+    HIP_TRY(launch_rhythm_mel(s, d_S, d_clips, n, tiles, pl->ch_melrec, (float*)pl->rh_db.p, (uint32_t*)pl->rh_max.p));
+    HIP_TRY(launch_rhythm_env(s, (const float*)pl->rh_db.p, (const uint32_t*)pl->rh_max.p, d_clips, n, frames, M, d_env));
+    HIP_TRY(launch_rhythm_tempogram(s, d_env, d_clips, n, tiles, tab, (double*)pl->rh_parts.p, d_tg));
+    HIP_TRY(launch_rhythm_reduce(s, d_env, d_clips, n, tab, (const double*)pl->rh_parts.p, (double*)pl->rh_acmean.p,
+                                 (double*)pl->rh_res.p));
+    h_res.resize((size_t)n * 4);
+    HIP_TRY(hipMemcpyAsync(h_res.data(), pl->rh_res.p, (size_t)n * 4 * sizeof(double), hipMemcpyDeviceToHost, s));
+    // the per-frame outputs: one copy when the caller's layout is the chunk's (packed clips in order), else one per clip
+    for (int which = 0; which < 2; ++which) {
+      float* dst = which ? out_tempogram : out_env;
+      const int64_t* off = which ? tg_off : env_off;
+      const float* src = which ? d_tg : d_env;
+      const int64_t rows = which ? win : 1;
+      if (!dst) continue;
+      bool packed = true;
+      for (int q = 0; q < n && packed; ++q) packed = off[idx[q]] - off[idx[0]] == rows * recs[q].frame_base;
+      if (packed) {
+        HIP_TRY(hipMemcpyAsync(dst + off[idx[0]], src, (size_t)(rows * frames) * sizeof(float), hipMemcpyDeviceToHost, s));
+      } else {
+        for (int q = 0; q < n; ++q)
+          HIP_TRY(hipMemcpyAsync(dst + off[idx[q]], src + rows * recs[q].frame_base, (size_t)(rows * recs[q].T) * sizeof(float), hipMemcpyDeviceToHost, s));
+      }
+    }
+    if (out_acmean) {
+      bool dense = idx[n - 1] - idx[0] == n - 1;        // no zero-length clip inside the chunk: the rows are the caller's
+      if (dense) {
+        HIP_TRY(hipMemcpyAsync(out_acmean + (size_t)win * idx[0], pl->rh_acmean.p, (size_t)n * win * sizeof(double), hipMemcpyDeviceToHost, s));
+      } else {
+        for (int q = 0; q < n; ++q)
+          HIP_TRY(hipMemcpyAsync(out_acmean + (size_t)win * idx[q], (const double*)pl->rh_acmean.p + (size_t)win * q, (size_t)win * sizeof(double), hipMemcpyDeviceToHost, s));
+      }
+    }
+    h_bad.resize(n);
+    HIP_TRY(hipMemcpyAsync(h_bad.data(), d_bad, n * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    for (int q = 0; q < n; ++q) {
+      const int i = idx[q];
+      out_status[i] = h_bad[q] ? AFX_CLIP_NONFINITE : AFX_CLIP_OK;
+      if (h_bad[q]) continue;                            // its rows are zero: so are the envelope, the tempogram and acmean
+      out_tempo[i] = h_res[4 * (size_t)q]; out_lag[i] = (int32_t)h_res[4 * (size_t)q + 3];
+      if (out_stats) { out_stats[2 * i] = h_res[4 * (size_t)q + 1]; out_stats[2 * i + 1] = h_res[4 * (size_t)q + 2]; }
     }
     c0 = c1;
   }

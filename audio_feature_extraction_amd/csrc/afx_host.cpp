@@ -1,5 +1,5 @@
 // Host-only part of libafx.so: the error string, the version, and the builders that need no device -- the clip records of
-// a batch (what prepare_descriptors uploads), the pYIN tables, the pYIN kernel dispatch (afx_f0_dispatch) and the chroma filterbank (afx_chroma_filters).  Together with afx_tables.cpp, afx_f0_tables.cpp and
+// a batch (what prepare_descriptors uploads), the pYIN tables, the pYIN kernel dispatch (afx_f0_dispatch) and the chroma filterbank (afx_chroma_filters) and the tempo table (afx_tempo_table).  Together with afx_tables.cpp, afx_f0_tables.cpp and
 // afx_wav.cpp this is everything that parses caller- or file-supplied data on the host; `make asan` builds exactly these
 // files (plus afx_host_stubs.cpp) with g++ -fsanitize=address,undefined as libafx_host_asan.so.
 #include <algorithm>
@@ -174,5 +174,29 @@ extern "C" int afx_chroma_filters(int sr, double tuning, float* out) {
     const double norm = std::max(std::sqrt(ss), DBL_MIN), o = (q[j] / 12.0 - 5.0) / 2.0, oct = std::exp(-0.5 * (o * o));
     for (int c = 0; c < 12; ++c) out[c * NB + j] = (float)(w[(c + 3) % 12] / norm * oct);     // roll(-3): row c is pitch class c + 3
   }
+  return AFX_OK;
+}
+
+// librosa.feature.tempo's table for librosa.beat.beat_track's call (hop 512, ac_size 8, start_bpm 120, std_bpm 1,
+// max_tempo 320): win = int(8 sr) // 512 lags, bpm = tempo_frequencies, the log-normal prior with every lag faster than
+// max_tempo removed (tests/rhythm_ref.py tempo_table is the spec).  float64 in the order numpy evaluates it.
+extern "C" int afx_tempo_table(int sr, int32_t* out_win, int32_t* out_kmin, double* out_bpm, double* out_logprior) {
+  if (sr <= 0) { set_error("afx_tempo_table: sr must be positive"); return AFX_ERR_INVALID; }
+  const int64_t win = ((int64_t)8 * sr) / 512;
+  if (win < 2 || win > 768) {
+    set_error("afx_tempo_table: the 8 s tempogram window must hold 2 .. 768 frames of hop 512 (128 <= sr <= 49215)");
+    return AFX_ERR_UNSUPPORTED;
+  }
+  int kmin = 0;
+  for (int k = 0; k < (int)win; ++k) {
+    const double bpm = k == 0 ? INFINITY : (60.0 * (double)sr) / (512.0 * (double)k);
+    if (kmin == 0 && bpm < 320.0) kmin = k;              // the first lag slower than max_tempo (0 when there is none)
+    const double d = std::log2(bpm) - std::log2(120.0);
+    if (out_bpm) out_bpm[k] = bpm;
+    if (out_logprior) out_logprior[k] = -0.5 * (d * d);
+  }
+  if (out_logprior) for (int k = 0; k < kmin; ++k) out_logprior[k] = -INFINITY;
+  if (out_win) *out_win = (int32_t)win;
+  if (out_kmin) *out_kmin = kmin;
   return AFX_OK;
 }

@@ -53,6 +53,10 @@ int afx_chroma_batch(afx_plan*, const void*, int, int, const int64_t*, const int
                      const int64_t*, float*, const int64_t*, double*, double*, int32_t*, int32_t*) {
   return no_device("afx_chroma_batch");
 }
+int afx_rhythm_batch(afx_plan*, const void*, int, int, const int64_t*, const int64_t*, int, int, float*, const int64_t*, float*,
+                     const int64_t*, double*, double*, int32_t*, double*, int32_t*) {
+  return no_device("afx_rhythm_batch");
+}
 int afx_resample_batch(afx_ctx*, const void*, int, int, const int64_t*, const int64_t*, int, int, int, const double*, int, float*,
                        int, const int64_t*, int64_t*) {
   return no_device("afx_resample_batch");

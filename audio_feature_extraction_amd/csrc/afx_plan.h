@@ -17,6 +17,7 @@
 #include "afx_frames3.h"
 #include "afx_internal.h"
 #include "afx_resample.h"
+#include "afx_rhythm.h"
 
 namespace afx {
 
@@ -75,6 +76,10 @@ struct afx_plan {
   // (built at first use), a chunk's off-grid filterbanks, the power rows, the peak records and the results
   DevBuf ch_grid, ch_extra, ch_mel, ch_s, ch_mag, ch_bin, ch_slot, ch_hist, ch_chroma, ch_melout, ch_parts;
   ChromaMel ch_melrec{};
+  // afx_rhythm_batch (with hp_clips, hp_y, hp_bad, ch_s, ch_mel): the window / bpm / logprior table (built at first use),
+  // the dB rows, the clip maxima, the envelope, the per-tile lag sums, the tempogram (when asked for) and the results
+  DevBuf rh_tab, rh_db, rh_max, rh_env, rh_parts, rh_tg, rh_acmean, rh_res;
+  RhythmTab rh_tabrec{};
   // cached per-batch descriptors
   std::vector<int64_t> c_off, c_len;
   std::vector<ClipDesc> h_clips;

@@ -328,6 +328,41 @@ int afx_chroma_batch(afx_plan* plan, const void* samples, int sample_fmt, int me
                      double* out_tuning, double* out_stats, int32_t* out_hist, int32_t* out_status);
 int afx_chroma_filters(int sr, double tuning, float* out /*[12 * 1025]*/);
 
+/* The rhythm group of 04_feature_extraction_experiment/feature_extractor.py:592-622: librosa.onset.onset_strength, the
+ * tempogram librosa.beat.beat_track asks librosa.feature.tempo for (win = int(8 sr) // 512 lags) and tempo's decision, at
+ * librosa 0.11's defaults (mel power of n_fft 2048 / hop 512, power_to_db with ref 1 and top_db 80, lag 1, the mean over
+ * the bands, centred; Hann autocorrelation window, linear_ramp padding, norm inf; start_bpm 120, std_bpm 1, max_tempo 320,
+ * mean aggregate), as tests/rhythm_ref.py restates them.  Beat positions are not computed.  Both symbols are newer than
+ * AFX_VERSION 107 says: a binding detects them by their presence.  The plan must be n_fft 2048 / hop 512 with
+ * AFX_WINDOW_HANN, at most 128 mel bands and 128 <= sr <= 49215 (2 <= win <= 768) -- AFX_ERR_UNSUPPORTED otherwise; sr and the
+ * mel bank are the plan's.  With T_i = 1 + lengths[i] / 512:
+ *   flags          AFX_FLAG_PREEMPH or 0 (AFX_FLAG_TRIM is unsupported)
+ *   out_env, env_off         NULL or host float: clip i's onset envelope, T_i values at out_env[env_off[i] ..]; its first
+ *                  three are 0, so a clip of T_i <= 3 has an all-zero envelope
+ *   out_tempogram, tg_off    NULL or host float (no performance requirement): win x T_i, row-major, at
+ *                  out_tempogram[tg_off[i] ..]; every frame divided by its largest magnitude (a frame below FLT_MIN is left)
+ *   out_acmean     NULL or host double[win * n_clips]: the mean of the tempogram over the frames
+ *   out_tempo, out_lag       host double / int32 [n_clips]: lag = the first maximum of log1p(1e6 acmean) + logprior,
+ *                  tempo = bpm[lag] (afx_tempo_table); lag 0 and tempo 0.0 when the envelope is all zero
+ *   out_stats      NULL or host double[2 n_clips]: mean and std (ddof 0) of the envelope
+ *   out_status     AFX_CLIP_TOO_SHORT for length 0 (one zero frame), AFX_CLIP_NONFINITE for a NaN / inf sample; a failed
+ *                  clip's envelope, tempogram and acmean are zero, its lag 0, its tempo and statistics NaN, and it never
+ *                  affects the other clips
+ * No float atomics: results are bit-reproducible and independent of what else is in the batch.  The batch runs in chunks
+ * whose device workspace stays within 2 GiB; a clip larger than that runs alone.
+ *
+ * afx_tempo_table (host-only): win, kmin (the first lag slower than 320 bpm), bpm[win] (bpm[0] = inf) and logprior[win]
+ * (-inf below kmin) for a sample rate at hop 512; any pointer may be NULL.  AFX_ERR_UNSUPPORTED when win is not in 2 .. 768. */
+int afx_tempo_table(int sr, int32_t* out_win, int32_t* out_kmin, double* out_bpm, double* out_logprior);
+int afx_rhythm_batch(afx_plan* plan, const void* samples, int sample_fmt, int mem_kind,
+                     const int64_t* offsets, const int64_t* lengths, int n_clips, int flags,
+                     float* out_env, const int64_t* env_off,
+                     float* out_tempogram, const int64_t* tg_off,
+                     double* out_acmean,
+                     double* out_tempo, int32_t* out_lag,
+                     double* out_stats,
+                     int32_t* out_status);
+
 /* Host-only (no device needed): the tables afx_f0_batch uploads, for inspection and tests.
  * info[8] = min_period, max_period, n_pitch_bins, band (transition half-width), candidate
  * capacity, lags kept, lags per lane, trough slots per lane.  beta[100] = Beta(2,18) mass of
