@@ -45,6 +45,7 @@ SYMBOLS = (
     "afx_wav_probe", "afx_wav_read_s16", "afx_batch_geometry", "afx_dtw_batch", "afx_hpss_batch",
     "afx_resample_design", "afx_resample_batch", "afx_rfft_host", "afx_wav_read_raw", "afx_decode_batch",
     "afx_chroma_batch", "afx_chroma_filters", "afx_rhythm_batch", "afx_tempo_table",
+    "afx_stft_chunks",
 )
 
 
@@ -127,6 +128,8 @@ def lib() -> C.CDLL:
         if hasattr(L, "afx_rhythm_batch"):                   # newer than version 107 says: found by their presence
             L.afx_rhythm_batch.argtypes = [vp, vp, i32, i32, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
             L.afx_tempo_table.argtypes = [i32, i32p, i32p, vp, vp]
+        if hasattr(L, "afx_stft_chunks"):                    # newer than version 107 says: found by its presence
+            L.afx_stft_chunks.argtypes = [vp, i32, vp, C.c_int64, vp]
         if hasattr(L, "afx_rfft_host"):                      # absent from a library built before the mixed-radix lengths
             L.afx_rfft_host.argtypes = [i32, vp, vp]
         _lib = L
@@ -279,6 +282,22 @@ def tempo_table(sr: int) -> dict:
     bpm, logprior = np.zeros(win.value, np.float64), np.zeros(win.value, np.float64)
     _check(lib().afx_tempo_table(int(sr), C.byref(win), C.byref(kmin), bpm.ctypes.data, logprior.ctypes.data), "afx_tempo_table")
     return {"win": int(win.value), "kmin": int(kmin.value), "bpm": bpm, "logprior": logprior}
+
+
+def stft_chunks(lengths, cost, budget: int) -> np.ndarray:
+    """Host-only: the chunk each clip falls into when afx_hpss_batch / afx_chroma_batch / afx_rhythm_batch cut a batch at
+    ``budget`` bytes (-1 for a clip of length 0).  ``cost``: bytes per frame, per tile, per sample and per clip, frames per
+    tile, most tiles of a chunk."""
+    if not hasattr(lib(), "afx_stft_chunks"):
+        raise NotImplementedError("this libafx has no afx_stft_chunks")
+    lengths = np.ascontiguousarray(lengths, np.int64)
+    cost = np.ascontiguousarray(cost, np.int64)
+    if lengths.ndim != 1 or cost.shape != (6,):
+        raise ValueError("lengths must be one-dimensional and cost hold 6 values")
+    out = np.zeros(lengths.shape[0], np.int32)
+    _check(lib().afx_stft_chunks(lengths.ctypes.data, int(lengths.shape[0]), cost.ctypes.data, int(budget), out.ctypes.data),
+           "afx_stft_chunks")
+    return out
 
 
 def resample_lengths(lengths, sr_in: int, sr_out: int) -> np.ndarray:

@@ -1,6 +1,8 @@
 // The plan-based feature entry points of libafx.so beside the MFCC / RMS pipeline (afx_api.cpp): pYIN f0, zero-crossing
-// rate, the spectral descriptors, preprocess_audio, harmonic-percussive separation, chroma / tuning / mel power and onset strength / tempogram / tempo.  Each reads: check -> begin ->
-// stage -> its own work -> finish, on the front end of afx_plan.h.
+// rate, the spectral descriptors, preprocess_audio, and the three STFT-based groups -- harmonic-percussive separation,
+// chroma / tuning / mel power, onset strength / tempogram / tempo -- which run in chunks on one front end of their own
+// (check_stft_plan .. end_stft_chunk below).  Each reads: check -> begin -> stage -> its own work -> finish, on the front end
+// of afx_plan.h.
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -262,6 +264,77 @@ extern "C" int afx_preprocess(afx_plan* pl, const float* y, int64_t n, float* ou
   return AFX_OK;
 }
 
+// ---- the chunked front end of the STFT-based groups: afx_hpss_batch, afx_chroma_batch, afx_rhythm_batch ----
+// what the three refuse of a plan and of flags; called before begin_plan_call, so that a refusal touches no device
+static int check_stft_plan(const char* who, const afx_plan* pl, int flags, int allowed, bool need_mel) {
+  const std::string w(who);
+  if (pl->p.n_fft != 2048 || pl->p.hop != 512 || pl->p.window != AFX_WINDOW_HANN || !pl->use_f3) {
+    set_error(w + ": the plan must have frame_length 2048, hop_length 512 and the Hann window (librosa's defaults)");
+    return AFX_ERR_UNSUPPORTED;
+  }
+  if (need_mel && pl->p.n_mels > 16 * kChromaMelGroups) { set_error(w + ": at most 128 mel bands"); return AFX_ERR_UNSUPPORTED; }
+  if (flags & AFX_FLAG_TRIM) { set_error(w + ": trim is not applied here; pass the preprocessed signal"); return AFX_ERR_UNSUPPORTED; }
+  if (flags & ~allowed) { set_error(w + ": unknown flag"); return AFX_ERR_INVALID; }
+  return AFX_OK;
+}
+
+// bytes per sample a chunk's copy of host input takes in pl->samples (device input is read where it lies)
+static int64_t upload_sample_bytes(int sample_fmt, int mem_kind) {
+  return mem_kind != AFX_MEM_HOST ? 0 : sample_fmt == AFX_FMT_S16 ? 2 : 4;
+}
+
+// A cut chunk on the device: [lo, hi) of a host batch in pl->samples with in_off rebased to it, the records in hp_clips,
+// hp_bad cleared and k_hpss_prep's float32 signal in hp_y
+static int stage_stft_chunk(afx_plan* pl, const void* samples, int sample_fmt, int mem_kind, int flags, StftChunk& ck) {
+  hipStream_t s = pl->ctx->stream;
+  const int n = (int)ck.recs.size();
+  int rc;
+  const void* d_in = samples;
+  if (mem_kind == AFX_MEM_HOST) {
+    const size_t esz = (size_t)upload_sample_bytes(sample_fmt, mem_kind);
+    if ((rc = ensure(pl->samples, (size_t)(ck.hi - ck.lo) * esz + 16)) != AFX_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(pl->samples.p, (const char*)samples + (size_t)ck.lo * esz, (size_t)(ck.hi - ck.lo) * esz, hipMemcpyHostToDevice, s));
+    for (HpssClip& r : ck.recs) r.in_off -= ck.lo;
+    d_in = pl->samples.p;
+  }
+  if ((rc = ensure(pl->hp_clips, n * sizeof(HpssClip))) != AFX_OK) return rc;
+  if ((rc = ensure(pl->hp_bad, n * sizeof(uint32_t))) != AFX_OK) return rc;
+  if ((rc = ensure(pl->hp_y, (size_t)ck.samples * sizeof(float) + 64)) != AFX_OK) return rc;
+  HIP_TRY(hipMemcpyAsync(pl->hp_clips.p, ck.recs.data(), n * sizeof(HpssClip), hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemsetAsync(pl->hp_bad.p, 0, n * sizeof(uint32_t), s));
+  HIP_TRY(launch_hpss_prep(s, d_in, sample_fmt, flags & AFX_FLAG_PREEMPH, pl->kp.preemph_b1, (const HpssClip*)pl->hp_clips.p, n,
+                           ck.max_len, (float*)pl->hp_y.p, (uint32_t*)pl->hp_bad.p));
+  return AFX_OK;
+}
+
+// Rows of a chunk to the caller's dst + off[clip]: `per` floats for every frame (by_frames) or every sample of a clip, as
+// they lie in src.  One copy when the caller's layout is the chunk's (packed clips in order), else one per clip.
+static int copy_rows_out(hipStream_t s, const StftChunk& ck, float* dst, const int64_t* off, const float* src, int64_t per,
+                         bool by_frames) {
+  const int n = (int)ck.recs.size();
+  auto base = [&](int q) { return per * (by_frames ? ck.recs[q].frame_base : ck.recs[q].y_off); };
+  bool packed = true;
+  for (int q = 0; q < n && packed; ++q) packed = off[ck.idx[q]] - off[ck.idx[0]] == base(q);
+  if (packed) {
+    HIP_TRY(hipMemcpyAsync(dst + off[ck.idx[0]], src, (size_t)(per * (by_frames ? ck.frames : ck.samples)) * sizeof(float), hipMemcpyDeviceToHost, s));
+    return AFX_OK;
+  }
+  for (int q = 0; q < n; ++q) {
+    const int64_t count = per * (by_frames ? (int64_t)ck.recs[q].T : ck.recs[q].len);
+    HIP_TRY(hipMemcpyAsync(dst + off[ck.idx[q]], src + base(q), (size_t)count * sizeof(float), hipMemcpyDeviceToHost, s));
+  }
+  return AFX_OK;
+}
+
+// the end of a chunk: hp_bad of its n clips on the host, the stream drained (every copy of the chunk has landed)
+static int end_stft_chunk(afx_plan* pl, int n, std::vector<uint32_t>& h_bad) {
+  hipStream_t s = pl->ctx->stream;
+  h_bad.resize(n);
+  HIP_TRY(hipMemcpyAsync(h_bad.data(), pl->hp_bad.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  return AFX_OK;
+}
+
 // ---- harmonic-percussive separation (librosa.effects.hpss / harmonic) and the harmonic features -----------------------
 extern "C" int afx_hpss_batch(afx_plan* pl, const void* samples, int sample_fmt, int mem_kind,
                               const int64_t* offsets, const int64_t* lengths, int n_clips, int flags,
@@ -271,12 +344,7 @@ extern "C" int afx_hpss_batch(afx_plan* pl, const void* samples, int sample_fmt,
   if (n_clips > 0 && !out_status) return null_arg("afx_hpss_batch");
   int rc = check_batch_args("afx_hpss_batch", pl, samples, sample_fmt, mem_kind, offsets, lengths, n_clips, true);
   if (rc != AFX_OK) return rc;
-  if (pl->p.n_fft != 2048 || pl->p.hop != 512 || pl->p.window != AFX_WINDOW_HANN || !pl->use_f3) {
-    set_error("afx_hpss_batch: the plan must have frame_length 2048, hop_length 512 and the Hann window (librosa's defaults)");
-    return AFX_ERR_UNSUPPORTED;
-  }
-  if (flags & AFX_FLAG_TRIM) { set_error("afx_hpss_batch: trim is not applied here; pass the preprocessed signal"); return AFX_ERR_UNSUPPORTED; }
-  if (flags & ~(AFX_FLAG_PREEMPH | AFX_FLAG_TRIM | AFX_HPSS_STORE_SPEC)) { set_error("afx_hpss_batch: unknown flag"); return AFX_ERR_INVALID; }
+  if ((rc = check_stft_plan("afx_hpss_batch", pl, flags, AFX_FLAG_PREEMPH | AFX_HPSS_STORE_SPEC, false)) != AFX_OK) return rc;
   if (sd && n_clips > 0 && (!out_spec || !spec_off)) { set_error("afx_hpss_batch: AFX_HPSS_STORE_SPEC needs out_spec and spec_off"); return AFX_ERR_INVALID; }
   if ((rc = check_clip_ranges("afx_hpss_batch", offsets, lengths, sd ? spec_off : nullptr, n_clips, INT64_MAX / 4)) != AFX_OK) return rc;
   const double nan = std::nan("");
@@ -297,47 +365,23 @@ extern "C" int afx_hpss_batch(afx_plan* pl, const void* samples, int sample_fmt,
   hipStream_t s = pl->ctx->stream;
   const bool want_p = out_perc != nullptr;
   const int nsig = want_p ? 3 : 2;                  // y, h (, p) and X, Yh (, Yp)
-  const size_t esz = sample_fmt == AFX_FMT_S16 ? 2 : 4;
-  const int64_t budget = dev_env().hpss_budget;
+  StftCost cost{};
+  cost.per_frame = kHpssPitch * 8 * nsig + kSpecFloats * 4 + (sd ? 3 * kHpssBins * 4 : 0);
+  cost.per_sample = 4 * nsig + upload_sample_bytes(sample_fmt, mem_kind);
+  cost.per_clip = 128;
+  cost.tile = kHpssTile; cost.tile_cap = 65535; cost.spec_floats = sd ? 3 * kHpssBins : 0;
   const HpssTabs tb{pl->f3.window, pl->f3.w1024, pl->f3.w2048};
-  std::vector<HpssClip> recs;
-  std::vector<int> idx;
+  StftChunk ck;
   std::vector<int64_t> h_off, h_len, d_off;
   std::vector<uint32_t> h_bad;
   std::vector<double> h_stats;
-  for (int c0 = 0; c0 < n_clips;) {
-    // one chunk: as many clips as the workspace budget holds (at least one); zero-length clips take no work
-    recs.clear(); idx.clear();
-    int64_t frames = 0, ysz = 0, specf = 0, bytes = 0, lo = INT64_MAX, hi = 0, max_len = 0;
-    int tiles = 0;
-    int c1 = c0;
-    for (; c1 < n_clips && (int)recs.size() < 32768; ++c1) {
-      const int64_t L = lengths[c1];
-      if (L == 0) continue;
-      const int64_t T = 1 + L / 512, nt = (T + kHpssTile - 1) / kHpssTile;
-      const int64_t pb = T * kHpssPitch * 8 * nsig + L * 4 * nsig + (mem_kind == AFX_MEM_HOST ? L * (int64_t)esz : 0) +
-                         T * kSpecFloats * 4 + (sd ? 3 * kHpssBins * T * 4 : 0) + 128;
-      if (!recs.empty() && (bytes + pb > budget || tiles + nt > 65535)) break;
-      HpssClip r{};
-      r.in_off = offsets[c1]; r.y_off = ysz; r.len = L; r.frame_base = frames; r.spec_off = specf;
-      r.T = (int32_t)T; r.tile_base = tiles;
-      recs.push_back(r); idx.push_back(c1);
-      frames += T; ysz += L; specf += sd ? 3 * kHpssBins * T : 0; tiles += (int)nt; bytes += pb;
-      lo = std::min(lo, offsets[c1]); hi = std::max(hi, offsets[c1] + L); max_len = std::max(max_len, L);
-    }
-    const int n = (int)recs.size();
-    if (n == 0) { c0 = c1; continue; }
-    const void* d_in = samples;
-    if (mem_kind == AFX_MEM_HOST) {
-      if ((rc = ensure(pl->samples, (size_t)(hi - lo) * esz + 16)) != AFX_OK) return rc;
-      HIP_TRY(hipMemcpyAsync(pl->samples.p, (const char*)samples + (size_t)lo * esz, (size_t)(hi - lo) * esz, hipMemcpyHostToDevice, s));
-      for (HpssClip& r : recs) r.in_off -= lo;
-      d_in = pl->samples.p;
-    }
-    const size_t spec_bytes = (size_t)frames * kHpssPitch * sizeof(float2), sig_bytes = (size_t)ysz * sizeof(float) + 64;
-    if ((rc = ensure(pl->hp_clips, n * sizeof(HpssClip))) != AFX_OK) return rc;
-    if ((rc = ensure(pl->hp_bad, n * sizeof(uint32_t))) != AFX_OK) return rc;
-    if ((rc = ensure(pl->hp_y, sig_bytes)) != AFX_OK) return rc;
+  for (int c0 = 0; c0 < n_clips; c0 = ck.next) {
+    cut_stft_chunk(offsets, lengths, n_clips, c0, dev_env().hpss_budget, cost, ck);
+    const int n = (int)ck.recs.size(), tiles = ck.tiles;
+    const int64_t frames = ck.frames, max_len = ck.max_len;
+    const std::vector<HpssClip>& recs = ck.recs;
+    if (n == 0) continue;
+    const size_t spec_bytes = (size_t)frames * kHpssPitch * sizeof(float2), sig_bytes = (size_t)ck.samples * sizeof(float) + 64;
     if ((rc = ensure(pl->hp_h, sig_bytes)) != AFX_OK) return rc;
     if ((rc = ensure(pl->hp_x, spec_bytes)) != AFX_OK) return rc;
     if ((rc = ensure(pl->hp_yh, spec_bytes)) != AFX_OK) return rc;
@@ -345,17 +389,15 @@ extern "C" int afx_hpss_batch(afx_plan* pl, const void* samples, int sample_fmt,
       if ((rc = ensure(pl->hp_p, sig_bytes)) != AFX_OK) return rc;
       if ((rc = ensure(pl->hp_yp, spec_bytes)) != AFX_OK) return rc;
     }
-    if (sd && (rc = ensure(pl->hp_spec, (size_t)specf * sizeof(float))) != AFX_OK) return rc;
+    if (sd && (rc = ensure(pl->hp_spec, (size_t)ck.spec_floats * sizeof(float))) != AFX_OK) return rc;
     if (out_stats && (rc = ensure(pl->hp_stats, (size_t)n * 4 * sizeof(double))) != AFX_OK) return rc;
+    if ((rc = stage_stft_chunk(pl, samples, sample_fmt, mem_kind, flags, ck)) != AFX_OK) return rc;
     const HpssClip* d_clips = (const HpssClip*)pl->hp_clips.p;
-    uint32_t* d_bad = (uint32_t*)pl->hp_bad.p;
-    float* d_y = (float*)pl->hp_y.p;
+    const uint32_t* d_bad = (const uint32_t*)pl->hp_bad.p;
+    const float* d_y = (const float*)pl->hp_y.p;
     float* d_h = (float*)pl->hp_h.p;
     float* d_p = want_p ? (float*)pl->hp_p.p : nullptr;
     float2* d_yp = want_p ? (float2*)pl->hp_yp.p : nullptr;
-    HIP_TRY(hipMemcpyAsync(pl->hp_clips.p, recs.data(), n * sizeof(HpssClip), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemsetAsync(d_bad, 0, n * sizeof(uint32_t), s));
-    HIP_TRY(launch_hpss_prep(s, d_in, sample_fmt, flags, pl->kp.preemph_b1, d_clips, n, max_len, d_y, d_bad));
     HIP_TRY(launch_hpss_stft(s, d_y, d_clips, d_bad, n, frames, tb, (float2*)pl->hp_x.p));
     HIP_TRY(launch_hpss_mask(s, (const float2*)pl->hp_x.p, d_clips, n, tiles, (float2*)pl->hp_yh.p, d_yp,
                              sd ? (float*)pl->hp_spec.p : nullptr));
@@ -374,36 +416,18 @@ extern "C" int afx_hpss_batch(afx_plan* pl, const void* samples, int sample_fmt,
       h_stats.resize((size_t)n * 4);
       HIP_TRY(hipMemcpyAsync(h_stats.data(), pl->hp_stats.p, (size_t)n * 4 * sizeof(double), hipMemcpyDeviceToHost, s));
     }
-    // the signals: one copy when the caller's layout is the chunk's (packed clips in order), else one per clip
-    bool packed = true;
-    for (int q = 0; q < n && packed; ++q) packed = offsets[idx[q]] - offsets[idx[0]] == recs[q].y_off;
-    for (int which = 0; which < 2; ++which) {
-      float* dst = which ? out_perc : out_harm;
-      const float* src = which ? d_p : d_h;
-      if (!dst) continue;
-      if (packed) {
-        HIP_TRY(hipMemcpyAsync(dst + offsets[idx[0]], src, (size_t)ysz * sizeof(float), hipMemcpyDeviceToHost, s));
-      } else {
-        for (int q = 0; q < n; ++q)
-          HIP_TRY(hipMemcpyAsync(dst + offsets[idx[q]], src + recs[q].y_off, (size_t)recs[q].len * sizeof(float), hipMemcpyDeviceToHost, s));
-      }
-    }
-    if (sd)
-      for (int q = 0; q < n; ++q)
-        HIP_TRY(hipMemcpyAsync(out_spec + spec_off[idx[q]], (const float*)pl->hp_spec.p + recs[q].spec_off,
-                               (size_t)3 * kHpssBins * recs[q].T * sizeof(float), hipMemcpyDeviceToHost, s));
-    h_bad.resize(n);
-    HIP_TRY(hipMemcpyAsync(h_bad.data(), d_bad, n * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
+    if (out_harm && (rc = copy_rows_out(s, ck, out_harm, offsets, d_h, 1, false)) != AFX_OK) return rc;
+    if (out_perc && (rc = copy_rows_out(s, ck, out_perc, offsets, d_p, 1, false)) != AFX_OK) return rc;
+    if (sd && (rc = copy_rows_out(s, ck, out_spec, spec_off, (const float*)pl->hp_spec.p, 3 * kHpssBins, true)) != AFX_OK) return rc;
+    if ((rc = end_stft_chunk(pl, n, h_bad)) != AFX_OK) return rc;
     for (int q = 0; q < n; ++q) {
-      const int i = idx[q];
+      const int i = ck.idx[q];
       out_status[i] = h_bad[q] ? AFX_CLIP_NONFINITE : AFX_CLIP_OK;
       if (out_stats && !h_bad[q]) {
         for (int k = 0; k < 4; ++k) out_stats[4 * i + k] = h_stats[4 * (size_t)q + k];
         if (recs[q].len < 2) out_stats[4 * i + 2] = out_stats[4 * i + 3] = nan;   // k_frames3s skips clips of one sample
       }
     }
-    c0 = c1;
   }
   return AFX_OK;
 }
@@ -472,13 +496,7 @@ extern "C" int afx_chroma_batch(afx_plan* pl, const void* samples, int sample_fm
   if (n_clips > 0 && !out_status) return null_arg(who);
   int rc = check_batch_args(who, pl, samples, sample_fmt, mem_kind, offsets, lengths, n_clips, true);
   if (rc != AFX_OK) return rc;
-  if (pl->p.n_fft != 2048 || pl->p.hop != 512 || pl->p.window != AFX_WINDOW_HANN || !pl->use_f3) {
-    set_error("afx_chroma_batch: the plan must have frame_length 2048, hop_length 512 and the Hann window (librosa's defaults)");
-    return AFX_ERR_UNSUPPORTED;
-  }
-  if (pl->p.n_mels > 16 * kChromaMelGroups) { set_error("afx_chroma_batch: at most 128 mel bands"); return AFX_ERR_UNSUPPORTED; }
-  if (flags & AFX_FLAG_TRIM) { set_error("afx_chroma_batch: trim is not applied here; pass the preprocessed signal"); return AFX_ERR_UNSUPPORTED; }
-  if (flags & ~(AFX_FLAG_PREEMPH | AFX_FLAG_TRIM | AFX_CHROMA_STORE_HIST)) { set_error("afx_chroma_batch: unknown flag"); return AFX_ERR_INVALID; }
+  if ((rc = check_stft_plan(who, pl, flags, AFX_FLAG_PREEMPH | AFX_CHROMA_STORE_HIST, true)) != AFX_OK) return rc;
   if (n_clips > 0 && ((out_chroma && !chroma_off) || (out_mel && !mel_off) || (sh && !out_hist))) {
     set_error("afx_chroma_batch: out_chroma needs chroma_off, out_mel needs mel_off, AFX_CHROMA_STORE_HIST needs out_hist");
     return AFX_ERR_INVALID;
@@ -512,46 +530,23 @@ extern "C" int afx_chroma_batch(afx_plan* pl, const void* samples, int sample_fm
     if (k0 > 0) { band.kmin = k0; band.nr = k1 - k0 + 1; }
   }
   const bool est = tuning_in == nullptr, want_mel = out_mel || out_stats;
-  const size_t esz = sample_fmt == AFX_FMT_S16 ? 2 : 4;
-  const int64_t budget = dev_env().chroma_budget;
   const HpssTabs tb{pl->f3.window, pl->f3.w1024, pl->f3.w2048};
-  std::vector<HpssClip> recs;
-  std::vector<int> idx;
+  StftCost cost{};
+  cost.per_frame = kHpssPowPitch * 4 + (est ? band.nr * 5 : 0) + 12 * 4 + (want_mel ? M * 4 : 0) + 32;
+  cost.per_sample = 4 + upload_sample_bytes(sample_fmt, mem_kind);
+  cost.per_clip = kChromaHist * 4 + 128;
+  cost.tile = 16; cost.tile_cap = INT32_MAX / 2;
+  StftChunk ck;
   std::vector<uint32_t> h_bad;
   std::vector<int32_t> h_slot, h_hist;
   std::vector<double> h_stats, extra_t;
   std::vector<float> w(12 * kHpssBins), eimg;
-  for (int c0 = 0; c0 < n_clips;) {
-    // one chunk: as many clips as the workspace budget holds (at least one); zero-length clips take no work
-    recs.clear(); idx.clear();
-    int64_t frames = 0, ysz = 0, bytes = 0, lo = INT64_MAX, hi = 0, max_len = 0;
-    int tiles = 0;
-    int c1 = c0;
-    for (; c1 < n_clips && (int)recs.size() < 32768; ++c1) {
-      const int64_t L = lengths[c1];
-      if (L == 0) continue;
-      const int64_t T = 1 + L / 512, nt = (T + 15) / 16;
-      const int64_t pb = T * (kHpssPowPitch * 4 + (est ? band.nr * 5 : 0) + 12 * 4 + (want_mel ? M * 4 : 0) + 32) + L * 4 +
-                         (mem_kind == AFX_MEM_HOST ? L * (int64_t)esz : 0) + kChromaHist * 4 + 128;
-      if (!recs.empty() && (bytes + pb > budget || (int64_t)tiles + nt > INT32_MAX / 2)) break;
-      HpssClip r{};
-      r.in_off = offsets[c1]; r.y_off = ysz; r.len = L; r.frame_base = frames; r.T = (int32_t)T; r.tile_base = tiles;
-      recs.push_back(r); idx.push_back(c1);
-      frames += T; ysz += L; tiles += (int)nt; bytes += pb;
-      lo = std::min(lo, offsets[c1]); hi = std::max(hi, offsets[c1] + L); max_len = std::max(max_len, L);
-    }
-    const int n = (int)recs.size();
-    if (n == 0) { c0 = c1; continue; }
-    const void* d_in = samples;
-    if (mem_kind == AFX_MEM_HOST) {
-      if ((rc = ensure(pl->samples, (size_t)(hi - lo) * esz + 16)) != AFX_OK) return rc;
-      HIP_TRY(hipMemcpyAsync(pl->samples.p, (const char*)samples + (size_t)lo * esz, (size_t)(hi - lo) * esz, hipMemcpyHostToDevice, s));
-      for (HpssClip& r : recs) r.in_off -= lo;
-      d_in = pl->samples.p;
-    }
-    if ((rc = ensure(pl->hp_clips, n * sizeof(HpssClip))) != AFX_OK) return rc;
-    if ((rc = ensure(pl->hp_bad, n * sizeof(uint32_t))) != AFX_OK) return rc;
-    if ((rc = ensure(pl->hp_y, (size_t)ysz * sizeof(float) + 64)) != AFX_OK) return rc;
+  for (int c0 = 0; c0 < n_clips; c0 = ck.next) {
+    cut_stft_chunk(offsets, lengths, n_clips, c0, dev_env().chroma_budget, cost, ck);
+    const int n = (int)ck.recs.size(), tiles = ck.tiles;
+    const int64_t frames = ck.frames;
+    const std::vector<int>& idx = ck.idx;
+    if (n == 0) continue;
     if ((rc = ensure(pl->ch_s, (size_t)frames * kHpssPowPitch * sizeof(float))) != AFX_OK) return rc;
     if ((rc = ensure(pl->ch_slot, n * sizeof(int32_t))) != AFX_OK) return rc;
     if ((rc = ensure(pl->ch_hist, (size_t)n * kChromaHist * sizeof(int32_t))) != AFX_OK) return rc;
@@ -565,16 +560,14 @@ extern "C" int afx_chroma_batch(afx_plan* pl, const void* samples, int sample_fm
       if ((rc = ensure(pl->ch_parts, (size_t)frames * 4 * sizeof(double))) != AFX_OK) return rc;
       if ((rc = ensure(pl->hp_stats, (size_t)n * 4 * sizeof(double))) != AFX_OK) return rc;
     }
+    if ((rc = stage_stft_chunk(pl, samples, sample_fmt, mem_kind, flags, ck)) != AFX_OK) return rc;
     const HpssClip* d_clips = (const HpssClip*)pl->hp_clips.p;
-    uint32_t* d_bad = (uint32_t*)pl->hp_bad.p;
-    float* d_y = (float*)pl->hp_y.p;
+    const uint32_t* d_bad = (const uint32_t*)pl->hp_bad.p;
+    const float* d_y = (const float*)pl->hp_y.p;
     float* d_S = (float*)pl->ch_s.p;
     int32_t* d_slot = (int32_t*)pl->ch_slot.p;
     float* d_mel = out_mel ? (float*)pl->ch_melout.p : nullptr;
     double* d_parts = out_stats ? (double*)pl->ch_parts.p : nullptr;
-    HIP_TRY(hipMemcpyAsync(pl->hp_clips.p, recs.data(), n * sizeof(HpssClip), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemsetAsync(d_bad, 0, n * sizeof(uint32_t), s));
-    HIP_TRY(launch_hpss_prep(s, d_in, sample_fmt, flags & AFX_FLAG_PREEMPH, pl->kp.preemph_b1, d_clips, n, max_len, d_y, d_bad));
     HIP_TRY(launch_hpss_stft_power(s, d_y, d_clips, d_bad, n, frames, tb, d_S));
     if (est) {
       if (band.nr > 0) HIP_TRY(launch_chroma_peaks(s, d_S, frames, band, (float*)pl->ch_mag.p, (uint8_t*)pl->ch_bin.p));
@@ -609,22 +602,8 @@ extern "C" int afx_chroma_batch(afx_plan* pl, const void* samples, int sample_fm
       h_stats.resize((size_t)n * 4);
       HIP_TRY(hipMemcpyAsync(h_stats.data(), pl->hp_stats.p, (size_t)n * 4 * sizeof(double), hipMemcpyDeviceToHost, s));
     }
-    // the matrices: one copy when the caller's layout is the chunk's (packed clips in order), else one per clip
-    for (int which = 0; which < 2; ++which) {
-      float* dst = which ? out_mel : out_chroma;
-      const int64_t* off = which ? mel_off : chroma_off;
-      const float* src = which ? d_mel : (const float*)pl->ch_chroma.p;
-      const int64_t rows = which ? M : 12;
-      if (!dst) continue;
-      bool packed = true;
-      for (int q = 0; q < n && packed; ++q) packed = off[idx[q]] - off[idx[0]] == rows * recs[q].frame_base;
-      if (packed) {
-        HIP_TRY(hipMemcpyAsync(dst + off[idx[0]], src, (size_t)(rows * frames) * sizeof(float), hipMemcpyDeviceToHost, s));
-      } else {
-        for (int q = 0; q < n; ++q)
-          HIP_TRY(hipMemcpyAsync(dst + off[idx[q]], src + rows * recs[q].frame_base, (size_t)(rows * recs[q].T) * sizeof(float), hipMemcpyDeviceToHost, s));
-      }
-    }
+    if (out_chroma && (rc = copy_rows_out(s, ck, out_chroma, chroma_off, (const float*)pl->ch_chroma.p, 12, true)) != AFX_OK) return rc;
+    if (out_mel && (rc = copy_rows_out(s, ck, out_mel, mel_off, d_mel, M, true)) != AFX_OK) return rc;
     if (est) {
       h_slot.resize(n);
       HIP_TRY(hipMemcpyAsync(h_slot.data(), d_slot, n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
@@ -633,9 +612,7 @@ extern "C" int afx_chroma_batch(afx_plan* pl, const void* samples, int sample_fm
         HIP_TRY(hipMemcpyAsync(h_hist.data(), pl->ch_hist.p, h_hist.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s));
       }
     }
-    h_bad.resize(n);
-    HIP_TRY(hipMemcpyAsync(h_bad.data(), d_bad, n * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
+    if ((rc = end_stft_chunk(pl, n, h_bad)) != AFX_OK) return rc;
     for (int q = 0; q < n; ++q) {
       const int i = idx[q];
       out_status[i] = h_bad[q] ? AFX_CLIP_NONFINITE : AFX_CLIP_OK;
@@ -644,7 +621,6 @@ extern "C" int afx_chroma_batch(afx_plan* pl, const void* samples, int sample_fm
       if (out_stats && !h_bad[q])
         for (int k = 0; k < 4; ++k) out_stats[4 * i + k] = h_stats[4 * (size_t)q + k];
     }
-    c0 = c1;
   }
   return AFX_OK;
 }
@@ -681,13 +657,7 @@ extern "C" int afx_rhythm_batch(afx_plan* pl, const void* samples, int sample_fm
   if (n_clips > 0 && (!out_status || !out_tempo || !out_lag)) return null_arg(who);
   int rc = check_batch_args(who, pl, samples, sample_fmt, mem_kind, offsets, lengths, n_clips, true);
   if (rc != AFX_OK) return rc;
-  if (pl->p.n_fft != 2048 || pl->p.hop != 512 || pl->p.window != AFX_WINDOW_HANN || !pl->use_f3) {
-    set_error("afx_rhythm_batch: the plan must have frame_length 2048, hop_length 512 and the Hann window (librosa's defaults)");
-    return AFX_ERR_UNSUPPORTED;
-  }
-  if (pl->p.n_mels > 16 * kChromaMelGroups) { set_error("afx_rhythm_batch: at most 128 mel bands"); return AFX_ERR_UNSUPPORTED; }
-  if (flags & AFX_FLAG_TRIM) { set_error("afx_rhythm_batch: trim is not applied here; pass the preprocessed signal"); return AFX_ERR_UNSUPPORTED; }
-  if (flags & ~(AFX_FLAG_PREEMPH | AFX_FLAG_TRIM)) { set_error("afx_rhythm_batch: unknown flag"); return AFX_ERR_INVALID; }
+  if ((rc = check_stft_plan(who, pl, flags, AFX_FLAG_PREEMPH, true)) != AFX_OK) return rc;
   int32_t win = 0;
   if (afx_tempo_table(pl->p.sr, &win, nullptr, nullptr, nullptr) != AFX_OK) {
     set_error("afx_rhythm_batch: the 8 s tempogram window must hold 2 .. 768 frames (128 <= sr <= 49215)");
@@ -717,44 +687,21 @@ extern "C" int afx_rhythm_batch(afx_plan* pl, const void* samples, int sample_fm
   hipStream_t s = pl->ctx->stream;
   const RhythmTab tab = pl->rh_tabrec;
   const bool want_tg = out_tempogram != nullptr;
-  const size_t esz = sample_fmt == AFX_FMT_S16 ? 2 : 4;
-  const int64_t budget = dev_env().rhythm_budget;
   const HpssTabs tb{pl->f3.window, pl->f3.w1024, pl->f3.w2048};
-  std::vector<HpssClip> recs;
-  std::vector<int> idx;
+  StftCost cost{};
+  cost.per_frame = kHpssPowPitch * 4 + kRhMels * 4 + 4 + (want_tg ? win * 4 : 0);
+  cost.per_tile = win * 8;
+  cost.per_sample = 4 + upload_sample_bytes(sample_fmt, mem_kind);
+  cost.per_clip = win * 8 + 128;
+  cost.tile = kRhTile; cost.tile_cap = INT32_MAX / 2;
+  StftChunk ck;
   std::vector<uint32_t> h_bad;
   std::vector<double> h_res;
-  for (int c0 = 0; c0 < n_clips;) {
-    // one chunk: as many clips as the workspace budget holds (at least one); zero-length clips take no work
-    recs.clear(); idx.clear();
-    int64_t frames = 0, ysz = 0, bytes = 0, lo = INT64_MAX, hi = 0, max_len = 0;
-    int tiles = 0;
-    int c1 = c0;
-    for (; c1 < n_clips && (int)recs.size() < 32768; ++c1) {
-      const int64_t L = lengths[c1];
-      if (L == 0) continue;
-      const int64_t T = 1 + L / 512, nt = (T + kRhTile - 1) / kRhTile;
-      const int64_t pb = T * (kHpssPowPitch * 4 + kRhMels * 4 + 4 + (want_tg ? win * 4 : 0)) + nt * win * 8 + L * 4 +
-                         (mem_kind == AFX_MEM_HOST ? L * (int64_t)esz : 0) + win * 8 + 128;
-      if (!recs.empty() && (bytes + pb > budget || (int64_t)tiles + nt > INT32_MAX / 2)) break;
-      HpssClip r{};
-      r.in_off = offsets[c1]; r.y_off = ysz; r.len = L; r.frame_base = frames; r.T = (int32_t)T; r.tile_base = tiles;
-      recs.push_back(r); idx.push_back(c1);
-      frames += T; ysz += L; tiles += (int)nt; bytes += pb;
-      lo = std::min(lo, offsets[c1]); hi = std::max(hi, offsets[c1] + L); max_len = std::max(max_len, L);
-    }
-    const int n = (int)recs.size();
-    if (n == 0) { c0 = c1; continue; }
-    const void* d_in = samples;
-    if (mem_kind == AFX_MEM_HOST) {
-      if ((rc = ensure(pl->samples, (size_t)(hi - lo) * esz + 16)) != AFX_OK) return rc;
-      HIP_TRY(hipMemcpyAsync(pl->samples.p, (const char*)samples + (size_t)lo * esz, (size_t)(hi - lo) * esz, hipMemcpyHostToDevice, s));
-      for (HpssClip& r : recs) r.in_off -= lo;
-      d_in = pl->samples.p;
-    }
-    if ((rc = ensure(pl->hp_clips, n * sizeof(HpssClip))) != AFX_OK) return rc;
-    if ((rc = ensure(pl->hp_bad, n * sizeof(uint32_t))) != AFX_OK) return rc;
-    if ((rc = ensure(pl->hp_y, (size_t)ysz * sizeof(float) + 64)) != AFX_OK) return rc;
+  for (int c0 = 0; c0 < n_clips; c0 = ck.next) {
+    cut_stft_chunk(offsets, lengths, n_clips, c0, dev_env().rhythm_budget, cost, ck);
+    const int n = (int)ck.recs.size(), tiles = ck.tiles;
+    const int64_t frames = ck.frames;
+    if (n == 0) continue;
     if ((rc = ensure(pl->ch_s, (size_t)frames * kHpssPowPitch * sizeof(float))) != AFX_OK) return rc;
     if ((rc = ensure(pl->rh_db, (size_t)frames * kRhMels * sizeof(float))) != AFX_OK) return rc;
     if ((rc = ensure(pl->rh_max, n * sizeof(uint32_t))) != AFX_OK) return rc;
@@ -763,16 +710,14 @@ extern "C" int afx_rhythm_batch(afx_plan* pl, const void* samples, int sample_fm
     if (want_tg && (rc = ensure(pl->rh_tg, (size_t)frames * win * sizeof(float))) != AFX_OK) return rc;
     if ((rc = ensure(pl->rh_acmean, (size_t)n * win * sizeof(double))) != AFX_OK) return rc;
     if ((rc = ensure(pl->rh_res, (size_t)n * 4 * sizeof(double))) != AFX_OK) return rc;
+    if ((rc = stage_stft_chunk(pl, samples, sample_fmt, mem_kind, flags, ck)) != AFX_OK) return rc;
     const HpssClip* d_clips = (const HpssClip*)pl->hp_clips.p;
-    uint32_t* d_bad = (uint32_t*)pl->hp_bad.p;
-    float* d_y = (float*)pl->hp_y.p;
+    const uint32_t* d_bad = (const uint32_t*)pl->hp_bad.p;
+    const float* d_y = (const float*)pl->hp_y.p;
     float* d_S = (float*)pl->ch_s.p;
     float* d_env = (float*)pl->rh_env.p;
     float* d_tg = want_tg ? (float*)pl->rh_tg.p : nullptr;
-    HIP_TRY(hipMemcpyAsync(pl->hp_clips.p, recs.data(), n * sizeof(HpssClip), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemsetAsync(d_bad, 0, n * sizeof(uint32_t), s));
     HIP_TRY(hipMemsetAsync(pl->rh_max.p, 0, n * sizeof(uint32_t), s));
-    HIP_TRY(launch_hpss_prep(s, d_in, sample_fmt, flags & AFX_FLAG_PREEMPH, pl->kp.preemph_b1, d_clips, n, max_len, d_y, d_bad));
     HIP_TRY(launch_hpss_stft_power(s, d_y, d_clips, d_bad, n, frames, tb, d_S));
     HIP_TRY(launch_rhythm_mel(s, d_S, d_clips, n, tiles, pl->ch_melrec, (float*)pl->rh_db.p, (uint32_t*)pl->rh_max.p));
     HIP_TRY(launch_rhythm_env(s, (const float*)pl->rh_db.p, (const uint32_t*)pl->rh_max.p, d_clips, n, frames, M, d_env));
@@ -781,42 +726,25 @@ extern "C" int afx_rhythm_batch(afx_plan* pl, const void* samples, int sample_fm
                                  (double*)pl->rh_res.p));
     h_res.resize((size_t)n * 4);
     HIP_TRY(hipMemcpyAsync(h_res.data(), pl->rh_res.p, (size_t)n * 4 * sizeof(double), hipMemcpyDeviceToHost, s));
-    // the per-frame outputs: one copy when the caller's layout is the chunk's (packed clips in order), else one per clip
-    for (int which = 0; which < 2; ++which) {
-      float* dst = which ? out_tempogram : out_env;
-      const int64_t* off = which ? tg_off : env_off;
-      const float* src = which ? d_tg : d_env;
-      const int64_t rows = which ? win : 1;
-      if (!dst) continue;
-      bool packed = true;
-      for (int q = 0; q < n && packed; ++q) packed = off[idx[q]] - off[idx[0]] == rows * recs[q].frame_base;
-      if (packed) {
-        HIP_TRY(hipMemcpyAsync(dst + off[idx[0]], src, (size_t)(rows * frames) * sizeof(float), hipMemcpyDeviceToHost, s));
-      } else {
-        for (int q = 0; q < n; ++q)
-          HIP_TRY(hipMemcpyAsync(dst + off[idx[q]], src + rows * recs[q].frame_base, (size_t)(rows * recs[q].T) * sizeof(float), hipMemcpyDeviceToHost, s));
-      }
-    }
+    if (out_env && (rc = copy_rows_out(s, ck, out_env, env_off, d_env, 1, true)) != AFX_OK) return rc;
+    if (out_tempogram && (rc = copy_rows_out(s, ck, out_tempogram, tg_off, d_tg, win, true)) != AFX_OK) return rc;
     if (out_acmean) {
-      bool dense = idx[n - 1] - idx[0] == n - 1;        // no zero-length clip inside the chunk: the rows are the caller's
+      bool dense = ck.idx[n - 1] - ck.idx[0] == n - 1;  // no zero-length clip inside the chunk: the rows are the caller's
       if (dense) {
-        HIP_TRY(hipMemcpyAsync(out_acmean + (size_t)win * idx[0], pl->rh_acmean.p, (size_t)n * win * sizeof(double), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(out_acmean + (size_t)win * ck.idx[0], pl->rh_acmean.p, (size_t)n * win * sizeof(double), hipMemcpyDeviceToHost, s));
       } else {
         for (int q = 0; q < n; ++q)
-          HIP_TRY(hipMemcpyAsync(out_acmean + (size_t)win * idx[q], (const double*)pl->rh_acmean.p + (size_t)win * q, (size_t)win * sizeof(double), hipMemcpyDeviceToHost, s));
+          HIP_TRY(hipMemcpyAsync(out_acmean + (size_t)win * ck.idx[q], (const double*)pl->rh_acmean.p + (size_t)win * q, (size_t)win * sizeof(double), hipMemcpyDeviceToHost, s));
       }
     }
-    h_bad.resize(n);
-    HIP_TRY(hipMemcpyAsync(h_bad.data(), d_bad, n * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
+    if ((rc = end_stft_chunk(pl, n, h_bad)) != AFX_OK) return rc;
     for (int q = 0; q < n; ++q) {
-      const int i = idx[q];
+      const int i = ck.idx[q];
       out_status[i] = h_bad[q] ? AFX_CLIP_NONFINITE : AFX_CLIP_OK;
       if (h_bad[q]) continue;                            // its rows are zero: so are the envelope, the tempogram and acmean
       out_tempo[i] = h_res[4 * (size_t)q]; out_lag[i] = (int32_t)h_res[4 * (size_t)q + 3];
       if (out_stats) { out_stats[2 * i] = h_res[4 * (size_t)q + 1]; out_stats[2 * i + 1] = h_res[4 * (size_t)q + 2]; }
     }
-    c0 = c1;
   }
   return AFX_OK;
 }

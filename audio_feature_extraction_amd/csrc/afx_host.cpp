@@ -1,7 +1,9 @@
 // Host-only part of libafx.so: the error string, the version, and the builders that need no device -- the clip records of
-// a batch (what prepare_descriptors uploads), the pYIN tables, the pYIN kernel dispatch (afx_f0_dispatch) and the chroma filterbank (afx_chroma_filters) and the tempo table (afx_tempo_table).  Together with afx_tables.cpp, afx_f0_tables.cpp and
-// afx_wav.cpp this is everything that parses caller- or file-supplied data on the host; `make asan` builds exactly these
-// files (plus afx_host_stubs.cpp) with g++ -fsanitize=address,undefined as libafx_host_asan.so.
+// a batch (what prepare_descriptors uploads), the chunk cut of the STFT-based groups (cut_stft_chunk, afx_stft_chunks), the
+// pYIN tables, the pYIN kernel dispatch (afx_f0_dispatch), the chroma filterbank (afx_chroma_filters) and the tempo table
+// (afx_tempo_table).  Together with afx_tables.cpp, afx_f0_tables.cpp and afx_wav.cpp this is everything that parses
+// caller- or file-supplied data on the host; `make asan` builds exactly these files (plus afx_host_stubs.cpp) with
+// g++ -fsanitize=address,undefined as libafx_host_asan.so.
 #include <algorithm>
 #include <cfloat>
 #include <cmath>
@@ -10,6 +12,7 @@
 
 #include "afx_device.h"
 #include "afx_f0.h"
+#include "afx_hpss.h"
 #include "afx_internal.h"
 #include "afx_mr.h"
 
@@ -48,6 +51,28 @@ bool build_clip_descs(int hop, int trim_hop, const int64_t* offsets, const int64
   }
   g.total_tpad = fb; g.total_tblk = tb; g.max_tblocks = std::max(max_tb, 1); g.max_tmax = max_tm; g.nblocks = (int)nblk;
   return true;
+}
+
+void cut_stft_chunk(const int64_t* offsets, const int64_t* lengths, int n_clips, int first, int64_t budget,
+                    const StftCost& cost, StftChunk& ck) {
+  ck.recs.clear(); ck.idx.clear();
+  ck.frames = ck.samples = ck.spec_floats = ck.hi = ck.max_len = 0; ck.lo = INT64_MAX; ck.tiles = 0;
+  int64_t bytes = 0;
+  int c1 = first;
+  for (; c1 < n_clips && (int)ck.recs.size() < kStftChunkClips; ++c1) {
+    const int64_t L = lengths[c1];
+    if (L == 0) continue;
+    const int64_t T = 1 + L / 512, nt = (T + cost.tile - 1) / cost.tile;
+    const int64_t pb = T * cost.per_frame + nt * cost.per_tile + L * cost.per_sample + cost.per_clip;
+    if (!ck.recs.empty() && (bytes + pb > budget || (int64_t)ck.tiles + nt > cost.tile_cap)) break;
+    HpssClip r{};
+    r.in_off = offsets[c1]; r.y_off = ck.samples; r.len = L; r.frame_base = ck.frames; r.spec_off = ck.spec_floats;
+    r.T = (int32_t)T; r.tile_base = ck.tiles;
+    ck.recs.push_back(r); ck.idx.push_back(c1);
+    ck.frames += T; ck.samples += L; ck.spec_floats += cost.spec_floats * T; ck.tiles += (int)nt; bytes += pb;
+    ck.lo = std::min(ck.lo, offsets[c1]); ck.hi = std::max(ck.hi, offsets[c1] + L); ck.max_len = std::max(ck.max_len, L);
+  }
+  ck.next = c1;
 }
 
 // One Stockham pass of radix R over N2 points, butterfly by butterfly as k_frames_mr's lanes take them.
@@ -149,6 +174,28 @@ extern "C" int afx_f0_dispatch(int sr, int n_fft, int hop, double fmin, double f
   const int32_t v[12] = {d.energy_lpw, d.epb, d.yin_n, d.yin_fpb, d.yin_sh, d.vit_nbt, d.vit_bandt, d.vit_tpt, d.bt_depth,
                          t.p.band, t.p.n_bins, d.yin_lds};
   std::memcpy(out, v, sizeof(v));
+  return AFX_OK;
+}
+
+extern "C" int afx_stft_chunks(const int64_t* lengths, int n_clips, const int64_t* cost, int64_t budget, int32_t* chunk_of) {
+  if (n_clips < 0 || !cost || (n_clips > 0 && (!lengths || !chunk_of))) { set_error("afx_stft_chunks: null/invalid argument"); return AFX_ERR_INVALID; }
+  // the sums of a chunk stay below 2^63: a clip costs less than 2^55 bytes, and a chunk is cut before it passes the budget
+  for (int k = 0; k < 6; ++k)
+    if (cost[k] < (k >= 4 ? 1 : 0) || cost[k] > (k >= 4 ? INT32_MAX : 1 << 20)) { set_error("afx_stft_chunks: cost out of range"); return AFX_ERR_INVALID; }
+  if (budget < 1 || budget > (int64_t)1 << 62) { set_error("afx_stft_chunks: budget must be in [1, 2^62]"); return AFX_ERR_INVALID; }
+  for (int i = 0; i < n_clips; ++i)
+    if (lengths[i] < 0 || lengths[i] > (int64_t)1 << 31) { set_error("afx_stft_chunks: lengths must be in [0, 2^31]"); return AFX_ERR_INVALID; }
+  const StftCost c{cost[0], cost[1], cost[2], cost[3], cost[4], cost[5], 0};
+  const std::vector<int64_t> offsets((size_t)n_clips, 0);
+  std::fill(chunk_of, chunk_of + n_clips, -1);
+  StftChunk ck;
+  int32_t chunk = 0;
+  for (int c0 = 0; c0 < n_clips; c0 = ck.next) {
+    cut_stft_chunk(offsets.data(), lengths, n_clips, c0, budget, c, ck);
+    if (ck.idx.empty()) continue;
+    for (int i : ck.idx) chunk_of[i] = chunk;
+    ++chunk;
+  }
   return AFX_OK;
 }
 

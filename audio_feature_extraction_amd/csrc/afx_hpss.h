@@ -2,6 +2,7 @@
 // STFT.  Workspace geometry, the per-clip record and the launchers.  Internal to libafx.so.
 #pragma once
 #include <cstdint>
+#include <vector>
 
 #include <hip/hip_runtime_api.h>
 
@@ -24,6 +25,33 @@ struct HpssClip {
   int32_t T;            // 1 + len / 512
   int32_t tile_base;    // first 64-frame tile of the clip (k_hpss_mask)
 };
+
+// What a clip costs the chunk of an STFT-based group (afx_hpss_batch, afx_chroma_batch, afx_rhythm_batch), in bytes of
+// device workspace: T per_frame + ceil(T / tile) per_tile + len per_sample + per_clip, T = 1 + len / 512
+struct StftCost {
+  int64_t per_frame, per_tile, per_sample, per_clip;
+  int64_t tile;         // frames per tile
+  int64_t tile_cap;     // most tiles a chunk may hold
+  int64_t spec_floats;  // floats of spec_off per frame (0 except for AFX_HPSS_STORE_SPEC)
+};
+
+// One chunk of a batch: the records of its clips (in_off is the caller's offset) and what they add up to
+struct StftChunk {
+  std::vector<HpssClip> recs;
+  std::vector<int> idx;               // recs[q] is clip idx[q] of the batch
+  int64_t frames, samples, spec_floats;
+  int64_t lo, hi, max_len;            // the chunk's clips lie in [lo, hi) of the caller's samples
+  int tiles;
+  int next;                           // the first clip of the batch the chunk does not hold
+};
+
+constexpr int kStftChunkClips = 32768;
+
+// The chunk that starts at clip `first` (afx_host.cpp; no device): zero-length clips are skipped and cost nothing, a chunk
+// holds at least one clip, and it ends before the clip that would take its bytes past the budget or its tiles past the
+// cap, or at kStftChunkClips records.  afx_stft_chunks hands the same rule to a caller without a device.
+void cut_stft_chunk(const int64_t* offsets, const int64_t* lengths, int n_clips, int first, int64_t budget,
+                    const StftCost& cost, StftChunk& ck);
 
 struct HpssTabs {
   const float* window;  // periodic Hann, 2048 floats

@@ -363,6 +363,15 @@ int afx_rhythm_batch(afx_plan* plan, const void* samples, int sample_fmt, int me
                      double* out_stats,
                      int32_t* out_status);
 
+/* Host-only: how afx_hpss_batch, afx_chroma_batch and afx_rhythm_batch cut a batch into chunks (one rule, the entry points
+ * differ in the cost record).  A clip of T = 1 + length / 512 frames costs T cost[0] + ceil(T / cost[4]) cost[1] +
+ * length cost[2] + cost[3] bytes of workspace; a chunk holds at least one clip and ends before the clip that would take
+ * its bytes past budget or its tiles (of cost[4] frames) past cost[5], or at 32768 clips.  chunk_of[i] = the chunk of
+ * clip i, -1 for a clip of length 0 (it is in no chunk and costs nothing).  Newer than AFX_VERSION 107 says: a binding
+ * detects it by its presence.  AFX_ERR_INVALID for a length outside [0, 2^31], a budget outside [1, 2^62], cost[0 .. 3]
+ * outside [0, 2^20] or cost[4], cost[5] outside [1, 2^31 - 1]. */
+int afx_stft_chunks(const int64_t* lengths, int n_clips, const int64_t* cost /*[6]*/, int64_t budget, int32_t* chunk_of);
+
 /* Host-only (no device needed): the tables afx_f0_batch uploads, for inspection and tests.
  * info[8] = min_period, max_period, n_pitch_bins, band (transition half-width), candidate
  * capacity, lags kept, lags per lane, trough slots per lane.  beta[100] = Beta(2,18) mass of

@@ -163,6 +163,50 @@ def test_chunked_batch_equals_one_chunk(plan, tmp_path):
     np.testing.assert_array_equal(z["stats"], ref["stats"])
 
 
+_LAYOUTS_LENGTHS = (5000, 12345, 700, 9000, 3000, 7000)
+_LAYOUTS_CHILD = r"""
+import sys
+import numpy as np
+sys.path.insert(0, sys.argv[1])
+from tests.test_gpu_hpss import _LAYOUTS_LENGTHS, _pack
+from audio_feature_extraction_amd import _native as N
+plan = N.Plan(N.Context(0), N.make_params(22050, 2048, 512, 13, 128, "hann"))
+rng = np.random.default_rng(6)
+sigs = [(0.4 * rng.standard_normal(n)).astype(np.float32) for n in _LAYOUTS_LENGTHS]
+y, off, ln = _pack(sigs)
+ref = plan.hpss_batch(y, off, ln, want_perc=True)
+assert (ref["status"] == 0).all()
+dev = plan.device_buffer(y.nbytes)
+dev.upload(y)
+d = plan.hpss_batch(dev.ptr, off, ln, mem=N.MEM_DEVICE, want_perc=True)
+dev.free()
+roff = np.zeros(len(sigs), np.int64)                   # the last clip first, 37 samples between neighbours
+for i in range(len(sigs) - 2, -1, -1):
+    roff[i] = roff[i + 1] + ln[i + 1] + 37
+ry = np.full(int(roff[0] + ln[0]), np.nan, np.float32)           # a gap that is read would poison its clip
+for s, o in zip(sigs, roff):
+    ry[o:o + s.size] = s
+r = plan.hpss_batch(ry, roff, ln, want_perc=True)
+for name, o in (("device", d), ("reversed", r)):
+    np.testing.assert_array_equal(o["status"], ref["status"], err_msg=name)
+    np.testing.assert_array_equal(o["stats"], ref["stats"], err_msg=name)
+    for k in ("harm", "perc"):
+        for i, (u, v) in enumerate(zip(o[k], ref[k])):
+            np.testing.assert_array_equal(u, v, err_msg="%s %s clip %d" % (name, k, i))
+"""
+
+
+def test_chunked_device_and_scattered_layouts_equal_the_packed_host_batch(N):
+    """Six clips at a budget of 900000 bytes are four chunks -- (5000), (12345, 700), (9000, 3000), (7000) -- whether the
+    samples are uploaded (16 bytes a sample with want_perc) or device-resident (12): chunks behind the first read device
+    input at offsets that are not rebased, and clips laid out in reverse order take the per-clip copy of the signals."""
+    per_frame = 1032 * 8 * 3 + 17 * 4
+    for per_sample in (4 * 3 + 4, 4 * 3):
+        assert N.stft_chunks(_LAYOUTS_LENGTHS, (per_frame, 0, per_sample, 128, 64, 65535), 900000).tolist() == [0, 1, 1, 2, 2, 3]
+    env = dict(os.environ, AFX_TEST_HPSS_BUDGET="900000")
+    subprocess.run(["timeout", "-k", "10", "120", sys.executable, "-c", _LAYOUTS_CHILD, ROOT], env=env, check=True, timeout=150)
+
+
 def test_s16_and_device_inputs_match_host_f32(plan, N):
     rng = np.random.default_rng(4)
     q = [rng.integers(-20000, 20000, n).astype(np.int16) for n in (5000, 12345, 700)]
