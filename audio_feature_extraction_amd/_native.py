@@ -33,6 +33,7 @@ SMP_KINDS = {"u8": SMP_U8, "s16": SMP_S16, "s24": SMP_S24, "s32": SMP_S32, "f32"
 SMP_BYTES = np.array([1, 2, 3, 4, 4, 8], np.int64)
 SMP_OF_WAV = {(1, 8): SMP_U8, (1, 16): SMP_S16, (1, 24): SMP_S24, (1, 32): SMP_S32, (3, 32): SMP_F32, (3, 64): SMP_F64}   # (tag, bits)
 DECODE_MAX_CHANNELS = 7
+FILT_PLAIN, FILT_EXPERIMENT = 0, 1
 K_NAMES = ("trim_blocks", "trim_decide", "frames", "dct", "stats")
 K_FRAMES = 2
 
@@ -46,6 +47,7 @@ SYMBOLS = (
     "afx_resample_design", "afx_resample_batch", "afx_rfft_host", "afx_wav_read_raw", "afx_decode_batch",
     "afx_chroma_batch", "afx_chroma_filters", "afx_rhythm_batch", "afx_tempo_table",
     "afx_stft_chunks",
+    "afx_butter_sos", "afx_filtfilt_geometry", "afx_sosfiltfilt_host", "afx_sosfiltfilt_batch",
 )
 
 
@@ -130,6 +132,11 @@ def lib() -> C.CDLL:
             L.afx_tempo_table.argtypes = [i32, i32p, i32p, vp, vp]
         if hasattr(L, "afx_stft_chunks"):                    # newer than version 107 says: found by its presence
             L.afx_stft_chunks.argtypes = [vp, i32, vp, C.c_int64, vp]
+        if hasattr(L, "afx_sosfiltfilt_batch"):              # newer than version 107 says: found by their presence
+            L.afx_butter_sos.argtypes = [i32, C.c_double, i32, vp]
+            L.afx_filtfilt_geometry.argtypes = [vp]
+            L.afx_sosfiltfilt_host.argtypes = [vp, i32, C.c_int64, vp, i32, i32, i32, C.c_float, vp, vp, vp]
+            L.afx_sosfiltfilt_batch.argtypes = [vp, vp, i32, i32, vp, vp, i32, vp, i32, i32, i32, C.c_float, vp, i32, vp, vp, vp]
         if hasattr(L, "afx_rfft_host"):                      # absent from a library built before the mixed-radix lengths
             L.afx_rfft_host.argtypes = [i32, vp, vp]
         _lib = L
@@ -298,6 +305,54 @@ def stft_chunks(lengths, cost, budget: int) -> np.ndarray:
     _check(lib().afx_stft_chunks(lengths.ctypes.data, int(lengths.shape[0]), cost.ctypes.data, int(budget), out.ctypes.data),
            "afx_stft_chunks")
     return out
+
+
+def _need_filt():
+    if not hasattr(lib(), "afx_sosfiltfilt_batch"):
+        raise NotImplementedError("this libafx has no afx_sosfiltfilt_batch")
+
+
+def _sos_array(sos) -> np.ndarray:
+    sos = np.ascontiguousarray(sos, np.float64)
+    if sos.ndim != 2 or sos.shape[1] != 6 or sos.shape[0] < 1:
+        raise ValueError("sos array must be shape (n_sections, 6)")
+    return sos
+
+
+def butter_sos(order: int, wn: float, highpass: bool) -> np.ndarray:
+    """Host-only: afx_butter_sos, the (order + 1) // 2 second-order sections of a digital Butterworth filter (wn: 1 = Nyquist)."""
+    _need_filt()
+    if int(order) < 1:
+        raise ValueError("the order must be at least 1")
+    sos = np.zeros(((int(order) + 1) // 2, 6), np.float64)
+    _check(lib().afx_butter_sos(int(order), float(wn), int(bool(highpass)), sos.ctypes.data), "afx_butter_sos")
+    return sos
+
+
+def filtfilt_geometry() -> dict:
+    """Host-only: the block decomposition of afx_sosfiltfilt_batch (samples per block, blocks per tile) and its bounds."""
+    _need_filt()
+    info = np.zeros(4, np.int32)
+    _check(lib().afx_filtfilt_geometry(info.ctypes.data), "afx_filtfilt_geometry")
+    return {"block": int(info[0]), "tile_blocks": int(info[1]), "tile": int(info[0]) * int(info[1]),
+            "max_sections": int(info[2]), "max_padlen": int(info[3])}
+
+
+def sosfiltfilt_host(x, sos, padlen: int, mode: int = FILT_PLAIN, preemph: float = 0.98) -> dict:
+    """Host-only: afx_sosfiltfilt_host, one int16 / float32 clip through the kernels' block decomposition on the CPU.
+    Returns out (float32; zeros when the clip failed), peak (max|x|, max|y|) and status."""
+    _need_filt()
+    sos = _sos_array(sos)
+    x = np.ascontiguousarray(x)
+    if x.ndim != 1 or x.dtype not in (np.int16, np.float32):
+        raise ValueError("x must be a one-dimensional int16 or float32 array")
+    out = np.zeros(x.size, np.float32)
+    peak = np.zeros(2, np.float64)
+    status = np.zeros(1, np.int32)
+    _check(lib().afx_sosfiltfilt_host(x.ctypes.data, FMT_S16 if x.dtype == np.int16 else FMT_F32, int(x.size), sos.ctypes.data,
+                                      int(sos.shape[0]), int(padlen), int(mode), float(preemph), out.ctypes.data,
+                                      peak.ctypes.data, status.ctypes.data), "afx_sosfiltfilt_host")
+    return {"out": out, "peak": peak, "status": int(status[0])}
 
 
 def resample_lengths(lengths, sr_in: int, sr_out: int) -> np.ndarray:
@@ -575,6 +630,41 @@ class Context(_Owner):
                                         0 if tp is None else int(tp.size), optr, okind, out_offsets.ctypes.data,
                                         got.ctypes.data), "afx_resample_batch")
         return {"out": out, "offsets": out_offsets, "lengths": got}
+
+    def sosfiltfilt_batch(self, samples, offsets, lengths, sos, padlen: int, mode: int = FILT_PLAIN, preemph: float = 0.98,
+                          fmt=None, out=None, out_offsets=None) -> dict:
+        """afx_sosfiltfilt_batch: clips samples[offsets[i] .. + lengths[i]) through the zero-phase cascade ``sos`` (FILT_PLAIN)
+        or through the experiment extractor's whole preprocess_audio around it (FILT_EXPERIMENT), float32 out.
+        ``samples``, ``out``, ``out_offsets``: as resample_batch (outputs have their inputs' lengths).  Returns out, offsets,
+        peak (max|x|, max|y| per clip) and status; the output range of a clip whose status is not CLIP_OK is not written."""
+        _need_filt()
+        offsets, lengths, n = _clip_arrays(offsets, lengths)
+        sos = _sos_array(sos)
+        fmt = _sample_fmt(samples, fmt)
+        sptr, kind = _sample_source(samples, fmt, offsets, lengths)
+        if out_offsets is None:
+            out_offsets = packed_offsets(np.maximum(lengths, 0), 4)
+        out_offsets = np.ascontiguousarray(out_offsets, np.int64).reshape(-1)
+        if out_offsets.shape[0] != n:
+            raise ValueError("out_offsets must have one entry per clip")
+        need = int((out_offsets + np.maximum(lengths, 0)).max()) if n else 0
+        if out is None:
+            out = np.zeros(need, np.float32)
+        if isinstance(out, np.ndarray):
+            if out.dtype != np.float32 or not out.flags.c_contiguous or out.size < need:
+                raise ValueError("out must be a C-contiguous float32 array that holds every clip")
+            optr, okind = out.ctypes.data, MEM_HOST
+        else:
+            if isinstance(out, DeviceBuffer) and out.nbytes < 4 * need:
+                raise ValueError("the output DeviceBuffer is too small")
+            optr, okind = (out.ptr if isinstance(out, DeviceBuffer) else int(out)), MEM_DEVICE
+        peak = np.zeros((n, 2), np.float64)
+        status = np.zeros(n, np.int32)
+        _check(lib().afx_sosfiltfilt_batch(self.handle, sptr, int(fmt), kind, offsets.ctypes.data, lengths.ctypes.data, n,
+                                           sos.ctypes.data, int(sos.shape[0]), int(padlen), int(mode), float(preemph),
+                                           optr, okind, out_offsets.ctypes.data, peak.ctypes.data, status.ctypes.data),
+               "afx_sosfiltfilt_batch")
+        return {"out": out, "offsets": out_offsets, "peak": peak, "status": status}
 
     def decode_batch(self, raw, byte_offsets, frames, kinds, channels, out=None, out_offsets=None) -> dict:
         """afx_decode_batch: raw WAVE data -> mono float32, bit for bit wavio.to_mono(wavio.to_float32(...)).  Clip i is

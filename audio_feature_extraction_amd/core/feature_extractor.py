@@ -399,6 +399,25 @@ class AudioFeatureExtractor:
         the GPU; the signal is taken as given and may be as short as one sample (tempo 0.0 up to three frames)."""
         return self.extract_rhythm_features_batch([y])[0]
 
+    def preprocess_experiment_batch(self, signals: Sequence[np.ndarray]) -> List[Optional[np.ndarray]]:
+        """``preprocess_experiment`` of many signals in one device pass; ``None`` for a clip the reference's
+        ``preprocess_audio`` returns None for (18 samples or fewer, or not finite)."""
+        from .. import filters
+        return filters.preprocess_experiment_batch(signals, self.sr, device=self._devices()[0])
+
+    def preprocess_experiment(self, y: np.ndarray) -> np.ndarray:
+        """音頻預處理：降噪和正規化 (04_feature_extraction_experiment/feature_extractor.py:133-154), the stage that experiment
+        class runs ahead of every feature group: peak normalisation, pre-emphasis 0.98, a 5th-order Butterworth high-pass at
+        200 Hz applied forward and backward (``scipy.signal.filtfilt``), peak normalisation, at this extractor's ``sr`` and on
+        the GPU.  float32 (the reference's float64 result rounded once).  Where the reference logs and returns None -- a
+        signal of 18 samples or fewer, a NaN / inf sample -- this raises ``ValueError``."""
+        from .. import filters
+        y = np.asarray(y)
+        out = filters._preprocess_experiment([y], self.sr, self._devices()[0])
+        if out["status"][0] != _native.CLIP_OK:
+            raise _status_error(int(out["status"][0]), "preprocess_experiment", int(y.size))
+        return out["clips"][0]
+
     @staticmethod
     def save_frame_features(features: Dict[str, np.ndarray], npz_path: str) -> None:
         """``np.savez(npz_path, **features)`` -- the reference's on-disk schema for frame-level features."""

@@ -344,3 +344,123 @@ extern "C" int afx_decode_batch(afx_ctx* ctx, const void* raw, int mem_kind, con
   }
   return AFX_OK;
 }
+
+// ---- zero-phase IIR filtering (scipy.signal.sosfiltfilt) and the experiment extractor's preprocess_audio around it -------
+extern "C" int afx_sosfiltfilt_batch(afx_ctx* ctx, const void* samples, int sample_fmt, int mem_kind,
+                                     const int64_t* offsets, const int64_t* lengths, int n_clips,
+                                     const double* sos, int n_sections, int padlen, int mode, float preemph,
+                                     float* out, int out_mem_kind, const int64_t* out_offsets,
+                                     double* out_peak, int32_t* out_status) {
+  const char* who = "afx_sosfiltfilt_batch";
+  if (!ctx || !sos || n_clips < 0 || (n_clips > 0 && (!offsets || !lengths || !out_offsets || !out_status))) return null_arg(who);
+  int rc;
+  if ((rc = check_sample_format(who, sample_fmt, mem_kind)) != AFX_OK) return rc;
+  if ((rc = check_sample_format(who, sample_fmt, out_mem_kind)) != AFX_OK) return rc;
+  if (mode != AFX_FILT_PLAIN && mode != AFX_FILT_EXPERIMENT) { set_error(std::string(who) + ": unknown mode"); return AFX_ERR_INVALID; }
+  if (n_sections < 1 || padlen < 0) { set_error(std::string(who) + ": n_sections must be >= 1 and padlen >= 0"); return AFX_ERR_INVALID; }
+  if (n_sections > kFiltMaxS || padlen > kFiltMaxPad) {
+    set_error(std::string(who) + ": more than 4 sections or padlen > 4096 is not supported");
+    return AFX_ERR_UNSUPPORTED;
+  }
+  if ((rc = check_clip_ranges(who, offsets, lengths, out_offsets, n_clips, INT64_MAX / 8)) != AFX_OK) return rc;
+  FiltTab tab;
+  const char* why = "";
+  if (!filt_build_tab(sos, n_sections, tab, &why)) { set_error(std::string(who) + ": " + why); return AFX_ERR_INVALID; }
+  bool any = false;
+  for (int i = 0; i < n_clips; ++i) {
+    const bool live = lengths[i] > padlen;
+    out_status[i] = live ? AFX_CLIP_OK : AFX_CLIP_TOO_SHORT;
+    if (out_peak) out_peak[2 * i] = out_peak[2 * i + 1] = 0.0;
+    any = any || live;
+  }
+  if (!any) return AFX_OK;
+  if (!samples || !out) { set_error(std::string(who) + ": null samples / out"); return AFX_ERR_INVALID; }
+
+  (void)hipGetLastError();
+  HIP_TRY(hipSetDevice(ctx->device));
+  hipStream_t s = ctx->stream;
+  if ((rc = ensure(ctx->ft_tab, sizeof(FiltTab))) != AFX_OK) return rc;
+  HIP_TRY(hipMemcpyAsync(ctx->ft_tab.p, &tab, sizeof(FiltTab), hipMemcpyHostToDevice, s));
+  const FiltTab* d_tab = (const FiltTab*)ctx->ft_tab.p;
+  const size_t esz = sample_fmt == AFX_FMT_S16 ? 2 : 4;
+  const bool h_in = mem_kind == AFX_MEM_HOST, h_out = out_mem_kind == AFX_MEM_HOST;
+  const int64_t budget = dev_env().filt_budget;
+  // bytes of one tile: the float64 workspace, the carries of its blocks, its maximum
+  constexpr int64_t kTileBytes = (int64_t)kFiltTile * 8 + (int64_t)kFiltB * kFiltZ * 8 + 8;
+  std::vector<FiltClip> recs;
+  std::vector<int> idx;
+  std::vector<FiltState> h_st;
+  std::vector<char> stage_in;
+  std::vector<float> stage_out;
+  for (int c0 = 0; c0 < n_clips;) {
+    // one chunk: as many clips as the workspace budget holds (at least one); clips too short to filter cost nothing
+    recs.clear(); idx.clear();
+    int64_t bytes = 0, tiles = 0, in_pos = 0, out_pos = 0;
+    int c1 = c0;
+    for (; c1 < n_clips; ++c1) {
+      const int64_t n = lengths[c1];
+      if (n <= padlen) continue;
+      const int64_t nt = (n + 2 * (int64_t)padlen + kFiltTile - 1) / kFiltTile;
+      const int64_t cb = nt * kTileBytes + (h_in ? n * (int64_t)esz : 0) + (h_out ? n * 4 : 0) + (int64_t)sizeof(FiltClip) + sizeof(FiltState);
+      if (!recs.empty() && (bytes + cb > budget || tiles + nt > (1 << 24) || recs.size() >= 32768)) break;
+      FiltClip r{};
+      r.n = n;
+      r.in_off = h_in ? in_pos : offsets[c1];
+      r.out_off = h_out ? out_pos : out_offsets[c1];
+      r.first_tile = (int32_t)tiles; r.n_tiles = (int32_t)nt;
+      recs.push_back(r); idx.push_back(c1);
+      bytes += cb; tiles += nt;
+      in_pos += (n + 3) / 4 * 4; out_pos += (n + 3) / 4 * 4;
+    }
+    c0 = c1;
+    if (recs.empty()) break;
+    if (tiles > (1 << 24)) { set_error(std::string(who) + ": clip too large for one launch"); return AFX_ERR_UNSUPPORTED; }
+    const int n = (int)recs.size(), nt = (int)tiles;
+    if ((rc = ensure(ctx->ft_clips, n * sizeof(FiltClip))) != AFX_OK) return rc;
+    if ((rc = ensure(ctx->ft_st, n * sizeof(FiltState))) != AFX_OK) return rc;
+    if ((rc = ensure(ctx->ft_w, (size_t)nt * kFiltTile * sizeof(double))) != AFX_OK) return rc;
+    if ((rc = ensure(ctx->ft_carry, (size_t)nt * kFiltB * kFiltZ * sizeof(double))) != AFX_OK) return rc;
+    if ((rc = ensure(ctx->ft_tmax, (size_t)nt * sizeof(double))) != AFX_OK) return rc;
+    const void* d_in = samples;
+    if (h_in) {
+      stage_in.assign((size_t)in_pos * esz, 0);
+      for (int q = 0; q < n; ++q)
+        std::memcpy(stage_in.data() + (size_t)recs[q].in_off * esz, (const char*)samples + (size_t)offsets[idx[q]] * esz, (size_t)recs[q].n * esz);
+      if ((rc = ensure(ctx->ft_in, stage_in.size())) != AFX_OK) return rc;
+      HIP_TRY(hipMemcpyAsync(ctx->ft_in.p, stage_in.data(), stage_in.size(), hipMemcpyHostToDevice, s));
+      d_in = ctx->ft_in.p;
+    }
+    float* d_out = out;
+    if (h_out) {
+      if ((rc = ensure(ctx->ft_out, (size_t)out_pos * sizeof(float))) != AFX_OK) return rc;
+      d_out = (float*)ctx->ft_out.p;
+    }
+    HIP_TRY(hipMemcpyAsync(ctx->ft_clips.p, recs.data(), n * sizeof(FiltClip), hipMemcpyHostToDevice, s));
+    const FiltClip* d_clips = (const FiltClip*)ctx->ft_clips.p;
+    FiltState* d_st = (FiltState*)ctx->ft_st.p;
+    double *W = (double*)ctx->ft_w.p, *carry = (double*)ctx->ft_carry.p, *tmax = (double*)ctx->ft_tmax.p;
+    const bool plain = mode == AFX_FILT_PLAIN;
+    HIP_TRY(launch_filt_peak(s, d_in, sample_fmt, d_clips, n, d_st));
+    HIP_TRY(launch_filt_forward(s, d_in, sample_fmt, mode, -preemph, padlen, n_sections, d_tab, d_clips, n, nt, d_st, W, carry));
+    HIP_TRY(launch_filt_scan(s, padlen, n_sections, d_tab, d_clips, n, d_st, carry, false));
+    HIP_TRY(launch_filt_backward(s, padlen, n_sections, d_tab, d_clips, n, nt, d_st, W, carry));
+    HIP_TRY(launch_filt_scan(s, padlen, n_sections, d_tab, d_clips, n, d_st, carry, true));
+    HIP_TRY(launch_filt_final(s, padlen, n_sections, d_tab, d_clips, n, nt, d_st, W, carry, tmax, plain ? d_out : nullptr));
+    HIP_TRY(launch_filt_clipmax(s, d_clips, n, tmax, d_st));
+    if (!plain) HIP_TRY(launch_filt_scale(s, padlen, d_clips, n, nt, d_st, W, d_out));
+    h_st.resize(n);
+    HIP_TRY(hipMemcpyAsync(h_st.data(), d_st, n * sizeof(FiltState), hipMemcpyDeviceToHost, s));
+    if (h_out) {
+      stage_out.resize((size_t)out_pos);
+      HIP_TRY(hipMemcpyAsync(stage_out.data(), d_out, (size_t)out_pos * sizeof(float), hipMemcpyDeviceToHost, s));
+    }
+    HIP_TRY(hipStreamSynchronize(s));
+    for (int q = 0; q < n; ++q) {
+      const int i = idx[q];
+      if (h_st[q].bad) { out_status[i] = AFX_CLIP_NONFINITE; continue; }     // its output range stays as the caller left it
+      if (out_peak) { out_peak[2 * i] = (double)h_st[q].peak_in; out_peak[2 * i + 1] = h_st[q].peak_out; }
+      if (h_out) std::memcpy(out + out_offsets[i], stage_out.data() + recs[q].out_off, (size_t)recs[q].n * sizeof(float));
+    }
+  }
+  return AFX_OK;
+}

@@ -14,6 +14,7 @@
 #include "afx_decode.h"
 #include "afx_device.h"
 #include "afx_f0.h"
+#include "afx_filt.h"
 #include "afx_frames3.h"
 #include "afx_internal.h"
 #include "afx_resample.h"
@@ -43,6 +44,9 @@ struct afx_ctx {
   } rs;
   DevBuf rs_g, rs_tstart, rs_clips, rs_in, rs_out;
   DevBuf dc_clips, dc_in, dc_out;      // afx_decode_batch: clip records, staging of host batches
+  // afx_sosfiltfilt_batch: tables, a chunk's clip records and states, the float64 workspace, the blocks' carries, the tile
+  // maxima, staging of host batches
+  DevBuf ft_tab, ft_clips, ft_st, ft_w, ft_carry, ft_tmax, ft_in, ft_out;
 };
 
 struct afx_plan {

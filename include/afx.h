@@ -456,6 +456,50 @@ int afx_resample_batch(afx_ctx* ctx, const void* samples, int sample_fmt, int me
                        const double* taps, int n_taps, float* out, int out_mem_kind,
                        const int64_t* out_offsets, int64_t* out_lengths);
 
+/* Zero-phase IIR filtering with scipy.signal.filtfilt semantics on cascaded second-order sections, and the experiment
+ * extractor's preprocess_audio (04_feature_extraction_experiment/feature_extractor.py:133-154) around it.  All four symbols
+ * are newer than AFX_VERSION 107 says: a binding detects them by their presence.
+ *
+ * The filter.  For a clip x[0 .. n) of float32 samples (S16: value / 32768), sections sos[S][6] = b0 b1 b2 1 a1 a2 (float64,
+ * a0 == 1, 1 <= S <= 4) and padlen (0 .. 4096; 18 is scipy's default for the experiment's 5th-order filter):
+ *   - odd extension by padlen on both sides, 2 x[0] - x[padlen .. 1] and 2 x[n - 1] - x[n - 2 .. n - padlen - 1], in the
+ *     samples' float32 (what scipy computes for a float32 array);
+ *   - a forward pass of the cascade in float64 from its step steady state (scipy.signal.sosfilt_zi) times the first extended
+ *     sample, a backward pass from the steady state times the forward pass's last output, the extension stripped;
+ *   - AFX_FILT_PLAIN: one rounding to float32.
+ * AFX_FILT_EXPERIMENT does the whole preprocess_audio: x / max|x| in float32 (unchanged when the peak is below FLT_MIN);
+ * librosa's pre-emphasis in float32 with its initial state (u[0] = x[0] + (2 x[0] - x[1]), u[i] = x[i] + (-preemph) x[i - 1],
+ * product and sum rounded separately); the filter above in float64; y / max|y| in float64 (unchanged below DBL_MIN); one
+ * rounding to float32.
+ * Per clip: AFX_CLIP_TOO_SHORT for n <= padlen (scipy raises; length 0 included) and AFX_CLIP_NONFINITE for a NaN / inf
+ * sample -- the output range of such a clip is not written; an all-zero clip is AFX_CLIP_OK with zeros out.
+ * The passes are computed in blocks of 64 samples whose end states are carried in the per-section state basis (see
+ * afx_filtfilt_geometry and DESIGN.md); results are bit-reproducible (no atomics, one fixed order of fused multiply-adds),
+ * a clip never reads its neighbours in the packed buffer, and its result depends neither on the rest of the batch nor on how
+ * the batch was cut into chunks.
+ *
+ * afx_butter_sos (host-only): the digital Butterworth filter of scipy.signal.butter(order, wn, output='sos') by the bilinear
+ * transform, (order + 1) / 2 rows of six; every section has unit gain at the far end of the pass band, so the rows are not
+ * scipy's but their product is.  order 1 .. 8 (AFX_ERR_UNSUPPORTED above), 0 < wn < 1 (1 = Nyquist; AFX_ERR_INVALID otherwise).
+ * afx_filtfilt_geometry (host-only): info[4] = samples per block, blocks per tile, most sections, largest padlen.
+ * afx_sosfiltfilt_host (host-only): one host clip through the same block decomposition, tables and fused operations in
+ * float64 on the CPU -- the specification of the kernels.  out_peak (NULL ok): max|x|, max|y| before the last scaling.
+ * afx_sosfiltfilt_batch: clip i = samples[offsets[i] .. + lengths[i]) (AFX_FMT_F32 / AFX_FMT_S16, host or device memory) is
+ * written to out[out_offsets[i] .. + lengths[i]) in host or device memory (out_mem_kind); out_peak (host, NULL ok) receives
+ * max|x| and max|y| per clip (zeros for a failed one), out_status (host) the afx_clip_status.  AFX_ERR_UNSUPPORTED for more
+ * than 4 sections or padlen > 4096; AFX_ERR_INVALID for negative offsets / lengths, an unknown mode, or sections that are
+ * not finite, not normalised to a0 = 1, or have a pole at z = 1. */
+enum { AFX_FILT_PLAIN = 0, AFX_FILT_EXPERIMENT = 1 };
+int afx_butter_sos(int order, double wn, int highpass, double* sos /*[(order + 1) / 2][6]*/);
+int afx_filtfilt_geometry(int32_t* info /*[4]*/);
+int afx_sosfiltfilt_host(const void* samples, int sample_fmt, int64_t n, const double* sos, int n_sections, int padlen,
+                         int mode, float preemph, float* out, double* out_peak /*[2]*/, int32_t* out_status);
+int afx_sosfiltfilt_batch(afx_ctx* ctx, const void* samples, int sample_fmt, int mem_kind,
+                          const int64_t* offsets, const int64_t* lengths, int n_clips,
+                          const double* sos, int n_sections, int padlen, int mode, float preemph,
+                          float* out, int out_mem_kind, const int64_t* out_offsets,
+                          double* out_peak /*[n_clips][2]*/, int32_t* out_status);
+
 /* Host-only (no device needed): the real FFT the frame kernel of the frame lengths that are not powers of two runs
  * (k_frames_mr), executed in float32 on the CPU with the same radix schedule, twiddle tables and operation order:
  * n_fft / 2 complex points through Stockham passes of radix 3, 5, 4, 8, then the real-FFT split.  out holds the

@@ -1,0 +1,166 @@
+"""Host-side checks of the zero-phase filter: afx_butter_sos against scipy, the symbols, the Python argument refusals, and
+afx_sosfiltfilt_host -- the kernels' block decomposition, tables and operation order run on the CPU -- against the
+restatement tests/filt_ref.py on the shape list of the GPU tests, at every rate, to the tolerance of filt_ref.  CPU only."""
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+import scipy.signal
+
+from tests import filt_ref as F
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "audio_feature_extraction_amd", "csrc")
+
+
+@pytest.fixture(scope="module")
+def N():
+    from audio_feature_extraction_amd import _native
+    return _native
+
+
+@pytest.mark.parametrize("highpass", [False, True])
+@pytest.mark.parametrize("order", range(1, 9))
+def test_butter_sos_has_scipys_response(N, order, highpass):
+    """compared through sosfreqz at 512 frequencies: the sections differ (unit gain each, another order), the cascade must
+    not.  1e-10 of the unit pass-band gain: coefficient rounding (1e-16) over the smallest pole distance from the unit
+    circle squared (wn = 0.01: 1e-4 at order 8) leaves 1e-12, with two decades of room."""
+    for wn in (0.01, 200 / 11025, 0.25, 0.5, 0.9):
+        sos = N.butter_sos(order, wn, highpass)
+        assert sos.shape == ((order + 1) // 2, 6) and (sos[:, 3] == 1).all()
+        ref = scipy.signal.butter(order, wn, "high" if highpass else "low", output="sos")
+        _, h = scipy.signal.sosfreqz(sos, 512)
+        _, hr = scipy.signal.sosfreqz(ref, 512)
+        assert np.max(np.abs(h - hr)) <= 1e-10, (order, wn, np.max(np.abs(h - hr)))
+        assert np.all(np.abs(np.roots([1, sos[0, 4], sos[0, 5]])) < 1)
+
+
+def test_butter_sos_refusals(N):
+    from audio_feature_extraction_amd import filters
+    with pytest.raises(NotImplementedError):
+        N.butter_sos(9, 0.1, True)
+    for wn in (0.0, 1.0, -0.1, 1.5, float("nan")):
+        with pytest.raises(ValueError, match="Digital filter critical frequencies must be 0 < Wn < 1"):
+            filters.butter_sos(5, wn, "high")
+    with pytest.raises(ValueError, match="is an invalid bandtype for filter"):
+        filters.butter_sos(5, 0.1, "nonsense")
+    with pytest.raises(ValueError, match="not supported"):
+        filters.butter_sos(5, 0.1, "bandpass")
+    with pytest.raises(ValueError):
+        filters.butter_sos(0, 0.1, "low")
+    np.testing.assert_array_equal(filters.butter_sos(5, 0.1, "highpass"), N.butter_sos(5, 0.1, True))
+
+
+def test_symbols_are_declared_bound_and_stubbed(N):
+    header = open(os.path.join(ROOT, "include", "afx.h")).read()
+    names = ("afx_butter_sos", "afx_filtfilt_geometry", "afx_sosfiltfilt_host", "afx_sosfiltfilt_batch")
+    for name in names:
+        assert name in N.SYMBOLS
+        assert re.search(r"\bint\s+" + name + r"\s*\(", header), name
+        assert hasattr(N.lib(), name)
+    assert re.search(r"#define\s+AFX_VERSION\s+107\b", header)                  # found by their presence
+    stubs = open(os.path.join(CSRC, "afx_host_stubs.cpp")).read()
+    assert "afx_sosfiltfilt_batch" in stubs
+    for name in names[:3]:                                                      # real in the host build
+        assert not re.search(r"\bint\s+" + name + r"\s*\(", stubs), name
+    mk = open(os.path.join(CSRC, "Makefile")).read()
+    asan_srcs = re.search(r"^ASAN_SRCS := (.*)$", mk, re.M).group(1)
+    assert "afx_filt_host.cpp" in asan_srcs and "afx_filt.hip" not in asan_srcs
+    assert "afx_filt.o" in mk and "afx_filt_host.o" in mk and "filtfilt-check:" in mk
+
+
+def test_geometry(N):
+    g = N.filtfilt_geometry()
+    assert g["tile"] == g["block"] * g["tile_blocks"] and g["block"] > 2 * F.PADLEN + 1 and g["max_sections"] == 4
+    assert g["max_padlen"] >= F.PADLEN
+
+
+def test_python_argument_checks():
+    """every refusal comes before a device is touched"""
+    from audio_feature_extraction_amd import filters, AudioFeatureExtractor
+    sos = filters.butter_sos(5, 0.1, "high")
+    x = np.zeros(100, np.float32)
+    with pytest.raises(ValueError, match=r"sos array must be shape \(n_sections, 6\)"):
+        filters.sosfiltfilt(np.zeros((3, 5)), x)
+    bad = sos.copy()
+    bad[1, 3] = 2.0
+    with pytest.raises(ValueError, match="should be all ones"):
+        filters.sosfiltfilt(bad, x)
+    with pytest.raises(NotImplementedError):
+        filters.sosfiltfilt(np.tile(sos[:1], (5, 1)), x)
+    with pytest.raises(ValueError, match="The length of the input vector x must be greater than padlen, which is 18."):
+        filters.sosfiltfilt(sos, x[:18])
+    with pytest.raises(ValueError, match="greater than padlen, which is 18"):
+        filters.filtfilt(*F.butter_ba(22050), x[:18])
+    with pytest.raises(ValueError, match="1-D"):
+        filters.sosfiltfilt(sos, np.zeros((2, 100), np.float32))
+    with pytest.raises(ValueError, match="1-D"):
+        filters.sosfiltfilt_batch(sos, [x, np.zeros((2, 100), np.float32)])
+    with pytest.raises(ValueError):
+        filters.sosfiltfilt(sos, x, padlen=-1)
+    assert filters.sosfiltfilt_batch(sos, []) == [] and filters.preprocess_experiment_batch([], 22050) == []
+    assert filters._default_padlen(sos) == 18 == filters.EXPERIMENT_PADLEN
+    assert callable(AudioFeatureExtractor.preprocess_experiment) and callable(AudioFeatureExtractor.preprocess_experiment_batch)
+
+
+def _sos(N, sr):
+    return N.butter_sos(5, 200 / (sr / 2), True)
+
+
+@pytest.mark.parametrize("sr", F.RATES)
+def test_host_executor_matches_the_restatement(N, sr):
+    """both modes on every shape of the GPU tests: pins the decomposition before any GPU run"""
+    g = N.filtfilt_geometry()
+    worst = [0.0, 0.0]
+    for k, n in enumerate(F.shape_lengths(g["block"], g["tile"])):
+        y = F.signal(n, sr, 100 + k)
+        plain = N.sosfiltfilt_host(y, _sos(N, sr), F.PADLEN, N.FILT_PLAIN)
+        exp = N.sosfiltfilt_host(y, _sos(N, sr), F.PADLEN, N.FILT_EXPERIMENT, F.COEF)
+        assert plain["status"] == exp["status"] == N.CLIP_OK and plain["out"].dtype == np.float32
+        rp, re_ = F.highpass(y, sr), F.preprocess_experiment(y, sr)
+        r0, r1 = F.error_ratio(plain["out"], rp, y, sr), F.error_ratio(exp["out"], re_, F.filter_input(y), sr)
+        print(f"sr {sr} n {n}: plain {r0:.3f} experiment {r1:.3f} of the bound")
+        assert r0 <= 1.0 and r1 <= 1.0, (sr, n, r0, r1)
+        assert plain["peak"][0] == np.max(np.abs(y)) and plain["peak"][1] == pytest.approx(np.max(np.abs(rp)), rel=1e-6)
+        assert np.max(np.abs(exp["out"])) == 1.0
+        worst = [max(worst[0], r0), max(worst[1], r1)]
+    print(f"sr {sr}: largest ratios to the bound (plain, experiment): {worst[0]:.3f} {worst[1]:.3f}")
+
+
+def test_host_executor_s16_statuses_and_other_filters(N):
+    sr = 22050
+    sos = _sos(N, sr)
+    q = F.to_s16(F.signal(700, sr, 5))
+    y = q.astype(np.float32) / np.float32(32768.0)
+    np.testing.assert_array_equal(N.sosfiltfilt_host(q, sos, F.PADLEN, N.FILT_EXPERIMENT, F.COEF)["out"],
+                                  N.sosfiltfilt_host(y, sos, F.PADLEN, N.FILT_EXPERIMENT, F.COEF)["out"])
+    for n in (0, 1, F.PADLEN):
+        r = N.sosfiltfilt_host(np.ones(n, np.float32), sos, F.PADLEN)
+        assert r["status"] == N.CLIP_TOO_SHORT and not r["out"].any()
+    bad = F.signal(300, sr, 6)
+    bad[299] = np.inf
+    assert N.sosfiltfilt_host(bad, sos, F.PADLEN)["status"] == N.CLIP_NONFINITE
+    z = N.sosfiltfilt_host(np.zeros(300, np.float32), sos, F.PADLEN, N.FILT_EXPERIMENT, F.COEF)
+    assert z["status"] == N.CLIP_OK and not z["out"].any() and not z["peak"].any()
+    # an 8th-order low-pass in scipy's own sections, another padlen: against scipy.signal.sosfiltfilt itself
+    ref_sos = scipy.signal.butter(8, 0.2, output="sos")
+    x = F.signal(1000, sr, 7)
+    for padlen in (0, 27, 500):
+        got = N.sosfiltfilt_host(x, ref_sos, padlen)["out"]
+        ref = scipy.signal.sosfiltfilt(ref_sos, x, padlen=padlen)
+        assert np.max(np.abs(got - ref)) <= 2.0 ** -23 * np.max(np.abs(ref))
+    with pytest.raises(NotImplementedError):
+        N.sosfiltfilt_host(x, np.tile(ref_sos[:1], (5, 1)), 18)
+    with pytest.raises(ValueError):
+        N.sosfiltfilt_host(x, ref_sos * 2.0, 18)                                # a0 != 1
+    with pytest.raises(ValueError):
+        N.sosfiltfilt_host(x, ref_sos, 18, mode=7)
+
+
+def test_filtfilt_check_program_is_clean():
+    """the host executor and the design under AddressSanitizer + UBSan: a stand-alone program, nothing preloaded"""
+    r = subprocess.run(["make", "-C", CSRC, "filtfilt-check"], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    assert "filtfilt_check: ok" in r.stdout
