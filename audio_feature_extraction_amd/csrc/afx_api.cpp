@@ -36,6 +36,7 @@ DevEnv::DevEnv() {
   host_blocks = getenv("AFX_HOST_BLOCKS") != nullptr;
   no_fused_tail = getenv("AFX_NO_FUSED_TAIL") != nullptr;
   if (const char* v = getenv("AFX_F3_WAVES")) f3_waves = atoi(v);
+  if (const char* v = getenv("AFX_F3_SPARE_CUS")) f3_spare_cus = atoi(v) < 0 ? -2 : atoi(v);   // checked against the CU count by afx_extract_submit
   if (const char* v = getenv("AFX_TAIL_MODE")) tail_mode = atoi(v);
   if (const char* v = getenv("AFX_TAIL_SKIP")) tail_skip = atoi(v) & 7;
   if (const char* v = getenv("AFX_TEST_CHUNK_CLIPS")) chunk_clips = std::max(1, std::min(32768, atoi(v)));
@@ -150,6 +151,28 @@ static int upload(afx_plan* pl, const T* host, size_t count, const T** dev) {
   return AFX_OK;
 }
 
+// The submitted, uncollected batches of the process by device and stream (afx_extract_submit .. afx_extract_collect): a
+// speculative launch leaves CUs free only while a batch of another stream is in flight (f3_spare_cus).
+static std::mutex g_submitted_mu;
+static std::vector<std::pair<int, hipStream_t>> g_submitted;
+static bool other_stream_in_flight(int device, hipStream_t s) {
+  std::lock_guard<std::mutex> lk(g_submitted_mu);
+  for (const auto& e : g_submitted) if (e.first == device && e.second != s) return true;
+  return false;
+}
+static void list_submitted(afx_plan* pl, hipStream_t s) {
+  std::lock_guard<std::mutex> lk(g_submitted_mu);
+  g_submitted.emplace_back(pl->device, s);
+  pl->pend.listed = true; pl->pend.stream = s;
+}
+static void unlist_submitted(afx_plan* pl) {
+  if (!pl->pend.listed) return;
+  pl->pend.listed = false;
+  std::lock_guard<std::mutex> lk(g_submitted_mu);
+  const auto it = std::find(g_submitted.begin(), g_submitted.end(), std::make_pair(pl->device, pl->pend.stream));
+  if (it != g_submitted.end()) g_submitted.erase(it);
+}
+
 extern "C" int afx_plan_create(afx_ctx* ctx, const afx_params* p, afx_plan** out) {
   if (!ctx || !p || !out) { set_error("afx_plan_create: null argument"); return AFX_ERR_INVALID; }
   *out = nullptr;
@@ -246,6 +269,7 @@ extern "C" void afx_plan_destroy(afx_plan* pl) {
   if (!pl) return;
   (void)hipSetDevice(pl->device);
   if (pl->pend.active && pl->ctx) (void)hipStreamSynchronize(pl->ctx->stream);   // a submitted batch still writes the plan's memory
+  unlist_submitted(pl);
   for (void* d : pl->table_allocs) (void)hipFree(d);
   for (void* q : pl->f0_allocs) (void)hipFree(q);
   release(pl->f0_in); release(pl->f0_ysig); release(pl->f0_energy); release(pl->f0_cnt); release(pl->f0_vp);
@@ -594,6 +618,8 @@ static int chunk_enqueue(afx_plan* pl, const void* samples, int fmt, int mem_kin
     spec.blocks = (const BlockDesc*)pl->blocks_spec.p; spec.nblocks = pl->nblocks; spec.spec = true;
     spec.blockmax = (float*)pl->blockmax.p; spec.bsum = (float*)pl->bsum.p;
     spec.work_ctr = dev_env().no_tickets ? nullptr : (int*)pl->n_items.p + 1;
+    // a submitted batch (another plan's step may be in flight) with the fused tail leaves a few CUs free for that step's chain
+    if (by_event && fused_tail) spec.spare_cus = f3_spare_cus(kp, pl->nblocks, pl->n_cu, other_stream_in_flight(pl->device, s));
     TIMED(AFX_K_FRAMES, launch_frames3_any(spec));
     TIMED(AFX_K_TRIM_DECIDE, launch_trim_decide3(s, d_clips, d_info, (const float*)pl->bsum.p, (const float*)pl->blockmax.p,
                                                  (BlockDesc*)pl->items.p, (int*)pl->n_items.p, max_items, (float*)pl->rms.p, n, kp));
@@ -686,7 +712,7 @@ static int chunk_enqueue(afx_plan* pl, const void* samples, int fmt, int mem_kin
   }
   HIP_TRY(launch_finish(s, d_info, n, (int*)pl->n_items.p, by_event ? pl->flag_dev : nullptr, by_event ? ++pl->seq : 0u));
   pl->info_clean_n = n;
-  if (by_event) HIP_TRY(hipEventRecord(pl->done, s));
+  if (by_event) { HIP_TRY(hipEventRecord(pl->done, s)); list_submitted(pl, s); }
   pl->pend.active = true; pl->pend.n = n; pl->pend.stats_bytes = stats_bytes;
   pl->pend.out_stats = out_stats; pl->pend.out_status = out_status; pl->pend.out_trim = out_trim; pl->pend.out_nframes = out_nframes;
   return AFX_OK;
@@ -696,6 +722,7 @@ static int chunk_finish(afx_plan* pl, bool by_event) {
   if (!pl->pend.active) { set_error("afx_extract_collect: nothing submitted"); return AFX_ERR_INVALID; }
   hipStream_t s = pl->ctx->stream;
   pl->pend.active = false;          // whatever happens below, the chunk is over
+  unlist_submitted(pl);
   if (by_event) {
     // spin on the flag; every so often ask the runtime, so that a failed launch ends the wait with its error
     for (unsigned it = 1; *pl->flag != pl->seq; ++it) {
@@ -763,6 +790,10 @@ extern "C" int afx_extract_submit(afx_plan* pl, const void* samples, int sample_
   if (n_clips == 0) { set_error("afx_extract_submit: empty batch"); return AFX_ERR_INVALID; }
   if (n_clips > dev_env().chunk_clips) { set_error("afx_extract_submit: more clips than one chunk holds; use afx_extract_batch"); return AFX_ERR_UNSUPPORTED; }
   if (pl->pend.active) { set_error("afx_extract_submit: the plan's previous batch has not been collected"); return AFX_ERR_INVALID; }
+  if (const int r = dev_env().f3_spare_cus; r != -1) {          // the developer switch, against this device
+    if (r < 0 || r % kF3Xcds) { set_error("AFX_F3_SPARE_CUS must be a non-negative multiple of 8 (one CU per XCD)"); return AFX_ERR_INVALID; }
+    if (r > pl->n_cu / 4) { set_error("AFX_F3_SPARE_CUS is above a quarter of the device's CUs"); return AFX_ERR_INVALID; }
+  }
   (void)hipGetLastError();
   HIP_TRY(hipSetDevice(pl->device));
   rc = chunk_enqueue(pl, samples, sample_fmt, mem_kind, offsets, lengths, n_clips, flags, out_stats, out_status, out_trim,

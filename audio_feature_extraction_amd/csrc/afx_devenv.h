@@ -20,6 +20,8 @@ struct DevEnv {
                                       // 5 / 6 one slot per wave + register-held images with four workgroups per CU, default / nt DMA (A/B)
   int tail_skip = 0;                  // libafx_dbg.so only: timing ablations of k_tail's one-slot form (1 no arithmetic, 2 no DMA, 4 no epilogue)
   int f3_waves = 0;                   // 12 / 16: force the workgroup size of the wave-level frame kernels
+  int f3_spare_cus = -1;              // AFX_F3_SPARE_CUS: workgroups taken off the speculative frame launch of a submitted batch, whatever its
+                                      // size (>= 0; -1 unset: the per-shape default on full grids only; -2 a negative value was given)
   int chunk_clips = 32768;
   int64_t f0_chunk_frames = 1280 * 1024;
   int64_t dtw_budget = (int64_t)2 << 30;   // device workspace bytes of one afx_dtw_batch chunk

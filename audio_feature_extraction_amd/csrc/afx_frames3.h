@@ -71,11 +71,21 @@ struct F3Launch {
   float* bsum = nullptr;
   bool spec = false;
   int* work_ctr = nullptr;
+  int spare_cus = 0;        // workgroups left off the grid (f3_spare_cus): on a full grid, CUs the launch never occupies
 };
-inline int f3_grid(const F3Launch& L, int waves) {      // one workgroup per CU at most, a block per wave at least
+// one workgroup per CU at most, a block per wave at least, less the spare ones (at least one stays).  The kernels take their
+// shares and ticket runs from gridDim.x, so any grid computes every block.
+inline int f3_grid(const F3Launch& L, int waves) {
   const int want = (L.nblocks + waves - 1) / waves;
-  return want < 1 ? 1 : (want < L.n_cu ? want : L.n_cu);
+  const int g = (want < L.n_cu ? want : L.n_cu) - L.spare_cus;
+  return g < 1 ? 1 : g;
 }
+// CUs the speculative launch of a submitted batch leaves free, so that the decide / redo / tail / finish chain of the other
+// plan's step in flight is placed while this launch runs.  A multiple of the XCD count -- workgroups are dealt
+// to the XCDs in turn, so each XCD keeps spare / kF3Xcds CUs -- and a quarter of the chip at most.
+// other_in_flight: a submitted batch of another stream of the device has not been collected yet.
+constexpr int kF3Xcds = 8;
+int f3_spare_cus(const KParams& kp, int nblocks, int n_cu, bool other_in_flight);     // afx_frames3.hip: the per-shape default, or the switch
 // n_fft 1024 / hop 256 (afx_frames3.hip), n_fft 2048 / hop 512 (afx_frames3s.hip: one frame per FFT, real-FFT split) and
 // n_fft 512 / hop 128 (afx_frames3d.hip: two frame pairs per wave); launch_frames3_any dispatches on kp.n_fft
 size_t frames3s_lds_bytes(int waves, const F3Tables& ft);

@@ -34,6 +34,7 @@
 //           the lane then owns Z[k] and Z[N-k], so X_A, X_B follow with adds only.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdlib>
 #include <type_traits>
 
@@ -531,6 +532,21 @@ int frames3_waves(const F3Tables& ft) {
   const int forced = dev_env().f3_waves;
   if (forced == 12 || forced == 16) return frames3_lds_bytes(forced, ft) <= 160 * 1024 ? forced : 12;
   return frames3_lds_bytes(16, ft) <= 160 * 1024 ? 16 : 12;
+}
+
+// Spare CUs of a submitted batch's speculative launch.  The switch takes its workgroups off any grid (tests reach the small
+// grids with it).  The default applies while another stream has a submitted batch in flight -- alone on the device, or
+// behind the other plan on one stream, the launch would only run on fewer CUs -- to a grid that is full, with at least the
+// initial share and one ticket run per wave.  It is per shape, from same-box A/B runs (profiles/spare_cus_ab.txt): two CUs
+// per shader engine at 1024 / 256 and 512 / 128; at 2048 / 512 no count gained more than the runs scatter.  Counts that
+// leave a shader engine without a free CU (8, 16, 24 of 256) gain nothing: the chain's workgroups are dealt to the engines
+// in turn and wait at the first full one.
+int f3_spare_cus(const KParams& kp, int nblocks, int n_cu, bool other_in_flight) {
+  const int forced = dev_env().f3_spare_cus;
+  if (forced >= 0) return forced;
+  if (!other_in_flight || nblocks < 2 * 16 * n_cu) return 0;
+  const int r = ((kp.n_fft == 1024 && kp.hop == 256) || (kp.n_fft == 512 && kp.hop == 128)) ? 64 : 0;
+  return std::min(r, n_cu / 4 / kF3Xcds * kF3Xcds);
 }
 
 template <int FMT, int WAVES, int NB0, int NB1, bool SPEC>

@@ -98,6 +98,8 @@ struct afx_plan {
   // a submitted, not yet collected chunk (afx_extract_submit / afx_extract_collect; afx_extract_batch = both, per chunk)
   struct Pending {
     bool active = false;
+    bool listed = false;             // in the list of submitted batches (afx_api.cpp) under `stream`
+    hipStream_t stream = nullptr;
     int n = 0;
     size_t stats_bytes = 0;
     float* out_stats = nullptr; int32_t* out_status = nullptr; int64_t* out_trim = nullptr; int32_t* out_nframes = nullptr;
