@@ -34,6 +34,10 @@ SMP_BYTES = np.array([1, 2, 3, 4, 4, 8], np.int64)
 SMP_OF_WAV = {(1, 8): SMP_U8, (1, 16): SMP_S16, (1, 24): SMP_S24, (1, 32): SMP_S32, (3, 32): SMP_F32, (3, 64): SMP_F64}   # (tag, bits)
 DECODE_MAX_CHANNELS = 7
 FILT_PLAIN, FILT_EXPERIMENT = 0, 1
+GROUP_SPECTRAL, GROUP_HARMONIC, GROUP_TIMBRE, GROUP_RHYTHM = 1, 2, 4, 8     # afx_groups_batch: the groups asked for
+GROUP_ALL = 15
+GROUPS_PREPROCESS, GROUPS_STORE_DESC = 16, 32                                # its flags, beside FLAG_PREEMPH
+GROUPS_STATS = 24                                                            # doubles per clip of its record
 K_NAMES = ("trim_blocks", "trim_decide", "frames", "dct", "stats")
 K_FRAMES = 2
 
@@ -48,6 +52,7 @@ SYMBOLS = (
     "afx_chroma_batch", "afx_chroma_filters", "afx_rhythm_batch", "afx_tempo_table",
     "afx_stft_chunks",
     "afx_butter_sos", "afx_filtfilt_geometry", "afx_sosfiltfilt_host", "afx_sosfiltfilt_batch",
+    "afx_groups_batch", "afx_groups_cost", "afx_groups_dct_table", "afx_groups_debug_rows",
 )
 
 
@@ -137,6 +142,11 @@ def lib() -> C.CDLL:
             L.afx_filtfilt_geometry.argtypes = [vp]
             L.afx_sosfiltfilt_host.argtypes = [vp, i32, C.c_int64, vp, i32, i32, i32, C.c_float, vp, vp, vp]
             L.afx_sosfiltfilt_batch.argtypes = [vp, vp, i32, i32, vp, vp, i32, vp, i32, i32, i32, C.c_float, vp, i32, vp, vp, vp]
+        if hasattr(L, "afx_groups_batch"):                   # newer than version 107 says: found by their presence
+            L.afx_groups_batch.argtypes = [vp, vp, i32, i32, vp, vp, i32, i32, i32, vp, vp, vp, vp]
+            L.afx_groups_cost.argtypes = [i32, i32, vp]
+            L.afx_groups_dct_table.argtypes = [i32, vp]
+            L.afx_groups_debug_rows.argtypes = [vp, vp, C.c_int64, i64p]
         if hasattr(L, "afx_rfft_host"):                      # absent from a library built before the mixed-radix lengths
             L.afx_rfft_host.argtypes = [i32, vp, vp]
         _lib = L
@@ -304,6 +314,29 @@ def stft_chunks(lengths, cost, budget: int) -> np.ndarray:
     out = np.zeros(lengths.shape[0], np.int32)
     _check(lib().afx_stft_chunks(lengths.ctypes.data, int(lengths.shape[0]), cost.ctypes.data, int(budget), out.ctypes.data),
            "afx_stft_chunks")
+    return out
+
+
+def _need_groups():
+    if not hasattr(lib(), "afx_groups_batch"):
+        raise NotImplementedError("this libafx has no afx_groups_batch")
+
+
+def groups_cost(groups: int, flags: int = 0) -> np.ndarray:
+    """Host-only: the cost record afx_groups_batch cuts a batch with (bytes per frame, per tile, per sample and per clip,
+    frames per tile, most tiles of a chunk), for ``stft_chunks``."""
+    _need_groups()
+    cost = np.zeros(6, np.int64)
+    _check(lib().afx_groups_cost(int(groups), int(flags), cost.ctypes.data), "afx_groups_cost")
+    return cost
+
+
+def groups_dct_table(n_mels: int = 128) -> np.ndarray:
+    """Host-only: rows 0 .. 12 of the orthonormal DCT-II of ``n_mels`` points as afx_groups_batch's MFCC statistics apply
+    them, [13, 128] float32 (columns past ``n_mels`` zero)."""
+    _need_groups()
+    out = np.zeros((13, 128), np.float32)
+    _check(lib().afx_groups_dct_table(int(n_mels), out.ctypes.data), "afx_groups_dct_table")
     return out
 
 
@@ -978,6 +1011,39 @@ class Plan(_Owner):
             out["acmean"] = acmean
         if want_stats:
             out["stats"] = stats
+        return out
+
+    def groups_batch(self, samples, offsets, lengths, groups: int = GROUP_ALL, flags: int = 0, fmt=FMT_F32, mem=MEM_HOST,
+                     preprocess: bool = False, store_desc: bool = False) -> dict:
+        """afx_groups_batch: the spectral, harmonic, timbre and rhythm groups of a ragged batch on one STFT (plan:
+        frame_length 2048, hop_length 512, Hann).  ``groups``: GROUP_* bits; ``preprocess``: the experiment extractor's
+        preprocess_audio on the device first.  Returns ``stats`` [n, 24] float64 (include/afx.h lists the fields; NaN for a
+        group not asked for and for a failed clip), ``tuning`` [n] float64, ``lag`` [n] int32, ``status`` [n] int32 and,
+        with ``store_desc`` (and GROUP_SPECTRAL), ``desc``: per clip the [T, 17] float32 rows of afx_spectral_batch's
+        layout (None for a clip of status CLIP_TOO_SHORT)."""
+        _need_groups()
+        offsets, lengths, n = _clip_arrays(offsets, lengths)
+        sptr, kind = _sample_source(samples, fmt, offsets, lengths, mem=mem)
+        if preprocess:
+            flags |= GROUPS_PREPROCESS
+        if store_desc:
+            flags |= GROUPS_STORE_DESC
+        stats = np.zeros((n, GROUPS_STATS), np.float64)
+        tuning, lag, status = np.zeros(n, np.float64), np.zeros(n, np.int32), np.zeros(n, np.int32)
+        _check(lib().afx_groups_batch(self.handle, sptr, int(fmt), kind, offsets.ctypes.data, lengths.ctypes.data, n,
+                                      int(flags), int(groups), stats.ctypes.data, tuning.ctypes.data, lag.ctypes.data,
+                                      status.ctypes.data), "afx_groups_batch")
+        out = {"stats": stats, "tuning": tuning, "lag": lag, "status": status}
+        if store_desc and groups & GROUP_SPECTRAL:
+            T = np.where(status == CLIP_TOO_SHORT, 0, 1 + lengths // self.params.hop)
+            rows = np.zeros(int(17 * T.sum()), np.float32)
+            count = C.c_int64()
+            _check(lib().afx_groups_debug_rows(self.handle, _ptr(rows) if rows.size else None, int(rows.size), C.byref(count)),
+                   "afx_groups_debug_rows")
+            if int(count.value) != rows.size:
+                raise AfxError(f"afx_groups_debug_rows: {count.value} floats kept, {rows.size} expected")
+            roff = packed_offsets(17 * T)
+            out["desc"] = [rows[roff[i]:roff[i] + 17 * T[i]].reshape(int(T[i]), 17) if T[i] else None for i in range(n)]
         return out
 
     def preprocess(self, y: np.ndarray):

@@ -399,6 +399,84 @@ class AudioFeatureExtractor:
         the GPU; the signal is taken as given and may be as short as one sample (tempo 0.0 up to three frames)."""
         return self.extract_rhythm_features_batch([y])[0]
 
+    _SPECTRAL_KEYS = tuple(f"spectral_{k}_{s}" for k in ("centroid", "bandwidth", "rolloff", "contrast") for s in ("mean", "std"))
+    _SIGNAL_GROUPS = ("spectral", "harmonic", "timbre", "rhythm")       # the reference's order in extract_all_features
+
+    @classmethod
+    def _group_bits(cls, groups: Sequence[str]) -> int:
+        if isinstance(groups, str):
+            groups = (groups,)
+        bits = 0
+        for g in groups:
+            if g not in cls._SIGNAL_GROUPS:
+                raise ValueError(f"unknown feature group {g!r}: expected some of {cls._SIGNAL_GROUPS}")
+            bits |= 1 << cls._SIGNAL_GROUPS.index(g)
+        if not bits:
+            raise ValueError(f"no feature group asked for: expected some of {cls._SIGNAL_GROUPS}")
+        return bits
+
+    def _signal_dict(self, bits: int, s: np.ndarray) -> Dict[str, Any]:
+        """One clip's record of afx_groups_batch as the merged dict, the asked groups in the reference's order."""
+        out: Dict[str, Any] = {}
+        if bits & _native.GROUP_SPECTRAL:
+            out.update(zip(self._SPECTRAL_KEYS, (float(v) for v in s[0:8])))
+        if bits & _native.GROUP_HARMONIC:
+            eh, ey, fm, fs = (float(v) for v in s[8:12])
+            out.update(zip(self._HARMONIC_KEYS, (eh, eh / (ey + 1e-8), fm, fs)))
+        if bits & _native.GROUP_TIMBRE:
+            out.update(zip(self._TIMBRE_KEYS, (float(v) for v in s[12:18])))
+        if bits & _native.GROUP_RHYTHM:
+            tempo, mean, std = (float(v) for v in s[18:21])
+            out.update(zip(self._RHYTHM_KEYS, (tempo, std / (mean + 1e-8), mean, std)))
+        return out
+
+    def _signal_features(self, signals: Sequence[np.ndarray], preprocess: bool, groups: Sequence[str]):
+        bits = self._group_bits(groups)
+        ys = [np.ascontiguousarray(y, dtype=np.float32) for y in signals]
+        for y in ys:
+            if y.ndim != 1:
+                raise ValueError(f"signals must be 1-D (mono), got shape {y.shape}")
+        if not ys:
+            return bits, None
+        lengths = np.array([y.size for y in ys], np.int64)
+        return bits, self._spectral_plan().groups_batch(np.concatenate(ys), _native.packed_offsets(lengths), lengths,
+                                                        groups=bits, preprocess=bool(preprocess))
+
+    def extract_signal_features_batch(self, signals: Sequence[np.ndarray], *, preprocess: bool = True,
+                                      groups: Sequence[str] = _SIGNAL_GROUPS) -> List[Optional[Dict[str, Any]]]:
+        """What the experiment extractor's ``extract_all_features`` computes per file from the signal
+        (04_feature_extraction_experiment/feature_extractor.py:624-687): its ``preprocess_audio`` and the spectral,
+        harmonic, timbre and rhythm groups, for many signals in one device pass -- one upload, one STFT, scalars back.
+        ``groups``: which of the four to compute; the dict holds their keys in the reference's order.  ``preprocess``
+        False takes the signals as given.  ``None`` for a clip the reference returns None for (its preprocess fails: 18
+        samples or fewer, or a NaN / inf sample; without the preprocess, an empty or non-finite clip)."""
+        bits, out = self._signal_features(signals, preprocess, groups)
+        if out is None:
+            return []
+        return [self._signal_dict(bits, out["stats"][i]) if st == _native.CLIP_OK else None
+                for i, st in enumerate(out["status"])]
+
+    def extract_signal_features(self, y: np.ndarray, *, preprocess: bool = True,
+                                groups: Sequence[str] = _SIGNAL_GROUPS) -> Dict[str, Any]:
+        """``extract_signal_features_batch`` of one signal; raises ``ValueError`` where that gives ``None``."""
+        bits, out = self._signal_features([y], preprocess, groups)
+        if out["status"][0] != _native.CLIP_OK:
+            raise _status_error(int(out["status"][0]), "extract_signal_features", int(np.size(y)))
+        return self._signal_dict(bits, out["stats"][0])
+
+    def extract_signal_features_files(self, paths: Sequence[str], *, preprocess: bool = True,
+                                      groups: Sequence[str] = _SIGNAL_GROUPS) -> List[Optional[Dict[str, Any]]]:
+        """``extract_signal_features_batch`` of WAV files loaded at this extractor's ``sr`` (``wavio.load_batch``), each dict
+        with the file's ``filename`` added, as the reference's ``extract_all_features`` adds it."""
+        import os
+        paths = [str(p) for p in paths]
+        res = self.extract_signal_features_batch([y for y, _ in wavio.load_batch(paths, sr=self.sr)],
+                                                 preprocess=preprocess, groups=groups)
+        for p, d in zip(paths, res):
+            if d is not None:
+                d["filename"] = os.path.basename(p)
+        return res
+
     def preprocess_experiment_batch(self, signals: Sequence[np.ndarray]) -> List[Optional[np.ndarray]]:
         """``preprocess_experiment`` of many signals in one device pass; ``None`` for a clip the reference's
         ``preprocess_audio`` returns None for (18 samples or fewer, or not finite)."""

@@ -45,6 +45,7 @@ DevEnv::DevEnv() {
   if (const char* v = getenv("AFX_TEST_HPSS_BUDGET")) hpss_budget = std::max<int64_t>(1, atoll(v));
   if (const char* v = getenv("AFX_TEST_CHROMA_BUDGET")) chroma_budget = std::max<int64_t>(1, atoll(v));
   if (const char* v = getenv("AFX_TEST_RHYTHM_BUDGET")) rhythm_budget = std::max<int64_t>(1, atoll(v));
+  if (const char* v = getenv("AFX_TEST_GROUPS_BUDGET")) groups_budget = std::max<int64_t>(1, atoll(v));
   if (const char* v = getenv("AFX_TEST_FILT_BUDGET")) filt_budget = std::max<int64_t>(1, atoll(v));
   f0_dump = getenv("AFX_F0_DUMP");
 }
@@ -282,7 +283,9 @@ extern "C" void afx_plan_destroy(afx_plan* pl) {
   for (DevBuf* b : {&pl->hp_clips, &pl->hp_y, &pl->hp_h, &pl->hp_p, &pl->hp_x, &pl->hp_yh, &pl->hp_yp, &pl->hp_bad, &pl->hp_stats, &pl->hp_spec,
                     &pl->ch_grid, &pl->ch_extra, &pl->ch_mel, &pl->ch_s, &pl->ch_mag, &pl->ch_bin, &pl->ch_slot, &pl->ch_hist, &pl->ch_chroma,
                     &pl->ch_melout, &pl->ch_parts,
-                    &pl->rh_tab, &pl->rh_db, &pl->rh_max, &pl->rh_env, &pl->rh_parts, &pl->rh_tg, &pl->rh_acmean, &pl->rh_res})
+                    &pl->rh_tab, &pl->rh_db, &pl->rh_max, &pl->rh_env, &pl->rh_parts, &pl->rh_tg, &pl->rh_acmean, &pl->rh_res,
+                    &pl->gp_clips64, &pl->gp_in, &pl->gp_filt, &pl->gp_desc, &pl->gp_hdesc, &pl->gp_doff, &pl->gp_sstats, &pl->gp_cstats,
+                    &pl->gp_mparts, &pl->gp_mstats, &pl->gp_dct, &pl->gp_rec, &pl->gp_ints})
     release(*b);
   if (pl->h_pin) (void)hipHostFree(pl->h_pin);
   if (pl->h_clips_pin) (void)hipHostFree(pl->h_clips_pin);

@@ -1,8 +1,8 @@
 // The plan-based feature entry points of libafx.so beside the MFCC / RMS pipeline (afx_api.cpp): pYIN f0, zero-crossing
 // rate, the spectral descriptors, preprocess_audio, and the three STFT-based groups -- harmonic-percussive separation,
 // chroma / tuning / mel power, onset strength / tempogram / tempo -- which run in chunks on one front end of their own
-// (check_stft_plan .. end_stft_chunk below).  Each reads: check -> begin -> stage -> its own work -> finish, on the front end
-// of afx_plan.h.
+// (check_stft_plan .. end_stft_chunk below), and afx_groups_batch, the pass that runs all of them on one STFT.  Each reads:
+// check -> begin -> stage -> its own work -> finish, on the front end of afx_plan.h.
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -16,6 +16,7 @@
 #include "afx_devenv.h"
 #include "afx_f0.h"
 #include "afx_frames3.h"
+#include "afx_groups.h"
 #include "afx_hpss.h"
 #include "afx_internal.h"
 #include "afx_plan.h"
@@ -486,6 +487,17 @@ static int chroma_setup(afx_plan* pl) {
   return AFX_OK;
 }
 
+// piptrack's band, with the spec's own comparisons: 150 <= k sr / 2048 < min(4000, sr / 2), inside bins 1 .. 1023
+static ChromaBand piptrack_band(int sr) {
+  ChromaBand band{1, 0, (float)((double)sr / 2048.0)};
+  const double df = (double)sr / 2048.0, fmax = std::min(4000.0, 0.5 * sr);
+  int k0 = -1, k1 = -1;
+  for (int k = 1; k < 1024; ++k)
+    if ((double)k * df >= 150.0 && (double)k * df < fmax) { if (k0 < 0) k0 = k; k1 = k; }
+  if (k0 > 0) { band.kmin = k0; band.nr = k1 - k0 + 1; }
+  return band;
+}
+
 extern "C" int afx_chroma_batch(afx_plan* pl, const void* samples, int sample_fmt, int mem_kind,
                                 const int64_t* offsets, const int64_t* lengths, int n_clips, int flags,
                                 const double* tuning_in, float* out_chroma, const int64_t* chroma_off,
@@ -520,15 +532,7 @@ extern "C" int afx_chroma_batch(afx_plan* pl, const void* samples, int sample_fm
   if ((rc = begin_plan_call(who, pl)) != AFX_OK) return rc;
   if ((rc = chroma_setup(pl)) != AFX_OK) return rc;
   hipStream_t s = pl->ctx->stream;
-  // piptrack's band, with the spec's own comparisons: 150 <= k sr / 2048 < min(4000, sr / 2), inside bins 1 .. 1023
-  ChromaBand band{1, 0, (float)((double)pl->p.sr / 2048.0)};
-  {
-    const double df = (double)pl->p.sr / 2048.0, fmax = std::min(4000.0, 0.5 * pl->p.sr);
-    int k0 = -1, k1 = -1;
-    for (int k = 1; k < 1024; ++k)
-      if ((double)k * df >= 150.0 && (double)k * df < fmax) { if (k0 < 0) k0 = k; k1 = k; }
-    if (k0 > 0) { band.kmin = k0; band.nr = k1 - k0 + 1; }
-  }
+  const ChromaBand band = piptrack_band(pl->p.sr);
   const bool est = tuning_in == nullptr, want_mel = out_mel || out_stats;
   const HpssTabs tb{pl->f3.window, pl->f3.w1024, pl->f3.w2048};
   StftCost cost{};
@@ -746,5 +750,293 @@ extern "C" int afx_rhythm_batch(afx_plan* pl, const void* samples, int sample_fm
       if (out_stats) { out_stats[2 * i] = h_res[4 * (size_t)q + 1]; out_stats[2 * i + 1] = h_res[4 * (size_t)q + 2]; }
     }
   }
+  return AFX_OK;
+}
+
+// ---- the spectral, harmonic, timbre and rhythm groups on one STFT (04_feature_extraction_experiment/feature_extractor.py:624-687;
+// DESIGN.md 18) ------------------------------------------------------------------------------------------------------------
+// the MFCC table, at first use
+static int groups_setup(afx_plan* pl) {
+  if (pl->gp_dct.p) return AFX_OK;
+  std::vector<float> t((size_t)kGroupsMfcc * kRhMels);
+  groups_dct_table(pl->p.n_mels, t.data());
+  DevBuf b;
+  int rc;
+  if ((rc = ensure(b, t.size() * sizeof(float))) != AFX_OK) return rc;
+  hipError_t e = hipMemcpy(b.p, t.data(), t.size() * sizeof(float), hipMemcpyHostToDevice);
+  if (e != hipSuccess) { release(b); set_error(std::string("afx_groups_batch: table upload: ") + hipGetErrorString(e)); return AFX_ERR_HIP; }
+  pl->gp_dct = b;                                      // set last: its presence marks the table as ready
+  return AFX_OK;
+}
+
+// The experiment preprocess of a cut chunk, with the launchers and in the order of afx_sosfiltfilt_batch: the clips of ck
+// (in_off: the caller's offsets) from the caller's device buffer or a copy of [lo, hi) in gp_in to gp_filt at y_off; the
+// records then name gp_filt as their input.  The states stay in the context's ft_st, one per record.
+static int groups_preprocess_chunk(afx_plan* pl, const void* samples, int sample_fmt, int mem_kind, int n_sections,
+                                   StftChunk& ck, std::vector<FiltClip>& frecs) {
+  afx_ctx* ctx = pl->ctx;
+  hipStream_t s = ctx->stream;
+  const int n = (int)ck.recs.size();
+  int rc;
+  const void* d_in = samples;
+  const bool h_in = mem_kind == AFX_MEM_HOST;
+  if (h_in) {
+    const size_t esz = (size_t)upload_sample_bytes(sample_fmt, mem_kind);
+    if ((rc = ensure(pl->gp_in, (size_t)(ck.hi - ck.lo) * esz + 16)) != AFX_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(pl->gp_in.p, (const char*)samples + (size_t)ck.lo * esz, (size_t)(ck.hi - ck.lo) * esz, hipMemcpyHostToDevice, s));
+    d_in = pl->gp_in.p;
+  }
+  frecs.resize(n);
+  int64_t tiles = 0;
+  for (int q = 0; q < n; ++q) {
+    const HpssClip& r = ck.recs[q];
+    const int64_t nt = (r.len + 2 * (int64_t)kGroupsPadlen + kFiltTile - 1) / kFiltTile;
+    frecs[q] = FiltClip{h_in ? r.in_off - ck.lo : r.in_off, r.y_off, r.len, (int32_t)tiles, (int32_t)nt};
+    tiles += nt;
+    if (tiles > (1 << 24)) { set_error("afx_groups_batch: clip too large for one launch"); return AFX_ERR_UNSUPPORTED; }
+  }
+  const int nt = (int)tiles;
+  if ((rc = ensure(ctx->ft_clips, n * sizeof(FiltClip))) != AFX_OK) return rc;
+  if ((rc = ensure(ctx->ft_st, n * sizeof(FiltState))) != AFX_OK) return rc;
+  if ((rc = ensure(ctx->ft_w, (size_t)nt * kFiltTile * sizeof(double))) != AFX_OK) return rc;
+  if ((rc = ensure(ctx->ft_carry, (size_t)nt * kFiltB * kFiltZ * sizeof(double))) != AFX_OK) return rc;
+  if ((rc = ensure(ctx->ft_tmax, (size_t)nt * sizeof(double))) != AFX_OK) return rc;
+  if ((rc = ensure(pl->gp_filt, (size_t)ck.samples * sizeof(float) + 64)) != AFX_OK) return rc;
+  HIP_TRY(hipMemcpyAsync(ctx->ft_clips.p, frecs.data(), n * sizeof(FiltClip), hipMemcpyHostToDevice, s));
+  const FiltTab* d_tab = (const FiltTab*)ctx->ft_tab.p;
+  const FiltClip* d_clips = (const FiltClip*)ctx->ft_clips.p;
+  FiltState* d_st = (FiltState*)ctx->ft_st.p;
+  double *W = (double*)ctx->ft_w.p, *carry = (double*)ctx->ft_carry.p, *tmax = (double*)ctx->ft_tmax.p;
+  const int padlen = kGroupsPadlen, S = n_sections;
+  HIP_TRY(launch_filt_peak(s, d_in, sample_fmt, d_clips, n, d_st));
+  HIP_TRY(launch_filt_forward(s, d_in, sample_fmt, AFX_FILT_EXPERIMENT, -0.98f, padlen, S, d_tab, d_clips, n, nt, d_st, W, carry));
+  HIP_TRY(launch_filt_scan(s, padlen, S, d_tab, d_clips, n, d_st, carry, false));
+  HIP_TRY(launch_filt_backward(s, padlen, S, d_tab, d_clips, n, nt, d_st, W, carry));
+  HIP_TRY(launch_filt_scan(s, padlen, S, d_tab, d_clips, n, d_st, carry, true));
+  HIP_TRY(launch_filt_final(s, padlen, S, d_tab, d_clips, n, nt, d_st, W, carry, tmax, nullptr));
+  HIP_TRY(launch_filt_clipmax(s, d_clips, n, tmax, d_st));
+  HIP_TRY(launch_filt_scale(s, padlen, d_clips, n, nt, d_st, W, (float*)pl->gp_filt.p));
+  for (HpssClip& r : ck.recs) r.in_off = r.y_off;
+  return AFX_OK;
+}
+
+extern "C" int afx_groups_batch(afx_plan* pl, const void* samples, int sample_fmt, int mem_kind,
+                                const int64_t* offsets, const int64_t* lengths, int n_clips, int flags, int groups,
+                                double* out_stats, double* out_tuning, int32_t* out_lag, int32_t* out_status) {
+  const char* who = "afx_groups_batch";
+  if (n_clips > 0 && (!out_stats || !out_status)) return null_arg(who);
+  int rc = check_batch_args(who, pl, samples, sample_fmt, mem_kind, offsets, lengths, n_clips, true);
+  if (rc != AFX_OK) return rc;
+  if (groups <= 0 || (groups & ~kGroupsAll)) { set_error("afx_groups_batch: groups must be a non-empty set of AFX_GROUP_* bits"); return AFX_ERR_INVALID; }
+  const bool sp = groups & AFX_GROUP_SPECTRAL, ha = groups & AFX_GROUP_HARMONIC, ti = groups & AFX_GROUP_TIMBRE, rh = groups & AFX_GROUP_RHYTHM;
+  const bool pre = (flags & AFX_GROUPS_PREPROCESS) != 0, keep = sp && (flags & AFX_GROUPS_STORE_DESC) != 0;
+  if ((rc = check_stft_plan(who, pl, flags, AFX_FLAG_PREEMPH | AFX_GROUPS_PREPROCESS | AFX_GROUPS_STORE_DESC, ti || rh)) != AFX_OK) return rc;
+  if (pre && (flags & AFX_FLAG_PREEMPH)) { set_error("afx_groups_batch: AFX_GROUPS_PREPROCESS has a pre-emphasis of its own; AFX_FLAG_PREEMPH cannot be added"); return AFX_ERR_INVALID; }
+  // only the centroid of h reads the bands of a plan that has none (sr <= 12.8 kHz): its bin width is all it needs
+  SpecBands sb{};
+  sb.hz_per_bin = (float)((double)pl->p.sr / 2048.0); sb.roll_percent = 0.85f;
+  if (sp && !spectral_bands(pl->p.sr, sb)) return AFX_ERR_UNSUPPORTED;
+  int32_t win = 0;
+  if (rh && afx_tempo_table(pl->p.sr, &win, nullptr, nullptr, nullptr) != AFX_OK) {
+    set_error("afx_groups_batch: the 8 s tempogram window must hold 2 .. 768 frames (128 <= sr <= 49215)");
+    return AFX_ERR_UNSUPPORTED;
+  }
+  FiltTab ftab;
+  int n_sections = 0;
+  if (pre) {
+    double sos[kFiltMaxS * 6];
+    n_sections = 3;
+    if ((rc = afx_butter_sos(5, 200.0 / ((double)pl->p.sr / 2.0), 1, sos)) != AFX_OK) return rc;
+    const char* why = "";
+    if (!filt_build_tab(sos, n_sections, ftab, &why)) { set_error(std::string(who) + ": " + why); return AFX_ERR_INVALID; }
+  }
+  if ((rc = check_clip_ranges(who, offsets, lengths, nullptr, n_clips, INT64_MAX / 4)) != AFX_OK) return rc;
+  const double nan = std::nan("");
+  // a clip the preprocess refuses (scipy's filtfilt needs more than padlen samples) is in no chunk, like an empty one
+  std::vector<int64_t> eff((size_t)n_clips);
+  for (int i = 0; i < n_clips; ++i) {
+    eff[i] = pre && lengths[i] <= kGroupsPadlen ? 0 : lengths[i];
+    out_status[i] = eff[i] == 0 ? AFX_CLIP_TOO_SHORT : AFX_CLIP_OK;
+    std::fill(out_stats + (size_t)kGroupsStats * i, out_stats + (size_t)kGroupsStats * (i + 1), nan);
+    if (out_tuning) out_tuning[i] = 0.0;
+    if (out_lag) out_lag[i] = 0;
+  }
+  if (n_clips == 0) return AFX_OK;
+  if ((rc = begin_plan_call(who, pl)) != AFX_OK) return rc;
+  if (ti && (rc = chroma_setup(pl)) != AFX_OK) return rc;
+  if (ti && (rc = groups_setup(pl)) != AFX_OK) return rc;
+  if (rh && (rc = rhythm_setup(pl)) != AFX_OK) return rc;
+  hipStream_t s = pl->ctx->stream;
+  if (pre) {
+    if ((rc = ensure(pl->ctx->ft_tab, sizeof(FiltTab))) != AFX_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(pl->ctx->ft_tab.p, &ftab, sizeof(FiltTab), hipMemcpyHostToDevice, s));
+  }
+  pl->gp_rows.clear();
+  const ChromaBand band = piptrack_band(pl->p.sr);
+  const RhythmTab tab = pl->rh_tabrec;
+  const HpssTabs tb{pl->f3.window, pl->f3.w1024, pl->f3.w2048};
+  const int M = pl->p.n_mels;
+  const bool need_s = sp || ti || rh;
+  StftCost cost{};
+  groups_cost(groups, pre, cost);
+  StftChunk ck;
+  std::vector<FiltClip> frecs;
+  std::vector<HpssClip> recs64;
+  std::vector<int64_t> d_off;
+  std::vector<uint32_t> h_bad;
+  std::vector<double> h_rec;
+  std::vector<int32_t> h_ints;
+  for (int c0 = 0; c0 < n_clips; c0 = ck.next) {
+    cut_stft_chunk(offsets, eff.data(), n_clips, c0, dev_env().groups_budget, cost, ck);
+    const int n = (int)ck.recs.size(), tiles = ck.tiles;
+    const int64_t frames = ck.frames;
+    if (n == 0) continue;
+    const size_t spec_bytes = (size_t)frames * kHpssPitch * sizeof(float2), sig_bytes = (size_t)ck.samples * sizeof(float) + 64;
+    const size_t desc_bytes = (size_t)frames * kSpecFloats * sizeof(float);
+    if (need_s && (rc = ensure(pl->ch_s, (size_t)frames * kHpssPowPitch * sizeof(float))) != AFX_OK) return rc;
+    if (sp) {
+      if ((rc = ensure(pl->gp_desc, desc_bytes)) != AFX_OK) return rc;
+      if ((rc = ensure(pl->gp_sstats, (size_t)n * 8 * sizeof(double))) != AFX_OK) return rc;
+    }
+    if (ha) {
+      if ((rc = ensure(pl->hp_h, sig_bytes)) != AFX_OK) return rc;
+      if ((rc = ensure(pl->hp_x, spec_bytes)) != AFX_OK) return rc;
+      if ((rc = ensure(pl->hp_yh, spec_bytes)) != AFX_OK) return rc;
+      if ((rc = ensure(pl->gp_clips64, n * sizeof(HpssClip))) != AFX_OK) return rc;
+      if ((rc = ensure(pl->gp_hdesc, desc_bytes)) != AFX_OK) return rc;
+      if ((rc = ensure(pl->gp_doff, n * sizeof(int64_t))) != AFX_OK) return rc;
+      if ((rc = ensure(pl->hp_stats, (size_t)n * 4 * sizeof(double))) != AFX_OK) return rc;
+    }
+    if (ti) {
+      if ((rc = ensure(pl->ch_slot, n * sizeof(int32_t))) != AFX_OK) return rc;
+      if ((rc = ensure(pl->ch_hist, (size_t)n * kChromaHist * sizeof(int32_t))) != AFX_OK) return rc;
+      if (band.nr > 0) {
+        if ((rc = ensure(pl->ch_mag, (size_t)frames * band.nr * sizeof(float))) != AFX_OK) return rc;
+        if ((rc = ensure(pl->ch_bin, (size_t)frames * band.nr)) != AFX_OK) return rc;
+      }
+      if ((rc = ensure(pl->ch_parts, (size_t)frames * 4 * sizeof(double))) != AFX_OK) return rc;
+      if ((rc = ensure(pl->gp_cstats, (size_t)n * 4 * sizeof(double))) != AFX_OK) return rc;
+      if ((rc = ensure(pl->gp_mparts, (size_t)frames * 2 * sizeof(double))) != AFX_OK) return rc;
+      if ((rc = ensure(pl->gp_mstats, (size_t)n * 2 * sizeof(double))) != AFX_OK) return rc;
+    }
+    if (ti || rh) {
+      if ((rc = ensure(pl->rh_db, (size_t)frames * kRhMels * sizeof(float))) != AFX_OK) return rc;
+      if ((rc = ensure(pl->rh_max, n * sizeof(uint32_t))) != AFX_OK) return rc;
+    }
+    if (rh) {
+      if ((rc = ensure(pl->rh_env, (size_t)frames * sizeof(float))) != AFX_OK) return rc;
+      if ((rc = ensure(pl->rh_parts, (size_t)tiles * win * sizeof(double))) != AFX_OK) return rc;
+      if ((rc = ensure(pl->rh_acmean, (size_t)n * win * sizeof(double))) != AFX_OK) return rc;
+      if ((rc = ensure(pl->rh_res, (size_t)n * 4 * sizeof(double))) != AFX_OK) return rc;
+    }
+    if ((rc = ensure(pl->gp_rec, (size_t)n * kGroupsStats * sizeof(double))) != AFX_OK) return rc;
+    if ((rc = ensure(pl->gp_ints, (size_t)n * 2 * sizeof(int32_t))) != AFX_OK) return rc;
+    // the chunk's signal: the caller's samples, or the preprocess's output, through the front end's prep either way
+    if (pre) {
+      if ((rc = groups_preprocess_chunk(pl, samples, sample_fmt, mem_kind, n_sections, ck, frecs)) != AFX_OK) return rc;
+      if ((rc = stage_stft_chunk(pl, pl->gp_filt.p, AFX_FMT_F32, AFX_MEM_DEVICE, 0, ck)) != AFX_OK) return rc;
+      HIP_TRY(launch_groups_mark_bad(s, (const FiltState*)pl->ctx->ft_st.p, n, (uint32_t*)pl->hp_bad.p));
+    } else if ((rc = stage_stft_chunk(pl, samples, sample_fmt, mem_kind, flags, ck)) != AFX_OK) {
+      return rc;
+    }
+    const HpssClip* d_clips = (const HpssClip*)pl->hp_clips.p;
+    const uint32_t* d_bad = (const uint32_t*)pl->hp_bad.p;
+    const float* d_y = (const float*)pl->hp_y.p;
+    float* d_S = need_s ? (float*)pl->ch_s.p : nullptr;
+    // one STFT of y: the complex rows when HPSS wants them (the power rows are then their squares), else the power rows
+    if (ha) {
+      HIP_TRY(launch_hpss_stft(s, d_y, d_clips, d_bad, n, frames, tb, (float2*)pl->hp_x.p));
+      if (need_s) HIP_TRY(launch_groups_square(s, (const float2*)pl->hp_x.p, frames, d_S));
+    } else {
+      HIP_TRY(launch_hpss_stft_power(s, d_y, d_clips, d_bad, n, frames, tb, d_S));
+    }
+    if (sp) {
+      HIP_TRY(launch_spec_rows(s, d_S, frames, sb, true, (float*)pl->gp_desc.p));
+      HIP_TRY(launch_spec_stats(s, (const float*)pl->gp_desc.p, d_clips, n, (double*)pl->gp_sstats.p));
+    }
+    if (ti) {
+      int32_t* d_slot = (int32_t*)pl->ch_slot.p;
+      if (band.nr > 0) HIP_TRY(launch_chroma_peaks(s, d_S, frames, band, (float*)pl->ch_mag.p, (uint8_t*)pl->ch_bin.p));
+      HIP_TRY(launch_chroma_tuning(s, d_clips, n, band, (const float*)pl->ch_mag.p, (const uint8_t*)pl->ch_bin.p, d_slot,
+                                   (int32_t*)pl->ch_hist.p));
+      HIP_TRY(launch_chroma_apply(s, d_S, d_clips, n, tiles, d_slot, (const float*)pl->ch_grid.p, (const float*)pl->ch_extra.p,
+                                  pl->ch_melrec, true, nullptr, nullptr, (double*)pl->ch_parts.p));
+      HIP_TRY(launch_chroma_stats(s, d_clips, n, M, (const double*)pl->ch_parts.p, (double*)pl->gp_cstats.p));
+    }
+    if (ti || rh) {
+      // the mel dB rows are k_rhythm_mel's output, whichever of the two groups reads them
+      HIP_TRY(hipMemsetAsync(pl->rh_max.p, 0, n * sizeof(uint32_t), s));
+      HIP_TRY(launch_rhythm_mel(s, d_S, d_clips, n, tiles, pl->ch_melrec, (float*)pl->rh_db.p, (uint32_t*)pl->rh_max.p));
+    }
+    if (ti) {
+      HIP_TRY(launch_mfcc_rows(s, (const float*)pl->rh_db.p, (const uint32_t*)pl->rh_max.p, d_clips, n, frames, M,
+                               (const float*)pl->gp_dct.p, (double*)pl->gp_mparts.p));
+      HIP_TRY(launch_mfcc_stats(s, (const double*)pl->gp_mparts.p, d_clips, n, (double*)pl->gp_mstats.p));
+    }
+    if (rh) {
+      float* d_env = (float*)pl->rh_env.p;
+      HIP_TRY(launch_rhythm_env(s, (const float*)pl->rh_db.p, (const uint32_t*)pl->rh_max.p, d_clips, n, frames, M, d_env));
+      HIP_TRY(launch_rhythm_tempogram(s, d_env, d_clips, n, tiles, tab, (double*)pl->rh_parts.p, nullptr));
+      HIP_TRY(launch_rhythm_reduce(s, d_env, d_clips, n, tab, (const double*)pl->rh_parts.p, (double*)pl->rh_acmean.p,
+                                   (double*)pl->rh_res.p));
+    }
+    if (ha) {
+      // k_hpss_mask's tiles hold 64 frames, the chunk's 16: the same records with tile_base counted in its tiles
+      recs64 = ck.recs;
+      int tiles64 = 0;
+      for (HpssClip& r : recs64) { r.tile_base = tiles64; tiles64 += (r.T + kHpssTile - 1) / kHpssTile; }
+      HIP_TRY(hipMemcpyAsync(pl->gp_clips64.p, recs64.data(), n * sizeof(HpssClip), hipMemcpyHostToDevice, s));
+      float* d_h = (float*)pl->hp_h.p;
+      HIP_TRY(launch_hpss_mask(s, (const float2*)pl->hp_x.p, (const HpssClip*)pl->gp_clips64.p, n, tiles64, (float2*)pl->hp_yh.p,
+                               nullptr, nullptr));
+      HIP_TRY(launch_hpss_irfft(s, (float2*)pl->hp_yh.p, nullptr, frames, tb));
+      HIP_TRY(launch_hpss_ola(s, (const float2*)pl->hp_yh.p, nullptr, d_clips, n, ck.max_len, tb, d_h, nullptr));
+      // spectral_centroid(y=h): X is dead behind the mask, so its space takes the power rows of h
+      float* d_Sh = (float*)pl->hp_x.p;
+      HIP_TRY(launch_hpss_stft_power(s, d_h, d_clips, d_bad, n, frames, tb, d_Sh));
+      HIP_TRY(launch_spec_rows(s, d_Sh, frames, sb, false, (float*)pl->gp_hdesc.p));
+      d_off.resize(n);
+      for (int q = 0; q < n; ++q) d_off[q] = kSpecFloats * ck.recs[q].frame_base;
+      HIP_TRY(hipMemcpyAsync(pl->gp_doff.p, d_off.data(), n * sizeof(int64_t), hipMemcpyHostToDevice, s));
+      HIP_TRY(launch_hpss_stats(s, d_y, d_h, d_clips, n, (const float*)pl->gp_hdesc.p, (const int64_t*)pl->gp_doff.p,
+                                (double*)pl->hp_stats.p));
+    }
+    GroupsSrc src{};
+    src.spec = sp ? (const double*)pl->gp_sstats.p : nullptr;
+    src.harm = ha ? (const double*)pl->hp_stats.p : nullptr;
+    src.chroma = ti ? (const double*)pl->gp_cstats.p : nullptr;
+    src.mfcc = ti ? (const double*)pl->gp_mstats.p : nullptr;
+    src.slot = ti ? (const int32_t*)pl->ch_slot.p : nullptr;
+    src.rhythm = rh ? (const double*)pl->rh_res.p : nullptr;
+    src.acmean = rh ? (const double*)pl->rh_acmean.p : nullptr;
+    src.filt = pre ? (const FiltState*)pl->ctx->ft_st.p : nullptr;
+    src.win = win;
+    HIP_TRY(launch_groups_record(s, src, d_clips, d_bad, n, (double*)pl->gp_rec.p, (int32_t*)pl->gp_ints.p));
+    h_rec.resize((size_t)n * kGroupsStats); h_ints.resize((size_t)n * 2);
+    HIP_TRY(hipMemcpyAsync(h_rec.data(), pl->gp_rec.p, h_rec.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(h_ints.data(), pl->gp_ints.p, h_ints.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    if (keep) {
+      const size_t at = pl->gp_rows.size();
+      pl->gp_rows.resize(at + (size_t)frames * kSpecFloats);
+      HIP_TRY(hipMemcpyAsync(pl->gp_rows.data() + at, pl->gp_desc.p, desc_bytes, hipMemcpyDeviceToHost, s));
+    }
+    if ((rc = end_stft_chunk(pl, n, h_bad)) != AFX_OK) return rc;
+    for (int q = 0; q < n; ++q) {
+      const int i = ck.idx[q];
+      out_status[i] = h_bad[q] ? AFX_CLIP_NONFINITE : AFX_CLIP_OK;
+      if (h_bad[q]) continue;
+      std::copy(h_rec.begin() + (size_t)q * kGroupsStats, h_rec.begin() + (size_t)(q + 1) * kGroupsStats, out_stats + (size_t)kGroupsStats * i);
+      if (out_tuning && ti) out_tuning[i] = (double)h_ints[2 * (size_t)q] * 0.01 + -0.5;
+      if (out_lag) out_lag[i] = h_ints[2 * (size_t)q + 1];
+    }
+  }
+  return AFX_OK;
+}
+
+extern "C" int afx_groups_debug_rows(afx_plan* pl, float* out, int64_t n_floats, int64_t* count) {
+  if (!pl || !count || n_floats < 0 || (n_floats > 0 && !out)) return null_arg("afx_groups_debug_rows");
+  const int64_t have = (int64_t)pl->gp_rows.size();
+  if (n_floats > 0) std::copy(pl->gp_rows.begin(), pl->gp_rows.begin() + std::min(have, n_floats), out);
+  *count = have;
   return AFX_OK;
 }

@@ -12,6 +12,7 @@
 
 #include "afx_device.h"
 #include "afx_f0.h"
+#include "afx_groups.h"
 #include "afx_hpss.h"
 #include "afx_internal.h"
 #include "afx_mr.h"
@@ -73,6 +74,36 @@ void cut_stft_chunk(const int64_t* offsets, const int64_t* lengths, int n_clips,
     ck.lo = std::min(ck.lo, offsets[c1]); ck.hi = std::max(ck.hi, offsets[c1] + L); ck.max_len = std::max(ck.max_len, L);
   }
   ck.next = c1;
+}
+
+// What a clip costs a chunk of afx_groups_batch.  Buffers whose lifetimes do not overlap share space: the power rows of h lie
+// where X lay (dead behind k_hpss_mask), so the harmonic group adds no power rows of its own.
+void groups_cost(int groups, bool preprocess, StftCost& cost) {
+  const bool sp = groups & AFX_GROUP_SPECTRAL, ha = groups & AFX_GROUP_HARMONIC, ti = groups & AFX_GROUP_TIMBRE, rh = groups & AFX_GROUP_RHYTHM;
+  constexpr int64_t kWin = kRhMaxWin, kBand = 1023, kDesc = kSpecFloats * 4;
+  cost = StftCost{};
+  cost.per_frame = ((sp || ti || rh) ? kHpssPowPitch * 4 : 0)              // the power rows of y
+                   + (sp ? kDesc : 0)                                      // its descriptor rows
+                   + (ha ? 2 * kHpssPitch * 8 + kDesc : 0)                 // X, Yh; the centroid rows of h
+                   + (ti ? kBand * 5 + 4 * 8 + 2 * 8 : 0)                  // piptrack's peaks, k_chroma_apply's and k_mfcc_rows' sums
+                   + ((ti || rh) ? kRhMels * 4 : 0)                        // the mel dB rows
+                   + (rh ? 4 : 0);                                         // the envelope
+  cost.per_tile = rh ? kWin * 8 : 0;
+  cost.per_sample = 4 + 4 + (ha ? 4 : 0)                                   // the upload, y, h
+                    + (preprocess ? 4 + 10 : 0);                           // the filter's output; its tiles (36 872 B per 4096 samples)
+  cost.per_clip = 128 + 8 * 4 + kGroupsStats * 8 + 2 * 4 + (sp ? 8 * 8 : 0) + (ha ? sizeof(HpssClip) + 4 * 8 : 0)
+                  + (ti ? kChromaHist * 4 + 4 * 8 + 2 * 8 : 0) + (rh ? kWin * 8 + 4 * 8 : 0)
+                  + (preprocess ? 2 * ((int64_t)kFiltTile * 8 + (int64_t)kFiltB * kFiltZ * 8 + 8) + sizeof(FiltClip) + sizeof(FiltState) : 0);
+  cost.tile = 16;
+  cost.tile_cap = ha ? 65535 : INT32_MAX / 2;             // k_hpss_mask's grid holds 65535 tiles of 64 frames: never more than these
+}
+
+void groups_dct_table(int n_mels, float* out) {
+  std::fill(out, out + kGroupsMfcc * kRhMels, 0.f);
+  const double M = (double)n_mels;
+  for (int k = 0; k < kGroupsMfcc; ++k)
+    for (int m = 0; m < n_mels; ++m)
+      out[k * kRhMels + m] = (float)(std::sqrt((k == 0 ? 1.0 : 2.0) / M) * std::cos(M_PI * (double)k * (2.0 * m + 1.0) / (2.0 * M)));
 }
 
 // One Stockham pass of radix R over N2 points, butterfly by butterfly as k_frames_mr's lanes take them.
@@ -196,6 +227,23 @@ extern "C" int afx_stft_chunks(const int64_t* lengths, int n_clips, const int64_
     for (int i : ck.idx) chunk_of[i] = chunk;
     ++chunk;
   }
+  return AFX_OK;
+}
+
+extern "C" int afx_groups_cost(int groups, int flags, int64_t* cost) {
+  if (!cost) { set_error("afx_groups_cost: null argument"); return AFX_ERR_INVALID; }
+  if (groups <= 0 || (groups & ~kGroupsAll)) { set_error("afx_groups_cost: groups must be a non-empty set of AFX_GROUP_* bits"); return AFX_ERR_INVALID; }
+  StftCost c;
+  groups_cost(groups, (flags & AFX_GROUPS_PREPROCESS) != 0, c);
+  const int64_t v[6] = {c.per_frame, c.per_tile, c.per_sample, c.per_clip, c.tile, c.tile_cap};
+  std::memcpy(cost, v, sizeof(v));
+  return AFX_OK;
+}
+
+extern "C" int afx_groups_dct_table(int n_mels, float* out) {
+  if (!out) { set_error("afx_groups_dct_table: null argument"); return AFX_ERR_INVALID; }
+  if (n_mels < 1 || n_mels > kRhMels) { set_error("afx_groups_dct_table: n_mels must be in 1 .. 128"); return AFX_ERR_INVALID; }
+  groups_dct_table(n_mels, out);
   return AFX_OK;
 }
 

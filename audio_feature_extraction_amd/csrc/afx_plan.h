@@ -16,6 +16,7 @@
 #include "afx_f0.h"
 #include "afx_filt.h"
 #include "afx_frames3.h"
+#include "afx_groups.h"
 #include "afx_internal.h"
 #include "afx_resample.h"
 #include "afx_rhythm.h"
@@ -84,6 +85,11 @@ struct afx_plan {
   // the dB rows, the clip maxima, the envelope, the per-tile lag sums, the tempogram (when asked for) and the results
   DevBuf rh_tab, rh_db, rh_max, rh_env, rh_parts, rh_tg, rh_acmean, rh_res;
   RhythmTab rh_tabrec{};
+  // afx_groups_batch (with the buffers of the three entry points above and the filter workspace of the context): the clip
+  // records with 64-frame tiles (k_hpss_mask), the preprocess's upload and output, the descriptor rows of y and the centroid
+  // rows of h, the per-group statistics, the MFCC table (built at first use) and per-frame sums, the records
+  DevBuf gp_clips64, gp_in, gp_filt, gp_desc, gp_hdesc, gp_doff, gp_sstats, gp_cstats, gp_mparts, gp_mstats, gp_dct, gp_rec, gp_ints;
+  std::vector<float> gp_rows;   // AFX_GROUPS_STORE_DESC: the 17-float rows of the last call, clip after clip (afx_groups_debug_rows)
   // cached per-batch descriptors
   std::vector<int64_t> c_off, c_len;
   std::vector<ClipDesc> h_clips;

@@ -372,6 +372,50 @@ int afx_rhythm_batch(afx_plan* plan, const void* samples, int sample_fmt, int me
  * outside [0, 2^20] or cost[4], cost[5] outside [1, 2^31 - 1]. */
 int afx_stft_chunks(const int64_t* lengths, int n_clips, const int64_t* cost /*[6]*/, int64_t budget, int32_t* chunk_of);
 
+/* The spectral, harmonic, timbre and rhythm groups of the experiment extractor in one pass
+ * (04_feature_extraction_experiment/feature_extractor.py:624-687 hands one preprocessed (y, sr) to all four): one upload,
+ * the preprocess on the device, one STFT of y per chunk, every group reading the same rows, scalars back.  All four symbols
+ * are newer than AFX_VERSION 107 says: a binding detects them by their presence.
+ *
+ * Plan: frame_length 2048, hop_length 512, Hann, as afx_hpss_batch; with AFX_GROUP_SPECTRAL sr > 12800 (six octave bands
+ * from 200 Hz), with AFX_GROUP_RHYTHM 128 <= sr <= 49215, with AFX_GROUP_TIMBRE or _RHYTHM at most 128 mel bands
+ * (AFX_ERR_UNSUPPORTED otherwise, as for AFX_FLAG_TRIM; AFX_ERR_INVALID for groups == 0, an unknown group or flag).
+ * flags: AFX_GROUPS_PREPROCESS runs afx_sosfiltfilt_batch's AFX_FILT_EXPERIMENT first (afx_butter_sos(5, 200 / (sr / 2),
+ * high-pass), padlen 18, pre-emphasis 0.98) and the groups see that call's output bit for bit; without it the samples are
+ * taken as given and AFX_FLAG_PREEMPH means what it means for afx_hpss_batch (with it, AFX_FLAG_PREEMPH is refused).
+ *
+ * out_stats[24 i ..], NaN for a group that was not asked for:
+ *   [0..8)    mean, std (ddof 0) of spectral_centroid, _bandwidth, _rolloff and _contrast (power_to_db(peak) -
+ *             power_to_db(valley), each matrix clamped 80 dB below its own maximum) at librosa's defaults
+ *   [8..12)   afx_hpss_batch's record: sum h^2, sum y^2, mean and std of spectral_centroid(h)
+ *   [12..16)  afx_chroma_batch's record: mean, std of the mel power matrix, mean, std of chroma_stft
+ *   [16..18)  mean, std of the 13 x T matrix librosa.feature.mfcc(y, sr, n_mfcc=13) (from one frame up)
+ *   [18..22)  tempo, mean and std of the onset envelope, the mean tempogram at the chosen lag
+ *   [22..24)  the preprocess's max|x| and max|y| (0 without AFX_GROUPS_PREPROCESS)
+ * out_tuning, out_lag (NULL ok): the tuning estimated for the clip (0.0 without AFX_GROUP_TIMBRE), the chosen tempogram
+ * lag.  out_status: AFX_CLIP_NONFINITE for a NaN / inf sample, AFX_CLIP_TOO_SHORT for length 0 and, with the preprocess,
+ * for 18 samples or fewer; such a clip's record is all NaN and it never affects another clip.  The centroid fields
+ * ([0..8), [10], [11]) of a clip of one sample are NaN.  Results are bit-reproducible and depend neither on the rest of
+ * the batch nor on how it was cut into chunks (2 GiB of workspace each).
+ *
+ * afx_groups_cost (host-only): the cost record afx_groups_batch cuts with, for afx_stft_chunks; it is an upper bound over
+ * plans (768 lags, 128 mel bands, float32 host samples) and so needs none.
+ * afx_groups_dct_table (host-only): rows 0 .. 12 of the orthonormal DCT-II of n_mels <= 128 points as out[13][128]
+ * (float64 rounded once; columns past n_mels are zero), the table of [16..18).
+ * afx_groups_debug_rows: with AFX_GROUPS_STORE_DESC and AFX_GROUP_SPECTRAL the call keeps the 17 floats per frame of
+ * afx_spectral_batch's layout on the host, clip after clip (a clip of status AFX_CLIP_TOO_SHORT has none); this copies the first
+ * min(n_floats, *count) of them out and sets *count to how many the last call kept. */
+enum { AFX_GROUP_SPECTRAL = 1, AFX_GROUP_HARMONIC = 2, AFX_GROUP_TIMBRE = 4, AFX_GROUP_RHYTHM = 8 };
+enum { AFX_GROUPS_PREPROCESS = 16, AFX_GROUPS_STORE_DESC = 32 };   /* in flags, beside AFX_FLAG_PREEMPH */
+int afx_groups_batch(afx_plan* plan, const void* samples, int sample_fmt, int mem_kind,
+                     const int64_t* offsets, const int64_t* lengths, int n_clips,
+                     int flags, int groups,
+                     double* out_stats /*[n_clips][24]*/, double* out_tuning, int32_t* out_lag,
+                     int32_t* out_status);
+int afx_groups_cost(int groups, int flags, int64_t* cost /*[6]*/);
+int afx_groups_dct_table(int n_mels, float* out /*[13][128]*/);
+int afx_groups_debug_rows(afx_plan* plan, float* out, int64_t n_floats, int64_t* count);
+
 /* Host-only (no device needed): the tables afx_f0_batch uploads, for inspection and tests.
  * info[8] = min_period, max_period, n_pitch_bins, band (transition half-width), candidate
  * capacity, lags kept, lags per lane, trough slots per lane.  beta[100] = Beta(2,18) mass of
