@@ -37,6 +37,8 @@ FILT_PLAIN, FILT_EXPERIMENT = 0, 1
 GROUP_SPECTRAL, GROUP_HARMONIC, GROUP_TIMBRE, GROUP_RHYTHM = 1, 2, 4, 8     # afx_groups_batch: the groups asked for
 GROUP_ALL = 15
 GROUPS_PREPROCESS, GROUPS_STORE_DESC = 16, 32                                # its flags, beside FLAG_PREEMPH
+BEAT_INPUT_ENVELOPE = 64                                                     # afx_beat_batch: the clips are onset envelopes
+BEAT_MAX_FPB = 768                                                           # frames per beat it holds
 GROUPS_STATS = 24                                                            # doubles per clip of its record
 K_NAMES = ("trim_blocks", "trim_decide", "frames", "dct", "stats")
 K_FRAMES = 2
@@ -53,6 +55,7 @@ SYMBOLS = (
     "afx_stft_chunks",
     "afx_butter_sos", "afx_filtfilt_geometry", "afx_sosfiltfilt_host", "afx_sosfiltfilt_batch",
     "afx_groups_batch", "afx_groups_cost", "afx_groups_dct_table", "afx_groups_debug_rows",
+    "afx_beat_track_host", "afx_beat_batch",
 )
 
 
@@ -147,6 +150,10 @@ def lib() -> C.CDLL:
             L.afx_groups_cost.argtypes = [i32, i32, vp]
             L.afx_groups_dct_table.argtypes = [i32, vp]
             L.afx_groups_debug_rows.argtypes = [vp, vp, C.c_int64, i64p]
+        if hasattr(L, "afx_beat_batch"):                     # newer than version 107 says: found by their presence
+            dbl = C.c_double
+            L.afx_beat_track_host.argtypes = [vp, C.c_int64, dbl, dbl, dbl, i32, vp, i64p, vp, vp, vp]
+            L.afx_beat_batch.argtypes = [vp, vp, i32, i32, vp, vp, i32, i32, vp, dbl, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
         if hasattr(L, "afx_rfft_host"):                      # absent from a library built before the mixed-radix lengths
             L.afx_rfft_host.argtypes = [i32, vp, vp]
         _lib = L
@@ -386,6 +393,26 @@ def sosfiltfilt_host(x, sos, padlen: int, mode: int = FILT_PLAIN, preemph: float
                                       int(sos.shape[0]), int(padlen), int(mode), float(preemph), out.ctypes.data,
                                       peak.ctypes.data, status.ctypes.data), "afx_sosfiltfilt_host")
     return {"out": out, "peak": peak, "status": int(status[0])}
+
+
+def beat_track_host(env, fps: float, bpm: float, tightness: float = 100.0, trim: bool = True) -> dict:
+    """Host-only: afx_beat_track_host, one float32 onset envelope through the beat tracker's definition in float64 on the
+    CPU.  Returns beats (int64 frames), mask (uint8 [T]), localscore, cumscore (float64 [T]) and backlink (int32 [T])."""
+    if not hasattr(lib(), "afx_beat_track_host"):
+        raise NotImplementedError("this libafx has no afx_beat_track_host")
+    env = np.ascontiguousarray(env)
+    if env.ndim != 1 or env.dtype != np.float32:
+        raise ValueError("env must be a one-dimensional float32 array")
+    T = int(env.size)
+    mask = np.zeros(T, np.uint8)
+    ls, cum, bl = np.zeros(T, np.float64), np.zeros(T, np.float64), np.zeros(T, np.int32)
+    nb = C.c_int64(0)
+    _check(lib().afx_beat_track_host(env.ctypes.data, T, float(fps), float(bpm), float(tightness), int(bool(trim)),
+                                     mask.ctypes.data, C.byref(nb), ls.ctypes.data, cum.ctypes.data, bl.ctypes.data),
+           "afx_beat_track_host")
+    beats = np.flatnonzero(mask).astype(np.int64)
+    assert beats.size == nb.value
+    return {"beats": beats, "mask": mask, "localscore": ls, "cumscore": cum, "backlink": bl}
 
 
 def resample_lengths(lengths, sr_in: int, sr_out: int) -> np.ndarray:
@@ -1011,6 +1038,44 @@ class Plan(_Owner):
             out["acmean"] = acmean
         if want_stats:
             out["stats"] = stats
+        return out
+
+    def beat_batch(self, samples, offsets, lengths, flags=0, fmt=FMT_F32, mem=MEM_HOST, envelopes: bool = False, bpm=None,
+                   tightness: float = 100.0, trim: bool = True, want_env: bool = False, want_scores: bool = False) -> dict:
+        """afx_beat_batch: the beat positions of librosa.beat.beat_track of a ragged batch (plan: frame_length 2048,
+        hop_length 512, Hann; sr <= 49215).  ``envelopes``: the clips are float32 onset envelopes (lengths in frames), not
+        samples.  ``bpm``: None, or one tempo per clip (0: the tempo afx_rhythm_batch decides).  Returns status [n] int32,
+        ``tempo`` [n] float64 (NaN for a failed clip), ``fpb`` and ``n_beats`` [n] int32, ``beats`` (list of int64 frame
+        indices), ``mask`` (list of (T,) uint8) and, as asked, ``env`` (list of (T,) float32) and ``localscore``,
+        ``cumscore`` (float64), ``backlink`` (int32) as lists of (T,) arrays."""
+        if not hasattr(lib(), "afx_beat_batch"):
+            raise NotImplementedError("this libafx has no afx_beat_batch")
+        offsets, lengths, n = _clip_arrays(offsets, lengths)
+        sptr, kind = _sample_source(samples, fmt, offsets, lengths, mem=mem)
+        T = lengths.copy() if envelopes else 1 + lengths // self.params.hop
+        foff = packed_offsets(T)
+        total = int(T.sum())
+        if bpm is not None:
+            bpm = np.ascontiguousarray(bpm, np.float64).reshape(-1)
+            if bpm.shape[0] != n:
+                raise ValueError("bpm must have one entry per clip")
+        mask = np.zeros(total, np.uint8)
+        env = np.zeros(total, np.float32) if want_env else None
+        ls = np.zeros(total, np.float64) if want_scores else None
+        cum = np.zeros(total, np.float64) if want_scores else None
+        bl = np.zeros(total, np.int32) if want_scores else None
+        tempo, fpb, nb, status = np.zeros(n, np.float64), np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros(n, np.int32)
+        _check(lib().afx_beat_batch(self.handle, sptr, int(fmt), kind, offsets.ctypes.data, lengths.ctypes.data, n,
+                                    int(flags) | (BEAT_INPUT_ENVELOPE if envelopes else 0), _ptr(bpm), float(tightness),
+                                    int(bool(trim)), mask.ctypes.data, foff.ctypes.data, nb.ctypes.data, tempo.ctypes.data,
+                                    fpb.ctypes.data, _ptr(env), _ptr(ls), _ptr(cum), _ptr(bl), status.ctypes.data), "afx_beat_batch")
+        cut = lambda a: [a[foff[i]:foff[i] + T[i]] for i in range(n)]
+        out = {"status": status, "tempo": tempo, "fpb": fpb, "n_beats": nb, "mask": cut(mask)}
+        out["beats"] = [np.flatnonzero(m).astype(np.int64) for m in out["mask"]]
+        if want_env:
+            out["env"] = cut(env)
+        if want_scores:
+            out["localscore"], out["cumscore"], out["backlink"] = cut(ls), cut(cum), cut(bl)
         return out
 
     def groups_batch(self, samples, offsets, lengths, groups: int = GROUP_ALL, flags: int = 0, fmt=FMT_F32, mem=MEM_HOST,

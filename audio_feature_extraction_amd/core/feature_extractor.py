@@ -395,9 +395,42 @@ class AudioFeatureExtractor:
     def extract_rhythm_features(self, y: np.ndarray) -> Dict[str, Any]:
         """提取節奏特徵 (04_feature_extraction_experiment/feature_extractor.py:592-622): the tempo
         ``librosa.beat.beat_track`` reports for ``librosa.onset.onset_strength(y)`` (the beat positions, which the reference
-        discards, are not computed), the mean and std of that envelope and their ratio, all at librosa's defaults and on
+        discards, are ``extract_beats``'), the mean and std of that envelope and their ratio, all at librosa's defaults and on
         the GPU; the signal is taken as given and may be as short as one sample (tempo 0.0 up to three frames)."""
         return self.extract_rhythm_features_batch([y])[0]
+
+    _BEAT_KEYS = ("tempo", "beat_frames", "beat_times", "beat_count", "beat_interval_mean", "beat_interval_std")
+
+    def extract_beats_batch(self, signals: Sequence[np.ndarray]) -> List[Dict[str, Any]]:
+        """``extract_beats`` of many signals in one device pass (a failing clip raises)."""
+        ys = [np.ascontiguousarray(y, dtype=np.float32) for y in signals]
+        if not ys:
+            return []
+        for y in ys:
+            if y.ndim != 1:
+                raise ValueError(f"signals must be 1-D (mono), got shape {y.shape}")
+        lengths = np.array([y.size for y in ys], np.int64)
+        plan = self._spectral_plan()
+        out = plan.beat_batch(np.concatenate(ys), _native.packed_offsets(lengths), lengths)
+        spf = 512.0 / float(plan.params.sr)                # seconds per frame
+        res = []
+        for i, st in enumerate(out["status"]):
+            if st != _native.CLIP_OK:
+                raise _status_error(int(st), "extract_beats")
+            frames = out["beats"][i]
+            gaps = np.diff(frames).astype(np.float64) * spf
+            few = frames.size < 2
+            res.append(dict(zip(self._BEAT_KEYS, (float(out["tempo"][i]), [int(f) for f in frames], [float(f) * spf for f in frames],
+                                                   int(frames.size), float("nan") if few else float(np.mean(gaps)),
+                                                   float("nan") if few else float(np.std(gaps))))))
+        return res
+
+    def extract_beats(self, y: np.ndarray) -> Dict[str, Any]:
+        """The beat positions ``librosa.beat.beat_track(onset_envelope=librosa.onset.onset_strength(y), sr=sr)`` finds -- the
+        second half of the call whose tempo ``extract_rhythm_features`` reports -- on the GPU: ``tempo``, ``beat_frames``
+        (hop 512), ``beat_times`` (seconds), ``beat_count`` and the mean and std (ddof 0) of the inter-beat interval in seconds
+        (NaN below two beats), as Python floats, ints and lists."""
+        return self.extract_beats_batch([y])[0]
 
     _SPECTRAL_KEYS = tuple(f"spectral_{k}_{s}" for k in ("centroid", "bandwidth", "rolloff", "contrast") for s in ("mean", "std"))
     _SIGNAL_GROUPS = ("spectral", "harmonic", "timbre", "rhythm")       # the reference's order in extract_all_features

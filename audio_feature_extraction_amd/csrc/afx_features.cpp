@@ -753,6 +753,184 @@ extern "C" int afx_rhythm_batch(afx_plan* pl, const void* samples, int sample_fm
   return AFX_OK;
 }
 
+// ---- beat positions (librosa.beat.beat_track, 04_feature_extraction_experiment/feature_extractor.py:604-607) ----
+// T values of `esz` bytes per frame of a chunk to the caller's dst + esz off[clip], as they lie in src: one copy when the
+// caller's layout is the chunk's, else one per clip
+static int copy_frames_out(hipStream_t s, const StftChunk& ck, void* dst, const int64_t* off, const void* src, size_t esz) {
+  const int n = (int)ck.recs.size();
+  bool packed = true;
+  for (int q = 0; q < n && packed; ++q) packed = off[ck.idx[q]] - off[ck.idx[0]] == ck.recs[q].frame_base;
+  if (packed) {
+    HIP_TRY(hipMemcpyAsync((char*)dst + esz * (size_t)off[ck.idx[0]], src, esz * (size_t)ck.frames, hipMemcpyDeviceToHost, s));
+    return AFX_OK;
+  }
+  for (int q = 0; q < n; ++q)
+    HIP_TRY(hipMemcpyAsync((char*)dst + esz * (size_t)off[ck.idx[q]], (const char*)src + esz * (size_t)ck.recs[q].frame_base,
+                           esz * (size_t)ck.recs[q].T, hipMemcpyDeviceToHost, s));
+  return AFX_OK;
+}
+
+extern "C" int afx_beat_batch(afx_plan* pl, const void* samples, int sample_fmt, int mem_kind,
+                              const int64_t* offsets, const int64_t* lengths, int n_clips, int flags,
+                              const double* in_bpm, double tightness, int trim,
+                              uint8_t* out_beats, const int64_t* frame_off,
+                              int32_t* out_n_beats, double* out_tempo, int32_t* out_fpb,
+                              float* out_env, double* out_localscore, double* out_cumscore, int32_t* out_backlink,
+                              int32_t* out_status) {
+  const char* who = "afx_beat_batch";
+  const bool envm = (flags & AFX_BEAT_INPUT_ENVELOPE) != 0;
+  if (n_clips > 0 && (!out_status || !out_tempo || !out_fpb || !out_n_beats || !out_beats || !frame_off)) return null_arg(who);
+  int rc = check_batch_args(who, pl, samples, sample_fmt, mem_kind, offsets, lengths, n_clips, true);
+  if (rc != AFX_OK) return rc;
+  if ((rc = check_stft_plan(who, pl, flags, AFX_FLAG_PREEMPH | AFX_BEAT_INPUT_ENVELOPE, true)) != AFX_OK) return rc;
+  if (envm && (flags & AFX_FLAG_PREEMPH)) { set_error("afx_beat_batch: AFX_FLAG_PREEMPH does not apply to envelopes"); return AFX_ERR_INVALID; }
+  if (envm && sample_fmt != AFX_FMT_F32) { set_error("afx_beat_batch: envelopes are float32"); return AFX_ERR_INVALID; }
+  if (!std::isfinite(tightness) || tightness <= 0.0) { set_error("afx_beat_batch: tightness must be finite and > 0"); return AFX_ERR_INVALID; }
+  int32_t win = 0;
+  if (afx_tempo_table(pl->p.sr, &win, nullptr, nullptr, nullptr) != AFX_OK) {
+    set_error("afx_beat_batch: the 8 s tempogram window must hold 2 .. 768 frames (128 <= sr <= 49215)");
+    return AFX_ERR_UNSUPPORTED;
+  }
+  if ((rc = check_clip_ranges(who, offsets, lengths, frame_off, n_clips, INT64_MAX / 8)) != AFX_OK) return rc;
+  const double fps = (double)pl->p.sr / 512.0;
+  for (int i = 0; i < n_clips; ++i) {
+    if (envm && lengths[i] > ((int64_t)1 << 22)) {
+      set_error("afx_beat_batch: clip " + std::to_string(i) + ": more than 2^22 frames is not supported");
+      return AFX_ERR_UNSUPPORTED;
+    }
+    int32_t f = 0;
+    if (in_bpm && (!std::isfinite(in_bpm[i]) || in_bpm[i] < 0.0 || (in_bpm[i] > 0.0 && !beat_fpb(fps, in_bpm[i], &f)))) {
+      set_error("afx_beat_batch: clip " + std::to_string(i) + ": the tempo must be finite, >= 0 and give 1 .. 768 frames per beat");
+      return AFX_ERR_INVALID;
+    }
+  }
+  // envelope mode cuts with sample counts that give the clips' frame counts: T frames = 1 + ((T - 1) 512 + 1) / 512
+  std::vector<int64_t> cut_len;
+  if (envm) {
+    cut_len.resize(n_clips);
+    for (int i = 0; i < n_clips; ++i) cut_len[i] = lengths[i] > 0 ? (lengths[i] - 1) * 512 + 1 : 0;
+  }
+  const int64_t* clens = envm ? cut_len.data() : lengths;
+  const double nan = std::nan("");
+  for (int i = 0; i < n_clips; ++i) {
+    out_status[i] = (!envm && lengths[i] == 0) ? AFX_CLIP_TOO_SHORT : AFX_CLIP_OK;
+    out_tempo[i] = (envm && lengths[i] == 0) ? 0.0 : nan;
+    out_fpb[i] = 0; out_n_beats[i] = 0;
+    if (!envm && lengths[i] == 0) {                        // one all-zero frame
+      const int64_t o = frame_off[i];
+      out_beats[o] = 0;
+      if (out_env) out_env[o] = 0.f;
+      if (out_localscore) out_localscore[o] = 0.0;
+      if (out_cumscore) out_cumscore[o] = 0.0;
+      if (out_backlink) out_backlink[o] = -1;
+    }
+  }
+  if (n_clips == 0) return AFX_OK;
+  if ((rc = begin_plan_call(who, pl)) != AFX_OK) return rc;
+  if ((rc = rhythm_setup(pl)) != AFX_OK) return rc;
+  hipStream_t s = pl->ctx->stream;
+  const RhythmTab tab = pl->rh_tabrec;
+  const HpssTabs tb{pl->f3.window, pl->f3.w1024, pl->f3.w2048};
+  const int M = pl->p.n_mels;
+  // afx_rhythm_batch's record (an envelope costs its upload instead of the STFT's rows) and, per frame, x, the two scores, the
+  // backlink and the flag
+  StftCost cost{};
+  cost.per_frame = (envm ? 4 + 4 : kHpssPowPitch * 4 + kRhMels * 4 + 4) + 3 * 8 + 4 + 1;
+  cost.per_tile = win * 8;
+  cost.per_sample = envm ? 0 : 4 + upload_sample_bytes(sample_fmt, mem_kind);
+  cost.per_clip = win * 8 + 128 + (int64_t)sizeof(BeatRec) + 8;
+  cost.tile = kRhTile; cost.tile_cap = INT32_MAX / 2;
+  StftChunk ck;
+  std::vector<uint32_t> h_bad;
+  std::vector<BeatRec> h_rec;
+  std::vector<double> h_bpm;
+  for (int c0 = 0; c0 < n_clips; c0 = ck.next) {
+    cut_stft_chunk(offsets, clens, n_clips, c0, dev_env().rhythm_budget, cost, ck);
+    const int n = (int)ck.recs.size(), tiles = ck.tiles;
+    const int64_t frames = ck.frames;
+    if (n == 0) continue;
+    if ((rc = ensure(pl->rh_env, (size_t)frames * sizeof(float))) != AFX_OK) return rc;
+    if ((rc = ensure(pl->rh_parts, (size_t)tiles * win * sizeof(double))) != AFX_OK) return rc;
+    if ((rc = ensure(pl->rh_acmean, (size_t)n * win * sizeof(double))) != AFX_OK) return rc;
+    if ((rc = ensure(pl->rh_res, (size_t)n * 4 * sizeof(double))) != AFX_OK) return rc;
+    if ((rc = ensure(pl->bt_x, (size_t)frames * sizeof(double))) != AFX_OK) return rc;
+    if ((rc = ensure(pl->bt_ls, (size_t)frames * sizeof(double))) != AFX_OK) return rc;
+    if ((rc = ensure(pl->bt_cum, (size_t)frames * sizeof(double))) != AFX_OK) return rc;
+    if ((rc = ensure(pl->bt_bl, (size_t)frames * sizeof(int32_t))) != AFX_OK) return rc;
+    if ((rc = ensure(pl->bt_beats, (size_t)frames)) != AFX_OK) return rc;
+    if ((rc = ensure(pl->bt_rec, (size_t)n * sizeof(BeatRec))) != AFX_OK) return rc;
+    float* d_env = (float*)pl->rh_env.p;
+    const HpssClip* d_clips = (const HpssClip*)pl->hp_clips.p;
+    const uint32_t* d_bad = (const uint32_t*)pl->hp_bad.p;
+    if (envm) {
+      // the chunk's envelopes, [lo, hi) of the caller's buffer
+      int64_t lo = INT64_MAX, hi = 0;
+      for (int q = 0; q < n; ++q) { lo = std::min(lo, offsets[ck.idx[q]]); hi = std::max(hi, offsets[ck.idx[q]] + lengths[ck.idx[q]]); }
+      const float* d_in = (const float*)samples;
+      for (HpssClip& r : ck.recs) r.len = r.T;
+      if (mem_kind == AFX_MEM_HOST) {
+        if ((rc = ensure(pl->samples, (size_t)(hi - lo) * sizeof(float) + 16)) != AFX_OK) return rc;
+        HIP_TRY(hipMemcpyAsync(pl->samples.p, (const float*)samples + lo, (size_t)(hi - lo) * sizeof(float), hipMemcpyHostToDevice, s));
+        for (HpssClip& r : ck.recs) r.in_off -= lo;
+        d_in = (const float*)pl->samples.p;
+      }
+      if ((rc = ensure(pl->hp_clips, n * sizeof(HpssClip))) != AFX_OK) return rc;
+      if ((rc = ensure(pl->hp_bad, n * sizeof(uint32_t))) != AFX_OK) return rc;
+      d_clips = (const HpssClip*)pl->hp_clips.p; d_bad = (const uint32_t*)pl->hp_bad.p;
+      HIP_TRY(hipMemcpyAsync(pl->hp_clips.p, ck.recs.data(), n * sizeof(HpssClip), hipMemcpyHostToDevice, s));
+      HIP_TRY(launch_beat_stage(s, d_in, d_clips, n, d_env, (uint32_t*)pl->hp_bad.p));
+    } else {
+      if ((rc = ensure(pl->ch_s, (size_t)frames * kHpssPowPitch * sizeof(float))) != AFX_OK) return rc;
+      if ((rc = ensure(pl->rh_db, (size_t)frames * kRhMels * sizeof(float))) != AFX_OK) return rc;
+      if ((rc = ensure(pl->rh_max, n * sizeof(uint32_t))) != AFX_OK) return rc;
+      if ((rc = stage_stft_chunk(pl, samples, sample_fmt, mem_kind, flags & AFX_FLAG_PREEMPH, ck)) != AFX_OK) return rc;
+      d_clips = (const HpssClip*)pl->hp_clips.p; d_bad = (const uint32_t*)pl->hp_bad.p;
+      float* d_S = (float*)pl->ch_s.p;
+      HIP_TRY(hipMemsetAsync(pl->rh_max.p, 0, n * sizeof(uint32_t), s));
+      HIP_TRY(launch_hpss_stft_power(s, (const float*)pl->hp_y.p, d_clips, d_bad, n, frames, tb, d_S));
+      HIP_TRY(launch_rhythm_mel(s, d_S, d_clips, n, tiles, pl->ch_melrec, (float*)pl->rh_db.p, (uint32_t*)pl->rh_max.p));
+      HIP_TRY(launch_rhythm_env(s, (const float*)pl->rh_db.p, (const uint32_t*)pl->rh_max.p, d_clips, n, frames, M, d_env));
+    }
+    HIP_TRY(launch_rhythm_tempogram(s, d_env, d_clips, n, tiles, tab, (double*)pl->rh_parts.p, nullptr));
+    HIP_TRY(launch_rhythm_reduce(s, d_env, d_clips, n, tab, (const double*)pl->rh_parts.p, (double*)pl->rh_acmean.p,
+                                 (double*)pl->rh_res.p));
+    const double* d_bpm = nullptr;
+    if (in_bpm) {
+      h_bpm.resize(n);
+      for (int q = 0; q < n; ++q) h_bpm[q] = in_bpm[ck.idx[q]];
+      if ((rc = ensure(pl->bt_bpm, (size_t)n * sizeof(double))) != AFX_OK) return rc;
+      HIP_TRY(hipMemcpyAsync(pl->bt_bpm.p, h_bpm.data(), (size_t)n * sizeof(double), hipMemcpyHostToDevice, s));
+      d_bpm = (const double*)pl->bt_bpm.p;
+    }
+    // a clip the dynamic programme does not run for keeps these: scores 0, backlinks -1, no flags
+    HIP_TRY(hipMemsetAsync(pl->bt_ls.p, 0, (size_t)frames * sizeof(double), s));
+    HIP_TRY(hipMemsetAsync(pl->bt_cum.p, 0, (size_t)frames * sizeof(double), s));
+    HIP_TRY(hipMemsetAsync(pl->bt_bl.p, 0xff, (size_t)frames * sizeof(int32_t), s));
+    HIP_TRY(hipMemsetAsync(pl->bt_beats.p, 0, (size_t)frames, s));
+    BeatRec* d_rec = (BeatRec*)pl->bt_rec.p;
+    HIP_TRY(launch_beat_score(s, d_env, d_clips, d_bad, n, (const double*)pl->rh_res.p, d_bpm, fps, (double*)pl->bt_x.p,
+                              (double*)pl->bt_ls.p, d_rec));
+    HIP_TRY(launch_beat_dp(s, d_clips, n, d_rec, (const double*)pl->bt_ls.p, tightness, (double*)pl->bt_cum.p, (int32_t*)pl->bt_bl.p));
+    HIP_TRY(launch_beat_finish(s, d_clips, n, (const double*)pl->bt_ls.p, (const double*)pl->bt_cum.p, (const int32_t*)pl->bt_bl.p,
+                               trim != 0, (uint64_t*)pl->bt_x.p, (uint8_t*)pl->bt_beats.p, d_rec));
+    h_rec.resize(n);
+    HIP_TRY(hipMemcpyAsync(h_rec.data(), d_rec, (size_t)n * sizeof(BeatRec), hipMemcpyDeviceToHost, s));
+    if ((rc = copy_frames_out(s, ck, out_beats, frame_off, pl->bt_beats.p, 1)) != AFX_OK) return rc;
+    if (out_env && (rc = copy_frames_out(s, ck, out_env, frame_off, d_env, sizeof(float))) != AFX_OK) return rc;
+    if (out_localscore && (rc = copy_frames_out(s, ck, out_localscore, frame_off, pl->bt_ls.p, sizeof(double))) != AFX_OK) return rc;
+    if (out_cumscore && (rc = copy_frames_out(s, ck, out_cumscore, frame_off, pl->bt_cum.p, sizeof(double))) != AFX_OK) return rc;
+    if (out_backlink && (rc = copy_frames_out(s, ck, out_backlink, frame_off, pl->bt_bl.p, sizeof(int32_t))) != AFX_OK) return rc;
+    if ((rc = end_stft_chunk(pl, n, h_bad)) != AFX_OK) return rc;
+    for (int q = 0; q < n; ++q) {
+      const int i = ck.idx[q];
+      out_status[i] = h_bad[q] ? AFX_CLIP_NONFINITE : AFX_CLIP_OK;
+      if (h_bad[q]) continue;                              // tempo NaN, no beats; its envelope and scores are zero
+      out_tempo[i] = h_rec[q].tempo; out_fpb[i] = h_rec[q].fpb; out_n_beats[i] = h_rec[q].n_beats;
+    }
+  }
+  return AFX_OK;
+}
+
 // ---- the spectral, harmonic, timbre and rhythm groups on one STFT (04_feature_extraction_experiment/feature_extractor.py:624-687;
 // DESIGN.md 18) ------------------------------------------------------------------------------------------------------------
 // the MFCC table, at first use

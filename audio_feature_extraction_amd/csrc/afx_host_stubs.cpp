@@ -1,6 +1,6 @@
 // Device entry points of the HOST-ONLY build (libafx_host_asan.so, `make asan`): every one fails loudly with
 // AFX_ERR_NO_DEVICE.  The sanitizer build exists to run the host-side parsers and table builders (afx_wav.cpp,
-// afx_tables.cpp, afx_f0_tables.cpp, afx_resample_tables.cpp, afx_filt_host.cpp, afx_host.cpp) under AddressSanitizer + UBSan on the CPU; GPU sanitizers are not
+// afx_tables.cpp, afx_f0_tables.cpp, afx_resample_tables.cpp, afx_filt_host.cpp, afx_beat_host.cpp, afx_host.cpp) under AddressSanitizer + UBSan on the CPU; GPU sanitizers are not
 // available on the target pool.  Never linked into libafx.so.
 #include <cstddef>
 #include <cstdint>
@@ -60,6 +60,10 @@ int afx_rhythm_batch(afx_plan*, const void*, int, int, const int64_t*, const int
 int afx_groups_batch(afx_plan*, const void*, int, int, const int64_t*, const int64_t*, int, int, int, double*, double*, int32_t*,
                      int32_t*) {
   return no_device("afx_groups_batch");
+}
+int afx_beat_batch(afx_plan*, const void*, int, int, const int64_t*, const int64_t*, int, int, const double*, double, int, uint8_t*,
+                   const int64_t*, int32_t*, double*, int32_t*, float*, double*, double*, int32_t*, int32_t*) {
+  return no_device("afx_beat_batch");
 }
 int afx_groups_debug_rows(afx_plan*, float*, int64_t, int64_t*) { return no_device("afx_groups_debug_rows"); }
 int afx_resample_batch(afx_ctx*, const void*, int, int, const int64_t*, const int64_t*, int, int, int, const double*, int, float*,

@@ -10,6 +10,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include "afx_beat.h"
 #include "afx_chroma.h"
 #include "afx_decode.h"
 #include "afx_device.h"
@@ -85,6 +86,9 @@ struct afx_plan {
   // the dB rows, the clip maxima, the envelope, the per-tile lag sums, the tempogram (when asked for) and the results
   DevBuf rh_tab, rh_db, rh_max, rh_env, rh_parts, rh_tg, rh_acmean, rh_res;
   RhythmTab rh_tabrec{};
+  // afx_beat_batch (with the buffers of afx_rhythm_batch): x = env / std (later the keys of the local maxima), the local and
+  // cumulative scores, the backlinks, the flags, the records, the caller's tempi
+  DevBuf bt_x, bt_ls, bt_cum, bt_bl, bt_beats, bt_rec, bt_bpm;
   // afx_groups_batch (with the buffers of the three entry points above and the filter workspace of the context): the clip
   // records with 64-frame tiles (k_hpss_mask), the preprocess's upload and output, the descriptor rows of y and the centroid
   // rows of h, the per-group statistics, the MFCC table (built at first use) and per-frame sums, the records

@@ -332,7 +332,7 @@ int afx_chroma_filters(int sr, double tuning, float* out /*[12 * 1025]*/);
  * tempogram librosa.beat.beat_track asks librosa.feature.tempo for (win = int(8 sr) // 512 lags) and tempo's decision, at
  * librosa 0.11's defaults (mel power of n_fft 2048 / hop 512, power_to_db with ref 1 and top_db 80, lag 1, the mean over
  * the bands, centred; Hann autocorrelation window, linear_ramp padding, norm inf; start_bpm 120, std_bpm 1, max_tempo 320,
- * mean aggregate), as tests/rhythm_ref.py restates them.  Beat positions are not computed.  Both symbols are newer than
+ * mean aggregate), as tests/rhythm_ref.py restates them.  Beat positions are afx_beat_batch's, below.  Both symbols are newer than
  * AFX_VERSION 107 says: a binding detects them by their presence.  The plan must be n_fft 2048 / hop 512 with
  * AFX_WINDOW_HANN, at most 128 mel bands and 128 <= sr <= 49215 (2 <= win <= 768) -- AFX_ERR_UNSUPPORTED otherwise; sr and the
  * mel bank are the plan's.  With T_i = 1 + lengths[i] / 512:
@@ -362,6 +362,51 @@ int afx_rhythm_batch(afx_plan* plan, const void* samples, int sample_fmt, int me
                      double* out_tempo, int32_t* out_lag,
                      double* out_stats,
                      int32_t* out_status);
+
+/* Beat positions: the second half of librosa.beat.beat_track(onset_envelope=env, sr=sr) (hop 512, trim by Ellis's
+ * beat-indexed rule), as tests/beat_ref.py restates it.  Both symbols are newer than AFX_VERSION 107 says: a binding detects
+ * them by their presence.  For an envelope env[T], fps = sr / 512 and a tempo bpm:
+ *   no beats       T < 2, an all-zero envelope, or bpm == 0 (librosa is undefined for T == 1; ours is no beats)
+ *   fpb            round(fps 60 / bpm), half to even, in [1, 768]; a tempo afx_rhythm_batch decided gives fpb == its lag
+ *   localscore     x = env / (std(env, ddof 1) + DBL_MIN) convolved ("same") with exp(-0.5 ((k - fpb) 32 / fpb)^2), k = 0 .. 2 fpb
+ *   cumscore[i]    localscore[i] + the largest of cumscore[loc] - tightness (log(i - loc) - log(fpb))^2 over loc = i - lo,
+ *                  i - lo - 1, .. i - 2 fpb (loc >= 0; lo = round(fpb / 2) half to even); the nearest predecessor wins a tie
+ *   backlink[i]    that loc, -1 without one and -1 until the first frame whose localscore reaches 0.01 max(localscore)
+ *   last beat      the largest local maximum of cumscore (> left, >= right; never frame 0) that reaches half the median of
+ *                  the local maxima; none: no beats
+ *   trim           with s[j] = localscore at beat j: smooth[j] = 0.5 s[j-1] + s[j] + 0.5 s[j+1]; the beats from the first to
+ *                  the last with smooth[j] > 0.5 sqrt(mean(smooth^2)) are kept
+ * all in float64.  A clip the dynamic programme does not run for has localscore and cumscore zero and every backlink -1.
+ *
+ * afx_beat_track_host (host-only): one envelope on the CPU -- the specification of the kernels.  out_mask[T]: 1 at a beat.
+ * AFX_ERR_INVALID for bpm < 0, a non-finite bpm, fps, tightness or envelope value, fps or tightness <= 0, or fpb outside
+ * [1, 768] when bpm > 0; AFX_ERR_UNSUPPORTED for more than 2^22 frames.
+ *
+ * afx_beat_batch: plan limits are afx_rhythm_batch's.  Without AFX_BEAT_INPUT_ENVELOPE the clips are samples and the
+ * envelope and the tempo are the ones afx_rhythm_batch computes for them (array-equal), T_i = 1 + lengths[i] / 512.  With it,
+ * samples holds float32 envelopes, lengths[i] = T_i <= 2^22, and the tempo is decided from the envelope the same way;
+ * AFX_FLAG_PREEMPH is refused (AFX_ERR_INVALID) and a NaN / inf value gives AFX_CLIP_NONFINITE.
+ *   in_bpm         NULL: every clip is tracked at the decided tempo; else per clip a tempo, 0 = the decided one
+ *                  (AFX_ERR_INVALID as for afx_beat_track_host)
+ *   out_beats, frame_off     host uint8: T_i flags at out_beats[frame_off[i] ..], 1 at a beat
+ *   out_n_beats, out_tempo, out_fpb      host [n_clips]: the count, the tempo tracked at, fpb (0 for tempo 0)
+ *   out_env, out_localscore, out_cumscore, out_backlink      NULL or host, T_i values at frame_off[i]
+ *   out_status     as afx_rhythm_batch's (AFX_CLIP_TOO_SHORT for a clip of 0 samples: one frame, no beats; an envelope of 0
+ *                  frames is AFX_CLIP_OK and writes nothing); a clip with tempo 0 or T < 2 has no beats and is AFX_CLIP_OK; a
+ *                  failed clip's outputs are zero, its tempo NaN, and it never affects another clip
+ * No float atomics: results are bit-reproducible and depend neither on the rest of the batch nor on the chunk cut. */
+enum { AFX_BEAT_INPUT_ENVELOPE = 64 };   /* in flags, beside AFX_FLAG_PREEMPH */
+int afx_beat_track_host(const float* env, int64_t T, double fps, double bpm, double tightness, int trim,
+                        uint8_t* out_mask /*[T]*/, int64_t* out_n_beats,
+                        double* out_localscore /*NULL ok, [T]*/, double* out_cumscore /*NULL ok*/, int32_t* out_backlink /*NULL ok*/);
+int afx_beat_batch(afx_plan* plan, const void* samples, int sample_fmt, int mem_kind,
+                   const int64_t* offsets, const int64_t* lengths, int n_clips, int flags,
+                   const double* in_bpm, double tightness, int trim,
+                   uint8_t* out_beats, const int64_t* frame_off,
+                   int32_t* out_n_beats, double* out_tempo, int32_t* out_fpb,
+                   float* out_env,
+                   double* out_localscore, double* out_cumscore, int32_t* out_backlink,
+                   int32_t* out_status);
 
 /* Host-only: how afx_hpss_batch, afx_chroma_batch and afx_rhythm_batch cut a batch into chunks (one rule, the entry points
  * differ in the cost record).  A clip of T = 1 + length / 512 frames costs T cost[0] + ceil(T / cost[4]) cost[1] +
