@@ -21,7 +21,8 @@ MEM_HOST, MEM_DEVICE = 0, 1
 FLAG_PREEMPH, FLAG_TRIM = 1, 2
 DTW_OK, DTW_NONFINITE, DTW_NO_PATH = 0, 1, 2
 DTW_METRICS = {"euclidean": 0, "sqeuclidean": 1, "cosine": 2}
-DTW_BACKTRACK, DTW_STORE_D = 1, 2
+DTW_BACKTRACK, DTW_STORE_D, DTW_SUBSEQ = 1, 2, 4
+DTW_MAX_STEPS, DTW_MAX_STEP = 5, 2       # afx_dtw_steps_batch: custom steps per list, and the largest component of one
 DTW_MAX_DIM = 128
 HPSS_STORE_SPEC = 4
 HPSS_BINS = 1025
@@ -56,6 +57,7 @@ SYMBOLS = (
     "afx_butter_sos", "afx_filtfilt_geometry", "afx_sosfiltfilt_host", "afx_sosfiltfilt_batch",
     "afx_groups_batch", "afx_groups_cost", "afx_groups_dct_table", "afx_groups_debug_rows",
     "afx_beat_track_host", "afx_beat_batch",
+    "afx_dtw_steps_batch",
 )
 
 
@@ -126,6 +128,9 @@ def lib() -> C.CDLL:
         L.afx_wav_read_s16.argtypes = [vp, i32, i32, vp, vp, vp, C.c_int64, vp, vp]
         L.afx_dtw_batch.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp]
         L.afx_hpss_batch.argtypes = [vp, vp, i32, i32, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp]
+        if hasattr(L, "afx_dtw_steps_batch"):                # newer than version 107 says: found by its presence
+            L.afx_dtw_steps_batch.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, i32, i32, i32, vp, i32, vp, vp,
+                                              vp, vp, vp, vp, vp, vp, vp, vp]
         if hasattr(L, "afx_resample_batch"):                 # absent from a library older than version 107
             L.afx_resample_design.argtypes = [i32, i32, vp, vp]
             L.afx_resample_batch.argtypes = [vp, vp, i32, i32, vp, vp, i32, i32, i32, vp, i32, vp, i32, vp, vp]
@@ -607,12 +612,30 @@ class Context(_Owner):
             lib().afx_destroy(self.handle)
             self.handle = None
 
+    def dtw_steps_batch(self, feats, x_off, x_len, y_off, y_len, band_r=None, metric: str = "euclidean",
+                        backtrack: bool = True, store_d: bool = False, steps=None, weights_add=None, weights_mul=None,
+                        subseq: bool = False) -> dict:
+        """afx_dtw_steps_batch: :meth:`dtw_batch` with a step list.  ``steps``: None (the default steps, with optional
+        weights of three entries) or an int array [n, 2] of (di, dj); ``weights_add`` / ``weights_mul``: None or one value
+        per step; ``subseq``: X is matched inside Y (as given: no swap).  Also returns ``end`` [n] int32, the column j* the
+        path starts at (M - 1 without ``subseq``)."""
+        st = None if steps is None else np.ascontiguousarray(steps, np.int32).reshape(-1, 2)
+        k = 3 if st is None else int(st.shape[0])
+        wa, wm = (None if w is None else np.ascontiguousarray(w, np.float64).reshape(-1) for w in (weights_add, weights_mul))
+        for w in (wa, wm):
+            if w is not None and w.shape[0] != k:
+                raise ValueError(f"a weight array has {w.shape[0]} entries for {k} steps")
+        return self._dtw(feats, x_off, x_len, y_off, y_len, band_r, metric, backtrack, store_d, (st, k, wa, wm, bool(subseq)))
+
     def dtw_batch(self, feats, x_off, x_len, y_off, y_len, band_r=None, metric: str = "euclidean",
                   backtrack: bool = True, store_d: bool = False) -> dict:
         """afx_dtw_batch: DTW of pairs of frame sequences held in one frame-major float32 buffer ``feats`` [frames, dim]
         (pair p aligns frames x_off[p] .. + x_len[p] with y_off[p] .. + y_len[p]).  ``band_r``: None, or per pair the
         band radius (< 0: unconstrained).  Returns cost [n] float64, status [n] int32 and, when asked, ``paths`` (list of
         [L, 2] int arrays, end to start; None for a failed pair) and ``D`` (list of [N, M] float64 arrays)."""
+        return self._dtw(feats, x_off, x_len, y_off, y_len, band_r, metric, backtrack, store_d, None)
+
+    def _dtw(self, feats, x_off, x_len, y_off, y_len, band_r, metric, backtrack, store_d, general) -> dict:
         feats = np.ascontiguousarray(feats, np.float32)
         if feats.ndim != 2:
             raise ValueError("feats must be [frames, dim]")
@@ -640,11 +663,23 @@ class Context(_Owner):
             cells = xl * yl
             doff = packed_offsets(cells)
             dmat = np.empty(int(cells.sum()), np.float64)
-        _check(lib().afx_dtw_batch(self.handle, feats.ctypes.data, dim, xo.ctypes.data, xl.ctypes.data, yo.ctypes.data,
-                                   yl.ctypes.data, _ptr(br), n, DTW_METRICS[metric], flags, cost.ctypes.data,
-                                   status.ctypes.data, _ptr(path), _ptr(poff), _ptr(plen), _ptr(dmat), _ptr(doff)),
-               "afx_dtw_batch")
         out = {"cost": cost, "status": status}
+        if general is None:
+            _check(lib().afx_dtw_batch(self.handle, feats.ctypes.data, dim, xo.ctypes.data, xl.ctypes.data, yo.ctypes.data,
+                                       yl.ctypes.data, _ptr(br), n, DTW_METRICS[metric], flags, cost.ctypes.data,
+                                       status.ctypes.data, _ptr(path), _ptr(poff), _ptr(plen), _ptr(dmat), _ptr(doff)),
+                   "afx_dtw_batch")
+        else:
+            st, k, wa, wm, subseq = general
+            if not hasattr(lib(), "afx_dtw_steps_batch"):
+                raise AfxError("this libafx.so has no afx_dtw_steps_batch: rebuild it")
+            out["end"] = end = np.zeros(n, np.int32)
+            _check(lib().afx_dtw_steps_batch(self.handle, feats.ctypes.data, dim, xo.ctypes.data, xl.ctypes.data,
+                                             yo.ctypes.data, yl.ctypes.data, _ptr(br), n, DTW_METRICS[metric],
+                                             flags | (DTW_SUBSEQ if subseq else 0), _ptr(st), k, _ptr(wa), _ptr(wm),
+                                             cost.ctypes.data, status.ctypes.data, _ptr(path), _ptr(poff), _ptr(plen),
+                                             _ptr(dmat), _ptr(doff), end.ctypes.data),
+                   "afx_dtw_steps_batch")
         if backtrack:
             path = path.astype(np.int64)
             out["paths"] = [path[poff[p]:poff[p] + plen[p]] if status[p] == DTW_OK else None for p in range(n)]

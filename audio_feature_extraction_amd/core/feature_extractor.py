@@ -572,8 +572,12 @@ class AudioFeatureExtractor:
         (05_dtw_alignment_experiment/dtw_alignment.py:1206-1250 loads ``npz['mfcc']``, :930-970 aligns it).
         ``teacher`` / ``student``: ``.wav`` files (MFCC, with ``stack_deltas`` + delta + delta2, computed on the GPU) or
         ``.npz`` files written by ``save_frame_features``.  ``dtw_kwargs`` go to ``sequence.dtw`` (metric,
-        global_constraints, band_rad).  Returns teacher_path, student_path, dtw_distance, normalized_distance (distance
-        over path length) and path (L x 2, teacher frame, student frame, end to start)."""
+        global_constraints, band_rad, and librosa's step_sizes_sigma, weights_add, weights_mul, subseq).  Returns
+        teacher_path, student_path, dtw_distance, normalized_distance (distance over path length) and path (L x 2, teacher
+        frame, student frame, end to start).  With ``subseq=True`` the shorter of the two is matched inside the longer --
+        a teacher utterance inside a student's take with lead-in and trailing noise: dtw_distance is the cost of that
+        match (the minimum of D's last row), the path covers only the matched span of the longer file, and
+        normalized_distance is still that cost over that path's length, so surplus frames no longer inflate either."""
         from .. import sequence
         f = self._frames_of([teacher, student], stack_deltas)
         cost, wp = sequence.dtw(f[str(teacher)], f[str(student)], **dtw_kwargs)
@@ -582,8 +586,9 @@ class AudioFeatureExtractor:
     def align_batch(self, pairs: Sequence[Tuple[str, str]], *, stack_deltas: bool = True,
                     **dtw_kwargs) -> List[Optional[Dict[str, Any]]]:
         """``align_files`` of many (teacher, student) pairs: every distinct file is extracted once (one GPU pass for the
-        ``.wav`` files) and all pairs are aligned in one ``sequence.dtw_batch`` call.  The list is aligned with ``pairs``;
-        a pair that fails is logged and None."""
+        ``.wav`` files) and all pairs are aligned in one ``sequence.dtw_batch`` call.  ``dtw_kwargs`` as in
+        ``align_files`` (the step arguments hold for every pair).  The list is aligned with ``pairs``; a pair that fails
+        is logged and None."""
         from .. import sequence
         f = self._frames_of([p for pr in pairs for p in pr], stack_deltas)
         res = sequence.dtw_batch([(f[str(t)], f[str(s)]) for t, s in pairs], **dtw_kwargs)

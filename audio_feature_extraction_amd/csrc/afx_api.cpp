@@ -77,7 +77,7 @@ extern "C" void afx_destroy(afx_ctx* ctx) {
   if (!ctx) return;
   (void)hipSetDevice(ctx->device);
   for (DevBuf* b : {&ctx->dtw_raw, &ctx->dtw_feats, &ctx->dtw_norms, &ctx->dtw_pairs, &ctx->dtw_codes, &ctx->dtw_rows, &ctx->dtw_d,
-                    &ctx->dtw_path, &ctx->dtw_cost, &ctx->dtw_status, &ctx->dtw_len, &ctx->rs_g, &ctx->rs_tstart, &ctx->rs_clips,
+                    &ctx->dtw_path, &ctx->dtw_cost, &ctx->dtw_status, &ctx->dtw_len, &ctx->dtw_end, &ctx->rs_g, &ctx->rs_tstart, &ctx->rs_clips,
                     &ctx->rs_in, &ctx->rs_out, &ctx->dc_clips, &ctx->dc_in, &ctx->dc_out, &ctx->ft_tab, &ctx->ft_clips, &ctx->ft_st,
                     &ctx->ft_w, &ctx->ft_carry, &ctx->ft_tmax, &ctx->ft_in, &ctx->ft_out})
     release(*b);

@@ -18,48 +18,49 @@
 #include "afx_resample.h"
 
 // ---- batched DTW (librosa.sequence.dtw): the alignment step the reference runs on the extracted MFCC frames ----------
-extern "C" int afx_dtw_batch(afx_ctx* ctx, const float* feats, int dim,
-                             const int64_t* x_off, const int64_t* x_len, const int64_t* y_off, const int64_t* y_len,
-                             const int32_t* band_r, int n_pairs, int metric, int flags,
-                             double* out_cost, int32_t* out_status,
-                             int32_t* out_path, const int64_t* path_off, int32_t* out_path_len,
-                             double* out_D, const int64_t* d_off) {
+// The body of afx_dtw_batch (T == nullptr: k_dtw, the default steps) and afx_dtw_steps_batch (T: k_dtw_steps).
+static int dtw_run(const std::string& who, afx_ctx* ctx, const float* feats, int dim,
+                   const int64_t* x_off, const int64_t* x_len, const int64_t* y_off, const int64_t* y_len,
+                   const int32_t* band_r, int n_pairs, int metric, int flags, const DtwSteps* T,
+                   double* out_cost, int32_t* out_status,
+                   int32_t* out_path, const int64_t* path_off, int32_t* out_path_len,
+                   double* out_D, const int64_t* d_off, int32_t* out_end) {
   const bool bt = (flags & AFX_DTW_BACKTRACK) != 0, sd = (flags & AFX_DTW_STORE_D) != 0;
   if (!ctx || n_pairs < 0 || (n_pairs > 0 && (!feats || !x_off || !x_len || !y_off || !y_len || !out_cost || !out_status))) {
-    set_error("afx_dtw_batch: null/invalid argument");
+    set_error(who + ": null/invalid argument");
     return AFX_ERR_INVALID;
   }
-  if (flags & ~(AFX_DTW_BACKTRACK | AFX_DTW_STORE_D)) { set_error("afx_dtw_batch: unknown flag"); return AFX_ERR_INVALID; }
+  if (flags & ~(AFX_DTW_BACKTRACK | AFX_DTW_STORE_D | (T ? AFX_DTW_SUBSEQ : 0))) { set_error(who + ": unknown flag"); return AFX_ERR_INVALID; }
   if (metric != AFX_DTW_EUCLIDEAN && metric != AFX_DTW_SQEUCLIDEAN && metric != AFX_DTW_COSINE) {
-    set_error("afx_dtw_batch: unknown metric");
+    set_error(who + ": unknown metric");
     return AFX_ERR_INVALID;
   }
   if (n_pairs > 0 && bt && (!out_path || !path_off || !out_path_len)) {
-    set_error("afx_dtw_batch: AFX_DTW_BACKTRACK needs out_path, path_off and out_path_len");
+    set_error(who + ": AFX_DTW_BACKTRACK needs out_path, path_off and out_path_len");
     return AFX_ERR_INVALID;
   }
-  if (n_pairs > 0 && sd && (!out_D || !d_off)) { set_error("afx_dtw_batch: AFX_DTW_STORE_D needs out_D and d_off"); return AFX_ERR_INVALID; }
-  if (dim < 1) { set_error("afx_dtw_batch: dim must be >= 1"); return AFX_ERR_INVALID; }
-  if (dim > kDtwMaxDim) { set_error("afx_dtw_batch: dim > 128 is not supported by the DTW kernel"); return AFX_ERR_UNSUPPORTED; }
+  if (n_pairs > 0 && sd && (!out_D || !d_off)) { set_error(who + ": AFX_DTW_STORE_D needs out_D and d_off"); return AFX_ERR_INVALID; }
+  if (dim < 1) { set_error(who + ": dim must be >= 1"); return AFX_ERR_INVALID; }
+  if (dim > kDtwMaxDim) { set_error(who + ": dim > 128 is not supported by the DTW kernel"); return AFX_ERR_UNSUPPORTED; }
   int64_t n_frames = 0;
   for (int p = 0; p < n_pairs; ++p) {
     if (x_off[p] < 0 || y_off[p] < 0 || x_len[p] < 1 || y_len[p] < 1 || x_off[p] > INT64_MAX / 2 || y_off[p] > INT64_MAX / 2 ||
         x_len[p] > INT32_MAX || y_len[p] > INT32_MAX) {
-      set_error("afx_dtw_batch: pair " + std::to_string(p) + ": offsets must be >= 0 and lengths >= 1");
+      set_error(who + ": pair " + std::to_string(p) + ": offsets must be >= 0 and lengths >= 1");
       return AFX_ERR_INVALID;
     }
     if (x_len[p] * y_len[p] > ((int64_t)1 << 31) || x_len[p] > (1 << 30) || y_len[p] > (1 << 30)) {
-      set_error("afx_dtw_batch: pair " + std::to_string(p) + ": N * M > 2^31 cells is not supported");
+      set_error(who + ": pair " + std::to_string(p) + ": N * M > 2^31 cells is not supported");
       return AFX_ERR_UNSUPPORTED;
     }
     if ((bt && path_off[p] < 0) || (sd && d_off[p] < 0)) {
-      set_error("afx_dtw_batch: pair " + std::to_string(p) + ": negative output offset");
+      set_error(who + ": pair " + std::to_string(p) + ": negative output offset");
       return AFX_ERR_INVALID;
     }
     n_frames = std::max(n_frames, std::max(x_off[p] + x_len[p], y_off[p] + y_len[p]));
   }
   if (n_pairs == 0) return AFX_OK;
-  if (n_frames > INT64_MAX / 4 / dim) { set_error("afx_dtw_batch: feature buffer too large"); return AFX_ERR_INVALID; }
+  if (n_frames > INT64_MAX / 4 / dim) { set_error(who + ": feature buffer too large"); return AFX_ERR_INVALID; }
 
   (void)hipGetLastError();
   HIP_TRY(hipSetDevice(ctx->device));
@@ -84,13 +85,13 @@ extern "C" int afx_dtw_batch(afx_ctx* ctx, const float* feats, int dim,
     int c1 = c0;
     while (c1 < n_pairs) {
       const int n = (int)x_len[c1], m = (int)y_len[c1];
-      const int64_t pc = bt ? dtw_code_words(n, m) : 0, pd = sd ? (int64_t)n * m : 0, pp = bt ? (int64_t)n + m - 1 : 0;
-      const int64_t pb = pc * 4 + pd * 8 + pp * 8 + (int64_t)m * 8 + (int64_t)sizeof(DtwPair) + 16;
+      const int64_t pc = !bt ? 0 : T ? dtw_steps_code_words(n, m) : dtw_code_words(n, m), pr = T ? 2 * (int64_t)m : m, pd = sd ? (int64_t)n * m : 0, pp = bt ? (int64_t)n + m - 1 : 0;
+      const int64_t pb = pc * 4 + pd * 8 + pp * 8 + pr * 8 + (int64_t)sizeof(DtwPair) + 16;
       if (c1 > c0 && bytes + pb > budget) break;
       DtwPair r{};
       r.x_frame = x_off[c1]; r.y_frame = y_off[c1];
       r.codes = bt ? codes : -1; r.d = sd ? dcells : -1; r.path = paths; r.row = rows;
-      r.n = n; r.m = m; r.qn = dtw_qn(m);
+      r.n = n; r.m = m; r.qn = T ? dtw_steps_qn(m) : dtw_qn(m);
       const int64_t rad = band_r ? band_r[c1] : -1;
       if (rad < 0) {
         r.lo = -(1 << 30); r.hi = 1 << 30;
@@ -100,7 +101,7 @@ extern "C" int afx_dtw_batch(afx_ctx* ctx, const float* feats, int dim,
         r.hi = (int32_t)(rr + (n < m ? off : 0));
       }
       recs.push_back(r);
-      codes += pc; dcells += pd; paths += pp; rows += m; bytes += pb;
+      codes += pc; dcells += pd; paths += pp; rows += pr; bytes += pb;
       ++c1;
     }
     const int n = c1 - c0;
@@ -108,6 +109,7 @@ extern "C" int afx_dtw_batch(afx_ctx* ctx, const float* feats, int dim,
     if ((rc = ensure(ctx->dtw_rows, (size_t)rows * sizeof(double))) != AFX_OK) return rc;
     if ((rc = ensure(ctx->dtw_cost, n * sizeof(double))) != AFX_OK) return rc;
     if ((rc = ensure(ctx->dtw_status, n * sizeof(int32_t))) != AFX_OK) return rc;
+    if (T && (rc = ensure(ctx->dtw_end, n * sizeof(int32_t))) != AFX_OK) return rc;
     if (bt) {
       if ((rc = ensure(ctx->dtw_codes, (size_t)codes * sizeof(uint32_t))) != AFX_OK) return rc;
       if ((rc = ensure(ctx->dtw_path, (size_t)paths * 2 * sizeof(int32_t))) != AFX_OK) return rc;
@@ -119,12 +121,23 @@ extern "C" int afx_dtw_batch(afx_ctx* ctx, const float* feats, int dim,
     }
     HIP_TRY(hipMemcpyAsync(ctx->dtw_pairs.p, recs.data(), n * sizeof(DtwPair), hipMemcpyHostToDevice, s));
     const DtwPair* d_pairs = (const DtwPair*)ctx->dtw_pairs.p;
-    HIP_TRY(launch_dtw(s, (const float*)ctx->dtw_feats.p, d_norms, dim, metric, d_pairs, n, (uint32_t*)ctx->dtw_codes.p,
-                       (double*)ctx->dtw_rows.p, (double*)ctx->dtw_d.p, (double*)ctx->dtw_cost.p,
-                       (int32_t*)ctx->dtw_status.p, bt, sd));
-    if (bt)
-      HIP_TRY(launch_dtw_backtrack(s, d_pairs, n, (const uint32_t*)ctx->dtw_codes.p, (const int32_t*)ctx->dtw_status.p,
-                                   (int32_t*)ctx->dtw_path.p, (int32_t*)ctx->dtw_len.p));
+    if (T) {
+      HIP_TRY(launch_dtw_steps(s, (const float*)ctx->dtw_feats.p, d_norms, dim, metric, d_pairs, n, *T,
+                               (uint32_t*)ctx->dtw_codes.p, (double*)ctx->dtw_rows.p, (double*)ctx->dtw_d.p,
+                               (double*)ctx->dtw_cost.p, (int32_t*)ctx->dtw_status.p, (int32_t*)ctx->dtw_end.p, bt, sd));
+      if (bt)
+        HIP_TRY(launch_dtw_steps_backtrack(s, d_pairs, n, *T, (const uint32_t*)ctx->dtw_codes.p,
+                                           (const int32_t*)ctx->dtw_status.p, (const int32_t*)ctx->dtw_end.p,
+                                           (int32_t*)ctx->dtw_path.p, (int32_t*)ctx->dtw_len.p));
+      if (out_end) HIP_TRY(hipMemcpyAsync(out_end + c0, ctx->dtw_end.p, n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    } else {
+      HIP_TRY(launch_dtw(s, (const float*)ctx->dtw_feats.p, d_norms, dim, metric, d_pairs, n, (uint32_t*)ctx->dtw_codes.p,
+                         (double*)ctx->dtw_rows.p, (double*)ctx->dtw_d.p, (double*)ctx->dtw_cost.p,
+                         (int32_t*)ctx->dtw_status.p, bt, sd));
+      if (bt)
+        HIP_TRY(launch_dtw_backtrack(s, d_pairs, n, (const uint32_t*)ctx->dtw_codes.p, (const int32_t*)ctx->dtw_status.p,
+                                     (int32_t*)ctx->dtw_path.p, (int32_t*)ctx->dtw_len.p));
+    }
     HIP_TRY(hipMemcpyAsync(out_cost + c0, ctx->dtw_cost.p, n * sizeof(double), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipMemcpyAsync(out_status + c0, ctx->dtw_status.p, n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
     if (bt) {
@@ -146,6 +159,69 @@ extern "C" int afx_dtw_batch(afx_ctx* ctx, const float* feats, int dim,
     c0 = c1;
   }
   return AFX_OK;
+}
+
+extern "C" int afx_dtw_batch(afx_ctx* ctx, const float* feats, int dim,
+                             const int64_t* x_off, const int64_t* x_len, const int64_t* y_off, const int64_t* y_len,
+                             const int32_t* band_r, int n_pairs, int metric, int flags,
+                             double* out_cost, int32_t* out_status,
+                             int32_t* out_path, const int64_t* path_off, int32_t* out_path_len,
+                             double* out_D, const int64_t* d_off) {
+  return dtw_run("afx_dtw_batch", ctx, feats, dim, x_off, x_len, y_off, y_len, band_r, n_pairs, metric, flags, nullptr,
+                 out_cost, out_status, out_path, path_off, out_path_len, out_D, d_off, nullptr);
+}
+
+// the step list of afx_dtw_steps_batch as the kernel takes it; false (and the error set) when the caller's is refused
+static bool dtw_step_list(const int32_t* steps, int n_steps, const double* w_add, const double* w_mul, bool subseq,
+                          DtwSteps& T, int& rc) {
+  const std::string who = "afx_dtw_steps_batch: ";
+  auto fail = [&](int code, const std::string& what) { set_error(who + what); rc = code; return false; };
+  T = DtwSteps{};
+  T.subseq = subseq ? 1 : 0;
+  if (!steps) {                                      // the default steps (1,1), (0,1), (1,0), weights optional
+    static const int32_t def_sel[3] = {4, 1, 3};
+    T.n = 3;
+    for (int k = 0; k < 3; ++k) { T.sel[k] = def_sel[k]; T.idx[k] = k; }
+  } else {
+    if (n_steps < 1) return fail(AFX_ERR_INVALID, "n_steps must be >= 1");
+    if (n_steps > kDtwMaxSteps) return fail(AFX_ERR_UNSUPPORTED, "more than 5 custom steps are not supported");
+    for (int k = 0; k < n_steps; ++k) {
+      const int32_t di = steps[2 * k], dj = steps[2 * k + 1];
+      if (di < 0 || dj < 0) return fail(AFX_ERR_INVALID, "step " + std::to_string(k) + " has a negative component");
+      if (di == 0 && dj == 0) return fail(AFX_ERR_INVALID, "step " + std::to_string(k) + " is (0, 0)");
+      if (di > 2 || dj > 2) return fail(AFX_ERR_UNSUPPORTED, "step " + std::to_string(k) + ": components above 2 are not supported");
+      T.sel[k] = di * 3 + dj;
+      T.idx[k] = 3 + k;                              // behind librosa's three defaults, whose inf weights never win
+    }
+    T.n = n_steps;
+  }
+  for (int k = 0; k < T.n; ++k) {
+    T.w_add[k] = w_add ? w_add[k] : 0.0;
+    T.w_mul[k] = w_mul ? w_mul[k] : 1.0;
+    if (!(T.w_add[k] >= 0.0) || !(T.w_mul[k] >= 0.0) || std::isinf(T.w_add[k]) || std::isinf(T.w_mul[k]))
+      return fail(AFX_ERR_INVALID, "weight " + std::to_string(k) + " is negative or not finite");
+  }
+  return true;
+}
+
+extern "C" int afx_dtw_steps_batch(afx_ctx* ctx, const float* feats, int dim,
+                                   const int64_t* x_off, const int64_t* x_len, const int64_t* y_off, const int64_t* y_len,
+                                   const int32_t* band_r, int n_pairs, int metric, int flags,
+                                   const int32_t* steps, int n_steps, const double* w_add, const double* w_mul,
+                                   double* out_cost, int32_t* out_status,
+                                   int32_t* out_path, const int64_t* path_off, int32_t* out_path_len,
+                                   double* out_D, const int64_t* d_off, int32_t* out_end) {
+  DtwSteps T;
+  int rc = AFX_OK;
+  if (!dtw_step_list(steps, n_steps, w_add, w_mul, (flags & AFX_DTW_SUBSEQ) != 0, T, rc)) return rc;
+  if (T.n == 1 && T.sel[0] == 4 && x_len && y_len)   // (1,1) alone cannot shorten a sequence (librosa raises)
+    for (int p = 0; p < n_pairs; ++p)
+      if (x_len[p] > y_len[p]) {
+        set_error("afx_dtw_steps_batch: pair " + std::to_string(p) + ": the step list [(1,1)] needs N <= M");
+        return AFX_ERR_INVALID;
+      }
+  return dtw_run("afx_dtw_steps_batch", ctx, feats, dim, x_off, x_len, y_off, y_len, band_r, n_pairs, metric, flags, &T,
+                 out_cost, out_status, out_path, path_off, out_path_len, out_D, d_off, out_end);
 }
 
 // ---- batched polyphase resampling (wavio.resample: the resampling half of librosa.load(path, sr=...)) -------------------

@@ -21,26 +21,16 @@
 
 #include "afx.h"
 #include "afx_dtw.h"
+#include "afx_dtw_dev.h"
 
 namespace afx {
 namespace {
 
-constexpr double kInf = __builtin_huge_val();
-typedef float f2 __attribute__((ext_vector_type(2)));   // v_pk_add_f32 / v_pk_fma_f32 operands
+constexpr double kInf = kDtwInf;
+typedef dtw_f2 f2;
 
-__device__ __forceinline__ double shr1(double v, double lane0) {
-  // lane l <- lane l-1 (wave_shr:1, DPP control 0x138); lane 0 keeps `lane0`
-  const int lo = __builtin_amdgcn_update_dpp(__double2loint(lane0), __double2loint(v), 0x138, 0xf, 0xf, false);
-  const int hi = __builtin_amdgcn_update_dpp(__double2hiint(lane0), __double2hiint(v), 0x138, 0xf, 0xf, false);
-  return __hiloint2double(hi, lo);
-}
-
-__device__ __forceinline__ double shl1(double v) {
-  // lane l <- lane l+1 (wave_shl:1, DPP control 0x130)
-  const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), 0x130, 0xf, 0xf, false);
-  const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), 0x130, 0xf, 0xf, false);
-  return __hiloint2double(hi, lo);
-}
+__device__ __forceinline__ double shr1(double v, double lane0) { return dtw_shr1(v, lane0); }
+__device__ __forceinline__ double shl1(double v) { return dtw_shl1(v); }
 
 // frame-major features of stride dim -> stride dimp (zero-padded, so that the DP reads whole 16-byte units without a
 // per-element test): one element per thread, coalesced on both sides
@@ -90,19 +80,7 @@ __global__ void __launch_bounds__(64) k_dtw(const float* __restrict__ feats, con
   const int N = P.n, M = P.m;
 
   // ---- NaN / inf anywhere in X or Y, or a zero-norm frame under cosine: librosa raises; the pair is skipped
-  bool bad = false;
-  {
-    const float* fx = feats + P.x_frame * DIMP;
-    const float* fy = feats + P.y_frame * DIMP;
-    const int64_t nx = (int64_t)N * DIMP, ny = (int64_t)M * DIMP;
-    for (int64_t e = l; e < nx; e += 64) bad |= !isfinite(fx[e]);
-    for (int64_t e = l; e < ny; e += 64) bad |= !isfinite(fy[e]);
-    if (METRIC == AFX_DTW_COSINE) {
-      for (int t = l; t < N; t += 64) bad |= !(norms[P.x_frame + t] > 0.f);
-      for (int t = l; t < M; t += 64) bad |= !(norms[P.y_frame + t] > 0.f);
-    }
-  }
-  if (__any(bad)) {
+  if (dtw_pair_nonfinite<DIMP, METRIC>(feats, norms, P, l)) {
     if (l == 0) { cost[blockIdx.x] = __builtin_nan(""); status[blockIdx.x] = AFX_DTW_NONFINITE; }
     return;
   }
@@ -184,42 +162,7 @@ __global__ void __launch_bounds__(64) k_dtw(const float* __restrict__ feats, con
 #pragma unroll
       for (int b = 0; b < kDtwTile; ++b) {
         const int s = c0 + b, j = s - l;
-        const float4* yp = reinterpret_cast<const float4*>(ys + slot * S);
-        float c;
-        if (METRIC == AFX_DTW_COSINE) {
-          f2 dot = f2{0.f, 0.f};
-#pragma unroll
-          for (int q = 0; q < DIMP / 4; ++q) {
-            const float4 y = yp[q];
-            if constexpr (DIMP <= 64) {
-              dot = __builtin_elementwise_fma(xr[2 * q], f2{y.x, y.y}, dot);
-              dot = __builtin_elementwise_fma(xr[2 * q + 1], f2{y.z, y.w}, dot);
-            } else {
-              dot.x = fmaf(xr[2 * q].x, y.x, dot.x); dot.y = fmaf(xr[2 * q].y, y.y, dot.y);
-              dot.x = fmaf(xr[2 * q + 1].x, y.z, dot.x); dot.y = fmaf(xr[2 * q + 1].y, y.w, dot.y);
-            }
-          }
-          const float ny = ys[slot * S + DIMP];
-          const float cs = fminf(1.f, fmaxf(-1.f, (dot.x + dot.y) / (nx * ny)));
-          c = 1.f - cs;
-        } else {
-          f2 acc = f2{0.f, 0.f};
-#pragma unroll
-          for (int q = 0; q < DIMP / 4; ++q) {
-            const float4 y = yp[q];
-            if constexpr (DIMP <= 64) {
-              const f2 d0 = xr[2 * q] - f2{y.x, y.y}, d1 = xr[2 * q + 1] - f2{y.z, y.w};
-              acc = __builtin_elementwise_fma(d0, d0, acc);
-              acc = __builtin_elementwise_fma(d1, d1, acc);
-            } else {     // scalar ops: the packed form's aligned register pairs push the 128-wide instance into spills
-              const float d0 = xr[2 * q].x - y.x, d1 = xr[2 * q].y - y.y, d2 = xr[2 * q + 1].x - y.z, d3 = xr[2 * q + 1].y - y.w;
-              acc.x = fmaf(d0, d0, acc.x); acc.y = fmaf(d1, d1, acc.y);
-              acc.x = fmaf(d2, d2, acc.x); acc.y = fmaf(d3, d3, acc.y);
-            }
-          }
-          c = acc.x + acc.y;
-          if (METRIC == AFX_DTW_EUCLIDEAN) c = sqrtf(c);
-        }
+        const float c = dtw_local_cost<DIMP, METRIC>(xr, nx, ys, slot);
         const int dj = j - i;
         const bool valid = rowok && j >= 0 && j < M;
         const bool inband = valid && dj > P.lo && dj < P.hi;

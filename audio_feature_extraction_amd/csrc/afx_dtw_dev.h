@@ -1,0 +1,100 @@
+// Device code the two DTW recurrence kernels share (k_dtw in afx_dtw.hip, k_dtw_steps in afx_dtw_steps.hip): the DPP lane
+// shifts of a double, the per-pair NaN / zero-norm test and the local cost of one cell.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+#include <type_traits>
+
+#include "afx.h"
+#include "afx_dtw.h"
+
+namespace afx {
+
+constexpr double kDtwInf = __builtin_huge_val();
+typedef float dtw_f2 __attribute__((ext_vector_type(2)));   // v_pk_add_f32 / v_pk_fma_f32 operands
+
+__device__ __forceinline__ double dtw_shr1(double v, double lane0) {
+  // lane l <- lane l-1 (wave_shr:1, DPP control 0x138); lane 0 keeps `lane0`
+  const int lo = __builtin_amdgcn_update_dpp(__double2loint(lane0), __double2loint(v), 0x138, 0xf, 0xf, false);
+  const int hi = __builtin_amdgcn_update_dpp(__double2hiint(lane0), __double2hiint(v), 0x138, 0xf, 0xf, false);
+  return __hiloint2double(hi, lo);
+}
+
+__device__ __forceinline__ double dtw_shl1(double v) {
+  // lane l <- lane l+1 (wave_shl:1, DPP control 0x130)
+  const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), 0x130, 0xf, 0xf, false);
+  const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), 0x130, 0xf, 0xf, false);
+  return __hiloint2double(hi, lo);
+}
+
+// NaN / inf anywhere in X or Y, or a zero-norm frame under cosine (librosa raises): true in every lane of the wave
+template <int DIMP, int METRIC>
+__device__ __forceinline__ bool dtw_pair_nonfinite(const float* __restrict__ feats, const float* __restrict__ norms,
+                                                   const DtwPair& P, int l) {
+  bool bad = false;
+  const float* fx = feats + P.x_frame * DIMP;
+  const float* fy = feats + P.y_frame * DIMP;
+  const int64_t nx = (int64_t)P.n * DIMP, ny = (int64_t)P.m * DIMP;
+  for (int64_t e = l; e < nx; e += 64) bad |= !isfinite(fx[e]);
+  for (int64_t e = l; e < ny; e += 64) bad |= !isfinite(fy[e]);
+  if (METRIC == AFX_DTW_COSINE) {
+    for (int t = l; t < P.n; t += 64) bad |= !(norms[P.x_frame + t] > 0.f);
+    for (int t = l; t < P.m; t += 64) bad |= !(norms[P.y_frame + t] > 0.f);
+  }
+  return __any(bad);
+}
+
+// the local cost of the lane's x row (xr, norm nx) against the y column in ring slot `slot` (stride S = DIMP + 4 floats,
+// the column's norm in float DIMP): float32, direct differences, as scipy's cdist.
+// XR: an array of DIMP / 2 register pairs, or anything indexed the same way that reads the row from LDS.  The LDS form
+// runs in pieces of eight 16-byte units: the accumulator and an offset that is always zero pass through an empty asm
+// between pieces, so a piece's reads cannot be issued before the piece before it is summed.  Left alone, the scheduler
+// issues all 64 reads of a 128-wide cell before the first subtraction and needs 256 registers to land them.
+template <int DIMP, int METRIC, class XR>
+__device__ __forceinline__ float dtw_local_cost(const XR& xr, float nx, const float* ys, int slot) {
+  constexpr int S = DIMP + 4;
+  constexpr bool kLdsRow = !std::is_array<XR>::value;
+  const float4* yp = reinterpret_cast<const float4*>(ys + slot * S);
+  int off = 0;
+  dtw_f2 acc = dtw_f2{0.f, 0.f};          // cosine: the dot product; otherwise the sum of squared differences
+#pragma unroll
+  for (int q = 0; q < DIMP / 4; ++q) {
+    if constexpr (kLdsRow) {
+      if (q > 0 && q % 8 == 0) asm volatile("" : "+v"(acc.x), "+v"(acc.y), "+v"(off));
+    }
+    const float4 y = yp[q + off];
+    const dtw_f2 x0 = xr[2 * (q + off)], x1 = xr[2 * (q + off) + 1];
+    if (METRIC == AFX_DTW_COSINE) {
+      if constexpr (DIMP <= 64) {
+        acc = __builtin_elementwise_fma(x0, dtw_f2{y.x, y.y}, acc);
+        acc = __builtin_elementwise_fma(x1, dtw_f2{y.z, y.w}, acc);
+      } else {
+        acc.x = fmaf(x0.x, y.x, acc.x); acc.y = fmaf(x0.y, y.y, acc.y);
+        acc.x = fmaf(x1.x, y.z, acc.x); acc.y = fmaf(x1.y, y.w, acc.y);
+      }
+    } else {
+      if constexpr (DIMP <= 64) {
+        const dtw_f2 d0 = x0 - dtw_f2{y.x, y.y}, d1 = x1 - dtw_f2{y.z, y.w};
+        acc = __builtin_elementwise_fma(d0, d0, acc);
+        acc = __builtin_elementwise_fma(d1, d1, acc);
+      } else {     // scalar ops: the packed form's aligned register pairs push the 128-wide instance into spills
+        const float d0 = x0.x - y.x, d1 = x0.y - y.y, d2 = x1.x - y.z, d3 = x1.y - y.w;
+        acc.x = fmaf(d0, d0, acc.x); acc.y = fmaf(d1, d1, acc.y);
+        acc.x = fmaf(d2, d2, acc.x); acc.y = fmaf(d3, d3, acc.y);
+      }
+    }
+  }
+  float c;
+  if (METRIC == AFX_DTW_COSINE) {
+    const float ny = ys[slot * S + DIMP];
+    const float cs = fminf(1.f, fmaxf(-1.f, (acc.x + acc.y) / (nx * ny)));
+    c = 1.f - cs;
+  } else {
+    c = acc.x + acc.y;
+    if (METRIC == AFX_DTW_EUCLIDEAN) c = sqrtf(c);
+  }
+  return c;
+}
+
+}  // namespace afx

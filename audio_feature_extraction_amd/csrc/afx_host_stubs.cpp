@@ -45,6 +45,11 @@ int afx_dtw_batch(afx_ctx*, const float*, int, const int64_t*, const int64_t*, c
                   int, int, int, double*, int32_t*, int32_t*, const int64_t*, int32_t*, double*, const int64_t*) {
   return no_device("afx_dtw_batch");
 }
+int afx_dtw_steps_batch(afx_ctx*, const float*, int, const int64_t*, const int64_t*, const int64_t*, const int64_t*,
+                        const int32_t*, int, int, int, const int32_t*, int, const double*, const double*, double*, int32_t*,
+                        int32_t*, const int64_t*, int32_t*, double*, const int64_t*, int32_t*) {
+  return no_device("afx_dtw_steps_batch");
+}
 int afx_hpss_batch(afx_plan*, const void*, int, int, const int64_t*, const int64_t*, int, int, float*, float*, double*, float*,
                    const int64_t*, int32_t*) {
   return no_device("afx_hpss_batch");

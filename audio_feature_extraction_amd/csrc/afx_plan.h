@@ -36,7 +36,7 @@ using namespace afx;
 struct afx_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
-  DevBuf dtw_raw, dtw_feats, dtw_norms, dtw_pairs, dtw_codes, dtw_rows, dtw_d, dtw_path, dtw_cost, dtw_status, dtw_len;   // afx_dtw_batch
+  DevBuf dtw_raw, dtw_feats, dtw_norms, dtw_pairs, dtw_codes, dtw_rows, dtw_d, dtw_path, dtw_cost, dtw_status, dtw_len, dtw_end;   // afx_dtw_batch, afx_dtw_steps_batch
   // afx_resample_batch: the tables of the last rate pair (or caller-supplied filter) used, and the staging of host batches
   struct {
     bool valid = false, custom = false;

@@ -53,13 +53,13 @@ typedef enum afx_clip_status {
 typedef enum afx_dtw_status {
   AFX_DTW_OK = 0,
   AFX_DTW_NONFINITE = 1,   /* NaN / inf feature, or a zero-norm frame under AFX_DTW_COSINE (librosa raises) */
-  AFX_DTW_NO_PATH = 2      /* D[N-1, M-1] is inf: the band admits no path (band radius 0) */
+  AFX_DTW_NO_PATH = 2      /* D[N-1, M-1] (subseq: all of row N-1) is inf: the band or the step list admits no path */
 } afx_dtw_status;
 
 /* local cost of afx_dtw_batch: scipy.spatial.distance.cdist's metrics of the same names */
 enum { AFX_DTW_EUCLIDEAN = 0, AFX_DTW_SQEUCLIDEAN = 1, AFX_DTW_COSINE = 2 };
 /* flags for afx_dtw_batch */
-enum { AFX_DTW_BACKTRACK = 1, AFX_DTW_STORE_D = 2 };
+enum { AFX_DTW_BACKTRACK = 1, AFX_DTW_STORE_D = 2, AFX_DTW_SUBSEQ = 4 /* afx_dtw_steps_batch only */ };
 /* afx_hpss_batch: with the AFX_FLAG_* bits, the debug output of the median stage */
 enum { AFX_HPSS_STORE_SPEC = 4 };
 
@@ -276,6 +276,33 @@ int afx_dtw_batch(afx_ctx* ctx, const float* feats, int dim,
                   double* out_cost, int32_t* out_status,
                   int32_t* out_path, const int64_t* path_off, int32_t* out_path_len,
                   double* out_D, const int64_t* d_off);
+
+/* afx_dtw_batch with librosa.sequence.dtw's step_sizes_sigma, weights_add, weights_mul and subseq.  Everything
+ * afx_dtw_batch takes means the same; in addition:
+ *   steps, n_steps  NULL: the default steps (1,1), (0,1), (1,0), with w_add / w_mul of 3 entries (n_steps is ignored).
+ *             Otherwise int32[n_steps][2], the caller's (di, dj) list: 1 .. 5 steps, components 0 .. 2
+ *             (AFX_ERR_UNSUPPORTED above either), no negative component and no (0, 0) (AFX_ERR_INVALID).  As in librosa
+ *             the list follows the three defaults, whose inf weights never win: the recorded step indices start at 3.
+ *             The list [(1,1)] alone needs N <= M for every pair (AFX_ERR_INVALID, as librosa raises).
+ *   w_add, w_mul  NULL (zeros / ones), or one double per step: candidate = D[i-di, j-dj] + (w_mul * C[i, j] + w_add), the
+ *             multiply and the add both rounded to float64, compared in list order with a strict <.  Negative, NaN and inf
+ *             weights are AFX_ERR_INVALID.
+ *   flags     also AFX_DTW_SUBSEQ: row 0 of D is seeded with C[0, :], the path ends at (N-1, j*) with j* the first argmin
+ *             of D[N-1, :] and is walked back to the first cell of row 0.  X is aligned inside Y as given: librosa's
+ *             swap for N > M is the caller's.
+ *   out_cost  D[N-1, M-1], or D[N-1, j*] under AFX_DTW_SUBSEQ
+ *   out_end   NULL, or host int32[n_pairs]: j* (M - 1 without AFX_DTW_SUBSEQ; -1 for a NONFINITE pair)
+ * Argument errors are reported before any device work.  Step codes take 4 bits per cell and a pair has two boundary
+ * rows; the chunks are cut with those sizes.  A call with steps == NULL, unit weights and no AFX_DTW_SUBSEQ computes what
+ * afx_dtw_batch computes, with this entry point's kernel.  Newer than AFX_VERSION 107 says: a binding detects it by its
+ * presence. */
+int afx_dtw_steps_batch(afx_ctx* ctx, const float* feats, int dim,
+                        const int64_t* x_off, const int64_t* x_len, const int64_t* y_off, const int64_t* y_len,
+                        const int32_t* band_r, int n_pairs, int metric, int flags,
+                        const int32_t* steps, int n_steps, const double* w_add, const double* w_mul,
+                        double* out_cost, int32_t* out_status,
+                        int32_t* out_path, const int64_t* path_off, int32_t* out_path_len,
+                        double* out_D, const int64_t* d_off, int32_t* out_end);
 
 /* librosa.effects.hpss / harmonic at librosa 0.11's defaults (kernel_size 31, power 2, margin 1) and the harmonic
  * features of 04_feature_extraction_experiment/feature_extractor.py:525-556 (librosa.effects.harmonic, then
