@@ -39,6 +39,9 @@ GROUP_SPECTRAL, GROUP_HARMONIC, GROUP_TIMBRE, GROUP_RHYTHM = 1, 2, 4, 8     # af
 GROUP_ALL = 15
 GROUPS_PREPROCESS, GROUPS_STORE_DESC = 16, 32                                # its flags, beside FLAG_PREEMPH
 BEAT_INPUT_ENVELOPE = 64                                                     # afx_beat_batch: the clips are onset envelopes
+DENOISE_SPECSUB, DENOISE_WIENER = 0, 1                                       # afx_denoise_batch: its modes
+DENOISE_RMS_GAIN, DENOISE_VAD = 128, 256                                     # its flags, beside FLAG_PREEMPH
+DENOISE_MAX_NOISE_FRAMES = 64
 BEAT_MAX_FPB = 768                                                           # frames per beat it holds
 GROUPS_STATS = 24                                                            # doubles per clip of its record
 K_NAMES = ("trim_blocks", "trim_decide", "frames", "dct", "stats")
@@ -58,6 +61,7 @@ SYMBOLS = (
     "afx_groups_batch", "afx_groups_cost", "afx_groups_dct_table", "afx_groups_debug_rows",
     "afx_beat_track_host", "afx_beat_batch",
     "afx_dtw_steps_batch",
+    "afx_denoise_batch", "afx_denoise_cost",
 )
 
 
@@ -159,6 +163,9 @@ def lib() -> C.CDLL:
             dbl = C.c_double
             L.afx_beat_track_host.argtypes = [vp, C.c_int64, dbl, dbl, dbl, i32, vp, i64p, vp, vp, vp]
             L.afx_beat_batch.argtypes = [vp, vp, i32, i32, vp, vp, i32, i32, vp, dbl, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+        if hasattr(L, "afx_denoise_batch"):                  # newer than version 107 says: found by their presence
+            L.afx_denoise_batch.argtypes = [vp, vp, i32, i32, vp, vp, i32, i32, i32, C.c_double, i32, vp, vp, vp]
+            L.afx_denoise_cost.argtypes = [i32, i32, i32, vp]
         if hasattr(L, "afx_rfft_host"):                      # absent from a library built before the mixed-radix lengths
             L.afx_rfft_host.argtypes = [i32, vp, vp]
         _lib = L
@@ -341,6 +348,39 @@ def groups_cost(groups: int, flags: int = 0) -> np.ndarray:
     cost = np.zeros(6, np.int64)
     _check(lib().afx_groups_cost(int(groups), int(flags), cost.ctypes.data), "afx_groups_cost")
     return cost
+
+
+def _need_denoise():
+    if not hasattr(lib(), "afx_denoise_batch"):
+        raise NotImplementedError("this libafx has no afx_denoise_batch")
+
+
+def denoise_cost(flags: int = 0, fmt: int = FMT_F32, mem: int = MEM_HOST) -> np.ndarray:
+    """Host-only: the cost record afx_denoise_batch cuts a batch with (bytes per frame, per tile, per sample, per clip;
+    frames per tile, most tiles of a chunk), for ``stft_chunks``."""
+    _need_denoise()
+    cost = np.zeros(6, np.int64)
+    _check(lib().afx_denoise_cost(int(flags), int(fmt), int(mem), cost.ctypes.data), "afx_denoise_cost")
+    return cost
+
+
+def denoise_check(params: "Params", flags: int, mode: int, beta: float, noise_frames: int) -> None:
+    """What afx_denoise_batch refuses of a plan's parameters and of its own arguments, raised as the call itself would
+    raise it (NotImplementedError: a plan or flag it does not support; ValueError: an invalid argument).  No device."""
+    if params.n_fft != 2048 or params.hop != 512 or params.window != WINDOW_HANN:
+        raise NotImplementedError("afx_denoise_batch: the plan must have frame_length 2048, hop_length 512 and the Hann window")
+    if flags & FLAG_TRIM:
+        raise NotImplementedError("afx_denoise_batch: trim is not applied here; pass the preprocessed signal")
+    if flags & ~(FLAG_PREEMPH | DENOISE_RMS_GAIN | DENOISE_VAD):
+        raise ValueError("afx_denoise_batch: unknown flag")
+    if mode not in (DENOISE_SPECSUB, DENOISE_WIENER):
+        raise ValueError("afx_denoise_batch: unknown mode")
+    if not (np.isfinite(beta) and beta >= 0):
+        raise ValueError("afx_denoise_batch: beta must be finite and >= 0")
+    if not 1 <= int(noise_frames) <= DENOISE_MAX_NOISE_FRAMES or int(noise_frames) != noise_frames:
+        raise ValueError("afx_denoise_batch: noise_frames must be in [1, 64]")
+    if flags & DENOISE_VAD and int(0.010 * params.sr) < 1:
+        raise ValueError("afx_denoise_batch: the VAD needs a sample rate of at least 100 Hz")
 
 
 def groups_dct_table(n_mels: int = 128) -> np.ndarray:
@@ -1004,6 +1044,27 @@ class Plan(_Owner):
         if store_spec:
             out["spec"] = [spec[soff[i]:soff[i] + 3 * HPSS_BINS * T[i]].reshape(3, HPSS_BINS, int(T[i])) for i in range(n)]
         return out
+
+    def denoise_batch(self, samples, offsets, lengths, *, mode: int = DENOISE_SPECSUB, beta: float = 0.01, noise_frames: int = 10,
+                      rms_gain: bool = False, vad: bool = False, fmt=FMT_F32, mem=MEM_HOST, flags: int = 0) -> dict:
+        """afx_denoise_batch: spectral subtraction (``DENOISE_SPECSUB``) or the Wiener filter (``DENOISE_WIENER``) of a ragged
+        batch on the 2048 / 512 Hann STFT; ``rms_gain`` and ``vad`` add the aligner's gain to RMS 0.1 in front and its
+        energy VAD behind.  ``samples`` as for ``hpss_batch``.  Returns ``out`` (a list of float32 arrays of the clips'
+        lengths, zero from 512 (len // 512) on), ``info`` [n, 4] float64 (gain, VAD threshold, speech frames, VAD frames)
+        and ``status`` [n] int32."""
+        _need_denoise()
+        flags = int(flags) | (DENOISE_RMS_GAIN if rms_gain else 0) | (DENOISE_VAD if vad else 0)
+        denoise_check(self.params, flags, mode, beta, noise_frames)
+        offsets, lengths, n = _clip_arrays(offsets, lengths)
+        sptr, kind = _sample_source(samples, fmt, offsets, lengths, mem=mem)
+        total = int((offsets + lengths).max()) if n else 0
+        out = np.zeros(total, np.float32)
+        info = np.zeros((n, 4), np.float64)
+        status = np.zeros(n, np.int32)
+        _check(lib().afx_denoise_batch(self.handle, sptr, int(fmt), kind, offsets.ctypes.data, lengths.ctypes.data, n, flags,
+                                       int(mode), float(beta), int(noise_frames), out.ctypes.data, info.ctypes.data,
+                                       status.ctypes.data), "afx_denoise_batch")
+        return {"out": [out[o:o + l] for o, l in zip(offsets, lengths)], "info": info, "status": status}
 
     def chroma_batch(self, samples, offsets, lengths, flags=0, fmt=FMT_F32, mem=MEM_HOST, tuning=None,
                      want_chroma: bool = True, want_mel: bool = False, want_stats: bool = True, store_hist: bool = False) -> dict:

@@ -529,6 +529,19 @@ class AudioFeatureExtractor:
             raise _status_error(int(out["status"][0]), "preprocess_experiment", int(y.size))
         return out["clips"][0]
 
+    def preprocess_alignment_batch(self, signals: Sequence[np.ndarray]) -> List[Optional[np.ndarray]]:
+        """``preprocess_alignment`` of many signals in one device pass; ``None`` for a clip of fewer than 512 samples or with
+        a NaN / inf sample."""
+        from .. import effects
+        return effects.preprocess_alignment_batch(signals, self.sr, device=self._devices()[0])
+
+    def preprocess_alignment(self, y: np.ndarray) -> np.ndarray:
+        """The conditioning 05_dtw_alignment_experiment/process_audio.py:13-51 gives a recording before the DTW aligner sees
+        it -- gain to RMS 0.1, spectral subtraction of the noise profile of the first ten frames, an energy VAD that zeroes
+        what lies outside its speech frames -- at this extractor's ``sr`` and on the GPU (``effects.preprocess_alignment``)."""
+        from .. import effects
+        return effects.preprocess_alignment(y, self.sr, device=self._devices()[0])
+
     @staticmethod
     def save_frame_features(features: Dict[str, np.ndarray], npz_path: str) -> None:
         """``np.savez(npz_path, **features)`` -- the reference's on-disk schema for frame-level features."""

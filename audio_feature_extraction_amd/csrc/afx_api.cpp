@@ -286,7 +286,8 @@ extern "C" void afx_plan_destroy(afx_plan* pl) {
                     &pl->rh_tab, &pl->rh_db, &pl->rh_max, &pl->rh_env, &pl->rh_parts, &pl->rh_tg, &pl->rh_acmean, &pl->rh_res,
                     &pl->bt_x, &pl->bt_ls, &pl->bt_cum, &pl->bt_bl, &pl->bt_beats, &pl->bt_rec, &pl->bt_bpm,
                     &pl->gp_clips64, &pl->gp_in, &pl->gp_filt, &pl->gp_desc, &pl->gp_hdesc, &pl->gp_doff, &pl->gp_sstats, &pl->gp_cstats,
-                    &pl->gp_mparts, &pl->gp_mstats, &pl->gp_dct, &pl->gp_rec, &pl->gp_ints})
+                    &pl->gp_mparts, &pl->gp_mstats, &pl->gp_dct, &pl->gp_rec, &pl->gp_ints,
+                    &pl->dn_prof, &pl->dn_info, &pl->dn_e})
     release(*b);
   if (pl->h_pin) (void)hipHostFree(pl->h_pin);
   if (pl->h_clips_pin) (void)hipHostFree(pl->h_clips_pin);

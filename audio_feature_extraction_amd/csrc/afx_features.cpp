@@ -12,6 +12,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include "afx_denoise.h"
 #include "afx_device.h"
 #include "afx_devenv.h"
 #include "afx_f0.h"
@@ -428,6 +429,79 @@ extern "C" int afx_hpss_batch(afx_plan* pl, const void* samples, int sample_fmt,
         for (int k = 0; k < 4; ++k) out_stats[4 * i + k] = h_stats[4 * (size_t)q + k];
         if (recs[q].len < 2) out_stats[4 * i + 2] = out_stats[4 * i + 3] = nan;   // k_frames3s skips clips of one sample
       }
+    }
+  }
+  return AFX_OK;
+}
+
+// ---- STFT-domain noise reduction and the aligner's preprocess (noise_reduction.py:15-92, process_audio.py:9-54) ----------
+// Per chunk: the gain, the profile rows, the fused frame kernel into hp_yh, HPSS's overlap-add into hp_h, the VAD's energies
+// and threshold, the finishing gather in place.  hp_y, hp_yh and hp_h are this call's for its duration.
+extern "C" int afx_denoise_batch(afx_plan* pl, const void* samples, int sample_fmt, int mem_kind,
+                                 const int64_t* offsets, const int64_t* lengths, int n_clips,
+                                 int flags, int mode, double beta, int noise_frames,
+                                 float* out, double* out_info, int32_t* out_status) {
+  const char* who = "afx_denoise_batch";
+  if (n_clips > 0 && (!out || !out_status)) return null_arg(who);
+  int rc = check_batch_args(who, pl, samples, sample_fmt, mem_kind, offsets, lengths, n_clips, true);
+  if (rc != AFX_OK) return rc;
+  if ((rc = check_stft_plan(who, pl, flags, AFX_FLAG_PREEMPH | AFX_DENOISE_RMS_GAIN | AFX_DENOISE_VAD, false)) != AFX_OK) return rc;
+  if (mode != AFX_DENOISE_SPECSUB && mode != AFX_DENOISE_WIENER) { set_error(std::string(who) + ": unknown mode"); return AFX_ERR_INVALID; }
+  if (!std::isfinite(beta) || beta < 0.0) { set_error(std::string(who) + ": beta must be finite and >= 0"); return AFX_ERR_INVALID; }
+  if (noise_frames < 1 || noise_frames > kDnMaxNoiseFrames) { set_error(std::string(who) + ": noise_frames must be in [1, 64]"); return AFX_ERR_INVALID; }
+  const bool rms = (flags & AFX_DENOISE_RMS_GAIN) != 0, want_vad = (flags & AFX_DENOISE_VAD) != 0;
+  DnVad vad{0, 0};
+  if (want_vad) {
+    vad.fl = (int)(0.025 * (double)pl->p.sr); vad.hop = (int)(0.010 * (double)pl->p.sr);
+    if (vad.hop < 1) { set_error(std::string(who) + ": the VAD needs a sample rate of at least 100 Hz"); return AFX_ERR_INVALID; }
+  }
+  if ((rc = check_clip_ranges(who, offsets, lengths, nullptr, n_clips, INT64_MAX / 4)) != AFX_OK) return rc;
+  const double nan = std::nan("");
+  for (int i = 0; i < n_clips; ++i) {
+    out_status[i] = lengths[i] == 0 ? AFX_CLIP_TOO_SHORT : AFX_CLIP_OK;
+    if (out_info) for (int k = 0; k < kDnInfo; ++k) out_info[kDnInfo * i + k] = nan;
+  }
+  if (n_clips == 0) return AFX_OK;
+  if ((rc = begin_plan_call(who, pl)) != AFX_OK) return rc;
+  hipStream_t s = pl->ctx->stream;
+  StftCost cost;
+  denoise_cost(flags, sample_fmt, mem_kind, cost);
+  const HpssTabs tb{pl->f3.window, pl->f3.w1024, pl->f3.w2048};
+  StftChunk ck;
+  std::vector<uint32_t> h_bad;
+  std::vector<double> h_info;
+  for (int c0 = 0; c0 < n_clips; c0 = ck.next) {
+    cut_stft_chunk(offsets, lengths, n_clips, c0, dev_env().hpss_budget, cost, ck);
+    const int n = (int)ck.recs.size();
+    if (n == 0) continue;
+    if ((rc = ensure(pl->hp_h, (size_t)ck.samples * sizeof(float) + 64)) != AFX_OK) return rc;
+    if ((rc = ensure(pl->hp_yh, (size_t)ck.frames * kHpssPitch * sizeof(float2))) != AFX_OK) return rc;
+    if ((rc = ensure(pl->dn_prof, (size_t)n * kDnProfPitch * sizeof(float))) != AFX_OK) return rc;
+    if ((rc = ensure(pl->dn_info, (size_t)n * kDnInfo * sizeof(double))) != AFX_OK) return rc;
+    if (want_vad && (rc = ensure(pl->dn_e, (size_t)(ck.samples + n) * sizeof(float) + 64)) != AFX_OK) return rc;
+    if ((rc = stage_stft_chunk(pl, samples, sample_fmt, mem_kind, flags, ck)) != AFX_OK) return rc;
+    const HpssClip* d_clips = (const HpssClip*)pl->hp_clips.p;
+    const uint32_t* d_bad = (const uint32_t*)pl->hp_bad.p;
+    const float* d_y = (const float*)pl->hp_y.p;
+    float* d_d = (float*)pl->hp_h.p;
+    float* d_e = want_vad ? (float*)pl->dn_e.p : nullptr;
+    double* d_info = (double*)pl->dn_info.p;
+    HIP_TRY(launch_dn_gain(s, d_y, d_clips, n, rms, d_info));
+    HIP_TRY(launch_dn_profile(s, d_y, d_clips, d_bad, n, noise_frames, mode == AFX_DENOISE_WIENER, d_info, tb, (float*)pl->dn_prof.p));
+    HIP_TRY(launch_dn_frames(s, d_y, d_clips, d_bad, n, ck.frames, mode == AFX_DENOISE_WIENER, (float)beta, d_info,
+                             (const float*)pl->dn_prof.p, tb, (float2*)pl->hp_yh.p));
+    HIP_TRY(launch_hpss_ola(s, (const float2*)pl->hp_yh.p, nullptr, d_clips, n, ck.max_len, tb, d_d, nullptr));
+    if (want_vad) HIP_TRY(launch_dn_vad(s, d_d, d_clips, d_bad, n, ck.max_len, vad, d_e, d_info));
+    HIP_TRY(launch_dn_finish(s, d_d, d_clips, d_bad, n, ck.max_len, vad, d_e, d_info));
+    h_info.resize((size_t)n * kDnInfo);
+    HIP_TRY(hipMemcpyAsync(h_info.data(), d_info, (size_t)n * kDnInfo * sizeof(double), hipMemcpyDeviceToHost, s));
+    if ((rc = copy_rows_out(s, ck, out, offsets, d_d, 1, false)) != AFX_OK) return rc;
+    if ((rc = end_stft_chunk(pl, n, h_bad)) != AFX_OK) return rc;
+    for (int q = 0; q < n; ++q) {
+      const int i = ck.idx[q];
+      out_status[i] = h_bad[q] ? AFX_CLIP_NONFINITE : (want_vad && ck.recs[q].len < 512) ? AFX_CLIP_TOO_SHORT : AFX_CLIP_OK;
+      if (out_info && out_status[i] == AFX_CLIP_OK)
+        for (int k = 0; k < kDnInfo; ++k) out_info[kDnInfo * i + k] = h_info[kDnInfo * (size_t)q + k];
     }
   }
   return AFX_OK;

@@ -13,6 +13,7 @@
 #include "afx_device.h"
 #include "afx_f0.h"
 #include "afx_groups.h"
+#include "afx_denoise.h"
 #include "afx_hpss.h"
 #include "afx_internal.h"
 #include "afx_mr.h"
@@ -96,6 +97,18 @@ void groups_cost(int groups, bool preprocess, StftCost& cost) {
                   + (preprocess ? 2 * ((int64_t)kFiltTile * 8 + (int64_t)kFiltB * kFiltZ * 8 + 8) + sizeof(FiltClip) + sizeof(FiltState) : 0);
   cost.tile = 16;
   cost.tile_cap = ha ? 65535 : INT32_MAX / 2;             // k_hpss_mask's grid holds 65535 tiles of 64 frames: never more than these
+}
+
+// What a clip costs a chunk of afx_denoise_batch: the rows k_dn_frames writes and k_hpss_ola reads; y, the output and the
+// upload; with the VAD the energies, which a clip of L samples has at most L + 1 of; the profile row, the record, the info.
+void denoise_cost(int flags, int sample_fmt, int mem_kind, StftCost& cost) {
+  const bool vad = (flags & AFX_DENOISE_VAD) != 0;
+  cost = StftCost{};
+  cost.per_frame = kHpssPitch * 8;
+  cost.per_sample = 4 + 4 + (mem_kind != AFX_MEM_HOST ? 0 : sample_fmt == AFX_FMT_S16 ? 2 : 4) + (vad ? 4 : 0);
+  cost.per_clip = 128 + kDnProfPitch * 4 + kDnInfo * 8 + (vad ? 4 : 0);
+  cost.tile = kHpssTile;                                  // no kernel here works in tiles; the count only has to fit an int
+  cost.tile_cap = INT32_MAX / 2;
 }
 
 void groups_dct_table(int n_mels, float* out) {
@@ -235,6 +248,21 @@ extern "C" int afx_groups_cost(int groups, int flags, int64_t* cost) {
   if (groups <= 0 || (groups & ~kGroupsAll)) { set_error("afx_groups_cost: groups must be a non-empty set of AFX_GROUP_* bits"); return AFX_ERR_INVALID; }
   StftCost c;
   groups_cost(groups, (flags & AFX_GROUPS_PREPROCESS) != 0, c);
+  const int64_t v[6] = {c.per_frame, c.per_tile, c.per_sample, c.per_clip, c.tile, c.tile_cap};
+  std::memcpy(cost, v, sizeof(v));
+  return AFX_OK;
+}
+
+extern "C" int afx_denoise_cost(int flags, int sample_fmt, int mem_kind, int64_t* cost) {
+  if (!cost) { set_error("afx_denoise_cost: null argument"); return AFX_ERR_INVALID; }
+  if (flags & AFX_FLAG_TRIM) { set_error("afx_denoise_cost: trim is not applied here; pass the preprocessed signal"); return AFX_ERR_UNSUPPORTED; }
+  if (flags & ~(AFX_FLAG_PREEMPH | AFX_DENOISE_RMS_GAIN | AFX_DENOISE_VAD)) { set_error("afx_denoise_cost: unknown flag"); return AFX_ERR_INVALID; }
+  if ((sample_fmt != AFX_FMT_F32 && sample_fmt != AFX_FMT_S16) || (mem_kind != AFX_MEM_HOST && mem_kind != AFX_MEM_DEVICE)) {
+    set_error("afx_denoise_cost: unknown sample format or memory kind");
+    return AFX_ERR_INVALID;
+  }
+  StftCost c;
+  denoise_cost(flags, sample_fmt, mem_kind, c);
   const int64_t v[6] = {c.per_frame, c.per_tile, c.per_sample, c.per_clip, c.tile, c.tile_cap};
   std::memcpy(cost, v, sizeof(v));
   return AFX_OK;

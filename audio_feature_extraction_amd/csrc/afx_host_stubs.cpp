@@ -70,6 +70,10 @@ int afx_beat_batch(afx_plan*, const void*, int, int, const int64_t*, const int64
                    const int64_t*, int32_t*, double*, int32_t*, float*, double*, double*, int32_t*, int32_t*) {
   return no_device("afx_beat_batch");
 }
+int afx_denoise_batch(afx_plan*, const void*, int, int, const int64_t*, const int64_t*, int, int, int, double, int, float*,
+                      double*, int32_t*) {
+  return no_device("afx_denoise_batch");
+}
 int afx_groups_debug_rows(afx_plan*, float*, int64_t, int64_t*) { return no_device("afx_groups_debug_rows"); }
 int afx_resample_batch(afx_ctx*, const void*, int, int, const int64_t*, const int64_t*, int, int, int, const double*, int, float*,
                        int, const int64_t*, int64_t*) {

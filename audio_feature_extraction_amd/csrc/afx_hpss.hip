@@ -17,8 +17,8 @@
 #include <cstdint>
 
 #include "afx.h"
-#include "afx_frames3_dev.h"
 #include "afx_hpss.h"
+#include "afx_hpss_dev.h"
 
 namespace afx {
 
@@ -83,38 +83,6 @@ __device__ __forceinline__ void hp_median16(const float* src, int ss, float* out
   }
 }
 
-__device__ __forceinline__ v2 hp_cmul(v2 a, v2 b) { return v2{a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x}; }
-
-// forward 1024-point complex FFT of buf (one wave's 1024 float2 in LDS), natural order in and out: five radix-4 Stockham
-// stages, four butterflies per lane.  Every wave of the workgroup calls it (the exchanges use workgroup barriers).
-__device__ __forceinline__ void hp_fft1024(v2* buf, const v2* __restrict__ w1024, int lane) {
-#pragma unroll
-  for (int st = 0; st < 5; ++st) {
-    const int ns = 1 << (2 * st), ts = 256 >> (2 * st);
-    __syncthreads();
-    v2 v[4][4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int j = lane + 64 * q, k = j & (ns - 1);
-#pragma unroll
-      for (int r = 0; r < 4; ++r) v[q][r] = buf[j + 256 * r];
-      if (st > 0) {
-#pragma unroll
-        for (int r = 1; r < 4; ++r) v[q][r] = hp_cmul(v[q][r], w1024[r * k * ts]);
-      }
-      f3_dft4(v[q][0], v[q][1], v[q][2], v[q][3]);
-    }
-    __syncthreads();
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int j = lane + 64 * q, k = j & (ns - 1), base = (j - k) * 4 + k;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) buf[base + r * ns] = v[q][r];
-    }
-  }
-  __syncthreads();
-}
-
 }  // namespace
 
 __global__ __launch_bounds__(256) void k_hpss_prep(const void* __restrict__ in, int fmt, int flags, float b1,
@@ -165,7 +133,8 @@ __global__ __launch_bounds__(256) void k_hpss_stft(const float* __restrict__ y, 
     buf[m] = v2{tb.window[2 * m] * a, tb.window[2 * m + 1] * b};
   }
   hp_fft1024(buf, (const v2*)tb.w1024, lane);
-  // real-FFT split: X[k] = (Z[k] + conj Z[N-k]) / 2 - i W2048^k (Z[k] - conj Z[N-k]) / 2
+  // real-FFT split: hp_split's expression written out (a call changes how the compiler packs it, not what it computes;
+  // written out, the kernel's instructions are the ones it has always had)
   const v2* W = (const v2*)tb.w2048;
   v2* row = (v2*)out + gg * kHpssPitch;
   float* prow = (float*)out + gg * kHpssPowPitch;
@@ -245,8 +214,7 @@ __global__ __launch_bounds__(256) void k_hpss_irfft(v2* __restrict__ Yh, v2* __r
   v2* row = (blockIdx.y ? Yp : Yh) + (live ? g : 0) * kHpssPitch;
   v2* buf = lds[wave];
   const v2* W = (const v2*)tb.w2048;
-  // Z'[k] = (X[k] + conj X[N-k]) + i conj(W2048^k) (X[k] - conj X[N-k]); the imaginary parts of X[0] and X[1024] are
-  // ignored (numpy's irfft); the forward FFT of conj Z' is the conjugate of the inverse
+  // conj Z' of hp_merge; the imaginary parts of X[0] and X[1024] are ignored (numpy's irfft)
 #pragma unroll 4
   for (int q = 0; q < 16; ++q) {
     const int k = lane + 64 * q;
@@ -254,10 +222,7 @@ __global__ __launch_bounds__(256) void k_hpss_irfft(v2* __restrict__ Yh, v2* __r
     if (live) {
       v2 xk = row[k], xn = row[1024 - k];
       if (k == 0) { xk.y = 0.f; xn.y = 0.f; }
-      const v2 e = v2{xk.x + xn.x, xk.y - xn.y}, d = v2{xk.x - xn.x, xk.y + xn.y};
-      const v2 w = W[k];
-      const v2 o = hp_cmul(d, v2{w.x, -w.y});
-      zc = v2{e.x - o.y, -(e.y + o.x)};
+      zc = hp_merge(xk, xn, W[k]);
     }
     buf[k] = zc;
   }

@@ -93,6 +93,9 @@ struct afx_plan {
   // records with 64-frame tiles (k_hpss_mask), the preprocess's upload and output, the descriptor rows of y and the centroid
   // rows of h, the per-group statistics, the MFCC table (built at first use) and per-frame sums, the records
   DevBuf gp_clips64, gp_in, gp_filt, gp_desc, gp_hdesc, gp_doff, gp_sstats, gp_cstats, gp_mparts, gp_mstats, gp_dct, gp_rec, gp_ints;
+  // afx_denoise_batch (with hp_clips, hp_y, hp_bad, the rows in hp_yh and the signal in hp_h): the profile rows, the per-clip
+  // info, the VAD energies
+  DevBuf dn_prof, dn_info, dn_e;
   std::vector<float> gp_rows;   // AFX_GROUPS_STORE_DESC: the 17-float rows of the last call, clip after clip (afx_groups_debug_rows)
   // cached per-batch descriptors
   std::vector<int64_t> c_off, c_len;

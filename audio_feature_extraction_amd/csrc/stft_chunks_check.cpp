@@ -62,6 +62,15 @@ int main() {
   cut({1}, hpss, big + 1, AFX_ERR_INVALID);
   const int64_t no_tile[6] = {1, 1, 1, 1, 0, 1};
   cut({1}, no_tile, 1, AFX_ERR_INVALID);
+  // afx_denoise_batch's record through its own entry point: six clips at 400000 bytes are (5000) (12345, 700) (9000, 3000) (7000)
+  int64_t dn[6] = {0, 0, 0, 0, 0, 0};
+  CHECK(afx_denoise_cost(0, AFX_FMT_F32, AFX_MEM_HOST, dn) == AFX_OK && dn[0] == 1032 * 8 && dn[2] == 12 && dn[3] == 128 + 1040 * 4 + 32);
+  c = cut({5000, 12345, 700, 9000, 3000, 7000}, dn, 400000);
+  CHECK(c[0] == 0 && c[1] == 1 && c[2] == 1 && c[3] == 2 && c[4] == 2 && c[5] == 3);
+  CHECK(afx_denoise_cost(AFX_DENOISE_VAD, AFX_FMT_S16, AFX_MEM_DEVICE, dn) == AFX_OK && dn[2] == 12 && dn[3] == 128 + 1040 * 4 + 36);
+  CHECK(afx_denoise_cost(AFX_FLAG_TRIM, AFX_FMT_F32, AFX_MEM_HOST, dn) == AFX_ERR_UNSUPPORTED);
+  CHECK(afx_denoise_cost(4, AFX_FMT_F32, AFX_MEM_HOST, dn) == AFX_ERR_INVALID);
+  CHECK(afx_denoise_cost(0, 9, AFX_MEM_HOST, dn) == AFX_ERR_INVALID && afx_denoise_cost(0, AFX_FMT_F32, AFX_MEM_HOST, nullptr) == AFX_ERR_INVALID);
   if (g_fail) { std::fprintf(stderr, "stft_chunks_check: %d check(s) failed\n", g_fail); return 1; }
   std::printf("stft_chunks_check: ok\n");
   return 0;

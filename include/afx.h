@@ -488,6 +488,43 @@ int afx_groups_cost(int groups, int flags, int64_t* cost /*[6]*/);
 int afx_groups_dct_table(int n_mels, float* out /*[13][128]*/);
 int afx_groups_debug_rows(afx_plan* plan, float* out, int64_t n_floats, int64_t* count);
 
+/* STFT-domain noise reduction: spectral_subtraction and wiener_filter of
+ * 00_audio_data_collection_experiment/noise_reduction.py:15-92 and the aligner's preprocess of
+ * 05_dtw_alignment_experiment/process_audio.py:9-54, as tests/denoise_ref.py restates them.  Both symbols are newer than
+ * AFX_VERSION 107 says: a binding detects them by their presence.  The plan must be n_fft 2048 / hop 512 with
+ * AFX_WINDOW_HANN (AFX_ERR_UNSUPPORTED otherwise, as for AFX_FLAG_TRIM).
+ *
+ * X is the centred (zero-padded) STFT of the clip, T = 1 + length / 512 frames, n = min(T, noise_frames):
+ *   AFX_DENOISE_SPECSUB  N[b] = mean over t < n of |X[b, t]|;    Y = X max(|X| - beta N, 0) / |X|, 0 where |X| = 0
+ *   AFX_DENOISE_WIENER   Np[b] = mean over t < n of |X[b, t]|^2; Y = X P / (P + Np + 2^-52), P = |X|^2 (beta is not read)
+ * then librosa.istft(Y, hop_length=512): window x irfft, overlap-add in increasing frame order, division by the window
+ * sum-square where it exceeds the float32 tiny.  That gives L' = 512 (length / 512) samples; out[L' .. length) is zero (the
+ * reference pads), and a clip shorter than 512 samples is all zero with status AFX_CLIP_OK.
+ *   flags  AFX_FLAG_PREEMPH (the plan's pre-emphasis first, as for afx_hpss_batch) and / or
+ *          AFX_DENOISE_RMS_GAIN  the STFT sees fl32(y g), g = fl32(0.1 / (sqrt(mean y^2) + 1e-6)), sum y^2 in float64
+ *          AFX_DENOISE_VAD       on the L' denoised samples d: e = librosa.feature.rms(d, frame_length int(0.025 sr),
+ *                                hop_length int(0.010 sr), center=True, zero padding), thr = 0.5 mean(e); out[j] = d[j] iff a
+ *                                frame i with e[i] > thr has i hop <= j < i hop + fl and i hop + fl <= L' (the copy windows
+ *                                are not centred although the RMS frames are), else 0; sr is the plan's
+ *          The aligner's preprocess is AFX_DENOISE_SPECSUB with both flags, beta 1, noise_frames 10; its result is out[0, L').
+ *   out       host float: clip i at out[offsets[i] .. + lengths[i]]
+ *   out_info  NULL or host double[n_clips][4]: the gain (1.0 without AFX_DENOISE_RMS_GAIN), the VAD threshold, the speech
+ *             frames and the VAD frames (NaN, 0, 0 without AFX_DENOISE_VAD); all NaN for a failed clip
+ *   out_status  AFX_CLIP_TOO_SHORT for length 0 and, with AFX_DENOISE_VAD, for fewer than 512 samples; AFX_CLIP_NONFINITE
+ *             for a NaN / inf sample; a failed clip's output is zero and it never affects another clip
+ * AFX_ERR_INVALID for an unknown mode or flag, beta negative or not finite, noise_frames outside [1, 64] and
+ * AFX_DENOISE_VAD with int(0.010 sr) < 1.  Results are bit-reproducible and depend neither on the rest of the batch, nor on
+ * how it was cut into chunks (2 GiB of workspace each), nor on the layout of the input.
+ *
+ * afx_denoise_cost (host-only): the cost record afx_denoise_batch cuts with, for afx_stft_chunks. */
+enum { AFX_DENOISE_SPECSUB = 0, AFX_DENOISE_WIENER = 1 };
+enum { AFX_DENOISE_RMS_GAIN = 128, AFX_DENOISE_VAD = 256 };   /* in flags, beside AFX_FLAG_PREEMPH */
+int afx_denoise_batch(afx_plan* plan, const void* samples, int sample_fmt, int mem_kind,
+                      const int64_t* offsets, const int64_t* lengths, int n_clips,
+                      int flags, int mode, double beta, int noise_frames,
+                      float* out, double* out_info /*[n_clips][4]*/, int32_t* out_status);
+int afx_denoise_cost(int flags, int sample_fmt, int mem_kind, int64_t* cost /*[6]*/);
+
 /* Host-only (no device needed): the tables afx_f0_batch uploads, for inspection and tests.
  * info[8] = min_period, max_period, n_pitch_bins, band (transition half-width), candidate
  * capacity, lags kept, lags per lane, trough slots per lane.  beta[100] = Beta(2,18) mass of
