@@ -2,6 +2,7 @@
 ``audio_feature_extraction_toolkit`` (reference __init__.py:1-6): same two exports."""
 from .core.feature_extractor import AudioFeatureExtractor
 from .evaluation.evaluator import FeatureEvaluator
+from . import quality  # noqa: F401  (the recording screen and the denoising scores; a module, not one of the two exports)
 
 __version__ = '0.1.0'
 

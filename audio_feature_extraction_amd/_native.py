@@ -43,6 +43,11 @@ DENOISE_SPECSUB, DENOISE_WIENER = 0, 1                                       # a
 DENOISE_RMS_GAIN, DENOISE_VAD = 128, 256                                     # its flags, beside FLAG_PREEMPH
 DENOISE_MAX_NOISE_FRAMES = 64
 BEAT_MAX_FPB = 768                                                           # frames per beat it holds
+ASSESS_N, COMPARE_N = 10, 10                                                 # doubles per record of afx_assess_batch / afx_compare_batch
+ASSESS_FIELDS = ("n_short", "silent", "longest_run", "max_rms_short", "mean_square", "peak", "noise_mean_square",
+                 "n_long", "rms_long_mean", "rms_long_std")
+COMPARE_FIELDS = ("n", "sum_r", "sum_d", "sum_rr", "sum_dd", "sum_rd", "sum_ee", "m2_r", "m2_d", "m2_rd")
+COST_ASSESS, COST_COMPARE = 0, 1                                             # afx_assess_cost: whose record
 GROUPS_STATS = 24                                                            # doubles per clip of its record
 K_NAMES = ("trim_blocks", "trim_decide", "frames", "dct", "stats")
 K_FRAMES = 2
@@ -62,6 +67,7 @@ SYMBOLS = (
     "afx_beat_track_host", "afx_beat_batch",
     "afx_dtw_steps_batch",
     "afx_denoise_batch", "afx_denoise_cost",
+    "afx_assess_batch", "afx_compare_batch", "afx_assess_host", "afx_compare_host", "afx_assess_cost",
 )
 
 
@@ -166,6 +172,12 @@ def lib() -> C.CDLL:
         if hasattr(L, "afx_denoise_batch"):                  # newer than version 107 says: found by their presence
             L.afx_denoise_batch.argtypes = [vp, vp, i32, i32, vp, vp, i32, i32, i32, C.c_double, i32, vp, vp, vp]
             L.afx_denoise_cost.argtypes = [i32, i32, i32, vp]
+        if hasattr(L, "afx_assess_batch"):                   # newer than version 107 says: found by their presence
+            L.afx_assess_cost.argtypes = [i32, i32, i32, vp]
+            L.afx_assess_host.argtypes = [vp, i32, C.c_int64, i32, i32, C.c_double, C.c_int64, vp, vp]
+            L.afx_compare_host.argtypes = [vp, vp, i32, C.c_int64, C.c_int64, vp, vp]
+            L.afx_assess_batch.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, i32, C.c_double, C.c_int64, vp, vp]
+            L.afx_compare_batch.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp, vp, i32, vp, vp]
         if hasattr(L, "afx_rfft_host"):                      # absent from a library built before the mixed-radix lengths
             L.afx_rfft_host.argtypes = [i32, vp, vp]
         _lib = L
@@ -381,6 +393,54 @@ def denoise_check(params: "Params", flags: int, mode: int, beta: float, noise_fr
         raise ValueError("afx_denoise_batch: noise_frames must be in [1, 64]")
     if flags & DENOISE_VAD and int(0.010 * params.sr) < 1:
         raise ValueError("afx_denoise_batch: the VAD needs a sample rate of at least 100 Hz")
+
+
+def _need_assess():
+    if not hasattr(lib(), "afx_assess_batch"):
+        raise NotImplementedError("this libafx has no afx_assess_batch")
+
+
+def assess_cost(what: int = COST_ASSESS, fmt: int = FMT_F32, mem: int = MEM_HOST) -> np.ndarray:
+    """Host-only: the cost record afx_assess_batch (COST_ASSESS) or afx_compare_batch (COST_COMPARE) cuts a batch with
+    (bytes per frame, per tile, per sample, per clip; frames per tile, most tiles of a chunk), for ``stft_chunks``."""
+    _need_assess()
+    cost = np.zeros(6, np.int64)
+    _check(lib().afx_assess_cost(int(what), int(fmt), int(mem), cost.ctypes.data), "afx_assess_cost")
+    return cost
+
+
+def _mono_clip(x, what: str) -> np.ndarray:
+    x = np.ascontiguousarray(x)
+    if x.ndim != 1 or x.dtype not in (np.int16, np.float32):
+        raise ValueError(f"{what} must be a one-dimensional int16 or float32 array")
+    return x
+
+
+def assess_host(x, frame_short: int, frame_long: int, threshold_db: float = -40.0, noise_cap: int = 2000) -> dict:
+    """Host-only: afx_assess_host, one int16 / float32 clip through the definitions of afx_assess_batch on the CPU.
+    Returns rec (float64 [ASSESS_N], NaN when the clip failed; ASSESS_FIELDS names the entries) and status."""
+    _need_assess()
+    x = _mono_clip(x, "x")
+    rec = np.zeros(ASSESS_N, np.float64)
+    status = np.zeros(1, np.int32)
+    _check(lib().afx_assess_host(x.ctypes.data, FMT_S16 if x.dtype == np.int16 else FMT_F32, int(x.size), int(frame_short),
+                                 int(frame_long), float(threshold_db), int(noise_cap), rec.ctypes.data, status.ctypes.data),
+           "afx_assess_host")
+    return {"rec": rec, "status": int(status[0])}
+
+
+def compare_host(ref, deg) -> dict:
+    """Host-only: afx_compare_host, one pair of int16 / float32 clips (both of one type) through the definitions of
+    afx_compare_batch on the CPU.  Returns rec (float64 [COMPARE_N]; COMPARE_FIELDS names the entries) and status."""
+    _need_assess()
+    ref, deg = _mono_clip(ref, "ref"), _mono_clip(deg, "deg")
+    if ref.dtype != deg.dtype:
+        raise ValueError("ref and deg must have one sample type")
+    rec = np.zeros(COMPARE_N, np.float64)
+    status = np.zeros(1, np.int32)
+    _check(lib().afx_compare_host(ref.ctypes.data, deg.ctypes.data, FMT_S16 if ref.dtype == np.int16 else FMT_F32,
+                                  int(ref.size), int(deg.size), rec.ctypes.data, status.ctypes.data), "afx_compare_host")
+    return {"rec": rec, "status": int(status[0])}
 
 
 def groups_dct_table(n_mels: int = 128) -> np.ndarray:
@@ -846,6 +906,49 @@ class Context(_Owner):
                                       kinds.ctypes.data, channels.ctypes.data, n, optr, okind, out_offsets.ctypes.data),
                "afx_decode_batch")
         return {"out": out, "offsets": out_offsets, "lengths": frames}
+
+    def assess_batch(self, samples, offsets, lengths, frame_short, frame_long, threshold_db: float = -40.0,
+                     noise_cap: int = 2000, fmt=None) -> dict:
+        """afx_assess_batch: the recording screen's reductions of clips samples[offsets[i] .. + lengths[i]), each with its own
+        two frame lengths (int(0.01 sr), int(0.1 sr) at the clip's rate).  ``samples``: an int16 / float32 numpy array
+        (host) or a DeviceBuffer / device pointer (``fmt`` required).  Returns rec (float64 [n, ASSESS_N], NaN rows for
+        failed clips; ASSESS_FIELDS names the columns) and status."""
+        _need_assess()
+        offsets, lengths, n = _clip_arrays(offsets, lengths)
+        fs = np.ascontiguousarray(frame_short, np.int32).reshape(-1)
+        fl = np.ascontiguousarray(frame_long, np.int32).reshape(-1)
+        if fs.shape[0] != n or fl.shape[0] != n:
+            raise ValueError("frame_short and frame_long must have one entry per clip")
+        fmt = _sample_fmt(samples, fmt)
+        sptr, kind = _sample_source(samples, fmt, offsets, np.maximum(lengths, 0))
+        rec = np.full((n, ASSESS_N), np.nan, np.float64)
+        status = np.zeros(n, np.int32)
+        _check(lib().afx_assess_batch(self.handle, sptr, int(fmt), kind, offsets.ctypes.data, lengths.ctypes.data,
+                                      fs.ctypes.data, fl.ctypes.data, n, float(threshold_db), int(noise_cap),
+                                      rec.ctypes.data, status.ctypes.data), "afx_assess_batch")
+        return {"rec": rec, "status": status}
+
+    def compare_batch(self, ref, ref_offsets, ref_lengths, deg, deg_offsets, deg_lengths, fmt=None) -> dict:
+        """afx_compare_batch: the sums behind correlation, MSE and the SNR of the difference for pairs
+        ref[ref_offsets[i] .. + ref_lengths[i]) / deg[deg_offsets[i] .. + deg_lengths[i]), over the shorter length of each
+        pair.  ``ref`` and ``deg``: numpy arrays of one sample type, or DeviceBuffers / device pointers (``fmt`` required;
+        they may be one buffer).  Returns rec (float64 [n, COMPARE_N]; COMPARE_FIELDS names the columns) and status."""
+        _need_assess()
+        ref_offsets, ref_lengths, n = _clip_arrays(ref_offsets, ref_lengths)
+        deg_offsets, deg_lengths, nd = _clip_arrays(deg_offsets, deg_lengths)
+        if nd != n:
+            raise ValueError("both sides must have one entry per pair")
+        if isinstance(ref, np.ndarray) != isinstance(deg, np.ndarray):
+            raise ValueError("ref and deg must both be host arrays or both be device memory")
+        fmt = _sample_fmt(ref, fmt)
+        rptr, kind = _sample_source(ref, fmt, ref_offsets, np.maximum(ref_lengths, 0))
+        dptr, _ = _sample_source(deg, fmt, deg_offsets, np.maximum(deg_lengths, 0))
+        rec = np.full((n, COMPARE_N), np.nan, np.float64)
+        status = np.zeros(n, np.int32)
+        _check(lib().afx_compare_batch(self.handle, rptr, dptr, int(fmt), kind, ref_offsets.ctypes.data, ref_lengths.ctypes.data,
+                                       deg_offsets.ctypes.data, deg_lengths.ctypes.data, n, rec.ctypes.data, status.ctypes.data),
+               "afx_compare_batch")
+        return {"rec": rec, "status": status}
 
 
 class Plan(_Owner):

@@ -540,3 +540,173 @@ extern "C" int afx_sosfiltfilt_batch(afx_ctx* ctx, const void* samples, int samp
   }
   return AFX_OK;
 }
+
+// ---- the recording screen and the compare sums (audio_format_assessment.py:143-300, audio_quality_assessment.py:150-280) ----
+// A chunk of either entry point: its clips' samples staged packed (8-element alignment: 16-byte loads) when they are the
+// host's, the records uploaded, two launches, the results and flags downloaded.
+extern "C" int afx_assess_batch(afx_ctx* ctx, const void* samples, int sample_fmt, int mem_kind,
+                                const int64_t* offsets, const int64_t* lengths, const int32_t* frame_short, const int32_t* frame_long,
+                                int n_clips, double threshold_db, int64_t noise_cap, double* out_rec, int32_t* out_status) {
+  const char* who = "afx_assess_batch";
+  if (!ctx || n_clips < 0 || (n_clips > 0 && (!offsets || !lengths || !frame_short || !frame_long || !out_rec || !out_status))) return null_arg(who);
+  int rc;
+  if ((rc = check_sample_format(who, sample_fmt, mem_kind)) != AFX_OK) return rc;
+  if ((rc = check_clip_ranges(who, offsets, lengths, nullptr, n_clips, INT64_MAX / 8)) != AFX_OK) return rc;
+  if (const char* why = assess_refusal(0, 1, 1, threshold_db, noise_cap)) { set_error(std::string(who) + ": " + why); return AFX_ERR_INVALID; }
+  bool any = false;
+  for (int i = 0; i < n_clips; ++i) {
+    if (const char* why = assess_refusal(lengths[i], frame_short[i], frame_long[i], threshold_db, noise_cap)) {
+      set_error(std::string(who) + ": clip " + std::to_string(i) + ": " + why);
+      return AFX_ERR_INVALID;
+    }
+    any = any || lengths[i] > 0;
+  }
+  const double nan = std::nan("");
+  for (int i = 0; i < n_clips; ++i) {
+    out_status[i] = lengths[i] == 0 ? AFX_CLIP_TOO_SHORT : AFX_CLIP_OK;
+    std::fill(out_rec + (size_t)AFX_ASSESS_N * i, out_rec + (size_t)AFX_ASSESS_N * (i + 1), nan);
+  }
+  if (!any) return AFX_OK;
+  if (!samples) { set_error(std::string(who) + ": null samples"); return AFX_ERR_INVALID; }
+  (void)hipGetLastError();
+  HIP_TRY(hipSetDevice(ctx->device));
+  hipStream_t s = ctx->stream;
+  const double thr_ratio = threshold_db > -80.0 ? std::pow(10.0, threshold_db / 10.0) : -1.0;
+  const size_t esz = sample_fmt == AFX_FMT_S16 ? 2 : 4;
+  const bool h_in = mem_kind == AFX_MEM_HOST;
+  StftCost cost;
+  assess_cost(AFX_COST_ASSESS, sample_fmt, mem_kind, cost);
+  StftChunk ck;
+  std::vector<AsClip> recs;
+  std::vector<char> stage;
+  std::vector<double> h_rec;
+  std::vector<int32_t> h_bad;
+  for (int c0 = 0; c0 < n_clips; c0 = ck.next) {
+    cut_stft_chunk(offsets, lengths, n_clips, c0, dev_env().assess_budget, cost, ck);
+    const int n = (int)ck.idx.size();
+    if (n == 0) continue;
+    recs.assign((size_t)n, AsClip{});
+    int64_t slots = 0, spans = 0, in_pos = 0;
+    for (int q = 0; q < n; ++q) {
+      const int i = ck.idx[q];
+      AsClip& r = recs[q];
+      r.len = lengths[i];
+      r.in_off = h_in ? in_pos : offsets[i];
+      r.nw = std::min<int64_t>((int64_t)(0.1 * (double)r.len), noise_cap);
+      r.fs = frame_short[i]; r.fl = frame_long[i];
+      r.ps_off = slots; slots += as_slots(r.len, r.fs);
+      r.pl_off = slots; slots += as_slots(r.len, r.fl);
+      r.span_base = spans; spans += as_spans(r.len);
+      in_pos += (r.len + 7) / 8 * 8;
+    }
+    if (spans > INT32_MAX / 2) { set_error(std::string(who) + ": chunk too large for one launch"); return AFX_ERR_UNSUPPORTED; }
+    if ((rc = ensure(ctx->as_clips, (size_t)n * sizeof(AsClip))) != AFX_OK) return rc;
+    if ((rc = ensure(ctx->as_pieces, (size_t)slots * sizeof(double))) != AFX_OK) return rc;
+    if ((rc = ensure(ctx->as_spans, (size_t)spans * sizeof(AsSpan))) != AFX_OK) return rc;
+    if ((rc = ensure(ctx->as_rec, (size_t)n * AFX_ASSESS_N * sizeof(double))) != AFX_OK) return rc;
+    if ((rc = ensure(ctx->as_bad, (size_t)n * sizeof(int32_t))) != AFX_OK) return rc;
+    const void* d_in = samples;
+    if (h_in) {
+      stage.assign((size_t)in_pos * esz, 0);
+      for (int q = 0; q < n; ++q)
+        std::memcpy(stage.data() + (size_t)recs[q].in_off * esz, (const char*)samples + (size_t)offsets[ck.idx[q]] * esz, (size_t)recs[q].len * esz);
+      if ((rc = ensure(ctx->as_in, stage.size())) != AFX_OK) return rc;
+      HIP_TRY(hipMemcpyAsync(ctx->as_in.p, stage.data(), stage.size(), hipMemcpyHostToDevice, s));
+      d_in = ctx->as_in.p;
+    }
+    HIP_TRY(hipMemcpyAsync(ctx->as_clips.p, recs.data(), (size_t)n * sizeof(AsClip), hipMemcpyHostToDevice, s));
+    HIP_TRY(launch_assess(s, d_in, sample_fmt, (const AsClip*)ctx->as_clips.p, n, (int)spans, thr_ratio, (double*)ctx->as_pieces.p,
+                          (AsSpan*)ctx->as_spans.p, (double*)ctx->as_rec.p, (int32_t*)ctx->as_bad.p));
+    h_rec.resize((size_t)n * AFX_ASSESS_N); h_bad.resize((size_t)n);
+    HIP_TRY(hipMemcpyAsync(h_rec.data(), ctx->as_rec.p, h_rec.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(h_bad.data(), ctx->as_bad.p, h_bad.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    for (int q = 0; q < n; ++q) {
+      const int i = ck.idx[q];
+      if (h_bad[q]) { out_status[i] = AFX_CLIP_NONFINITE; continue; }
+      std::memcpy(out_rec + (size_t)AFX_ASSESS_N * i, h_rec.data() + (size_t)AFX_ASSESS_N * q, AFX_ASSESS_N * sizeof(double));
+    }
+  }
+  return AFX_OK;
+}
+
+extern "C" int afx_compare_batch(afx_ctx* ctx, const void* ref, const void* deg, int sample_fmt, int mem_kind,
+                                 const int64_t* ref_offsets, const int64_t* ref_lengths, const int64_t* deg_offsets,
+                                 const int64_t* deg_lengths, int n_pairs, double* out_rec, int32_t* out_status) {
+  const char* who = "afx_compare_batch";
+  if (!ctx || n_pairs < 0 || (n_pairs > 0 && (!ref_offsets || !ref_lengths || !deg_offsets || !deg_lengths || !out_rec || !out_status))) return null_arg(who);
+  int rc;
+  if ((rc = check_sample_format(who, sample_fmt, mem_kind)) != AFX_OK) return rc;
+  if ((rc = check_clip_ranges(who, ref_offsets, ref_lengths, nullptr, n_pairs, INT64_MAX / 8)) != AFX_OK) return rc;
+  if ((rc = check_clip_ranges(who, deg_offsets, deg_lengths, nullptr, n_pairs, INT64_MAX / 8)) != AFX_OK) return rc;
+  std::vector<int64_t> lens((size_t)n_pairs);
+  const double nan = std::nan("");
+  bool any = false;
+  for (int i = 0; i < n_pairs; ++i) {
+    lens[i] = std::min(ref_lengths[i], deg_lengths[i]);
+    out_status[i] = lens[i] == 0 ? AFX_CLIP_TOO_SHORT : AFX_CLIP_OK;
+    std::fill(out_rec + (size_t)AFX_COMPARE_N * i, out_rec + (size_t)AFX_COMPARE_N * (i + 1), nan);
+    any = any || lens[i] > 0;
+  }
+  if (!any) return AFX_OK;
+  if (!ref || !deg) { set_error(std::string(who) + ": null samples"); return AFX_ERR_INVALID; }
+  (void)hipGetLastError();
+  HIP_TRY(hipSetDevice(ctx->device));
+  hipStream_t s = ctx->stream;
+  const size_t esz = sample_fmt == AFX_FMT_S16 ? 2 : 4;
+  const bool h_in = mem_kind == AFX_MEM_HOST;
+  StftCost cost;
+  assess_cost(AFX_COST_COMPARE, sample_fmt, mem_kind, cost);
+  StftChunk ck;
+  std::vector<CmpPair> recs;
+  std::vector<char> stage;
+  std::vector<double> h_rec;
+  std::vector<int32_t> h_bad;
+  for (int c0 = 0; c0 < n_pairs; c0 = ck.next) {
+    cut_stft_chunk(ref_offsets, lens.data(), n_pairs, c0, dev_env().assess_budget, cost, ck);
+    const int n = (int)ck.idx.size();
+    if (n == 0) continue;
+    recs.assign((size_t)n, CmpPair{});
+    int64_t spans = 0, in_pos = 0;
+    for (int q = 0; q < n; ++q) {
+      const int i = ck.idx[q];
+      CmpPair& r = recs[q];
+      r.n = lens[i];
+      const int64_t slot = (r.n + 7) / 8 * 8;
+      r.r_off = h_in ? in_pos : ref_offsets[i];
+      r.d_off = h_in ? in_pos + slot : deg_offsets[i];
+      r.span_base = spans; spans += as_spans(r.n);
+      in_pos += 2 * slot;
+    }
+    if (spans > INT32_MAX / 2) { set_error(std::string(who) + ": chunk too large for one launch"); return AFX_ERR_UNSUPPORTED; }
+    if ((rc = ensure(ctx->as_clips, (size_t)n * sizeof(CmpPair))) != AFX_OK) return rc;
+    if ((rc = ensure(ctx->as_pieces, (size_t)spans * kCmpSpanDoubles * sizeof(double))) != AFX_OK) return rc;
+    if ((rc = ensure(ctx->as_rec, (size_t)n * AFX_COMPARE_N * sizeof(double))) != AFX_OK) return rc;
+    if ((rc = ensure(ctx->as_bad, (size_t)n * sizeof(int32_t))) != AFX_OK) return rc;
+    const void *d_ref = ref, *d_deg = deg;
+    if (h_in) {
+      stage.assign((size_t)in_pos * esz, 0);
+      for (int q = 0; q < n; ++q) {
+        const int i = ck.idx[q];
+        std::memcpy(stage.data() + (size_t)recs[q].r_off * esz, (const char*)ref + (size_t)ref_offsets[i] * esz, (size_t)recs[q].n * esz);
+        std::memcpy(stage.data() + (size_t)recs[q].d_off * esz, (const char*)deg + (size_t)deg_offsets[i] * esz, (size_t)recs[q].n * esz);
+      }
+      if ((rc = ensure(ctx->as_in, stage.size())) != AFX_OK) return rc;
+      HIP_TRY(hipMemcpyAsync(ctx->as_in.p, stage.data(), stage.size(), hipMemcpyHostToDevice, s));
+      d_ref = d_deg = ctx->as_in.p;
+    }
+    HIP_TRY(hipMemcpyAsync(ctx->as_clips.p, recs.data(), (size_t)n * sizeof(CmpPair), hipMemcpyHostToDevice, s));
+    HIP_TRY(launch_compare(s, d_ref, d_deg, sample_fmt, (const CmpPair*)ctx->as_clips.p, n, (int)spans, (double*)ctx->as_pieces.p,
+                           (double*)ctx->as_rec.p, (int32_t*)ctx->as_bad.p));
+    h_rec.resize((size_t)n * AFX_COMPARE_N); h_bad.resize((size_t)n);
+    HIP_TRY(hipMemcpyAsync(h_rec.data(), ctx->as_rec.p, h_rec.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(h_bad.data(), ctx->as_bad.p, h_bad.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    for (int q = 0; q < n; ++q) {
+      const int i = ck.idx[q];
+      if (h_bad[q]) { out_status[i] = AFX_CLIP_NONFINITE; continue; }
+      std::memcpy(out_rec + (size_t)AFX_COMPARE_N * i, h_rec.data() + (size_t)AFX_COMPARE_N * q, AFX_COMPARE_N * sizeof(double));
+    }
+  }
+  return AFX_OK;
+}

@@ -1,6 +1,6 @@
 // Device entry points of the HOST-ONLY build (libafx_host_asan.so, `make asan`): every one fails loudly with
 // AFX_ERR_NO_DEVICE.  The sanitizer build exists to run the host-side parsers and table builders (afx_wav.cpp,
-// afx_tables.cpp, afx_f0_tables.cpp, afx_resample_tables.cpp, afx_filt_host.cpp, afx_beat_host.cpp, afx_host.cpp) under AddressSanitizer + UBSan on the CPU; GPU sanitizers are not
+// afx_tables.cpp, afx_f0_tables.cpp, afx_resample_tables.cpp, afx_filt_host.cpp, afx_beat_host.cpp, afx_assess_host.cpp, afx_host.cpp) under AddressSanitizer + UBSan on the CPU; GPU sanitizers are not
 // available on the target pool.  Never linked into libafx.so.
 #include <cstddef>
 #include <cstdint>
@@ -86,5 +86,13 @@ int afx_decode_batch(afx_ctx*, const void*, int, const int64_t*, const int64_t*,
 int afx_sosfiltfilt_batch(afx_ctx*, const void*, int, int, const int64_t*, const int64_t*, int, const double*, int, int, int, float,
                           float*, int, const int64_t*, double*, int32_t*) {
   return no_device("afx_sosfiltfilt_batch");
+}
+int afx_assess_batch(afx_ctx*, const void*, int, int, const int64_t*, const int64_t*, const int32_t*, const int32_t*, int, double,
+                     int64_t, double*, int32_t*) {
+  return no_device("afx_assess_batch");
+}
+int afx_compare_batch(afx_ctx*, const void*, const void*, int, int, const int64_t*, const int64_t*, const int64_t*, const int64_t*,
+                      int, double*, int32_t*) {
+  return no_device("afx_compare_batch");
 }
 }

@@ -10,6 +10,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include "afx_assess.h"
 #include "afx_beat.h"
 #include "afx_chroma.h"
 #include "afx_decode.h"
@@ -49,6 +50,9 @@ struct afx_ctx {
   // afx_sosfiltfilt_batch: tables, a chunk's clip records and states, the float64 workspace, the blocks' carries, the tile
   // maxima, staging of host batches
   DevBuf ft_tab, ft_clips, ft_st, ft_w, ft_carry, ft_tmax, ft_in, ft_out;
+  // afx_assess_batch / afx_compare_batch: a chunk's records, the pieces (the spans' sums of a pair), the span records, the
+  // results and flags, staging of host batches
+  DevBuf as_clips, as_pieces, as_spans, as_rec, as_bad, as_in;
 };
 
 struct afx_plan {

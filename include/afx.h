@@ -653,6 +653,64 @@ int afx_sosfiltfilt_batch(afx_ctx* ctx, const void* samples, int sample_fmt, int
                           float* out, int out_mem_kind, const int64_t* out_offsets,
                           double* out_peak /*[n_clips][2]*/, int32_t* out_status);
 
+/* The recording screen of 00_audio_data_collection_experiment/audio_format_assessment.py:143-300 (detect_silence,
+ * check_volume_levels, check_amplitude_stability, estimate_snr) and the sums behind the scores of
+ * audio_quality_assessment.py:150-280 (SNR of the difference, Pearson correlation, MSE), as per-clip reductions.  All five
+ * symbols are newer than AFX_VERSION 107 says: a binding detects them by their presence.
+ *
+ * afx_assess_batch: clip i = samples[offsets[i] .. + lengths[i]) (AFX_FMT_F32 / AFX_FMT_S16 taken as value / 32768, host or
+ * device memory) with its own frame lengths frame_short[i], frame_long[i] >= 1 (the screen's int(0.01 sr) and int(0.1 sr) at
+ * the clip's own rate: a batch may mix rates).  Framing is librosa.feature.rms(frame_length = hop_length = fl, center=True)
+ * with zero padding: 1 + (len + 2 (fl / 2) - fl) / fl frames -- 1 + len / fl for an even fl, 1 + (len - 1) / fl for an odd
+ * one such as 441 --, frame t = samples [t fl - fl / 2, t fl - fl / 2 + fl) cut to the clip, its mean square
+ * p_t = sum y^2 / fl.  out_rec holds AFX_ASSESS_N doubles per clip:
+ *   [0] n_short        the frames of frame_short
+ *   [1] silent         short frames with rms_db < threshold_db, rms_db = librosa.amplitude_to_db(rms, ref=np.max) =
+ *                      max(10 log10(max(1e-10, p_t)) - 10 log10(max(1e-10, max p)), -80); decided in float64 as
+ *                      max(1e-10, p_t) < max(1e-10, max p) 10^(threshold_db / 10), never when threshold_db <= -80
+ *   [2] longest_run    longest run of consecutive silent frames, in frames (a run that reaches the last frame counts)
+ *   [3] max_rms_short  sqrt(max p)
+ *   [4] mean_square    sum y^2 / len
+ *   [5] peak           max |y| (exact)
+ *   [6] noise_mean_square   mean of y^2 over the first min(int(0.1 len), noise_cap) samples; NaN when there are none
+ *   [7] n_long, [8] rms_long_mean, [9] rms_long_std   the long framing: frames, mean and population standard deviation
+ *                      (around that mean) of sqrt(p_t)
+ * Squares of float32 samples are exact in float64 and are summed there.  out_status (host): AFX_CLIP_TOO_SHORT for length 0,
+ * AFX_CLIP_NONFINITE for a NaN / inf sample; the record of a failed clip is NaN and no other clip is affected.  The samples
+ * are read from device memory once; no atomics: a clip's record is bit-reproducible and depends neither on the rest of the
+ * batch, nor on the clip's place in it or in the buffer, nor on how the batch is cut into chunks (afx_stft_chunks with the
+ * record of afx_assess_cost).  AFX_ERR_INVALID for a frame length < 1, negative offsets / lengths / noise_cap, a threshold
+ * that is not finite.
+ *
+ * afx_compare_batch: pair i = ref[ref_offsets[i] .. + ref_lengths[i]) and deg[deg_offsets[i] .. + deg_lengths[i]), both of
+ * sample_fmt in mem_kind (they may be one buffer); n = min of the two lengths samples of each are used.  out_rec holds
+ * AFX_COMPARE_N doubles per pair: n, sum r, sum d, sum r^2, sum d^2, sum r d, sum (d - r)^2 -- float64 sums of float32
+ * samples, the difference d - r alone taken in float32 first (numpy's degraded - reference) -- and, for the correlation of
+ * signals with an offset, which those sums cancel in, the centred sums [7] sum (r - mean r)^2, [8] sum (d - mean d)^2,
+ * [9] sum (r - mean r)(d - mean d): centred per span of 4096 samples on the span's means and joined around the pair's
+ * (sum M_i + n_i (mean_i - mean)^2), still in one read.  Status values, reproducibility and independence as above
+ * (AFX_CLIP_TOO_SHORT: n == 0).
+ *
+ * afx_assess_host / afx_compare_host (host-only): one clip / one pair through the same definitions in plain C++, sums in
+ * sample order -- the specification of the kernels; they agree with them to rounding of the float64 sums, counts exactly.
+ * afx_assess_cost (host-only): cost[6] for afx_stft_chunks, what = AFX_COST_ASSESS or AFX_COST_COMPARE (bytes per frame,
+ * tile, sample, clip; frames per tile, most tiles).  The frame lengths are the caller's, so the record bounds the
+ * workspace by the clip's samples: 17 bytes each (+ the upload) and 256 per clip; 1 (+ both uploads) for a pair. */
+enum { AFX_ASSESS_N = 10, AFX_COMPARE_N = 10 };
+enum { AFX_COST_ASSESS = 0, AFX_COST_COMPARE = 1 };
+int afx_assess_cost(int what, int sample_fmt, int mem_kind, int64_t* cost /*[6]*/);
+int afx_assess_host(const void* samples, int sample_fmt, int64_t n, int32_t frame_short, int32_t frame_long,
+                    double threshold_db, int64_t noise_cap, double* out_rec /*[AFX_ASSESS_N]*/, int32_t* out_status);
+int afx_compare_host(const void* ref, const void* deg, int sample_fmt, int64_t n_ref, int64_t n_deg,
+                     double* out_rec /*[AFX_COMPARE_N]*/, int32_t* out_status);
+int afx_assess_batch(afx_ctx* ctx, const void* samples, int sample_fmt, int mem_kind,
+                     const int64_t* offsets, const int64_t* lengths, const int32_t* frame_short, const int32_t* frame_long,
+                     int n_clips, double threshold_db, int64_t noise_cap,
+                     double* out_rec /*[n_clips][AFX_ASSESS_N]*/, int32_t* out_status);
+int afx_compare_batch(afx_ctx* ctx, const void* ref, const void* deg, int sample_fmt, int mem_kind,
+                      const int64_t* ref_offsets, const int64_t* ref_lengths, const int64_t* deg_offsets,
+                      const int64_t* deg_lengths, int n_pairs, double* out_rec /*[n_pairs][AFX_COMPARE_N]*/, int32_t* out_status);
+
 /* Host-only (no device needed): the real FFT the frame kernel of the frame lengths that are not powers of two runs
  * (k_frames_mr), executed in float32 on the CPU with the same radix schedule, twiddle tables and operation order:
  * n_fft / 2 complex points through Stockham passes of radix 3, 5, 4, 8, then the real-FFT split.  out holds the
