@@ -5,6 +5,11 @@ the step steady state), and the experiment extractor's ``preprocess_audio`` buil
 The passes run in ``libafx.so`` (``afx_sosfiltfilt_batch``) on cascaded second-order sections in float64; there is no CPU
 fallback.  Signals are taken as float32 (what the extractors hold); results are float32.
 
+Sections.  ``sosfiltfilt``, ``sosfiltfilt_batch`` and ``filtfilt`` accept any ``(n, 6)`` section array with ``n <= 4`` and
+``a0 == 1`` -- scipy's own sections of any design (Butterworth, elliptic, Chebyshev), band-pass sections, gain-only and
+first-order sections included -- and any ``padlen`` from 0 to 4096.  Only the designer ``butter_sos`` is
+limited to low- and high-pass.
+
 Conditioning.  ``filtfilt(b, a, x)`` goes through ``scipy.signal.tf2sos``: the engine never runs the (b, a) recursion.  For
 the high-pass filters of the extractors (200 Hz, order 5) the poles cluster near z = 1 and the float64 (b, a) recursion of
 scipy is itself only defined to 3e-10 of the peak at 22.05 kHz and 7e-9 at 48 kHz (its distance from the same recursion in

@@ -13,6 +13,7 @@ is the one float32 rounding of the result, <= 2^-25 for |v| <= 1, with a factor 
 division.  The second is the reference's own indeterminacy: the distance between scipy's sosfiltfilt and filtfilt on the
 case's filter input, i.e. between two float64 evaluations of the same filter.  It is computed from scipy alone, and every
 case must keep it below 2^-20 (asserted where the bound is used)."""
+import collections.abc
 import functools
 
 import numpy as np
@@ -103,3 +104,119 @@ def error_ratio(got: np.ndarray, ref: np.ndarray, u: np.ndarray, sr: int) -> flo
     peak = float(np.max(np.abs(ref)))
     assert peak > 0
     return float(np.max(np.abs(got.astype(np.float64) - ref))) / peak / bound(u, sr)
+
+
+# ---- any sections, any padlen: the cases the filter tests share beyond the experiment's 5th-order high-pass ---------------
+# The reference is scipy.signal.sosfiltfilt itself.  Sections in general have no well-conditioned (b, a) form, so the
+# reference's indeterminacy is measured between two float64 evaluations of the same linear filter that scipy offers for any
+# sections: the cascade in its given order and in the reverse order.  The bound keeps the formula of the module docstring.
+
+SHAPE_SR = 22050                                        # only names the tone of signal(): the filters are given by Wn
+SHAPE_PADLENS = (0, 1, 18, 63, 64, 65, 2048, 4095, 4096)
+SHAPE_FILTER_SECTIONS = {                               # name -> section count (the kernels' template argument)
+    "hp1_200hz_22k": 1, "lp2_0.1": 1,
+    "lp3_0.1": 2, "hp4_80hz_48k": 2, "ellip4_0.2": 2, "band2_0.1_0.3": 2,
+    "lp6_0.25": 3, "cheby2_5_hp_0.05": 3, "gain_lp4_0.1": 3,
+    "hp7_0.02": 4, "lp8_0.05": 4, "lp8_0.01": 4, "hp8_200hz_48k": 4, "scipy_lp8_0.05": 4, "gain2_lp4_0.1": 4,
+}
+EXPERIMENT_PAIRS = (("hp1_200hz_22k", 2048), ("lp8_0.05", 4096))   # experiment mode on other filters: S = 1 and S = 4
+
+
+def _gain(g: float) -> np.ndarray:
+    return np.array([[g, 0.0, 0.0, 1.0, 0.0, 0.0]])
+
+
+@functools.lru_cache(maxsize=None)
+def _shape_filter(name: str) -> np.ndarray:
+    from audio_feature_extraction_amd import _native as N
+    own = {"hp1_200hz_22k": (1, 200 / 11025, True), "lp2_0.1": (2, 0.1, False), "lp3_0.1": (3, 0.1, False),
+           "hp4_80hz_48k": (4, 80 / 24000, True), "lp6_0.25": (6, 0.25, False), "hp7_0.02": (7, 0.02, True),
+           "lp8_0.05": (8, 0.05, False), "lp8_0.01": (8, 0.01, False), "hp8_200hz_48k": (8, 200 / 24000, True)}
+    if name in own:
+        sos = N.butter_sos(*own[name])
+    elif name == "ellip4_0.2":                          # zeros on the unit circle: b2 != 0 with b1 != -2 b0
+        sos = scipy.signal.ellip(4, 0.5, 60, 0.2, output="sos")
+    elif name == "band2_0.1_0.3":
+        sos = scipy.signal.butter(2, [0.1, 0.3], "band", output="sos")
+    elif name == "cheby2_5_hp_0.05":
+        sos = scipy.signal.cheby2(5, 40, 0.05, "high", output="sos")
+    elif name == "scipy_lp8_0.05":                      # the whole gain in the first section, scipy's order
+        sos = scipy.signal.butter(8, 0.05, output="sos")
+    elif name == "gain_lp4_0.1":                        # a gain-only section [g, 0, 0, 1, 0, 0] in front
+        sos = np.concatenate([_gain(0.75), N.butter_sos(4, 0.1, False)])
+    elif name == "gain2_lp4_0.1":
+        sos = np.concatenate([_gain(1.5), _gain(0.5), N.butter_sos(4, 0.1, False)])
+    else:
+        raise KeyError(name)
+    sos = np.ascontiguousarray(sos, np.float64)
+    assert sos.shape == (SHAPE_FILTER_SECTIONS[name], 6), (name, sos.shape)
+    sos.setflags(write=False)
+    return sos
+
+
+class _ShapeFilters(collections.abc.Mapping):
+    """name -> sections, built when first asked for (the project's own come from the built library)"""
+
+    def __getitem__(self, name):
+        return _shape_filter(name)
+
+    def __iter__(self):
+        return iter(SHAPE_FILTER_SECTIONS)
+
+    def __len__(self):
+        return len(SHAPE_FILTER_SECTIONS)
+
+
+SHAPE_FILTERS = _ShapeFilters()
+
+
+def shape_lengths_general(block: int, tile: int, p: int):
+    """shape_lengths at padlen p, and the lengths either side of one and of two tiles that it leaves out; only clips the
+    filter takes (n > p) of at least two samples.  With p = tile the first tile of every clip is extension only."""
+    ns = shape_lengths(block, tile, p) + (tile - 2 * p - 1, 2 * tile - 2 * p, 2 * tile - 2 * p + 1)
+    return tuple(dict.fromkeys(n for n in ns if n > max(p, 1)))
+
+
+@functools.lru_cache(maxsize=None)
+def shape_clip(name: str, p: int, n: int) -> np.ndarray:
+    """the clip of one case: signal() with a seed of the case's own"""
+    seed = 1000 * list(SHAPE_FILTER_SECTIONS).index(name) + 37 * SHAPE_PADLENS.index(p) + n % 997
+    y = signal(n, SHAPE_SR, seed)
+    y.setflags(write=False)
+    return y
+
+
+def sos_reference(sos: np.ndarray, u: np.ndarray, padlen: int) -> np.ndarray:
+    """scipy.signal.sosfiltfilt on the float32 u: the odd extension in float32, the passes in float64 (what filt_e restates)"""
+    assert u.dtype == np.float32
+    return scipy.signal.sosfiltfilt(np.array(sos, np.float64), u, padlen=padlen)     # a writable copy: scipy refuses others
+
+
+def sos_conditioning(sos: np.ndarray, u: np.ndarray, padlen: int) -> float:
+    """max|sosfiltfilt(sos) - sosfiltfilt(sos[::-1])| / max|sosfiltfilt(sos)|: exactly 0 for one section"""
+    ref = sos_reference(sos, u, padlen)
+    peak = float(np.max(np.abs(ref)))
+    assert peak > 0
+    return float(np.max(np.abs(sos_reference(np.ascontiguousarray(sos[::-1]), u, padlen) - ref))) / peak
+
+
+def sos_bound(sos: np.ndarray, u: np.ndarray, padlen: int) -> float:
+    c = sos_conditioning(sos, u, padlen)
+    assert c <= MAX_CONDITIONING, (u.size, padlen, c)
+    return EPS32 + 4.0 * c
+
+
+@functools.lru_cache(maxsize=None)
+def shape_case(name: str, p: int, n: int):
+    """(reference, bound) of one case: computed once, shared, never modified"""
+    sos, u = SHAPE_FILTERS[name], shape_clip(name, p, n)
+    ref = sos_reference(sos, u, p)
+    ref.setflags(write=False)
+    return ref, sos_bound(sos, u, p)
+
+
+def sos_error_ratio(got: np.ndarray, ref: np.ndarray, bnd: float) -> float:
+    """max|got - ref| over the reference's peak, as a fraction of the bound"""
+    peak = float(np.max(np.abs(ref)))
+    assert peak > 0
+    return float(np.max(np.abs(got.astype(np.float64) - ref))) / peak / bnd

@@ -159,6 +159,72 @@ def test_host_executor_s16_statuses_and_other_filters(N):
         N.sosfiltfilt_host(x, ref_sos, 18, mode=7)
 
 
+def test_general_case_list_covers_every_section_count_and_padlen(N):
+    """what the GPU shape tests rely on: pinned here so that they cannot quietly lose cases"""
+    g = N.filtfilt_geometry()
+    assert (g["block"], g["tile"], g["max_sections"], g["max_padlen"]) == (64, 4096, 4, 4096)
+    assert F.SHAPE_PADLENS == (0, 1, 18, 63, 64, 65, 2048, 4095, 4096) and max(F.SHAPE_PADLENS) == g["max_padlen"]
+    assert len(F.SHAPE_FILTERS) == 15
+    assert sorted(set(F.SHAPE_FILTER_SECTIONS.values())) == [1, 2, 3, 4]
+    dc = {name: abs(np.prod(sos[:, :3].sum(axis=1) / sos[:, 3:].sum(axis=1))) for name, sos in F.SHAPE_FILTERS.items()}
+    for s in (1, 2, 3, 4):                                  # a filter that passes DC and one that blocks it, at every S
+        gains = [dc[name] for name, k in F.SHAPE_FILTER_SECTIONS.items() if k == s]
+        assert min(gains) < 1e-9 and max(gains) > 0.5, (s, gains)
+    foreign = F.SHAPE_FILTERS["ellip4_0.2"]
+    assert (foreign[:, 2] != 0).all() and (foreign[:, 1] != -2 * foreign[:, 0]).all()
+    first_order = F.SHAPE_FILTERS["lp3_0.1"]
+    assert ((first_order[:, 2] == 0) & (first_order[:, 5] == 0)).sum() == 1
+    for p in F.SHAPE_PADLENS:
+        ns = F.shape_lengths_general(g["block"], g["tile"], p)
+        assert len(ns) == len(set(ns)) >= 3 and min(ns) > max(p, 1), (p, ns)
+        tiles = {(n + 2 * p + g["tile"] - 1) // g["tile"] for n in ns}
+        assert max(tiles) >= 4 and (p >= 2048 or {1, 2, 3} <= tiles), (p, tiles)
+    assert F.shape_lengths_general(64, 4096, 18)[:9] == F.shape_lengths(64, 4096)
+    assert F.shape_lengths_general(64, 4096, 4096) == (4097, 4098, 12305)     # the first tile is extension only
+    for name, p in F.EXPERIMENT_PAIRS:
+        assert F.SHAPE_FILTER_SECTIONS[name] != 3 and p in F.SHAPE_PADLENS
+    from audio_feature_extraction_amd import filters
+    for order in range(1, 9):                               # scipy's default padlen: 3 * (2 n_sections + 1 - shared zeros)
+        for bt in ("low", "high"):
+            assert filters._default_padlen(filters.butter_sos(order, 0.1, bt)) == 3 * (order + 1)
+
+
+@pytest.mark.parametrize("name", list(F.SHAPE_FILTER_SECTIONS))
+def test_host_executor_matches_scipy_on_every_general_case(N, name):
+    """every (padlen, length) of the filter: the reference is usable (a peak, conditioning below the cap: asserted where the
+    bound is formed) and afx_sosfiltfilt_host lies within the bound"""
+    g = N.filtfilt_geometry()
+    sos = F.SHAPE_FILTERS[name]
+    worst, cond = 0.0, 0.0
+    for p in F.SHAPE_PADLENS:
+        for n in F.shape_lengths_general(g["block"], g["tile"], p):
+            u = F.shape_clip(name, p, n)
+            ref, bnd = F.shape_case(name, p, n)
+            h = N.sosfiltfilt_host(u, sos, p)
+            assert h["status"] == N.CLIP_OK and h["out"].dtype == np.float32
+            ratio = F.sos_error_ratio(h["out"], ref, bnd)
+            assert ratio <= 1.0, (name, p, n, ratio)
+            assert h["peak"][0] == np.max(np.abs(u)) and h["peak"][1] == pytest.approx(np.max(np.abs(ref)), rel=1e-6)
+            worst, cond = max(worst, ratio), max(cond, (bnd - F.EPS32) / 4.0)
+        assert N.sosfiltfilt_host(F.signal(p, F.SHAPE_SR, 50), sos, p)["status"] == N.CLIP_TOO_SHORT
+    print(f"{name}: largest ratio to the bound {worst:.3f}, largest conditioning {cond:.2e}")
+
+
+@pytest.mark.parametrize("name,p", F.EXPERIMENT_PAIRS)
+def test_host_executor_experiment_mode_on_other_filters(N, name, p):
+    g = N.filtfilt_geometry()
+    sos = F.SHAPE_FILTERS[name]
+    for n in F.shape_lengths_general(g["block"], g["tile"], p):
+        y = F.shape_clip(name, p, n)
+        h = N.sosfiltfilt_host(y, sos, p, N.FILT_EXPERIMENT, F.COEF)
+        ref = F.normalize(F.sos_reference(sos, F.filter_input(y), p))
+        assert h["status"] == N.CLIP_OK
+        err = float(np.max(np.abs(h["out"].astype(np.float64) - ref)))
+        print(f"{name} padlen {p} n {n}: {err / F.EPS32:.3f} of 2^-23")
+        assert err <= F.EPS32, (name, p, n, err)
+        assert np.max(np.abs(h["out"])) == 1.0
+
+
 def test_filtfilt_check_program_is_clean():
     """the host executor and the design under AddressSanitizer + UBSan: a stand-alone program, nothing preloaded"""
     r = subprocess.run(["make", "-C", CSRC, "filtfilt-check"], capture_output=True, text=True, timeout=600)
