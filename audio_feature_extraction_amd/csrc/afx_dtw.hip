@@ -207,62 +207,28 @@ __global__ void __launch_bounds__(64) k_dtw(const float* __restrict__ feats, con
 
 __global__ void k_dtw_backtrack(const DtwPair* __restrict__ pairs, int n_pairs, const uint32_t* __restrict__ codes,
                                 const int32_t* __restrict__ status, int32_t* __restrict__ path, int32_t* __restrict__ len) {
-  const int p = blockIdx.x * blockDim.x + threadIdx.x;
-  if (p >= n_pairs) return;
-  const DtwPair P = pairs[p];
-  if (status[p] != AFX_DTW_OK) { len[p] = 0; return; }
-  const uint32_t* cw = codes + P.codes;
-  int2* out = reinterpret_cast<int2*>(path) + P.path;
-  int i = P.n - 1, j = P.m - 1, k = 0;
-  const int kmax = P.n + P.m - 1;
-  while (k < kmax) {
-    out[k++] = make_int2(i, j);
-    if (i == 0 && j == 0) break;
-    const int l = i & 63, s = j + l;
-    const uint32_t w = cw[((int64_t)(i >> 6) * P.qn + (s >> 4)) * 64 + l];
-    const uint32_t code = (w >> (2 * (s & 15))) & 3u;
-    if (code == 0) { --i; --j; } else if (code == 1) { --j; } else { --i; }
-    if (i < 0 || j < 0) break;             // cannot happen on a finite D; keeps a corrupted walk in bounds
-  }
-  len[p] = k;
-}
-
-template <int DIMP>
-hipError_t launch_dim(hipStream_t s, const float* feats, const float* norms, int metric, const DtwPair* pairs,
-                      int n_pairs, uint32_t* codes, double* rows, double* dmat, double* cost, int32_t* status,
-                      int backtrack, int store_d) {
-  const dim3 grid(n_pairs), block(64);
-  if (metric == AFX_DTW_EUCLIDEAN)
-    k_dtw<DIMP, AFX_DTW_EUCLIDEAN><<<grid, block, 0, s>>>(feats, norms, pairs, codes, rows, dmat, cost, status,
-                                                          backtrack, store_d);
-  else if (metric == AFX_DTW_SQEUCLIDEAN)
-    k_dtw<DIMP, AFX_DTW_SQEUCLIDEAN><<<grid, block, 0, s>>>(feats, norms, pairs, codes, rows, dmat, cost, status,
-                                                            backtrack, store_d);
-  else
-    k_dtw<DIMP, AFX_DTW_COSINE><<<grid, block, 0, s>>>(feats, norms, pairs, codes, rows, dmat, cost, status,
-                                                       backtrack, store_d);
-  return hipGetLastError();
+  dtw_backtrack_walk<2>(pairs, n_pairs, codes, status, nullptr, false, path, len, [](uint32_t code, int& i, int& j) {
+    i -= code != 1;                        // 0: (1,1), 1: (0,1), 2: (1,0)
+    j -= code < 2;
+    return true;
+  });
 }
 
 }  // namespace
 
-int dtw_dimp(int dim) { return dim <= 8 ? 8 : dim <= 16 ? 16 : dim <= 24 ? 24 : dim <= 40 ? 40 : dim <= 64 ? 64 : 128; }
+int dtw_dimp(int dim) {
+  return dtw_with_dimp(dim, [](auto dimp) { return (int)decltype(dimp)::value; });
+}
 
 hipError_t launch_dtw_pack(hipStream_t s, const float* feats, int dim, int64_t n_frames, float* packed, float* norms) {
   if (n_frames <= 0) return hipSuccess;
   const int dimp = dtw_dimp(dim);
   const int64_t n_elems = n_frames * dimp;
   k_dtw_pack<<<dim3((unsigned)((n_elems + 255) / 256)), dim3(256), 0, s>>>(feats, dim, dimp, n_elems, packed);
-  const dim3 g((unsigned)((n_frames + 255) / 256)), b(256);
-  switch (dimp) {
-    case 8: k_dtw_norms<8><<<g, b, 0, s>>>(packed, n_frames, norms); break;
-    case 16: k_dtw_norms<16><<<g, b, 0, s>>>(packed, n_frames, norms); break;
-    case 24: k_dtw_norms<24><<<g, b, 0, s>>>(packed, n_frames, norms); break;
-    case 40: k_dtw_norms<40><<<g, b, 0, s>>>(packed, n_frames, norms); break;
-    case 64: k_dtw_norms<64><<<g, b, 0, s>>>(packed, n_frames, norms); break;
-    default: k_dtw_norms<128><<<g, b, 0, s>>>(packed, n_frames, norms); break;
-  }
-  return hipGetLastError();
+  return dtw_with_dimp(dim, [&](auto dimp_c) {
+    k_dtw_norms<decltype(dimp_c)::value><<<dim3((unsigned)((n_frames + 255) / 256)), dim3(256), 0, s>>>(packed, n_frames, norms);
+    return hipGetLastError();
+  });
 }
 
 hipError_t launch_dtw_fill_inf(hipStream_t s, double* p, int64_t n) {
@@ -276,13 +242,11 @@ hipError_t launch_dtw(hipStream_t s, const float* feats, const float* norms, int
                       int n_pairs, uint32_t* codes, double* rows, double* dmat, double* cost, int32_t* status,
                       bool backtrack, bool store_d) {
   if (n_pairs <= 0) return hipSuccess;
-  const int bt = backtrack ? 1 : 0, sd = store_d ? 1 : 0;
-  if (dim <= 8) return launch_dim<8>(s, feats, norms, metric, pairs, n_pairs, codes, rows, dmat, cost, status, bt, sd);
-  if (dim <= 16) return launch_dim<16>(s, feats, norms, metric, pairs, n_pairs, codes, rows, dmat, cost, status, bt, sd);
-  if (dim <= 24) return launch_dim<24>(s, feats, norms, metric, pairs, n_pairs, codes, rows, dmat, cost, status, bt, sd);
-  if (dim <= 40) return launch_dim<40>(s, feats, norms, metric, pairs, n_pairs, codes, rows, dmat, cost, status, bt, sd);
-  if (dim <= 64) return launch_dim<64>(s, feats, norms, metric, pairs, n_pairs, codes, rows, dmat, cost, status, bt, sd);
-  return launch_dim<128>(s, feats, norms, metric, pairs, n_pairs, codes, rows, dmat, cost, status, bt, sd);
+  return dtw_dispatch(dim, metric, [&](auto dimp, auto met) {
+    k_dtw<decltype(dimp)::value, decltype(met)::value><<<dim3(n_pairs), dim3(64), 0, s>>>(
+        feats, norms, pairs, codes, rows, dmat, cost, status, backtrack ? 1 : 0, store_d ? 1 : 0);
+    return hipGetLastError();
+  });
 }
 
 hipError_t launch_dtw_backtrack(hipStream_t s, const DtwPair* pairs, int n_pairs, const uint32_t* codes,

@@ -1,5 +1,6 @@
-// Device code the two DTW recurrence kernels share (k_dtw in afx_dtw.hip, k_dtw_steps in afx_dtw_steps.hip): the DPP lane
-// shifts of a double, the per-pair NaN / zero-norm test and the local cost of one cell.
+// What the two DTW kernel files share (k_dtw in afx_dtw.hip, k_dtw_steps in afx_dtw_steps.hip): the (dim, metric) ->
+// instantiation dispatch, the DPP lane shifts of a double, the per-pair NaN / zero-norm test, the local cost of one cell
+// and the back-track.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -10,6 +11,26 @@
 #include "afx_dtw.h"
 
 namespace afx {
+
+// Host side: f(std::integral_constant<int, DIMP>) for the compiled width that serves `dim` (dtw_dimp is this list) ...
+template <class F>
+auto dtw_with_dimp(int dim, F&& f) {
+  if (dim <= 8) return f(std::integral_constant<int, 8>{});
+  if (dim <= 16) return f(std::integral_constant<int, 16>{});
+  if (dim <= 24) return f(std::integral_constant<int, 24>{});
+  if (dim <= 40) return f(std::integral_constant<int, 40>{});
+  if (dim <= 64) return f(std::integral_constant<int, 64>{});
+  return f(std::integral_constant<int, 128>{});
+}
+// ... and f(DIMP, METRIC), both as integral constants, for the kernels that are templates over the metric too
+template <class F>
+auto dtw_dispatch(int dim, int metric, F&& f) {
+  return dtw_with_dimp(dim, [&](auto dimp) {
+    if (metric == AFX_DTW_EUCLIDEAN) return f(dimp, std::integral_constant<int, AFX_DTW_EUCLIDEAN>{});
+    if (metric == AFX_DTW_SQEUCLIDEAN) return f(dimp, std::integral_constant<int, AFX_DTW_SQEUCLIDEAN>{});
+    return f(dimp, std::integral_constant<int, AFX_DTW_COSINE>{});
+  });
+}
 
 constexpr double kDtwInf = __builtin_huge_val();
 typedef float dtw_f2 __attribute__((ext_vector_type(2)));   // v_pk_add_f32 / v_pk_fma_f32 operands
@@ -95,6 +116,35 @@ __device__ __forceinline__ float dtw_local_cost(const XR& xr, float nx, const fl
     if (METRIC == AFX_DTW_EUCLIDEAN) c = sqrtf(c);
   }
   return c;
+}
+
+// The back-track of both kernels, one lane per pair: from (N-1, end[p]), or (N-1, M-1) without `end`, along the recorded
+// steps to (0, 0), or to the first cell of row 0 (row0_ends).  BITS: the width of a step code, 32 / BITS wavefront steps
+// per word, layout [strip][word][lane].  back(code, i, j) takes one step back; false on a code that no step wrote.
+// path[2k], path[2k+1] = i, j; len[p] = L (0 for a failed pair).
+template <int BITS, class Back>
+__device__ __forceinline__ void dtw_backtrack_walk(const DtwPair* __restrict__ pairs, int n_pairs,
+                                                   const uint32_t* __restrict__ codes, const int32_t* __restrict__ status,
+                                                   const int32_t* __restrict__ end, bool row0_ends,
+                                                   int32_t* __restrict__ path, int32_t* __restrict__ len, Back back) {
+  constexpr int PER = 32 / BITS;           // steps per word: 16 or 8
+  const int p = blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= n_pairs) return;
+  const DtwPair P = pairs[p];
+  if (status[p] != AFX_DTW_OK) { len[p] = 0; return; }
+  const uint32_t* cw = codes + P.codes;
+  int2* out = reinterpret_cast<int2*>(path) + P.path;
+  int i = P.n - 1, j = end ? end[p] : P.m - 1, k = 0;
+  const int kmax = P.n + P.m - 1;
+  while (k < kmax && j >= 0 && j < P.m) {
+    out[k++] = make_int2(i, j);
+    if (i == 0 && (row0_ends || j == 0)) break;
+    const unsigned l = i & 63, s = j + l;
+    const uint32_t w = cw[((int64_t)(i >> 6) * P.qn + s / PER) * 64 + l];
+    // neither can happen on a finite D: an unwritten code would spin a corrupted walk, a step out of the matrix leave bounds
+    if (!back((w >> (BITS * (s % PER))) & ((1u << BITS) - 1u), i, j) || i < 0 || j < 0) break;
+  }
+  len[p] = k;
 }
 
 }  // namespace afx

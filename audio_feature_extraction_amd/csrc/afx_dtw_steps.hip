@@ -227,49 +227,17 @@ __global__ void __launch_bounds__(64) k_dtw_steps(const float* __restrict__ feat
   }
 }
 
-// one lane per pair: from (N-1, end[p]) back along the recorded steps
 __global__ void k_dtw_steps_backtrack(const DtwPair* __restrict__ pairs, int n_pairs, const DtwSteps T,
                                       const uint32_t* __restrict__ codes, const int32_t* __restrict__ status,
                                       const int32_t* __restrict__ end, int32_t* __restrict__ path, int32_t* __restrict__ len) {
-  const int p = blockIdx.x * blockDim.x + threadIdx.x;
-  if (p >= n_pairs) return;
-  const DtwPair P = pairs[p];
-  if (status[p] != AFX_DTW_OK) { len[p] = 0; return; }
   uint32_t table = 0;                      // selector (di * 3 + dj) by recorded index, 4 bits each
   for (int k = 0; k < T.n; ++k) table |= (uint32_t)T.sel[k] << (4 * T.idx[k]);
-  const uint32_t* cw = codes + P.codes;
-  int2* out = reinterpret_cast<int2*>(path) + P.path;
-  int i = P.n - 1, j = end[p], k = 0;
-  const int kmax = P.n + P.m - 1;
-  while (k < kmax && j >= 0 && j < P.m) {
-    out[k++] = make_int2(i, j);
-    if (i == 0 && (T.subseq || j == 0)) break;
-    const int l = i & 63, s = j + l;
-    const uint32_t w = cw[((int64_t)(i >> 6) * P.qn + (s >> 3)) * 64 + l];
-    const uint32_t sel = (table >> (4 * ((w >> (4 * (s & 7))) & 7u))) & 15u;
-    if (sel == 0) break;                   // cannot happen on a finite D; keeps a corrupted walk from spinning
+  dtw_backtrack_walk<4>(pairs, n_pairs, codes, status, end, T.subseq != 0, path, len, [table](uint32_t code, int& i, int& j) {
+    const uint32_t sel = (table >> (4 * (code & 7u))) & 15u;
     i -= (int)(sel / 3u);
     j -= (int)(sel % 3u);
-    if (i < 0 || j < 0) break;             // as above: keeps it in bounds
-  }
-  len[p] = k;
-}
-
-template <int DIMP>
-hipError_t launch_dim(hipStream_t s, const float* feats, const float* norms, int metric, const DtwPair* pairs, int n_pairs,
-                      const DtwSteps& T, uint32_t* codes, double* rows, double* dmat, double* cost, int32_t* status,
-                      int32_t* end, int backtrack, int store_d) {
-  const dim3 grid(n_pairs), block(64);
-  if (metric == AFX_DTW_EUCLIDEAN)
-    k_dtw_steps<DIMP, AFX_DTW_EUCLIDEAN><<<grid, block, 0, s>>>(feats, norms, pairs, T, codes, rows, dmat, cost, status, end,
-                                                                backtrack, store_d);
-  else if (metric == AFX_DTW_SQEUCLIDEAN)
-    k_dtw_steps<DIMP, AFX_DTW_SQEUCLIDEAN><<<grid, block, 0, s>>>(feats, norms, pairs, T, codes, rows, dmat, cost, status, end,
-                                                                  backtrack, store_d);
-  else
-    k_dtw_steps<DIMP, AFX_DTW_COSINE><<<grid, block, 0, s>>>(feats, norms, pairs, T, codes, rows, dmat, cost, status, end,
-                                                             backtrack, store_d);
-  return hipGetLastError();
+    return sel != 0;                       // 0: an index no step of the list recorded
+  });
 }
 
 }  // namespace
@@ -278,15 +246,11 @@ hipError_t launch_dtw_steps(hipStream_t s, const float* feats, const float* norm
                             int n_pairs, const DtwSteps& T, uint32_t* codes, double* rows, double* dmat, double* cost,
                             int32_t* status, int32_t* end, bool backtrack, bool store_d) {
   if (n_pairs <= 0) return hipSuccess;
-  const int bt = backtrack ? 1 : 0, sd = store_d ? 1 : 0;
-  switch (dtw_dimp(dim)) {
-    case 8: return launch_dim<8>(s, feats, norms, metric, pairs, n_pairs, T, codes, rows, dmat, cost, status, end, bt, sd);
-    case 16: return launch_dim<16>(s, feats, norms, metric, pairs, n_pairs, T, codes, rows, dmat, cost, status, end, bt, sd);
-    case 24: return launch_dim<24>(s, feats, norms, metric, pairs, n_pairs, T, codes, rows, dmat, cost, status, end, bt, sd);
-    case 40: return launch_dim<40>(s, feats, norms, metric, pairs, n_pairs, T, codes, rows, dmat, cost, status, end, bt, sd);
-    case 64: return launch_dim<64>(s, feats, norms, metric, pairs, n_pairs, T, codes, rows, dmat, cost, status, end, bt, sd);
-    default: return launch_dim<128>(s, feats, norms, metric, pairs, n_pairs, T, codes, rows, dmat, cost, status, end, bt, sd);
-  }
+  return dtw_dispatch(dim, metric, [&](auto dimp, auto met) {
+    k_dtw_steps<decltype(dimp)::value, decltype(met)::value><<<dim3(n_pairs), dim3(64), 0, s>>>(
+        feats, norms, pairs, T, codes, rows, dmat, cost, status, end, backtrack ? 1 : 0, store_d ? 1 : 0);
+    return hipGetLastError();
+  });
 }
 
 hipError_t launch_dtw_steps_backtrack(hipStream_t s, const DtwPair* pairs, int n_pairs, const DtwSteps& T,

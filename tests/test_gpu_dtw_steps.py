@@ -327,3 +327,31 @@ def test_default_arguments_take_the_default_path(seq):
     cg, wpg = seq.dtw(Xr, Yr, weights_add=[0.0, 0.0, 0.0])           # the other kernel, the same local cost: bit-equal
     assert cg == cost
     np.testing.assert_array_equal(wpg, wp)
+
+
+_BOTH_SHAPES = [(65, 130), (130, 66), (1, 72), (64, 64), (129, 73)]
+
+
+@pytest.mark.parametrize("dim", [13, 39, 128])
+@pytest.mark.parametrize("metric", ["euclidean", "sqeuclidean", "cosine"])
+def test_both_kernels_agree_bit_for_bit_on_the_default_steps(seq, metric, dim):
+    """k_dtw (dtw_batch) and k_dtw_steps on the default list with no weights (dtw_steps_batch) form the same float64 sums
+    from the same float32 local cost (1.0 * c + 0.0 == c), so status, cost, every D and every path are equal, not close:
+    seeded standard-normal features, strip / tile / ring edges, with and without a band of 0.25 min(N, M)."""
+    rng = np.random.default_rng(1000 * dim + len(metric))
+    lens = [k for nm in _BOTH_SHAPES for k in nm]
+    feats = rng.standard_normal((sum(lens), dim)).astype(np.float32)
+    offs = np.concatenate([[0], np.cumsum(lens)[:-1]])
+    xo, yo, xl, yl = offs[0::2], offs[1::2], np.array(lens[0::2]), np.array(lens[1::2])
+    ctx = seq._context(0)
+    for band in (None, [int(round(0.25 * min(n, m))) for n, m in _BOTH_SHAPES]):
+        a = ctx.dtw_batch(feats, xo, xl, yo, yl, band, metric, True, True)
+        b = ctx.dtw_steps_batch(feats, xo, xl, yo, yl, band, metric, True, True, steps=None, weights_add=None, weights_mul=None)
+        np.testing.assert_array_equal(a["status"], b["status"])
+        np.testing.assert_array_equal(a["cost"], b["cost"])
+        assert band is not None or (a["status"] == 0).all()
+        for p in range(len(_BOTH_SHAPES)):
+            np.testing.assert_array_equal(a["D"][p], b["D"][p])
+            assert (a["paths"][p] is None) == (b["paths"][p] is None)
+            if a["paths"][p] is not None:
+                np.testing.assert_array_equal(a["paths"][p], b["paths"][p])
