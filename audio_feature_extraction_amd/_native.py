@@ -48,6 +48,9 @@ ASSESS_FIELDS = ("n_short", "silent", "longest_run", "max_rms_short", "mean_squa
                  "n_long", "rms_long_mean", "rms_long_std")
 COMPARE_FIELDS = ("n", "sum_r", "sum_d", "sum_rr", "sum_dd", "sum_rd", "sum_ee", "m2_r", "m2_d", "m2_rd")
 COST_ASSESS, COST_COMPARE = 0, 1                                             # afx_assess_cost: whose record
+SPECDIST_N = 4                                                               # doubles per record of afx_specdist_batch
+SPECDIST_FIELDS = ("n", "sum_dist", "sum_rr", "sum_dd")
+CFFT_MAX_N = 1 << 21                                                         # samples of a clip the device transforms
 GROUPS_STATS = 24                                                            # doubles per clip of its record
 K_NAMES = ("trim_blocks", "trim_decide", "frames", "dct", "stats")
 K_FRAMES = 2
@@ -68,6 +71,7 @@ SYMBOLS = (
     "afx_dtw_steps_batch",
     "afx_denoise_batch", "afx_denoise_cost",
     "afx_assess_batch", "afx_compare_batch", "afx_assess_host", "afx_compare_host", "afx_assess_cost",
+    "afx_specdist_batch", "afx_clip_fft_batch", "afx_specdist_host", "afx_clip_fft_host", "afx_specdist_cost",
 )
 
 
@@ -178,6 +182,12 @@ def lib() -> C.CDLL:
             L.afx_compare_host.argtypes = [vp, vp, i32, C.c_int64, C.c_int64, vp, vp]
             L.afx_assess_batch.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, i32, C.c_double, C.c_int64, vp, vp]
             L.afx_compare_batch.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp, vp, i32, vp, vp]
+        if hasattr(L, "afx_specdist_batch"):                 # newer than version 107 says: found by their presence
+            L.afx_specdist_cost.argtypes = [i32, i32, vp]
+            L.afx_specdist_host.argtypes = [vp, vp, i32, C.c_int64, C.c_int64, vp, vp]
+            L.afx_clip_fft_host.argtypes = [vp, i32, C.c_int64, vp, vp]
+            L.afx_specdist_batch.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp, vp, i32, vp, vp]
+            L.afx_clip_fft_batch.argtypes = [vp, vp, i32, i32, vp, vp, i32, vp, vp, vp]
         if hasattr(L, "afx_rfft_host"):                      # absent from a library built before the mixed-radix lengths
             L.afx_rfft_host.argtypes = [i32, vp, vp]
         _lib = L
@@ -441,6 +451,47 @@ def compare_host(ref, deg) -> dict:
     _check(lib().afx_compare_host(ref.ctypes.data, deg.ctypes.data, FMT_S16 if ref.dtype == np.int16 else FMT_F32,
                                   int(ref.size), int(deg.size), rec.ctypes.data, status.ctypes.data), "afx_compare_host")
     return {"rec": rec, "status": int(status[0])}
+
+
+def _need_specdist():
+    if not hasattr(lib(), "afx_specdist_batch"):
+        raise NotImplementedError("this libafx has no afx_specdist_batch")
+
+
+def specdist_cost(fmt: int = FMT_F32, mem: int = MEM_HOST) -> np.ndarray:
+    """Host-only: the cost record afx_specdist_batch / afx_clip_fft_batch cut a batch with (bytes per frame, per tile, per
+    sample, per clip; frames per tile, most tiles of a chunk), for ``stft_chunks``."""
+    _need_specdist()
+    cost = np.zeros(6, np.int64)
+    _check(lib().afx_specdist_cost(int(fmt), int(mem), cost.ctypes.data), "afx_specdist_cost")
+    return cost
+
+
+def specdist_host(ref, deg) -> dict:
+    """Host-only: afx_specdist_host, one pair of int16 / float32 clips (both of one type) through the definitions of
+    afx_specdist_batch on the CPU.  Returns rec (float64 [SPECDIST_N]; SPECDIST_FIELDS names the entries) and status."""
+    _need_specdist()
+    ref, deg = _mono_clip(ref, "ref"), _mono_clip(deg, "deg")
+    if ref.dtype != deg.dtype:
+        raise ValueError("ref and deg must have one sample type")
+    rec = np.zeros(SPECDIST_N, np.float64)
+    status = np.zeros(1, np.int32)
+    _check(lib().afx_specdist_host(ref.ctypes.data, deg.ctypes.data, FMT_S16 if ref.dtype == np.int16 else FMT_F32,
+                                   int(ref.size), int(deg.size), rec.ctypes.data, status.ctypes.data), "afx_specdist_host")
+    return {"rec": rec, "status": int(status[0])}
+
+
+def clip_fft_host(x) -> dict:
+    """Host-only: afx_clip_fft_host, np.fft.rfft of one int16 / float32 clip by the Bluestein transform of
+    afx_clip_fft_batch on the CPU.  Returns bins (complex128 [n // 2 + 1]; empty for an empty clip, NaN for a clip that is
+    not finite everywhere) and status."""
+    _need_specdist()
+    x = _mono_clip(x, "x")
+    bins = np.zeros(x.size // 2 + 1 if x.size else 0, np.complex128)
+    status = np.zeros(1, np.int32)
+    _check(lib().afx_clip_fft_host(x.ctypes.data, FMT_S16 if x.dtype == np.int16 else FMT_F32, int(x.size),
+                                   bins.ctypes.data, status.ctypes.data), "afx_clip_fft_host")
+    return {"bins": bins, "status": int(status[0])}
 
 
 def groups_dct_table(n_mels: int = 128) -> np.ndarray:
@@ -949,6 +1000,46 @@ class Context(_Owner):
                                        deg_offsets.ctypes.data, deg_lengths.ctypes.data, n, rec.ctypes.data, status.ctypes.data),
                "afx_compare_batch")
         return {"rec": rec, "status": status}
+
+    def specdist_batch(self, ref, ref_offsets, ref_lengths, deg, deg_offsets, deg_lengths, fmt=None) -> dict:
+        """afx_specdist_batch: for the pairs of ``compare_batch`` (same arguments), over the shorter length n of each pair,
+        the sums behind the spectral distance of the two whole-clip magnitude spectra.  Returns rec (float64
+        [n, SPECDIST_N]; SPECDIST_FIELDS names the columns) and status.  NotImplementedError past CFFT_MAX_N samples."""
+        _need_specdist()
+        ref_offsets, ref_lengths, n = _clip_arrays(ref_offsets, ref_lengths)
+        deg_offsets, deg_lengths, nd = _clip_arrays(deg_offsets, deg_lengths)
+        if nd != n:
+            raise ValueError("both sides must have one entry per pair")
+        if isinstance(ref, np.ndarray) != isinstance(deg, np.ndarray):
+            raise ValueError("ref and deg must both be host arrays or both be device memory")
+        fmt = _sample_fmt(ref, fmt)
+        rptr, kind = _sample_source(ref, fmt, ref_offsets, np.maximum(ref_lengths, 0))
+        dptr, _ = _sample_source(deg, fmt, deg_offsets, np.maximum(deg_lengths, 0))
+        rec = np.full((n, SPECDIST_N), np.nan, np.float64)
+        status = np.zeros(n, np.int32)
+        _check(lib().afx_specdist_batch(self.handle, rptr, dptr, int(fmt), kind, ref_offsets.ctypes.data, ref_lengths.ctypes.data,
+                                        deg_offsets.ctypes.data, deg_lengths.ctypes.data, n, rec.ctypes.data, status.ctypes.data),
+               "afx_specdist_batch")
+        return {"rec": rec, "status": status}
+
+    def clip_fft_batch(self, samples, offsets, lengths, fmt=None) -> dict:
+        """afx_clip_fft_batch: np.fft.rfft of every clip samples[offsets[i] .. + lengths[i]), whatever its length.
+        ``samples``: an int16 / float32 numpy array (host) or a DeviceBuffer / device pointer (``fmt`` required).  Returns
+        bins (complex128, clip after clip), offsets (where each clip's lengths[i] // 2 + 1 bins begin) and status (a clip
+        with a NaN / inf sample: NaN bins; an empty clip: no bins)."""
+        _need_specdist()
+        offsets, lengths, n = _clip_arrays(offsets, lengths)
+        fmt = _sample_fmt(samples, fmt)
+        sptr, kind = _sample_source(samples, fmt, offsets, np.maximum(lengths, 0))
+        nb = np.where(lengths > 0, np.maximum(lengths, 0) // 2 + 1, 0).astype(np.int64)
+        out_offsets = np.zeros(n, np.int64)
+        if n:
+            out_offsets[1:] = np.cumsum(nb)[:-1]
+        bins = np.zeros(max(int(nb.sum()), 1), np.complex128)
+        status = np.zeros(n, np.int32)
+        _check(lib().afx_clip_fft_batch(self.handle, sptr, int(fmt), kind, offsets.ctypes.data, lengths.ctypes.data, n,
+                                        bins.ctypes.data, out_offsets.ctypes.data, status.ctypes.data), "afx_clip_fft_batch")
+        return {"bins": bins[:int(nb.sum())], "offsets": out_offsets, "counts": nb, "status": status}
 
 
 class Plan(_Owner):

@@ -710,3 +710,188 @@ extern "C" int afx_compare_batch(afx_ctx* ctx, const void* ref, const void* deg,
   }
   return AFX_OK;
 }
+
+// ---- the whole-clip DFT and the spectral term of the PESQ-like score (audio_quality_assessment.py:150-201) ----
+// The body of afx_specdist_batch (deg given: z = r + i d, out_rec) and afx_clip_fft_batch (deg == nullptr: out_bins at
+// out_offsets).  A chunk: its samples staged packed when they are the host's, one filter job per distinct length and one
+// signal job per pair -- those of M <= 4096 first --, the filter launches, the signal launches, the tail or the copies.
+static int cfft_run(const char* who, afx_ctx* ctx, const void* ref, const void* deg, int sample_fmt, int mem_kind,
+                    const int64_t* ref_offsets, const int64_t* deg_offsets, const int64_t* lens, int n_pairs,
+                    double* out_rec, double* out_bins, const int64_t* out_offsets, int32_t* out_status) {
+  (void)hipGetLastError();
+  HIP_TRY(hipSetDevice(ctx->device));
+  hipStream_t s = ctx->stream;
+  int rc;
+  if (!ctx->cf_tw_ready) {
+    std::vector<double> tw((size_t)kCfTile);
+    cf_twiddle_table(tw.data());
+    if ((rc = ensure(ctx->cf_tw, tw.size() * sizeof(double))) != AFX_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(ctx->cf_tw.p, tw.data(), tw.size() * sizeof(double), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipStreamSynchronize(s));                                  // tw dies with this scope
+    ctx->cf_tw_ready = true;
+  }
+  const size_t esz = sample_fmt == AFX_FMT_S16 ? 2 : 4;
+  const bool h_in = mem_kind == AFX_MEM_HOST, pair = deg != nullptr;
+  StftCost cost;
+  specdist_cost(sample_fmt, mem_kind, cost);
+  StftChunk ck;
+  std::vector<CfJob> jobs, filt_jobs;
+  std::vector<int> order, slot_of;
+  std::vector<int64_t> distinct, in_r, in_d;
+  std::vector<char> stage;
+  std::vector<double> h_rec;
+  std::vector<int32_t> h_bad;
+  const double nan = std::nan("");
+  for (int c0 = 0; c0 < n_pairs; c0 = ck.next) {
+    cut_stft_chunk(ref_offsets, lens, n_pairs, c0, dev_env().specdist_budget, cost, ck);
+    const int n = (int)ck.idx.size();
+    if (n == 0) continue;
+    // the staging's layout, in the chunk's order
+    in_r.assign((size_t)n, 0); in_d.assign((size_t)n, -1);
+    int64_t in_pos = 0;
+    for (int q = 0; q < n; ++q) {
+      const int i = ck.idx[q];
+      const int64_t slot = (lens[i] + 7) / 8 * 8;
+      in_r[q] = h_in ? in_pos : ref_offsets[i];
+      if (pair) in_d[q] = h_in ? in_pos + slot : deg_offsets[i];
+      in_pos += (pair ? 2 : 1) * slot;
+    }
+    // the distinct lengths, ascending: their filters, then the jobs -- either list with its M <= kCfTile first
+    distinct.clear();
+    for (int q = 0; q < n; ++q) distinct.push_back(lens[ck.idx[q]]);
+    std::sort(distinct.begin(), distinct.end());
+    distinct.erase(std::unique(distinct.begin(), distinct.end()), distinct.end());
+    filt_jobs.assign(distinct.size(), CfJob{});
+    int64_t filt_pts = 0, f_blocks = 0;
+    int f_small = 0;
+    for (size_t k = 0; k < distinct.size(); ++k) {                     // ascending n: ascending M, the small ones first
+      CfJob& f = filt_jobs[k];
+      f.n = distinct[k]; f.r_off = 0; f.d_off = -1;
+      f.logM = cf_log_m(f.n); f.logM1 = cf_log_m1(f.logM);
+      f.work_off = f.filt_off = filt_pts; filt_pts += (int64_t)1 << f.logM;
+      if (f.logM <= kCfTileLog) { ++f_small; f.blk_base = 0; }
+      else { f.blk_base = f_blocks; f_blocks += cf_tiles(f.logM); }
+    }
+    order.resize((size_t)n);
+    std::iota(order.begin(), order.end(), 0);
+    std::stable_partition(order.begin(), order.end(), [&](int q) { return cf_log_m(lens[ck.idx[q]]) <= kCfTileLog; });
+    jobs.assign((size_t)n, CfJob{});
+    int64_t work_pts = 0, j_blocks = 0;
+    int j_small = 0;
+    for (int p = 0; p < n; ++p) {
+      const int q = order[p];
+      CfJob& j = jobs[p];
+      j.n = lens[ck.idx[q]]; j.r_off = in_r[q]; j.d_off = in_d[q];
+      j.logM = cf_log_m(j.n); j.logM1 = cf_log_m1(j.logM);
+      j.work_off = work_pts; work_pts += (int64_t)1 << j.logM;
+      j.filt_off = filt_jobs[(size_t)(std::lower_bound(distinct.begin(), distinct.end(), j.n) - distinct.begin())].filt_off;
+      if (j.logM <= kCfTileLog) { ++j_small; j.blk_base = 0; }
+      else { j.blk_base = j_blocks; j_blocks += cf_tiles(j.logM); }
+    }
+    if (j_blocks > INT32_MAX / 2 || f_blocks > INT32_MAX / 2) { set_error(std::string(who) + ": chunk too large for one launch"); return AFX_ERR_UNSUPPORTED; }
+    const size_t nf = filt_jobs.size();
+    if ((rc = ensure(ctx->cf_jobs, (nf + (size_t)n) * sizeof(CfJob))) != AFX_OK) return rc;
+    if ((rc = ensure(ctx->cf_filt, (size_t)filt_pts * 16)) != AFX_OK) return rc;
+    if ((rc = ensure(ctx->cf_work, (size_t)work_pts * 16)) != AFX_OK) return rc;
+    if ((rc = ensure(ctx->cf_rec, (size_t)n * AFX_SPECDIST_N * sizeof(double))) != AFX_OK) return rc;
+    if ((rc = ensure(ctx->cf_bad, (size_t)n * 2 * sizeof(int32_t))) != AFX_OK) return rc;
+    const void *d_ref = ref, *d_deg = deg;
+    if (h_in) {
+      stage.assign((size_t)std::max<int64_t>(in_pos, 1) * esz, 0);
+      for (int q = 0; q < n; ++q) {
+        const int i = ck.idx[q];
+        std::memcpy(stage.data() + (size_t)in_r[q] * esz, (const char*)ref + (size_t)ref_offsets[i] * esz, (size_t)lens[i] * esz);
+        if (pair) std::memcpy(stage.data() + (size_t)in_d[q] * esz, (const char*)deg + (size_t)deg_offsets[i] * esz, (size_t)lens[i] * esz);
+      }
+      if ((rc = ensure(ctx->cf_in, stage.size())) != AFX_OK) return rc;
+      HIP_TRY(hipMemcpyAsync(ctx->cf_in.p, stage.data(), stage.size(), hipMemcpyHostToDevice, s));
+      d_ref = ctx->cf_in.p;
+      d_deg = pair ? ctx->cf_in.p : nullptr;
+    }
+    CfJob* d_fjobs = (CfJob*)ctx->cf_jobs.p;
+    CfJob* d_jobs = d_fjobs + nf;
+    HIP_TRY(hipMemcpyAsync(d_fjobs, filt_jobs.data(), nf * sizeof(CfJob), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d_jobs, jobs.data(), (size_t)n * sizeof(CfJob), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemsetAsync(ctx->cf_bad.p, 0, (size_t)n * 2 * sizeof(int32_t), s));
+    const double* tw = (const double*)ctx->cf_tw.p;
+    HIP_TRY(launch_cfft_filters(s, d_fjobs, f_small, (int)nf - f_small, (int)f_blocks, tw, (double*)ctx->cf_filt.p));
+    HIP_TRY(launch_cfft(s, d_ref, d_deg, sample_fmt, d_jobs, j_small, n - j_small, (int)j_blocks, tw, (const double*)ctx->cf_filt.p,
+                        (double*)ctx->cf_work.p, (int32_t*)ctx->cf_bad.p));
+    h_bad.resize((size_t)n * 2);
+    if (pair) {
+      HIP_TRY(launch_specdist_tail(s, d_jobs, n, (const double*)ctx->cf_work.p, (const int32_t*)ctx->cf_bad.p, (double*)ctx->cf_rec.p));
+      h_rec.resize((size_t)n * AFX_SPECDIST_N);
+      HIP_TRY(hipMemcpyAsync(h_rec.data(), ctx->cf_rec.p, h_rec.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+    }
+    HIP_TRY(hipMemcpyAsync(h_bad.data(), ctx->cf_bad.p, h_bad.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    for (int p = 0; p < n; ++p) {
+      const int i = ck.idx[order[p]];
+      const bool isbad = h_bad[2 * p] != 0;
+      if (isbad) out_status[i] = AFX_CLIP_NONFINITE;
+      if (pair) {
+        if (!isbad) std::memcpy(out_rec + (size_t)AFX_SPECDIST_N * i, h_rec.data() + (size_t)AFX_SPECDIST_N * p, AFX_SPECDIST_N * sizeof(double));
+        continue;
+      }
+      double* dst = out_bins + 2 * out_offsets[i];
+      const size_t bins = (size_t)(lens[i] / 2 + 1);
+      if (isbad) { std::fill(dst, dst + 2 * bins, nan); continue; }
+      HIP_TRY(hipMemcpyAsync(dst, (const char*)ctx->cf_work.p + (size_t)jobs[p].work_off * 16, bins * 16, hipMemcpyDeviceToHost, s));
+    }
+    if (!pair) HIP_TRY(hipStreamSynchronize(s));
+  }
+  return AFX_OK;
+}
+
+extern "C" int afx_specdist_batch(afx_ctx* ctx, const void* ref, const void* deg, int sample_fmt, int mem_kind,
+                                  const int64_t* ref_offsets, const int64_t* ref_lengths, const int64_t* deg_offsets,
+                                  const int64_t* deg_lengths, int n_pairs, double* out_rec, int32_t* out_status) {
+  const char* who = "afx_specdist_batch";
+  if (!ctx || n_pairs < 0 || (n_pairs > 0 && (!ref_offsets || !ref_lengths || !deg_offsets || !deg_lengths || !out_rec || !out_status))) return null_arg(who);
+  int rc;
+  if ((rc = check_sample_format(who, sample_fmt, mem_kind)) != AFX_OK) return rc;
+  if ((rc = check_clip_ranges(who, ref_offsets, ref_lengths, nullptr, n_pairs, INT64_MAX / 8)) != AFX_OK) return rc;
+  if ((rc = check_clip_ranges(who, deg_offsets, deg_lengths, nullptr, n_pairs, INT64_MAX / 8)) != AFX_OK) return rc;
+  std::vector<int64_t> lens((size_t)n_pairs);
+  bool any = false;
+  for (int i = 0; i < n_pairs; ++i) {
+    lens[i] = std::min(ref_lengths[i], deg_lengths[i]);
+    if (lens[i] > kCfMaxN) {
+      set_error(std::string(who) + ": pair " + std::to_string(i) + ": more than 2^21 samples are not supported");
+      return AFX_ERR_UNSUPPORTED;
+    }
+    any = any || lens[i] > 0;
+  }
+  const double nan = std::nan("");
+  for (int i = 0; i < n_pairs; ++i) {
+    out_status[i] = lens[i] == 0 ? AFX_CLIP_TOO_SHORT : AFX_CLIP_OK;
+    std::fill(out_rec + (size_t)AFX_SPECDIST_N * i, out_rec + (size_t)AFX_SPECDIST_N * (i + 1), nan);
+  }
+  if (!any) return AFX_OK;
+  if (!ref || !deg) { set_error(std::string(who) + ": null samples"); return AFX_ERR_INVALID; }
+  return cfft_run(who, ctx, ref, deg, sample_fmt, mem_kind, ref_offsets, deg_offsets, lens.data(), n_pairs, out_rec, nullptr, nullptr,
+                  out_status);
+}
+
+extern "C" int afx_clip_fft_batch(afx_ctx* ctx, const void* samples, int sample_fmt, int mem_kind, const int64_t* offsets,
+                                  const int64_t* lengths, int n_clips, double* out, const int64_t* out_offsets,
+                                  int32_t* out_status) {
+  const char* who = "afx_clip_fft_batch";
+  if (!ctx || n_clips < 0 || (n_clips > 0 && (!offsets || !lengths || !out_offsets || !out_status))) return null_arg(who);
+  int rc;
+  if ((rc = check_sample_format(who, sample_fmt, mem_kind)) != AFX_OK) return rc;
+  if ((rc = check_clip_ranges(who, offsets, lengths, out_offsets, n_clips, INT64_MAX / 32)) != AFX_OK) return rc;
+  bool any = false;
+  for (int i = 0; i < n_clips; ++i) {
+    if (lengths[i] > kCfMaxN) {
+      set_error(std::string(who) + ": clip " + std::to_string(i) + ": more than 2^21 samples are not supported");
+      return AFX_ERR_UNSUPPORTED;
+    }
+    any = any || lengths[i] > 0;
+  }
+  for (int i = 0; i < n_clips; ++i) out_status[i] = lengths[i] == 0 ? AFX_CLIP_TOO_SHORT : AFX_CLIP_OK;
+  if (!any) return AFX_OK;
+  if (!samples || !out) { set_error(std::string(who) + ": null samples or output"); return AFX_ERR_INVALID; }
+  return cfft_run(who, ctx, samples, nullptr, sample_fmt, mem_kind, offsets, nullptr, lengths, n_clips, nullptr, out, out_offsets,
+                  out_status);
+}

@@ -1,6 +1,6 @@
 // Device entry points of the HOST-ONLY build (libafx_host_asan.so, `make asan`): every one fails loudly with
 // AFX_ERR_NO_DEVICE.  The sanitizer build exists to run the host-side parsers and table builders (afx_wav.cpp,
-// afx_tables.cpp, afx_f0_tables.cpp, afx_resample_tables.cpp, afx_filt_host.cpp, afx_beat_host.cpp, afx_assess_host.cpp, afx_host.cpp) under AddressSanitizer + UBSan on the CPU; GPU sanitizers are not
+// afx_tables.cpp, afx_f0_tables.cpp, afx_resample_tables.cpp, afx_filt_host.cpp, afx_beat_host.cpp, afx_assess_host.cpp, afx_cfft_host.cpp, afx_host.cpp) under AddressSanitizer + UBSan on the CPU; GPU sanitizers are not
 // available on the target pool.  Never linked into libafx.so.
 #include <cstddef>
 #include <cstdint>
@@ -94,5 +94,12 @@ int afx_assess_batch(afx_ctx*, const void*, int, int, const int64_t*, const int6
 int afx_compare_batch(afx_ctx*, const void*, const void*, int, int, const int64_t*, const int64_t*, const int64_t*, const int64_t*,
                       int, double*, int32_t*) {
   return no_device("afx_compare_batch");
+}
+int afx_specdist_batch(afx_ctx*, const void*, const void*, int, int, const int64_t*, const int64_t*, const int64_t*, const int64_t*,
+                       int, double*, int32_t*) {
+  return no_device("afx_specdist_batch");
+}
+int afx_clip_fft_batch(afx_ctx*, const void*, int, int, const int64_t*, const int64_t*, int, double*, const int64_t*, int32_t*) {
+  return no_device("afx_clip_fft_batch");
 }
 }

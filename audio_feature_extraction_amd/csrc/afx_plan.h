@@ -12,6 +12,7 @@
 
 #include "afx_assess.h"
 #include "afx_beat.h"
+#include "afx_cfft.h"
 #include "afx_chroma.h"
 #include "afx_decode.h"
 #include "afx_device.h"
@@ -53,6 +54,10 @@ struct afx_ctx {
   // afx_assess_batch / afx_compare_batch: a chunk's records, the pieces (the spans' sums of a pair), the span records, the
   // results and flags, staging of host batches
   DevBuf as_clips, as_pieces, as_spans, as_rec, as_bad, as_in;
+  // afx_specdist_batch / afx_clip_fft_batch: the stage twiddle table (built at first use), a chunk's job records, the
+  // transforms' points, the filter spectra, the results and flags, staging of host batches
+  DevBuf cf_tw, cf_jobs, cf_work, cf_filt, cf_rec, cf_bad, cf_in;
+  bool cf_tw_ready = false;
 };
 
 struct afx_plan {

@@ -9,11 +9,13 @@ data chunks are read natively, decoded and mixed down on the device, and the dec
 
 The scores that judge a noise reducer (audio_quality_assessment.py: ``estimate_snr`` and the ``*_alternative`` scores the
 reference falls back to without pypesq / pystoi): ``estimate_snr``, ``stoi_like``, ``compare_batch``,
-``evaluate_noise_reduction``, from the sums of ``afx_compare_batch``.
+``evaluate_noise_reduction``, from the sums of ``afx_compare_batch``; ``pesq_like``, ``spec_dist`` and their ``_batch``
+forms, whose spectral term is a float64 DFT of the whole clip at whatever length it has (``afx_specdist_batch``: Bluestein's
+algorithm over a power of two).  ``clip_rfft`` / ``clip_rfft_batch`` hand that transform out as ``np.fft.rfft``.
 
-With no GPU visible every function runs libafx's host executors (``afx_assess_host`` / ``afx_compare_host``), the same
-definitions in plain C++.  Not here: the PESQ-like score (its spectral term is an FFT of the whole clip), the real pesq /
-stoi packages, WebM input, plots and reports."""
+With no GPU visible every function runs libafx's host executors (``afx_assess_host`` / ``afx_compare_host`` /
+``afx_specdist_host`` / ``afx_clip_fft_host``), the same definitions in plain C++; so does a clip longer than the device
+transforms (2^21 samples).  Not here: the real pesq / stoi packages, WebM input, plots and reports."""
 from __future__ import annotations
 
 import os
@@ -300,10 +302,135 @@ def estimate_snr(y, *, device: int = 0):
     return assess(y, 16000, device=device)["snr"]       # the noise window does not depend on the rate
 
 
-def evaluate_noise_reduction(y, sr: int, reference=None, *, device: int = 0) -> dict:
+def _pair_clips(pairs, who: str):
+    """The two sides of every pair as float32 (int16 taken as value / 32768), with ``compare_batch``'s refusals: 1-D
+    only, and the two sides of a pair of one sample type."""
+    refs = _clips([p[0] for p in pairs])
+    degs = _clips([p[1] for p in pairs])
+    for i, (r, d) in enumerate(zip(refs, degs)):
+        if r.dtype != d.dtype:
+            raise ValueError(f"{who}: pair {i} mixes int16 and float32")
+    refs = [wavio.to_float32(r, "s16") if r.dtype == np.int16 else r for r in refs]
+    degs = [wavio.to_float32(d, "s16") if d.dtype == np.int16 else d for d in degs]
+    return refs, degs
+
+
+def _specdist_records(refs, degs, device) -> tuple:
+    """(rec [n, SPECDIST_N], status [n]) of float32 pairs: one device call for the pairs the device takes, the host
+    executor for the others (over ``_native.CFFT_MAX_N`` samples) and for all of them when no GPU is visible."""
+    n = len(refs)
+    rec = np.full((n, _native.SPECDIST_N), np.nan, np.float64)
+    status = np.zeros(n, np.int32)
+    gpu = _on_gpu() and hasattr(_native.lib(), "afx_specdist_batch")
+    dev = [i for i in range(n) if gpu and min(refs[i].size, degs[i].size) <= _native.CFFT_MAX_N]
+    for i in sorted(set(range(n)) - set(dev)):
+        r = _native.specdist_host(refs[i], degs[i])
+        rec[i], status[i] = r["rec"], r["status"]
+    if dev:
+        m = [min(refs[i].size, degs[i].size) for i in dev]             # only the common part is sent
+        lens = np.array(m + m, np.int64)
+        both = np.concatenate([refs[i][:k] for i, k in zip(dev, m)] + [degs[i][:k] for i, k in zip(dev, m)]) if sum(m) else np.zeros(1, np.float32)
+        offs = _native.packed_offsets(lens)
+        lock, ctx = _ctx(device)
+        with lock:
+            r = ctx.specdist_batch(both, offs[:len(dev)], lens[:len(dev)], both, offs[len(dev):], lens[len(dev):])
+        rec[dev], status[dev] = r["rec"], r["status"]
+    return rec, status
+
+
+def spec_dist_batch(pairs: Sequence, *, device: int = 0) -> List[float]:
+    """For every (reference, degraded) pair of mono signals, over the shorter length n of the two, the spectral term of the
+    reference's ``calculate_pesq_alternative``: mean over all n bins of ||fft(ref)| - |fft(deg)|| / (|fft(ref)| + 1e-10),
+    the DFTs of the whole clips in float64, whatever n is.  One device pass."""
+    refs, degs = _pair_clips(pairs, "spec_dist_batch")
+    if not refs:
+        return []
+    rec, status = _specdist_records(refs, degs, device)
+    _raise_status("spec_dist_batch", status)
+    return [float(rec[i][1] / rec[i][0]) for i in range(len(refs))]
+
+
+def spec_dist(reference, degraded, *, device: int = 0) -> float:
+    """``spec_dist_batch`` of one pair."""
+    return spec_dist_batch([(reference, degraded)], device=device)[0]
+
+
+def _pesq_from(corr: float, snr, dist: float) -> float:
+    """calculate_pesq_alternative's weighting (:186-199), with Python's min and max as there: a NaN term stays NaN."""
+    snr_score = min(max((snr - 5) / 35, 0), 1)
+    corr_score = max(corr, 0)
+    spec_score = 1 - min(dist, 1)
+    return 1 + 3.5 * (0.4 * snr_score + 0.4 * corr_score + 0.2 * spec_score)
+
+
+def pesq_like_batch(pairs: Sequence, *, device: int = 0) -> List[dict]:
+    """The reference's ``calculate_pesq_alternative`` (what ``calculate_pesq`` computes without the pypesq package, on the
+    signals as they are) for every (reference, degraded) pair, over the shorter length of the two: snr (of the difference;
+    100 when it is zero), correlation, spec_dist and pesq = 1 + 3.5 (0.4 clip((snr - 5) / 35, 0, 1) + 0.4 max(correlation, 0)
+    + 0.2 (1 - min(spec_dist, 1))), in 1 .. 4.5; NaN for a constant input, as the reference's is.  One compare record and
+    one spectral record per pair."""
+    refs, degs = _pair_clips(pairs, "pesq_like_batch")
+    if not refs:
+        return []
+    cmp = compare_batch(list(zip(refs, degs)), device=device)
+    rec, status = _specdist_records(refs, degs, device)
+    _raise_status("pesq_like_batch", status)
+    out = []
+    for i, c in enumerate(cmp):
+        dist = float(rec[i][1] / rec[i][0])
+        out.append({"snr": c["snr"], "correlation": c["correlation"], "spec_dist": dist,
+                    "pesq": _pesq_from(c["correlation"], c["snr"], dist)})
+    return out
+
+
+def pesq_like(reference, degraded, *, device: int = 0) -> float:
+    """The PESQ-like score of one pair (``pesq_like_batch``)."""
+    return pesq_like_batch([(reference, degraded)], device=device)[0]["pesq"]
+
+
+def clip_rfft_batch(clips: Sequence, *, device: int = 0) -> List[np.ndarray]:
+    """``np.fft.rfft`` of every mono clip (float32, or int16 taken as value / 32768) in float64, whatever its length -- a
+    prime, 220500 = 2^2 3^2 5^3 7^2 -- as complex128 arrays of len // 2 + 1 bins (no bins for an empty clip).  One device
+    pass; clips over ``_native.CFFT_MAX_N`` samples go through the host executor."""
+    clips = _clips(clips)
+    n = len(clips)
+    out: List[Optional[np.ndarray]] = [None] * n
+    status = np.zeros(n, np.int32)
+    gpu = _on_gpu() and hasattr(_native.lib(), "afx_clip_fft_batch")
+    for i, c in enumerate(clips):
+        if not gpu or c.size > _native.CFFT_MAX_N:
+            r = _native.clip_fft_host(c)
+            out[i], status[i] = r["bins"], r["status"]
+    if gpu:
+        lock, ctx = _ctx(device)
+        for dt in (np.int16, np.float32):
+            idx = [i for i, c in enumerate(clips) if c.dtype == dt and out[i] is None]
+            if not idx:
+                continue
+            lens = np.array([clips[i].size for i in idx], np.int64)
+            buf = np.concatenate([clips[i] for i in idx]) if lens.sum() else np.zeros(1, dt)
+            with lock:
+                r = ctx.clip_fft_batch(buf, _native.packed_offsets(lens), lens)
+            for k, i in enumerate(idx):
+                out[i] = r["bins"][r["offsets"][k]:r["offsets"][k] + r["counts"][k]].copy()
+                status[i] = r["status"][k]
+    bad = np.flatnonzero(status == _native.CLIP_NONFINITE)
+    if bad.size:
+        raise ValueError(f"clip_rfft_batch: signal {int(bad[0])} is not finite everywhere")
+    return out
+
+
+def clip_rfft(y, *, device: int = 0) -> np.ndarray:
+    """``np.fft.rfft(y)`` of one whole clip in float64 (``clip_rfft_batch``)."""
+    return clip_rfft_batch([y], device=device)[0]
+
+
+def evaluate_noise_reduction(y, sr: int, reference=None, *, pesq: bool = False, device: int = 0) -> dict:
     """The reference's ``evaluate_audio_quality`` on an in-memory signal: ``effects.spectral_subtraction`` and
     ``effects.wiener_filter`` at their defaults, then {original, spectral_subtraction, wiener_filter} x {snr, stoi}, each
-    STOI-like score against ``reference`` (default: the original itself, as the reference does without a teacher file)."""
+    STOI-like score against ``reference`` (default: the original itself, as the reference does without a teacher file).
+    ``pesq=True``: each entry is the reference's {snr, pesq, stoi}, pesq the PESQ-like score (``pesq_like``) against the
+    same reference; the three pairs have one length, so their transforms share one filter spectrum."""
     from . import effects
     y = np.ascontiguousarray(y, np.float32)
     ref = y if reference is None else np.ascontiguousarray(reference, np.float32)
@@ -312,4 +439,7 @@ def evaluate_noise_reduction(y, sr: int, reference=None, *, device: int = 0) -> 
     names = list(outs)
     snr = assess_batch([outs[k] for k in names], sr, device=device)
     sc = compare_batch([(ref, outs[k]) for k in names], device=device)
-    return {k: {"snr": snr[i]["snr"], "stoi": sc[i]["stoi"]} for i, k in enumerate(names)}
+    if not pesq:
+        return {k: {"snr": snr[i]["snr"], "stoi": sc[i]["stoi"]} for i, k in enumerate(names)}
+    pq = pesq_like_batch([(ref, outs[k]) for k in names], device=device)
+    return {k: {"snr": snr[i]["snr"], "pesq": pq[i]["pesq"], "stoi": sc[i]["stoi"]} for i, k in enumerate(names)}

@@ -711,6 +711,47 @@ int afx_compare_batch(afx_ctx* ctx, const void* ref, const void* deg, int sample
                       const int64_t* ref_offsets, const int64_t* ref_lengths, const int64_t* deg_offsets,
                       const int64_t* deg_lengths, int n_pairs, double* out_rec /*[n_pairs][AFX_COMPARE_N]*/, int32_t* out_status);
 
+/* The DFT of a whole clip, of any length, in float64, and the third term of the reference's PESQ-like score
+ * (audio_quality_assessment.py:150-201, calculate_pesq_alternative): spec_dist = mean_k(| |R_k| - |D_k| | / (|R_k| + 1e-10))
+ * over all N bins of R = np.fft.fft(reference), D = np.fft.fft(degraded).  All five symbols are newer than AFX_VERSION 107
+ * says: a binding detects them by their presence.
+ *
+ * The transform is Bluestein's algorithm over the power of two M >= 2 N - 1: the chirp exp(-i pi k^2 / N) with its phase
+ * reduced in integers (k^2 mod 2 N), three radix-2 transforms of M points in float64, the spectrum of the chirp filter
+ * computed once per distinct N of a chunk.  N <= AFX_CFFT_MAX_N = 2^21 samples on the device (AFX_ERR_UNSUPPORTED above:
+ * nothing is computed); the host executors take up to 2^27.
+ *
+ * afx_specdist_batch: the pairs of afx_compare_batch (same arguments; n = min of the two lengths).  The two real signals
+ * of a pair go through ONE transform, Z = DFT(r + i d), R_k = (Z_k + conj Z_{N-k}) / 2, D_k = (Z_k - conj Z_{N-k}) / 2i.
+ * out_rec holds AFX_SPECDIST_N doubles per pair: n, sum_k | |R_k| - |D_k| | / (|R_k| + 1e-10), sum_k |R_k|^2,
+ * sum_k |D_k|^2 (Parseval: sum_k |R_k|^2 = n sum r^2), each over all n bins in an order that depends on n alone.  A pair
+ * whose sides are equal sample for sample has D = R by definition, not to rounding: its distance is exactly 0, as numpy's is.
+ * out_status (host): AFX_CLIP_TOO_SHORT for n == 0, AFX_CLIP_NONFINITE for a NaN / inf sample; the record of a failed pair is
+ * NaN and no other pair is affected.  No atomics: a record is bit-reproducible and depends neither on the rest of the batch,
+ * nor on the pair's place in it or in the buffer, nor on how the batch is cut into chunks (afx_stft_chunks with the record
+ * of afx_specdist_cost).
+ *
+ * afx_clip_fft_batch: np.fft.rfft of clip i = samples[offsets[i] .. + lengths[i]): bins 0 .. N / 2 as interleaved float64
+ * (re, im) at out[2 out_offsets[i] ..) in host memory, 2 (N / 2 + 1) doubles (NaN for a clip with a NaN / inf sample;
+ * nothing is written for length 0).  The same transform with a zero imaginary part.
+ *
+ * afx_specdist_host / afx_clip_fft_host (host-only): one pair / one clip through the same definitions in plain C++ -- the
+ * specification of the kernels; they agree with them to rounding.
+ * afx_specdist_cost (host-only): cost[6] for afx_stft_chunks (bytes per frame, tile, sample, clip; frames per tile, most
+ * tiles).  M < 4 n, so the work and the filter spectrum (counted for every pair, though pairs of one n share it) are
+ * bounded by 128 bytes a sample, plus the uploads of both sides; 256 per pair. */
+enum { AFX_SPECDIST_N = 4 };
+#define AFX_CFFT_MAX_N (1 << 21)
+int afx_specdist_cost(int sample_fmt, int mem_kind, int64_t* cost /*[6]*/);
+int afx_specdist_host(const void* ref, const void* deg, int sample_fmt, int64_t n_ref, int64_t n_deg,
+                      double* out_rec /*[AFX_SPECDIST_N]*/, int32_t* out_status);
+int afx_clip_fft_host(const void* samples, int sample_fmt, int64_t n, double* out /*[2 * (n / 2 + 1)]*/, int32_t* out_status);
+int afx_specdist_batch(afx_ctx* ctx, const void* ref, const void* deg, int sample_fmt, int mem_kind,
+                       const int64_t* ref_offsets, const int64_t* ref_lengths, const int64_t* deg_offsets,
+                       const int64_t* deg_lengths, int n_pairs, double* out_rec /*[n_pairs][AFX_SPECDIST_N]*/, int32_t* out_status);
+int afx_clip_fft_batch(afx_ctx* ctx, const void* samples, int sample_fmt, int mem_kind, const int64_t* offsets,
+                       const int64_t* lengths, int n_clips, double* out, const int64_t* out_offsets, int32_t* out_status);
+
 /* Host-only (no device needed): the real FFT the frame kernel of the frame lengths that are not powers of two runs
  * (k_frames_mr), executed in float32 on the CPU with the same radix schedule, twiddle tables and operation order:
  * n_fft / 2 complex points through Stockham passes of radix 3, 5, 4, 8, then the real-FFT split.  out holds the
