@@ -51,6 +51,10 @@ COST_ASSESS, COST_COMPARE = 0, 1                                             # a
 SPECDIST_N = 4                                                               # doubles per record of afx_specdist_batch
 SPECDIST_FIELDS = ("n", "sum_dist", "sum_rr", "sum_dd")
 CFFT_MAX_N = 1 << 21                                                         # samples of a clip the device transforms
+EZ_PREPROCESS, EZ_ENERGY, EZ_ZCR = 1, 2, 4                                    # afx_energy_zcr_batch: its flags
+EZ_N = 12                                                                    # doubles per clip of its record
+EZ_FIELDS = ("T", "fl", "hop", "energy_mean", "energy_std", "energy_p10", "zcr_mean", "zcr_std", "zcr_local_stability",
+             "peak_smooth", "peak_in", "peak_filt")
 GROUPS_STATS = 24                                                            # doubles per clip of its record
 K_NAMES = ("trim_blocks", "trim_decide", "frames", "dct", "stats")
 K_FRAMES = 2
@@ -72,6 +76,8 @@ SYMBOLS = (
     "afx_denoise_batch", "afx_denoise_cost",
     "afx_assess_batch", "afx_compare_batch", "afx_assess_host", "afx_compare_host", "afx_assess_cost",
     "afx_specdist_batch", "afx_clip_fft_batch", "afx_specdist_host", "afx_clip_fft_host", "afx_specdist_cost",
+    "afx_smooth_geometry", "afx_savgol_tables", "afx_medfilt_host", "afx_savgol_host", "afx_energy_zcr_host",
+    "afx_medfilt_batch", "afx_savgol_batch", "afx_energy_zcr_batch",
 )
 
 
@@ -188,6 +194,16 @@ def lib() -> C.CDLL:
             L.afx_clip_fft_host.argtypes = [vp, i32, C.c_int64, vp, vp]
             L.afx_specdist_batch.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp, vp, i32, vp, vp]
             L.afx_clip_fft_batch.argtypes = [vp, vp, i32, i32, vp, vp, i32, vp, vp, vp]
+        if hasattr(L, "afx_medfilt_batch"):                  # newer than version 107 says: found by their presence
+            dbl = C.c_double
+            L.afx_smooth_geometry.argtypes = [vp]
+            L.afx_savgol_tables.argtypes = [i32, i32, i32, dbl, vp, vp, vp]
+            L.afx_medfilt_host.argtypes = [vp, i32, C.c_int64, i32, vp, vp]
+            L.afx_savgol_host.argtypes = [vp, i32, C.c_int64, i32, i32, i32, dbl, vp, vp]
+            L.afx_energy_zcr_host.argtypes = [vp, C.c_int64, i32, i32, i32, vp, vp]
+            L.afx_medfilt_batch.argtypes = [vp, vp, i32, i32, vp, vp, i32, i32, vp, i32, vp, vp]
+            L.afx_savgol_batch.argtypes = [vp, vp, i32, i32, vp, vp, i32, i32, i32, i32, dbl, vp, i32, vp, vp]
+            L.afx_energy_zcr_batch.argtypes = [vp, vp, i32, i32, vp, vp, i32, i32, i32, i32, i32, vp, vp]
         if hasattr(L, "afx_rfft_host"):                      # absent from a library built before the mixed-radix lengths
             L.afx_rfft_host.argtypes = [i32, vp, vp]
         _lib = L
@@ -551,6 +567,69 @@ def sosfiltfilt_host(x, sos, padlen: int, mode: int = FILT_PLAIN, preemph: float
     return {"out": out, "peak": peak, "status": int(status[0])}
 
 
+def _need_smooth():
+    if not hasattr(lib(), "afx_medfilt_batch"):
+        raise NotImplementedError("this libafx has no afx_medfilt_batch")
+
+
+def smooth_geometry() -> dict:
+    """Host-only: the tile of afx_medfilt_batch / afx_savgol_batch (samples a workgroup stages) and their bounds."""
+    _need_smooth()
+    info = np.zeros(4, np.int32)
+    _check(lib().afx_smooth_geometry(info.ctypes.data), "afx_smooth_geometry")
+    return {"tile": int(info[0]), "max_window": int(info[1]), "max_polyorder": int(info[2]), "max_deriv": int(info[3])}
+
+
+def savgol_tables(window_length: int, polyorder: int, deriv: int = 0, delta: float = 1.0) -> dict:
+    """Host-only: afx_savgol_tables.  coeffs [W] (scipy.signal.savgol_coeffs' order), left / right [W // 2, W]: the first /
+    last W // 2 outputs as weights over the first / last W samples."""
+    _need_smooth()
+    W = max(int(window_length), 1)
+    coeffs, left, right = np.zeros(W, np.float64), np.zeros((W // 2, W), np.float64), np.zeros((W // 2, W), np.float64)
+    _check(lib().afx_savgol_tables(int(window_length), int(polyorder), int(deriv), float(delta), coeffs.ctypes.data,
+                                   left.ctypes.data, right.ctypes.data), "afx_savgol_tables")
+    return {"coeffs": coeffs, "left": left, "right": right}
+
+
+def medfilt_host(x, kernel_size: int = 3) -> dict:
+    """Host-only: afx_medfilt_host, one int16 / float32 clip through the kernels' median on the CPU.  Returns out (float32;
+    zeros when the clip failed) and status."""
+    _need_smooth()
+    x = _mono_clip(x, "x")
+    out = np.zeros(x.size, np.float32)
+    status = np.zeros(1, np.int32)
+    _check(lib().afx_medfilt_host(x.ctypes.data, FMT_S16 if x.dtype == np.int16 else FMT_F32, int(x.size), int(kernel_size),
+                                  out.ctypes.data, status.ctypes.data), "afx_medfilt_host")
+    return {"out": out, "status": int(status[0])}
+
+
+def savgol_host(x, window_length: int, polyorder: int, deriv: int = 0, delta: float = 1.0) -> dict:
+    """Host-only: afx_savgol_host, one int16 / float32 clip through the kernels' fused chains on the CPU.  Returns out
+    (float32; zeros when the clip failed) and status."""
+    _need_smooth()
+    x = _mono_clip(x, "x")
+    out = np.zeros(x.size, np.float32)
+    status = np.zeros(1, np.int32)
+    _check(lib().afx_savgol_host(x.ctypes.data, FMT_S16 if x.dtype == np.int16 else FMT_F32, int(x.size), int(window_length),
+                                 int(polyorder), int(deriv), float(delta), out.ctypes.data, status.ctypes.data),
+           "afx_savgol_host")
+    return {"out": out, "status": int(status[0])}
+
+
+def energy_zcr_host(y, frame_length: int = 2048, hop_length: int = 512, flags: int = EZ_ENERGY | EZ_ZCR) -> dict:
+    """Host-only: afx_energy_zcr_host, one float32 clip (already preprocessed) through the operations of
+    afx_energy_zcr_batch on the CPU.  Returns rec (float64 [EZ_N]; EZ_FIELDS names the entries) and status."""
+    _need_smooth()
+    y = np.ascontiguousarray(y)
+    if y.ndim != 1 or y.dtype != np.float32:
+        raise ValueError("y must be a one-dimensional float32 array")
+    rec = np.zeros(EZ_N, np.float64)
+    status = np.zeros(1, np.int32)
+    _check(lib().afx_energy_zcr_host(y.ctypes.data, int(y.size), int(frame_length), int(hop_length), int(flags),
+                                     rec.ctypes.data, status.ctypes.data), "afx_energy_zcr_host")
+    return {"rec": rec, "status": int(status[0])}
+
+
 def beat_track_host(env, fps: float, bpm: float, tightness: float = 100.0, trim: bool = True) -> dict:
     """Host-only: afx_beat_track_host, one float32 onset envelope through the beat tracker's definition in float64 on the
     CPU.  Returns beats (int64 frames), mask (uint8 [T]), localscore, cumscore (float64 [T]) and backlink (int32 [T])."""
@@ -911,6 +990,70 @@ class Context(_Owner):
                                            optr, okind, out_offsets.ctypes.data, peak.ctypes.data, status.ctypes.data),
                "afx_sosfiltfilt_batch")
         return {"out": out, "offsets": out_offsets, "peak": peak, "status": status}
+
+    def _smooth_out(self, lengths, n, out, out_offsets):
+        """-> (out, out_offsets, pointer, memory kind) of a filter whose outputs have their inputs' lengths (resample_batch's
+        conventions for ``out`` and ``out_offsets``)"""
+        if out_offsets is None:
+            out_offsets = packed_offsets(np.maximum(lengths, 0), 4)
+        out_offsets = np.ascontiguousarray(out_offsets, np.int64).reshape(-1)
+        if out_offsets.shape[0] != n:
+            raise ValueError("out_offsets must have one entry per clip")
+        need = int((out_offsets + np.maximum(lengths, 0)).max()) if n else 0
+        if out is None:
+            out = np.zeros(need, np.float32)
+        if isinstance(out, np.ndarray):
+            if out.dtype != np.float32 or not out.flags.c_contiguous or out.size < need:
+                raise ValueError("out must be a C-contiguous float32 array that holds every clip")
+            return out, out_offsets, out.ctypes.data, MEM_HOST
+        if isinstance(out, DeviceBuffer) and out.nbytes < 4 * need:
+            raise ValueError("the output DeviceBuffer is too small")
+        return out, out_offsets, (out.ptr if isinstance(out, DeviceBuffer) else int(out)), MEM_DEVICE
+
+    def medfilt_batch(self, samples, offsets, lengths, kernel_size: int = 3, fmt=None, out=None, out_offsets=None) -> dict:
+        """afx_medfilt_batch: scipy.signal.medfilt(x, kernel_size) of the clips samples[offsets[i] .. + lengths[i]), float32
+        out.  ``samples``, ``out``, ``out_offsets``: as sosfiltfilt_batch.  Returns out, offsets and status; the output range
+        of a clip whose status is not CLIP_OK (empty, or not finite) is not written."""
+        _need_smooth()
+        offsets, lengths, n = _clip_arrays(offsets, lengths)
+        fmt = _sample_fmt(samples, fmt)
+        sptr, kind = _sample_source(samples, fmt, offsets, lengths)
+        out, out_offsets, optr, okind = self._smooth_out(lengths, n, out, out_offsets)
+        status = np.zeros(n, np.int32)
+        _check(lib().afx_medfilt_batch(self.handle, sptr, int(fmt), kind, offsets.ctypes.data, lengths.ctypes.data, n,
+                                       int(kernel_size), optr, okind, out_offsets.ctypes.data, status.ctypes.data),
+               "afx_medfilt_batch")
+        return {"out": out, "offsets": out_offsets, "status": status}
+
+    def savgol_batch(self, samples, offsets, lengths, window_length: int, polyorder: int, deriv: int = 0, delta: float = 1.0,
+                     fmt=None, out=None, out_offsets=None) -> dict:
+        """afx_savgol_batch: scipy.signal.savgol_filter(x, window_length, polyorder, deriv, delta, mode='interp') of the
+        clips, float32 out; otherwise as medfilt_batch (a clip shorter than the window is CLIP_TOO_SHORT)."""
+        _need_smooth()
+        offsets, lengths, n = _clip_arrays(offsets, lengths)
+        fmt = _sample_fmt(samples, fmt)
+        sptr, kind = _sample_source(samples, fmt, offsets, lengths)
+        out, out_offsets, optr, okind = self._smooth_out(lengths, n, out, out_offsets)
+        status = np.zeros(n, np.int32)
+        _check(lib().afx_savgol_batch(self.handle, sptr, int(fmt), kind, offsets.ctypes.data, lengths.ctypes.data, n,
+                                      int(window_length), int(polyorder), int(deriv), float(delta), optr, okind,
+                                      out_offsets.ctypes.data, status.ctypes.data), "afx_savgol_batch")
+        return {"out": out, "offsets": out_offsets, "status": status}
+
+    def energy_zcr_batch(self, samples, offsets, lengths, sr: int, frame_length: int = 2048, hop_length: int = 512,
+                         flags: int = EZ_PREPROCESS | EZ_ENERGY | EZ_ZCR, fmt=None) -> dict:
+        """afx_energy_zcr_batch: the experiment extractor's energy and ZCR groups of the clips at rate ``sr``.  Returns rec
+        (float64 [n, EZ_N]; EZ_FIELDS names the entries; NaN for a group not asked for and for a failed clip) and status."""
+        _need_smooth()
+        offsets, lengths, n = _clip_arrays(offsets, lengths)
+        fmt = _sample_fmt(samples, fmt)
+        sptr, kind = _sample_source(samples, fmt, offsets, lengths)
+        rec = np.zeros((n, EZ_N), np.float64)
+        status = np.zeros(n, np.int32)
+        _check(lib().afx_energy_zcr_batch(self.handle, sptr, int(fmt), kind, offsets.ctypes.data, lengths.ctypes.data, n,
+                                          int(sr), int(frame_length), int(hop_length), int(flags), rec.ctypes.data,
+                                          status.ctypes.data), "afx_energy_zcr_batch")
+        return {"rec": rec, "status": status}
 
     def decode_batch(self, raw, byte_offsets, frames, kinds, channels, out=None, out_offsets=None) -> dict:
         """afx_decode_batch: raw WAVE data -> mono float32, bit for bit wavio.to_mono(wavio.to_float32(...)).  Clip i is

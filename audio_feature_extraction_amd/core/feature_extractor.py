@@ -510,6 +510,107 @@ class AudioFeatureExtractor:
                 d["filename"] = os.path.basename(p)
         return res
 
+    # ------------------------------------------------------------------ the experiment's energy and ZCR groups
+    _ENERGY_KEYS = ("energy_mean", "energy_std", "energy_cv", "energy_snr", "energy_range_valid", "energy_stability",
+                    "energy_snr_valid", "energy_quality_score")
+    _ZCR_KEYS = ("zcr_mean", "zcr_std", "zcr_cv", "zcr_local_stability", "zcr_range_valid", "zcr_stability",
+                 "zcr_local_stable", "zcr_quality_score")
+
+    @classmethod
+    def _energy_dict(cls, rec: np.ndarray) -> Dict[str, Any]:
+        """The energy group's dict from a record of afx_energy_zcr_batch: thresholds and score of
+        04_feature_extraction_experiment/feature_extractor.py:367-399."""
+        i = _native.EZ_FIELDS.index
+        mean, std, floor = float(rec[i("energy_mean")]), float(rec[i("energy_std")]), float(rec[i("energy_p10")])
+        cv = std / mean if mean != 0 else float("inf")
+        snr = 20 * float(np.log10(mean / floor)) if floor > 0 else 0
+        range_valid = bool(5.67e-03 <= mean <= 2.62e+00)
+        stability = bool(cv <= 0.3)
+        snr_valid = bool(snr >= 20)
+        score = 1.0
+        for ok in (range_valid, stability, snr_valid):
+            if not ok:
+                score -= 0.3
+        return dict(zip(cls._ENERGY_KEYS, (mean, std, cv, snr, range_valid, stability, snr_valid, max(0.0, score))))
+
+    @classmethod
+    def _zcr_dict(cls, rec: np.ndarray) -> Dict[str, Any]:
+        """The ZCR group's dict from a record of afx_energy_zcr_batch: thresholds and score of :444-480."""
+        i = _native.EZ_FIELDS.index
+        mean, std, local = float(rec[i("zcr_mean")]), float(rec[i("zcr_std")]), float(rec[i("zcr_local_stability")])
+        cv = std / mean if mean != 0 else float("inf")
+        range_valid = bool(0.034 <= mean <= 0.491)
+        stability = bool(cv <= 0.35)
+        local_stable = bool(local <= 0.1)
+        score = 1.0
+        for ok, cost in ((range_valid, 0.4), (stability, 0.3), (local_stable, 0.3)):
+            if not ok:
+                score -= cost
+        return dict(zip(cls._ZCR_KEYS, (mean, std, cv, local, range_valid, stability, local_stable, max(0.0, score))))
+
+    @classmethod
+    def _energy_zcr_dicts(cls, flags: int, rec: np.ndarray, status: np.ndarray) -> List[Optional[Dict[str, Any]]]:
+        out: List[Optional[Dict[str, Any]]] = []
+        for r, st in zip(rec, status):
+            if st != _native.CLIP_OK:
+                out.append(None)
+                continue
+            d: Dict[str, Any] = {}
+            if flags & _native.EZ_ENERGY:
+                d.update(cls._energy_dict(r))
+            if flags & _native.EZ_ZCR:
+                d.update(cls._zcr_dict(r))
+            out.append(d)
+        return out
+
+    def _energy_zcr(self, signals: Sequence[np.ndarray], flags: int, frame_length: int, hop_length: int):
+        ys = [np.ascontiguousarray(y, dtype=np.float32) for y in signals]
+        for y in ys:
+            if y.ndim != 1:
+                raise ValueError(f"signals must be 1-D (mono), got shape {y.shape}")
+        if frame_length < 64 or frame_length > 2048 or frame_length & (frame_length - 1):
+            raise ValueError("frame_length must be a power of two in [64, 2048]")
+        if hop_length < 1:
+            raise ValueError("hop_length must be positive")
+        if not ys:
+            return None
+        from .. import filters
+        lengths = np.array([y.size for y in ys], np.int64)
+        return filters._ctx(self._devices()[0]).energy_zcr_batch(np.concatenate(ys), _native.packed_offsets(lengths), lengths,
+                                                                 self.sr, frame_length, hop_length, flags)
+
+    def extract_energy_zcr_features_batch(self, signals: Sequence[np.ndarray], *, preprocess: bool = True,
+                                          frame_length: int = 2048, hop_length: int = 512) -> List[Optional[Dict[str, Any]]]:
+        """The energy group (04_feature_extraction_experiment/feature_extractor.py:341-403) and the ZCR group (:405-483) of
+        the experiment extractor for many signals at this extractor's ``sr`` in one device pass: its ``preprocess_audio``,
+        ``librosa.feature.rms``, and ``medfilt(3)`` -> ``savgol_filter(11, 3)`` -> peak normalisation ->
+        ``zero_crossing_rate``; one upload, scalars back.  ``frame_length`` / ``hop_length`` default to that class's 2048 /
+        512 and are adjusted per clip as its ``_adjust_frame_length`` does.  The dict holds the reference's sixteen keys,
+        energy first.  ``None`` for a clip the reference returns None for (18 samples or fewer, or a NaN / inf sample;
+        without the preprocess, an empty or non-finite clip)."""
+        flags = _native.EZ_ENERGY | _native.EZ_ZCR | (_native.EZ_PREPROCESS if preprocess else 0)
+        out = self._energy_zcr(signals, flags, frame_length, hop_length)
+        return [] if out is None else self._energy_zcr_dicts(flags, out["rec"], out["status"])
+
+    def _one_energy_zcr(self, y: np.ndarray, group: int, what: str) -> Dict[str, Any]:
+        flags = group | _native.EZ_PREPROCESS
+        out = self._energy_zcr([y], flags, 2048, 512)
+        if out["status"][0] == _native.CLIP_TOO_SHORT:           # what the reference's filtfilt raises and its caller logs
+            raise ValueError(f"The length of the input vector x must be greater than padlen, which is 18. ({what})")
+        if out["status"][0] != _native.CLIP_OK:
+            raise _status_error(int(out["status"][0]), what, int(np.size(y)))
+        return self._energy_zcr_dicts(flags, out["rec"], out["status"])[0]
+
+    def extract_energy_features(self, y: np.ndarray) -> Dict[str, Any]:
+        """The experiment extractor's ``extract_energy`` (:341-403) of one signal, its preprocess included; raises
+        ``ValueError`` where the reference returns None."""
+        return self._one_energy_zcr(y, _native.EZ_ENERGY, "extract_energy_features")
+
+    def extract_zcr_features(self, y: np.ndarray) -> Dict[str, Any]:
+        """The experiment extractor's ``extract_zcr`` (:405-483) of one signal, its preprocess included; raises
+        ``ValueError`` where the reference returns None."""
+        return self._one_energy_zcr(y, _native.EZ_ZCR, "extract_zcr_features")
+
     def preprocess_experiment_batch(self, signals: Sequence[np.ndarray]) -> List[Optional[np.ndarray]]:
         """``preprocess_experiment`` of many signals in one device pass; ``None`` for a clip the reference's
         ``preprocess_audio`` returns None for (18 samples or fewer, or not finite)."""

@@ -49,6 +49,7 @@ DevEnv::DevEnv() {
   if (const char* v = getenv("AFX_TEST_FILT_BUDGET")) filt_budget = std::max<int64_t>(1, atoll(v));
   if (const char* v = getenv("AFX_TEST_ASSESS_BUDGET")) assess_budget = std::max<int64_t>(1, atoll(v));
   if (const char* v = getenv("AFX_TEST_SPECDIST_BUDGET")) specdist_budget = std::max<int64_t>(1, atoll(v));
+  if (const char* v = getenv("AFX_TEST_SMOOTH_BUDGET")) smooth_budget = std::max<int64_t>(1, atoll(v));
   f0_dump = getenv("AFX_F0_DUMP");
 }
 const DevEnv& dev_env() { static const DevEnv e; return e; }
@@ -83,7 +84,8 @@ extern "C" void afx_destroy(afx_ctx* ctx) {
                     &ctx->rs_in, &ctx->rs_out, &ctx->dc_clips, &ctx->dc_in, &ctx->dc_out, &ctx->ft_tab, &ctx->ft_clips, &ctx->ft_st,
                     &ctx->ft_w, &ctx->ft_carry, &ctx->ft_tmax, &ctx->ft_in, &ctx->ft_out, &ctx->as_clips, &ctx->as_pieces, &ctx->as_spans,
                     &ctx->as_rec, &ctx->as_bad, &ctx->as_in, &ctx->cf_tw, &ctx->cf_jobs, &ctx->cf_work, &ctx->cf_filt, &ctx->cf_rec,
-                    &ctx->cf_bad, &ctx->cf_in})
+                    &ctx->cf_bad, &ctx->cf_in, &ctx->sm_tab, &ctx->sm_clips, &ctx->sm_bad, &ctx->sm_in, &ctx->sm_out, &ctx->ez_clips,
+                    &ctx->ez_y, &ctx->ez_m, &ctx->ez_s, &ctx->ez_neg, &ctx->ez_peak, &ctx->ez_energy, &ctx->ez_rate, &ctx->ez_rec})
     release(*b);
   if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
   delete ctx;

@@ -2,6 +2,7 @@
 // conversion / mix-down of raw WAVE data.
 #include <algorithm>
 #include <cmath>
+#include <cstddef>
 #include <cstdlib>
 #include <cstring>
 #include <numeric>
@@ -894,4 +895,338 @@ extern "C" int afx_clip_fft_batch(afx_ctx* ctx, const void* samples, int sample_
   if (!samples || !out) { set_error(std::string(who) + ": null samples or output"); return AFX_ERR_INVALID; }
   return cfft_run(who, ctx, samples, nullptr, sample_fmt, mem_kind, offsets, nullptr, lengths, n_clips, nullptr, out, out_offsets,
                   out_status);
+}
+
+// ---- scipy.signal.medfilt / savgol_filter on samples, and the experiment extractor's energy and ZCR groups ----------------
+// What a clip of n samples costs a chunk of the three entry points below, in device bytes (the chunk rule of
+// afx_sosfiltfilt_batch: as many clips as the budget holds, at least one).
+struct SmoothCost {
+  int64_t per_sample = 0;        // staging of host samples and of a host result, the workspace signals
+  int64_t per_frame = 0;         // the frame rows of the groups
+  int64_t per_filt_tile = 0;     // the preprocess's workspace
+  int64_t per_clip = 0;          // records, flags, results
+  int64_t of(int64_t n, int64_t frames, int64_t filt_tiles) const {
+    return per_sample * ((n + 3) / 4 * 4) + per_frame * frames + per_filt_tile * filt_tiles + per_clip;
+  }
+};
+constexpr int kSmoothMaxClips = 1 << 20;       // records of a chunk
+constexpr int64_t kSmoothMaxTiles = 1 << 24;   // workgroups of a launch
+
+// The body of afx_medfilt_batch (tab == nullptr: the median of K) and afx_savgol_batch (tab: its tables): clips of min_n
+// samples or more, chunk by chunk -- the samples staged packed when they are the host's, the records uploaded, the
+// non-finite check and the filter launched, the result copied back when it is the host's.
+static int smooth_run(const char* who, afx_ctx* ctx, const void* samples, int sample_fmt, int mem_kind, const int64_t* offsets,
+                      const int64_t* lengths, int n_clips, int K, const SgTab* tab, int64_t min_n, float* out, int out_mem_kind,
+                      const int64_t* out_offsets, int32_t* out_status) {
+  int rc;
+  bool any = false;
+  for (int i = 0; i < n_clips; ++i) {
+    const bool live = lengths[i] >= min_n;
+    out_status[i] = live ? AFX_CLIP_OK : AFX_CLIP_TOO_SHORT;
+    any = any || live;
+  }
+  if (!any) return AFX_OK;
+  if (!samples || !out) { set_error(std::string(who) + ": null samples / out"); return AFX_ERR_INVALID; }
+  (void)hipGetLastError();
+  HIP_TRY(hipSetDevice(ctx->device));
+  hipStream_t s = ctx->stream;
+  if (tab) {
+    if ((rc = ensure(ctx->sm_tab, sizeof(SgTab))) != AFX_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(ctx->sm_tab.p, tab, sizeof(SgTab), hipMemcpyHostToDevice, s));
+  }
+  const size_t esz = sample_fmt == AFX_FMT_S16 ? 2 : 4;
+  const bool h_in = mem_kind == AFX_MEM_HOST, h_out = out_mem_kind == AFX_MEM_HOST;
+  SmoothCost cost;
+  cost.per_sample = (h_in ? (int64_t)esz : 0) + (h_out ? 4 : 0);
+  cost.per_clip = (int64_t)sizeof(SmClip) + 4;
+  const int64_t budget = dev_env().smooth_budget;
+  std::vector<SmClip> recs;
+  std::vector<int> idx;
+  std::vector<uint32_t> h_bad;
+  std::vector<char> stage_in;
+  std::vector<float> stage_out;
+  for (int c0 = 0; c0 < n_clips;) {
+    recs.clear(); idx.clear();
+    int64_t bytes = 0, tiles = 0, in_pos = 0, out_pos = 0;
+    int c1 = c0;
+    for (; c1 < n_clips; ++c1) {
+      const int64_t n = lengths[c1];
+      if (n < min_n) continue;
+      const int64_t nt = (n + kSmTile - 1) / kSmTile, cb = cost.of(n, 0, 0);
+      if (!recs.empty() && (bytes + cb > budget || tiles + nt > kSmoothMaxTiles || (int)recs.size() >= kSmoothMaxClips)) break;
+      SmClip r{};
+      r.n = n;
+      r.in_off = h_in ? in_pos : offsets[c1];
+      r.out_off = h_out ? out_pos : out_offsets[c1];
+      r.first_tile = (int32_t)tiles; r.n_tiles = (int32_t)nt;
+      recs.push_back(r); idx.push_back(c1);
+      bytes += cb; tiles += nt;
+      in_pos += (n + 3) / 4 * 4; out_pos += (n + 3) / 4 * 4;
+    }
+    c0 = c1;
+    if (recs.empty()) break;
+    if (tiles > kSmoothMaxTiles) { set_error(std::string(who) + ": clip too large for one launch"); return AFX_ERR_UNSUPPORTED; }
+    const int n = (int)recs.size(), nt = (int)tiles;
+    if ((rc = ensure(ctx->sm_clips, n * sizeof(SmClip))) != AFX_OK) return rc;
+    if ((rc = ensure(ctx->sm_bad, n * sizeof(uint32_t))) != AFX_OK) return rc;
+    const void* d_in = samples;
+    if (h_in) {
+      stage_in.assign((size_t)in_pos * esz, 0);
+      for (int q = 0; q < n; ++q)
+        std::memcpy(stage_in.data() + (size_t)recs[q].in_off * esz, (const char*)samples + (size_t)offsets[idx[q]] * esz, (size_t)recs[q].n * esz);
+      if ((rc = ensure(ctx->sm_in, stage_in.size())) != AFX_OK) return rc;
+      HIP_TRY(hipMemcpyAsync(ctx->sm_in.p, stage_in.data(), stage_in.size(), hipMemcpyHostToDevice, s));
+      d_in = ctx->sm_in.p;
+    }
+    float* d_out = out;
+    if (h_out) {
+      if ((rc = ensure(ctx->sm_out, (size_t)out_pos * sizeof(float))) != AFX_OK) return rc;
+      d_out = (float*)ctx->sm_out.p;
+    }
+    HIP_TRY(hipMemcpyAsync(ctx->sm_clips.p, recs.data(), n * sizeof(SmClip), hipMemcpyHostToDevice, s));
+    const SmClip* d_clips = (const SmClip*)ctx->sm_clips.p;
+    uint32_t* d_bad = (uint32_t*)ctx->sm_bad.p;
+    HIP_TRY(launch_sm_check(s, d_in, sample_fmt, d_clips, n, d_bad));
+    if (tab) HIP_TRY(launch_savgol(s, d_in, sample_fmt, (const SgTab*)ctx->sm_tab.p, 0, d_clips, n, nt, d_bad, 1, d_out));
+    else HIP_TRY(launch_medfilt(s, d_in, sample_fmt, K, d_clips, n, nt, d_bad, 1, d_out));
+    h_bad.resize(n);
+    HIP_TRY(hipMemcpyAsync(h_bad.data(), d_bad, n * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    if (h_out) {
+      stage_out.resize((size_t)out_pos);
+      HIP_TRY(hipMemcpyAsync(stage_out.data(), d_out, (size_t)out_pos * sizeof(float), hipMemcpyDeviceToHost, s));
+    }
+    HIP_TRY(hipStreamSynchronize(s));
+    for (int q = 0; q < n; ++q) {
+      const int i = idx[q];
+      if (h_bad[q]) { out_status[i] = AFX_CLIP_NONFINITE; continue; }       // its output range stays as the caller left it
+      if (h_out) std::memcpy(out + out_offsets[i], stage_out.data() + recs[q].out_off, (size_t)recs[q].n * sizeof(float));
+    }
+  }
+  return AFX_OK;
+}
+
+static int smooth_args(const char* who, afx_ctx* ctx, int sample_fmt, int mem_kind, const int64_t* offsets, const int64_t* lengths,
+                       int n_clips, int out_mem_kind, const int64_t* out_offsets, const int32_t* out_status) {
+  if (!ctx || n_clips < 0 || (n_clips > 0 && (!offsets || !lengths || !out_offsets || !out_status))) return null_arg(who);
+  int rc;
+  if ((rc = check_sample_format(who, sample_fmt, mem_kind)) != AFX_OK) return rc;
+  if ((rc = check_sample_format(who, sample_fmt, out_mem_kind)) != AFX_OK) return rc;
+  return check_clip_ranges(who, offsets, lengths, out_offsets, n_clips, INT64_MAX / 8);
+}
+
+extern "C" int afx_medfilt_batch(afx_ctx* ctx, const void* samples, int sample_fmt, int mem_kind,
+                                 const int64_t* offsets, const int64_t* lengths, int n_clips, int kernel_size,
+                                 float* out, int out_mem_kind, const int64_t* out_offsets, int32_t* out_status) {
+  const char* who = "afx_medfilt_batch";
+  int code;
+  if (const char* why = medfilt_refusal(kernel_size, &code)) { set_error(std::string(who) + ": " + why); return code; }
+  if (int rc = smooth_args(who, ctx, sample_fmt, mem_kind, offsets, lengths, n_clips, out_mem_kind, out_offsets, out_status)) return rc;
+  return smooth_run(who, ctx, samples, sample_fmt, mem_kind, offsets, lengths, n_clips, kernel_size, nullptr, 1, out, out_mem_kind,
+                    out_offsets, out_status);
+}
+
+extern "C" int afx_savgol_batch(afx_ctx* ctx, const void* samples, int sample_fmt, int mem_kind,
+                                const int64_t* offsets, const int64_t* lengths, int n_clips,
+                                int window_length, int polyorder, int deriv, double delta,
+                                float* out, int out_mem_kind, const int64_t* out_offsets, int32_t* out_status) {
+  const char* who = "afx_savgol_batch";
+  int code;
+  if (const char* why = savgol_refusal(window_length, polyorder, deriv, delta, &code)) { set_error(std::string(who) + ": " + why); return code; }
+  if (int rc = smooth_args(who, ctx, sample_fmt, mem_kind, offsets, lengths, n_clips, out_mem_kind, out_offsets, out_status)) return rc;
+  SgTab tab;
+  savgol_build_tab(window_length, polyorder, deriv, delta, tab);
+  return smooth_run(who, ctx, samples, sample_fmt, mem_kind, offsets, lengths, n_clips, 0, &tab, window_length, out, out_mem_kind,
+                    out_offsets, out_status);
+}
+
+// One upload, the preprocess with the launchers and in the order of afx_sosfiltfilt_batch, the ZCR chain with the launchers
+// of the two entry points above, the frame rows of both groups in one launch, the statistics; only the records come back.
+extern "C" int afx_energy_zcr_batch(afx_ctx* ctx, const void* samples, int sample_fmt, int mem_kind,
+                                    const int64_t* offsets, const int64_t* lengths, int n_clips,
+                                    int sr, int frame_length, int hop_length, int flags, double* out_rec, int32_t* out_status) {
+  const char* who = "afx_energy_zcr_batch";
+  if (!ctx || n_clips < 0 || (n_clips > 0 && (!offsets || !lengths || !out_rec || !out_status))) return null_arg(who);
+  int rc, code;
+  if ((rc = check_sample_format(who, sample_fmt, mem_kind)) != AFX_OK) return rc;
+  if (const char* why = ez_refusal(sr, frame_length, hop_length, flags, &code)) { set_error(std::string(who) + ": " + why); return code; }
+  if ((rc = check_clip_ranges(who, offsets, lengths, nullptr, n_clips, INT64_MAX / 8)) != AFX_OK) return rc;
+  const bool pre = flags & AFX_EZ_PREPROCESS, en = flags & AFX_EZ_ENERGY, zc = flags & AFX_EZ_ZCR;
+  constexpr int kPadlen = 18;                  // scipy's default for the experiment's 5th-order filter
+  const int64_t min_n = pre ? kPadlen + 1 : 1;
+  const double nan = std::nan("");
+  bool any = false;
+  for (int i = 0; i < n_clips; ++i) {
+    out_status[i] = lengths[i] >= min_n ? AFX_CLIP_OK : AFX_CLIP_TOO_SHORT;
+    std::fill(out_rec + (size_t)AFX_EZ_N * i, out_rec + (size_t)AFX_EZ_N * (i + 1), nan);
+    any = any || lengths[i] >= min_n;
+  }
+  if (!any) return AFX_OK;
+  if (!samples) { set_error(std::string(who) + ": null samples"); return AFX_ERR_INVALID; }
+  (void)hipGetLastError();
+  HIP_TRY(hipSetDevice(ctx->device));
+  hipStream_t s = ctx->stream;
+  constexpr int kSections = 3;
+  if (pre) {
+    double sos[kSections * 6];
+    FiltTab ftab;
+    const char* why = "";
+    if ((rc = afx_butter_sos(5, 200.0 / ((double)sr / 2.0), 1, sos)) != AFX_OK) return rc;
+    if (!filt_build_tab(sos, kSections, ftab, &why)) { set_error(std::string(who) + ": " + why); return AFX_ERR_INVALID; }
+    if ((rc = ensure(ctx->ft_tab, sizeof(FiltTab))) != AFX_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(ctx->ft_tab.p, &ftab, sizeof(FiltTab), hipMemcpyHostToDevice, s));
+  }
+  if (zc) {
+    SgTab tab;
+    savgol_build_tab(11, 3, 0, 1.0, tab);
+    if ((rc = ensure(ctx->sm_tab, sizeof(SgTab))) != AFX_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(ctx->sm_tab.p, &tab, sizeof(SgTab), hipMemcpyHostToDevice, s));
+  }
+  const size_t esz = sample_fmt == AFX_FMT_S16 ? 2 : 4;
+  const bool h_in = mem_kind == AFX_MEM_HOST;
+  SmoothCost cost;
+  cost.per_sample = (h_in ? (int64_t)esz : 0) + (pre ? 4 : 0) + (zc ? 4 + 4 + 1 : 0);
+  cost.per_frame = (en ? 8 : 0) + (zc ? 8 : 0);
+  cost.per_filt_tile = pre ? (int64_t)kFiltTile * 8 + (int64_t)kFiltB * kFiltZ * 8 + 8 : 0;
+  cost.per_clip = (int64_t)sizeof(FiltClip) + sizeof(FiltState) + 2 * sizeof(SmClip) + sizeof(EzClip) + 4 + 4 + AFX_EZ_N * 8;
+  const int64_t budget = dev_env().smooth_budget;
+  std::vector<FiltClip> frecs;
+  std::vector<SmClip> srecs;
+  std::vector<EzClip> erecs;
+  std::vector<int> idx;
+  std::vector<FiltState> h_st;
+  std::vector<uint32_t> h_bad;
+  std::vector<float> h_peak;
+  std::vector<double> h_rec;
+  std::vector<char> stage_in;
+  for (int c0 = 0; c0 < n_clips;) {
+    frecs.clear(); erecs.clear(); idx.clear();
+    int64_t bytes = 0, ftiles = 0, stiles = 0, frames = 0, in_pos = 0, pos = 0;
+    int c1 = c0;
+    for (; c1 < n_clips; ++c1) {
+      const int64_t n = lengths[c1];
+      if (n < min_n) continue;
+      const EzFrame fr = ez_framing(n, frame_length, hop_length);
+      const int64_t nft = pre ? (n + 2 * (int64_t)kPadlen + kFiltTile - 1) / kFiltTile : 0, nst = (n + kSmTile - 1) / kSmTile;
+      const int64_t cb = cost.of(n, fr.T, nft);
+      if (!erecs.empty() && (bytes + cb > budget || ftiles + nft > kSmoothMaxTiles || stiles + nst > kSmoothMaxTiles ||
+                             frames + fr.T > ((int64_t)1 << 30) || (int)erecs.size() >= kSmoothMaxClips)) break;
+      const int64_t src_off = h_in ? in_pos : offsets[c1];
+      frecs.push_back(FiltClip{src_off, pos, n, (int32_t)ftiles, (int32_t)nft});
+      EzClip e{};
+      e.y_off = pre ? pos : src_off; e.off = pos; e.n = n; e.T = fr.T; e.first_frame = frames; e.fl = fr.fl; e.hop = fr.hop;
+      erecs.push_back(e); idx.push_back(c1);
+      bytes += cb; ftiles += nft; stiles += nst; frames += fr.T;
+      in_pos += (n + 3) / 4 * 4; pos += (n + 3) / 4 * 4;
+    }
+    c0 = c1;
+    if (erecs.empty()) break;
+    if (ftiles > kSmoothMaxTiles || stiles > kSmoothMaxTiles || frames > ((int64_t)1 << 30)) {
+      set_error(std::string(who) + ": clip too large for one launch");
+      return AFX_ERR_UNSUPPORTED;
+    }
+    const int n = (int)erecs.size(), nft = (int)ftiles, nst = (int)stiles;
+    // the ZCR chain's tile records: [0, n) from the groups' input into the workspace (the median), [n, 2 n) within it
+    srecs.resize((size_t)2 * n);
+    for (int q = 0, t = 0; q < n; ++q) {
+      const int32_t k = (int32_t)((erecs[q].n + kSmTile - 1) / kSmTile);
+      srecs[q] = SmClip{erecs[q].y_off, erecs[q].off, erecs[q].n, t, k};
+      srecs[n + q] = SmClip{erecs[q].off, erecs[q].off, erecs[q].n, t, k};
+      t += k;
+    }
+    const void* d_in = samples;
+    if (h_in) {
+      stage_in.assign((size_t)in_pos * esz, 0);
+      for (int q = 0; q < n; ++q)
+        std::memcpy(stage_in.data() + (size_t)frecs[q].in_off * esz, (const char*)samples + (size_t)offsets[idx[q]] * esz, (size_t)frecs[q].n * esz);
+      if ((rc = ensure(ctx->sm_in, stage_in.size())) != AFX_OK) return rc;
+      HIP_TRY(hipMemcpyAsync(ctx->sm_in.p, stage_in.data(), stage_in.size(), hipMemcpyHostToDevice, s));
+      d_in = ctx->sm_in.p;
+    }
+    if ((rc = ensure(ctx->ez_clips, n * sizeof(EzClip))) != AFX_OK) return rc;
+    if ((rc = ensure(ctx->sm_clips, 2 * n * sizeof(SmClip))) != AFX_OK) return rc;
+    if ((rc = ensure(ctx->ez_rec, (size_t)n * AFX_EZ_N * sizeof(double))) != AFX_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(ctx->ez_clips.p, erecs.data(), n * sizeof(EzClip), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(ctx->sm_clips.p, srecs.data(), 2 * n * sizeof(SmClip), hipMemcpyHostToDevice, s));
+    const EzClip* d_eclips = (const EzClip*)ctx->ez_clips.p;
+    const SmClip* d_sclips = (const SmClip*)ctx->sm_clips.p;
+    const void* d_y = d_in;                    // the groups' input
+    int y_fmt = sample_fmt;
+    const uint32_t* d_bad;
+    int bad_stride;
+    if (pre) {
+      if ((rc = ensure(ctx->ft_clips, n * sizeof(FiltClip))) != AFX_OK) return rc;
+      if ((rc = ensure(ctx->ft_st, n * sizeof(FiltState))) != AFX_OK) return rc;
+      if ((rc = ensure(ctx->ft_w, (size_t)nft * kFiltTile * sizeof(double))) != AFX_OK) return rc;
+      if ((rc = ensure(ctx->ft_carry, (size_t)nft * kFiltB * kFiltZ * sizeof(double))) != AFX_OK) return rc;
+      if ((rc = ensure(ctx->ft_tmax, (size_t)nft * sizeof(double))) != AFX_OK) return rc;
+      if ((rc = ensure(ctx->ez_y, (size_t)pos * sizeof(float))) != AFX_OK) return rc;
+      HIP_TRY(hipMemcpyAsync(ctx->ft_clips.p, frecs.data(), n * sizeof(FiltClip), hipMemcpyHostToDevice, s));
+      const FiltTab* d_tab = (const FiltTab*)ctx->ft_tab.p;
+      const FiltClip* d_fclips = (const FiltClip*)ctx->ft_clips.p;
+      FiltState* d_st = (FiltState*)ctx->ft_st.p;
+      double *W = (double*)ctx->ft_w.p, *carry = (double*)ctx->ft_carry.p, *tmax = (double*)ctx->ft_tmax.p;
+      HIP_TRY(launch_filt_peak(s, d_in, sample_fmt, d_fclips, n, d_st));
+      HIP_TRY(launch_filt_forward(s, d_in, sample_fmt, AFX_FILT_EXPERIMENT, -0.98f, kPadlen, kSections, d_tab, d_fclips, n, nft, d_st, W, carry));
+      HIP_TRY(launch_filt_scan(s, kPadlen, kSections, d_tab, d_fclips, n, d_st, carry, false));
+      HIP_TRY(launch_filt_backward(s, kPadlen, kSections, d_tab, d_fclips, n, nft, d_st, W, carry));
+      HIP_TRY(launch_filt_scan(s, kPadlen, kSections, d_tab, d_fclips, n, d_st, carry, true));
+      HIP_TRY(launch_filt_final(s, kPadlen, kSections, d_tab, d_fclips, n, nft, d_st, W, carry, tmax, nullptr));
+      HIP_TRY(launch_filt_clipmax(s, d_fclips, n, tmax, d_st));
+      HIP_TRY(launch_filt_scale(s, kPadlen, d_fclips, n, nft, d_st, W, (float*)ctx->ez_y.p));
+      d_y = ctx->ez_y.p; y_fmt = AFX_FMT_F32;
+      static_assert(offsetof(FiltState, bad) == 12 && sizeof(FiltState) == 16, "the flag of record c is word 4 c + 3");
+      d_bad = (const uint32_t*)ctx->ft_st.p + 3; bad_stride = 4;
+    } else {
+      if ((rc = ensure(ctx->sm_bad, n * sizeof(uint32_t))) != AFX_OK) return rc;
+      HIP_TRY(launch_sm_check(s, d_in, sample_fmt, d_sclips, n, (uint32_t*)ctx->sm_bad.p));
+      d_bad = (const uint32_t*)ctx->sm_bad.p; bad_stride = 1;
+    }
+    if (zc) {
+      if ((rc = ensure(ctx->ez_m, (size_t)pos * sizeof(float))) != AFX_OK) return rc;
+      if ((rc = ensure(ctx->ez_s, (size_t)pos * sizeof(float))) != AFX_OK) return rc;
+      if ((rc = ensure(ctx->ez_neg, (size_t)pos)) != AFX_OK) return rc;
+      if ((rc = ensure(ctx->ez_peak, n * sizeof(float))) != AFX_OK) return rc;
+      if ((rc = ensure(ctx->ez_rate, (size_t)frames * sizeof(double))) != AFX_OK) return rc;
+      HIP_TRY(launch_medfilt(s, d_y, y_fmt, 3, d_sclips, n, nst, d_bad, bad_stride, (float*)ctx->ez_m.p));
+      // the reference's guard: savgol_filter(11, 3) only when len(y) > 11; shorter clips pass through
+      HIP_TRY(launch_savgol(s, ctx->ez_m.p, AFX_FMT_F32, (const SgTab*)ctx->sm_tab.p, 12, d_sclips + n, n, nst, d_bad, bad_stride, (float*)ctx->ez_s.p));
+      HIP_TRY(launch_ez_peak(s, (const float*)ctx->ez_s.p, d_eclips, n, d_bad, bad_stride, (float*)ctx->ez_peak.p));
+      HIP_TRY(launch_ez_sign(s, (const float*)ctx->ez_s.p, d_sclips + n, n, nst, d_bad, bad_stride, (const float*)ctx->ez_peak.p, (uint8_t*)ctx->ez_neg.p));
+    }
+    if (en && (rc = ensure(ctx->ez_energy, (size_t)frames * sizeof(double))) != AFX_OK) return rc;
+    if (en || zc) {
+      HIP_TRY(launch_ez_frames(s, en ? d_y : nullptr, y_fmt, zc ? (const uint8_t*)ctx->ez_neg.p : nullptr, d_eclips, n, frames, d_bad,
+                               bad_stride, (double*)ctx->ez_energy.p, (double*)ctx->ez_rate.p));
+      HIP_TRY(launch_ez_stats(s, d_eclips, n, d_bad, bad_stride, flags, (const double*)ctx->ez_energy.p, (const double*)ctx->ez_rate.p,
+                              (double*)ctx->ez_rec.p));
+      h_rec.resize((size_t)n * AFX_EZ_N);
+      HIP_TRY(hipMemcpyAsync(h_rec.data(), ctx->ez_rec.p, h_rec.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+    }
+    if (zc) {
+      h_peak.resize(n);
+      HIP_TRY(hipMemcpyAsync(h_peak.data(), ctx->ez_peak.p, n * sizeof(float), hipMemcpyDeviceToHost, s));
+    }
+    if (pre) {
+      h_st.resize(n);
+      HIP_TRY(hipMemcpyAsync(h_st.data(), ctx->ft_st.p, n * sizeof(FiltState), hipMemcpyDeviceToHost, s));
+    } else {
+      h_bad.resize(n);
+      HIP_TRY(hipMemcpyAsync(h_bad.data(), ctx->sm_bad.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    }
+    HIP_TRY(hipStreamSynchronize(s));
+    for (int q = 0; q < n; ++q) {
+      const int i = idx[q];
+      if (pre ? h_st[q].bad : h_bad[q]) { out_status[i] = AFX_CLIP_NONFINITE; continue; }
+      double* r = out_rec + (size_t)AFX_EZ_N * i;
+      const double* g = h_rec.data() + (size_t)AFX_EZ_N * q;
+      r[AFX_EZ_T] = (double)erecs[q].T; r[AFX_EZ_FL] = erecs[q].fl; r[AFX_EZ_HOP] = erecs[q].hop;
+      if (en) { r[AFX_EZ_ENERGY_MEAN] = g[AFX_EZ_ENERGY_MEAN]; r[AFX_EZ_ENERGY_STD] = g[AFX_EZ_ENERGY_STD]; r[AFX_EZ_ENERGY_P10] = g[AFX_EZ_ENERGY_P10]; }
+      if (zc) {
+        r[AFX_EZ_ZCR_MEAN] = g[AFX_EZ_ZCR_MEAN]; r[AFX_EZ_ZCR_STD] = g[AFX_EZ_ZCR_STD]; r[AFX_EZ_ZCR_LOCAL] = g[AFX_EZ_ZCR_LOCAL];
+        r[AFX_EZ_PEAK_SMOOTH] = (double)h_peak[q];
+      }
+      if (pre) { r[AFX_EZ_PEAK_IN] = (double)h_st[q].peak_in; r[AFX_EZ_PEAK_FILT] = h_st[q].peak_out; }
+    }
+  }
+  return AFX_OK;
 }

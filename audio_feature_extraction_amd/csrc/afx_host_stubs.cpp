@@ -1,6 +1,6 @@
 // Device entry points of the HOST-ONLY build (libafx_host_asan.so, `make asan`): every one fails loudly with
 // AFX_ERR_NO_DEVICE.  The sanitizer build exists to run the host-side parsers and table builders (afx_wav.cpp,
-// afx_tables.cpp, afx_f0_tables.cpp, afx_resample_tables.cpp, afx_filt_host.cpp, afx_beat_host.cpp, afx_assess_host.cpp, afx_cfft_host.cpp, afx_host.cpp) under AddressSanitizer + UBSan on the CPU; GPU sanitizers are not
+// afx_tables.cpp, afx_f0_tables.cpp, afx_resample_tables.cpp, afx_filt_host.cpp, afx_beat_host.cpp, afx_assess_host.cpp, afx_cfft_host.cpp, afx_smooth_host.cpp, afx_host.cpp) under AddressSanitizer + UBSan on the CPU; GPU sanitizers are not
 // available on the target pool.  Never linked into libafx.so.
 #include <cstddef>
 #include <cstdint>
@@ -101,5 +101,17 @@ int afx_specdist_batch(afx_ctx*, const void*, const void*, int, int, const int64
 }
 int afx_clip_fft_batch(afx_ctx*, const void*, int, int, const int64_t*, const int64_t*, int, double*, const int64_t*, int32_t*) {
   return no_device("afx_clip_fft_batch");
+}
+int afx_medfilt_batch(afx_ctx*, const void*, int, int, const int64_t*, const int64_t*, int, int, float*, int, const int64_t*,
+                      int32_t*) {
+  return no_device("afx_medfilt_batch");
+}
+int afx_savgol_batch(afx_ctx*, const void*, int, int, const int64_t*, const int64_t*, int, int, int, int, double, float*, int,
+                     const int64_t*, int32_t*) {
+  return no_device("afx_savgol_batch");
+}
+int afx_energy_zcr_batch(afx_ctx*, const void*, int, int, const int64_t*, const int64_t*, int, int, int, int, int, double*,
+                         int32_t*) {
+  return no_device("afx_energy_zcr_batch");
 }
 }

@@ -23,6 +23,7 @@
 #include "afx_internal.h"
 #include "afx_resample.h"
 #include "afx_rhythm.h"
+#include "afx_smooth.h"
 
 namespace afx {
 
@@ -58,6 +59,11 @@ struct afx_ctx {
   // transforms' points, the filter spectra, the results and flags, staging of host batches
   DevBuf cf_tw, cf_jobs, cf_work, cf_filt, cf_rec, cf_bad, cf_in;
   bool cf_tw_ready = false;
+  // afx_medfilt_batch / afx_savgol_batch: the Savitzky-Golay tables, a chunk's clip records and non-finite flags, staging of
+  // host batches.  afx_energy_zcr_batch (with these and the filter workspace above): the frame records, the preprocessed,
+  // median-filtered and smoothed signals, the sign plane, the smoothed peaks, the frame rows of both groups, the records
+  DevBuf sm_tab, sm_clips, sm_bad, sm_in, sm_out;
+  DevBuf ez_clips, ez_y, ez_m, ez_s, ez_neg, ez_peak, ez_energy, ez_rate, ez_rec;
 };
 
 struct afx_plan {

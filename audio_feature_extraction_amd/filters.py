@@ -10,6 +10,11 @@ Sections.  ``sosfiltfilt``, ``sosfiltfilt_batch`` and ``filtfilt`` accept any ``
 first-order sections included -- and any ``padlen`` from 0 to 4096.  Only the designer ``butter_sos`` is
 limited to low- and high-pass.
 
+Smoothers.  ``medfilt`` and ``savgol_filter`` (and their ``_batch`` forms) are ``scipy.signal.medfilt`` (zero padding, odd
+kernels up to 31; value-exact) and ``scipy.signal.savgol_filter(mode='interp')`` (odd windows 3 .. 31, order up to 5,
+derivative up to 2; float64 chains of fused multiply-adds, one rounding to float32) on samples, in ``afx_medfilt_batch`` /
+``afx_savgol_batch``.
+
 Conditioning.  ``filtfilt(b, a, x)`` goes through ``scipy.signal.tf2sos``: the engine never runs the (b, a) recursion.  For
 the high-pass filters of the extractors (200 Hz, order 5) the poles cluster near z = 1 and the float64 (b, a) recursion of
 scipy is itself only defined to 3e-10 of the peak at 22.05 kHz and 7e-9 at 48 kHz (its distance from the same recursion in
@@ -123,6 +128,104 @@ def filtfilt(b, a, x, padlen: Optional[int] = None, *, device: int = 0) -> np.nd
     if padlen is None:
         padlen = 3 * max(a.size, b.size)
     return sosfiltfilt(scipy.signal.tf2sos(b, a), x, padlen=padlen, device=device)
+
+
+MAX_WINDOW, MAX_POLYORDER, MAX_DERIV = 31, 5, 2          # what afx_medfilt_batch / afx_savgol_batch compile in
+
+
+def _check_kernel_size(kernel_size) -> int:
+    k = np.asarray(kernel_size)
+    if k.ndim > 1 or k.size != 1:
+        raise ValueError("kernel_size must be a scalar (clips are one-dimensional)")
+    k = int(k.reshape(()))
+    if k < 1:
+        raise ValueError("kernel_size must be positive")
+    if k % 2 != 1:
+        raise ValueError("Each element of kernel_size should be odd.")
+    if k > MAX_WINDOW:
+        raise NotImplementedError(f"kernel sizes above {MAX_WINDOW} are not supported")
+    return k
+
+
+def _smooth_clips(out: dict, lengths) -> List[Optional[np.ndarray]]:
+    return [out["out"][o:o + n].copy() if st == _native.CLIP_OK else None
+            for o, n, st in zip(out["offsets"], lengths, out["status"])]
+
+
+def medfilt_batch(clips: Sequence[np.ndarray], kernel_size: int = 3, *, device: int = 0) -> List[Optional[np.ndarray]]:
+    """``scipy.signal.medfilt(x, kernel_size)`` of many mono clips in one device pass: float32 arrays of their inputs'
+    lengths (value-exact: every output is one of the inputs or the zero padding), ``None`` for an empty clip or one that is
+    not finite."""
+    k = _check_kernel_size(kernel_size)
+    cl = [_as_clip(c, f"clip {i}") for i, c in enumerate(clips)]
+    if not cl:
+        return []
+    lengths = np.array([c.size for c in cl], np.int64)
+    return _smooth_clips(_ctx(device).medfilt_batch(np.concatenate(cl), _native.packed_offsets(lengths), lengths, k), lengths)
+
+
+def medfilt(x, kernel_size: int = 3, *, device: int = 0) -> np.ndarray:
+    """``scipy.signal.medfilt(x, kernel_size)`` of one mono signal (zero padding; odd ``kernel_size`` up to 31), float32."""
+    k = _check_kernel_size(kernel_size)
+    x = _as_clip(x, "x")
+    if x.size == 0:
+        return x.copy()
+    y = medfilt_batch([x], k, device=device)[0]
+    if y is None:
+        raise ValueError("array must not contain infs or NaNs")
+    return y
+
+
+def _check_savgol(window_length, polyorder, deriv, delta, mode) -> tuple:
+    if mode not in ("mirror", "constant", "nearest", "interp", "wrap"):
+        raise ValueError("mode must be 'mirror', 'constant', 'nearest' 'wrap' or 'interp'.")
+    if mode != "interp":
+        raise NotImplementedError(f"mode={mode!r} is not supported (only 'interp')")
+    w, p, d = int(window_length), int(polyorder), int(deriv)
+    if w != window_length or p != polyorder or d != deriv:
+        raise ValueError("window_length, polyorder and deriv must be integers")
+    if w < 1:
+        raise ValueError("window_length must be a positive integer")
+    if p < 0 or d < 0:
+        raise ValueError("polyorder and deriv must be nonnegative integers")
+    if p >= w:
+        raise ValueError("polyorder must be less than window_length.")
+    delta = float(delta)
+    if not np.isfinite(delta) or delta == 0.0:
+        raise ValueError("delta must be finite and not 0")
+    if w % 2 == 0 or w < 3 or w > MAX_WINDOW:
+        raise NotImplementedError(f"window_length must be odd and in 3 .. {MAX_WINDOW}")
+    if p > MAX_POLYORDER or d > MAX_DERIV:
+        raise NotImplementedError(f"polyorder above {MAX_POLYORDER} or deriv above {MAX_DERIV} is not supported")
+    return w, p, d, delta
+
+
+def savgol_filter_batch(clips: Sequence[np.ndarray], window_length: int, polyorder: int, deriv: int = 0, delta: float = 1.0,
+                        mode: str = "interp", *, device: int = 0) -> List[Optional[np.ndarray]]:
+    """``scipy.signal.savgol_filter(x, window_length, polyorder, deriv, delta, mode='interp')`` of many mono clips in one
+    device pass: the float32 samples widened to float64, results rounded once to float32; ``None`` for a clip scipy would
+    refuse (shorter than the window) or one that is not finite."""
+    w, p, d, delta = _check_savgol(window_length, polyorder, deriv, delta, mode)
+    cl = [_as_clip(c, f"clip {i}") for i, c in enumerate(clips)]
+    if not cl:
+        return []
+    lengths = np.array([c.size for c in cl], np.int64)
+    return _smooth_clips(_ctx(device).savgol_batch(np.concatenate(cl), _native.packed_offsets(lengths), lengths, w, p, d, delta),
+                         lengths)
+
+
+def savgol_filter(x, window_length: int, polyorder: int, deriv: int = 0, delta: float = 1.0, mode: str = "interp", *,
+                  device: int = 0) -> np.ndarray:
+    """``scipy.signal.savgol_filter(x, window_length, polyorder, deriv=deriv, delta=delta, mode='interp')`` of one mono signal,
+    float32 (odd ``window_length`` 3 .. 31, ``polyorder`` up to 5, ``deriv`` up to 2)."""
+    w, p, d, delta = _check_savgol(window_length, polyorder, deriv, delta, mode)
+    x = _as_clip(x, "x")
+    if x.size < w:
+        raise ValueError("If mode is 'interp', window_length must be less than or equal to the size of x.")
+    y = savgol_filter_batch([x], w, p, d, delta, device=device)[0]
+    if y is None:
+        raise ValueError("array must not contain infs or NaNs")
+    return y
 
 
 EXPERIMENT_COEF, EXPERIMENT_CUTOFF_HZ, EXPERIMENT_ORDER, EXPERIMENT_PADLEN = 0.98, 200.0, 5, 18

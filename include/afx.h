@@ -653,6 +653,93 @@ int afx_sosfiltfilt_batch(afx_ctx* ctx, const void* samples, int sample_fmt, int
                           float* out, int out_mem_kind, const int64_t* out_offsets,
                           double* out_peak /*[n_clips][2]*/, int32_t* out_status);
 
+/* Sample-domain smoothers with scipy semantics, and the experiment extractor's energy and ZCR groups
+ * (04_feature_extraction_experiment/feature_extractor.py:341-483) built on them.  All eight symbols are newer than AFX_VERSION
+ * 107 says: a binding detects them by their presence.  Clips, formats and memory kinds are those of afx_sosfiltfilt_batch;
+ * outputs are float32 of their inputs' lengths.  Results are bit-reproducible, a clip never reads its neighbours in the
+ * packed buffer, and its result depends neither on the rest of the batch nor on how the batch was cut into chunks.
+ *
+ * afx_medfilt_batch: scipy.signal.medfilt(x, kernel_size).  kernel_size odd, 1 .. 31 (an even or non-positive one is
+ * AFX_ERR_INVALID, a larger one AFX_ERR_UNSUPPORTED); out[i] = the median of x[i - h .. i + h], h = kernel_size / 2, with
+ * zeros outside [0, n), so a kernel longer than the clip is legal.  The result is one of the inputs or 0: value-exact; a
+ * zero result is always +0.  Per clip: AFX_CLIP_TOO_SHORT for length 0, AFX_CLIP_NONFINITE for a NaN / inf sample -- the
+ * output range of such a clip is not written.
+ *
+ * afx_savgol_batch: scipy.signal.savgol_filter(x, window_length, polyorder, deriv=deriv, delta=delta, mode='interp') of the
+ * float32 samples widened to float64.  window_length odd, 3 .. 31; 0 <= polyorder <= 5, polyorder < window_length;
+ * deriv 0 .. 2; delta finite and not 0.  AFX_ERR_INVALID for a negative or zero window_length, a negative polyorder or deriv,
+ * polyorder >= window_length or a bad delta; AFX_ERR_UNSUPPORTED for an even window_length, window_length 1 or above 31,
+ * polyorder above 5, deriv above 2 -- all before any device work.  Interior outputs are the window_length taps of
+ * scipy.signal.savgol_coeffs; the first and last window_length / 2 outputs are the degree-polyorder least-squares polynomial
+ * through the clip's first / last window_length samples, evaluated (deriv times differentiated) at the output's position.
+ * Every output is one chain of float64 fused multiply-adds over window_length samples in ascending order, rounded once to
+ * float32.  Per clip: AFX_CLIP_TOO_SHORT for n < window_length (scipy raises), AFX_CLIP_NONFINITE as above.
+ * afx_savgol_tables (host-only): the interior taps in scipy.signal.savgol_coeffs' (convolution) order and the two edge
+ * matrices, row r = output r (left) / n - window_length / 2 + r (right) as weights over the first / last window_length
+ * samples in ascending order; float64, from a centred and scaled abscissa.
+ * afx_medfilt_host, afx_savgol_host (host-only): one host clip through the same code on the CPU -- the specification of the
+ * kernels, bit for bit.
+ * afx_smooth_geometry (host-only): info[4] = samples per tile, largest kernel_size / window_length, largest polyorder,
+ * largest deriv.
+ *
+ * afx_energy_zcr_batch: the energy group (:341-403) and the ZCR group (:405-483) of clips at rate sr in one call: one
+ * upload, AFX_EZ_N doubles per clip back.  flags: AFX_EZ_PREPROCESS runs afx_sosfiltfilt_batch's AFX_FILT_EXPERIMENT first
+ * (afx_butter_sos(5, 200 / (sr / 2), 1), padlen 18, pre-emphasis 0.98; the groups see that call's float32 output bit for
+ * bit; clips of 18 samples or fewer are AFX_CLIP_TOO_SHORT); without it only an empty clip is.  AFX_EZ_ENERGY, AFX_EZ_ZCR:
+ * the groups to compute; the fields of a group not asked for, and every field of a failed clip, are NaN.
+ * Framing per clip (:42-60): fl = frame_length when n >= frame_length, else max(64, 2^floor(log2 n));
+ * hop = min(hop_length, fl / 4); T = 1 + n / hop.  frame_length: a power of two in [64, 2048]; hop_length >= 1; sr >= 1 and,
+ * with AFX_EZ_PREPROCESS, above 400 (the cutoff must lie below Nyquist): AFX_ERR_INVALID otherwise.
+ *   energy  librosa.feature.rms(center=True, zero padding): the squares of the float32 samples summed in float64, mean
+ *           square over fl, square root in float64; its mean, population standard deviation and np.percentile(energy, 10)
+ *           (numpy's linear rule on the two exact order statistics).
+ *   ZCR     afx_medfilt_batch(3), then afx_savgol_batch(11, 3, 0, 1.0) when n > 11, float32 between the stages;
+ *           peak = max |s|; a sample counts as +0 when fabs((double)s / (double)peak) <= 1e-10, and every sample does when
+ *           the peak is below FLT_MIN (librosa.util.normalize leaves such a signal as it is); frames are centred with edge
+ *           padding, a crossing is a change of sign bit between neighbours, a frame's first sample never is one, the rate is
+ *           count / fl in float64; the mean and population standard deviation of the rates, and local_stability: the mean
+ *           over i in 0 .. T - w of the population standard deviation of rates[i .. i + w), w = min(10, T); the standard
+ *           deviation itself when w == 1.  (The reference passes pad_mode='reflect', a keyword librosa.feature.
+ *           zero_crossing_rate does not have; this is librosa's own edge padding.)
+ * Sums run in one fixed order: a lane's own terms ascending, then a halving tree over the lanes.
+ * afx_energy_zcr_host (host-only): one float32 clip, already preprocessed, through the same operations on the CPU;
+ * rec[AFX_EZ_PEAK_IN] and rec[AFX_EZ_PEAK_FILT] stay NaN. */
+enum { AFX_EZ_PREPROCESS = 1, AFX_EZ_ENERGY = 2, AFX_EZ_ZCR = 4 };
+enum {
+  AFX_EZ_T = 0,            /* frames */
+  AFX_EZ_FL = 1,           /* the clip's frame length */
+  AFX_EZ_HOP = 2,          /* the clip's hop */
+  AFX_EZ_ENERGY_MEAN = 3,
+  AFX_EZ_ENERGY_STD = 4,
+  AFX_EZ_ENERGY_P10 = 5,
+  AFX_EZ_ZCR_MEAN = 6,
+  AFX_EZ_ZCR_STD = 7,
+  AFX_EZ_ZCR_LOCAL = 8,    /* local_stability */
+  AFX_EZ_PEAK_SMOOTH = 9,  /* max |s| of the smoothed signal (ZCR group) */
+  AFX_EZ_PEAK_IN = 10,     /* the preprocess's max |x| */
+  AFX_EZ_PEAK_FILT = 11,   /* the preprocess's max |y| before its last scaling */
+  AFX_EZ_N = 12
+};
+int afx_smooth_geometry(int32_t* info /*[4]*/);
+int afx_savgol_tables(int window_length, int polyorder, int deriv, double delta, double* coeffs /*[W]*/,
+                      double* left /*[W / 2][W]*/, double* right /*[W / 2][W]*/);
+int afx_medfilt_host(const void* samples, int sample_fmt, int64_t n, int kernel_size, float* out, int32_t* out_status);
+int afx_savgol_host(const void* samples, int sample_fmt, int64_t n, int window_length, int polyorder, int deriv, double delta,
+                    float* out, int32_t* out_status);
+int afx_energy_zcr_host(const float* samples, int64_t n, int frame_length, int hop_length, int flags,
+                        double* out_rec /*[AFX_EZ_N]*/, int32_t* out_status);
+int afx_medfilt_batch(afx_ctx* ctx, const void* samples, int sample_fmt, int mem_kind,
+                      const int64_t* offsets, const int64_t* lengths, int n_clips, int kernel_size,
+                      float* out, int out_mem_kind, const int64_t* out_offsets, int32_t* out_status);
+int afx_savgol_batch(afx_ctx* ctx, const void* samples, int sample_fmt, int mem_kind,
+                     const int64_t* offsets, const int64_t* lengths, int n_clips,
+                     int window_length, int polyorder, int deriv, double delta,
+                     float* out, int out_mem_kind, const int64_t* out_offsets, int32_t* out_status);
+int afx_energy_zcr_batch(afx_ctx* ctx, const void* samples, int sample_fmt, int mem_kind,
+                         const int64_t* offsets, const int64_t* lengths, int n_clips,
+                         int sr, int frame_length, int hop_length, int flags,
+                         double* out_rec /*[n_clips][AFX_EZ_N]*/, int32_t* out_status);
+
 /* The recording screen of 00_audio_data_collection_experiment/audio_format_assessment.py:143-300 (detect_silence,
  * check_volume_levels, check_amplitude_stability, estimate_snr) and the sums behind the scores of
  * audio_quality_assessment.py:150-280 (SNR of the difference, Pearson correlation, MSE), as per-clip reductions.  All five
