@@ -35,6 +35,7 @@ DevEnv::DevEnv() {
   no_dct16l = getenv("AFX_NO_DCT16L") != nullptr;
   host_blocks = getenv("AFX_HOST_BLOCKS") != nullptr;
   no_fused_tail = getenv("AFX_NO_FUSED_TAIL") != nullptr;
+  if (const char* v = getenv("AFX_F3_XCHG2")) f3_xchg2 = !strcmp(v, "lds") ? 1 : !strcmp(v, "swap") ? 2 : 0;
   if (const char* v = getenv("AFX_F3_WAVES")) f3_waves = atoi(v);
   if (const char* v = getenv("AFX_F3_SPARE_CUS")) f3_spare_cus = atoi(v) < 0 ? -2 : atoi(v);   // checked against the CU count by afx_extract_submit
   if (const char* v = getenv("AFX_TAIL_MODE")) tail_mode = atoi(v);

@@ -19,6 +19,8 @@ struct DevEnv {
   int tail_mode = 0;                  // k_tail: 1 registers, 2 / 3 / 4 LDS-DMA ring of 4 waves x 4 tiles / 8 x 2 / 4 x 2 with two workgroups per CU,
                                       // 5 / 6 one slot per wave + register-held images with four workgroups per CU, default / nt DMA (A/B)
   int tail_skip = 0;                  // libafx_dbg.so only: timing ablations of k_tail's one-slot form (1 no arithmetic, 2 no DMA, 4 no epilogue)
+  int f3_xchg2 = 0;                   // AFX_F3_XCHG2: k_frames3 / k_frames3s hand the butterfly-ja half of FFT exchange 2 over through LDS (1, "lds":
+                                      // the form before the lane swaps) or by lane swaps (2, "swap"); 0 unset: the per-shape default (A/B, tests)
   int f3_waves = 0;                   // 12 / 16: force the workgroup size of the wave-level frame kernels
   int f3_spare_cus = -1;              // AFX_F3_SPARE_CUS: workgroups taken off the speculative frame launch of a submitted batch, whatever its
                                       // size (>= 0; -1 unset: the per-shape default on full grids only; -2 a negative value was given)

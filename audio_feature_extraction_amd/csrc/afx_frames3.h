@@ -86,6 +86,10 @@ inline int f3_grid(const F3Launch& L, int waves) {
 // other_in_flight: a submitted batch of another stream of the device has not been collected yet.
 constexpr int kF3Xcds = 8;
 int f3_spare_cus(const KParams& kp, int nblocks, int n_cu, bool other_in_flight);     // afx_frames3.hip: the per-shape default, or the switch
+// How k_frames3 and k_frames3s hand the second FFT exchange's butterfly-ja half from pass 2 to pass 3: true by lane swaps
+// (the half is a transpose between lane rows and registers), false through the LDS image like the other half.  The
+// per-shape default, or the switch AFX_F3_XCHG2 (afx_devenv.h); the results are the same bits either way.
+bool f3_xchg2_swap(const KParams& kp);     // afx_frames3.hip
 // n_fft 1024 / hop 256 (afx_frames3.hip), n_fft 2048 / hop 512 (afx_frames3s.hip: one frame per FFT, real-FFT split) and
 // n_fft 512 / hop 128 (afx_frames3d.hip: two frame pairs per wave); launch_frames3_any dispatches on kp.n_fft
 size_t frames3s_lds_bytes(int waves, const F3Tables& ft);

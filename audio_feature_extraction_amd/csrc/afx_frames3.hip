@@ -29,7 +29,9 @@
 //   pass 1  radix 16 over u (lane l holds points l + 64 u)                 -> Y[l][k1]
 //   xchg 1  image [k1][66] (transposed; base + immediate on both sides, conflict-free both ways), lane reads l_src = (l>>4) + 4u, k1 = l & 15
 //   pass 2  two radix-8 butterflies (a = (l>>4) + 4i, over r: l_src = a + 8r), twiddle W_128^(k1 r)
-//   xchg 2  image [a][128] at j = k1 + 16 k2, plain layout (both sides conflict-free)
+//   xchg 2  image [a][128] at j = k1 + 16 k2, plain layout (both sides conflict-free) for k2 >= 4, the half butterfly jb
+//           reads; the half butterfly ja reads (k2 < 4) is a transpose between lane rows and registers and goes by lane
+//           swaps (f3_transpose_rows4; XSWAP = false: all of it through the image, the form it replaced)
 //   pass 3  radix 8 over a for butterflies ja = l and jb = 128 - l (lane 0: 0 and 64), twiddle W_1024^(a j):
 //           the lane then owns Z[k] and Z[N-k], so X_A, X_B follow with adds only.
 #include <hip/hip_runtime.h>
@@ -50,8 +52,12 @@ size_t frames3_lds_bytes(int waves, const F3Tables& ft) {
 }
 
 // NB0, NB1 > 0: the mel schedule is known at compile time to be two rounds of width 1 with NB0 and NB1 batches (the
-// reference's 22050 Hz / 128 mels is 2 and 7): the tap walk is then straight-line code, every LDS read of a round in
-// flight before its first FMA.  NB0 = 0: any schedule, batches behind uniform branches.
+// reference's 22050 Hz / 128 mels is 2 and 7): the tap walk is then straight-line code.  hipcc does not put a whole round's
+// reads in flight before its first FMA: the 2-batch round issues five of its six reads, then waits for them one by one; the
+// 7-batch round has the first batch's three reads and two more in flight, then takes the rest three reads (one batch) at a
+// time with an s_waitcnt lgkmcnt(0) after each three.  The kernel is bound by LDS throughput there, not by that latency
+// (the wave is raised above its SIMD mates for the phase), so the walk is left as the compiler schedules it.
+// NB0 = 0: any schedule, batches behind uniform branches.
 // SPEC (the first launch of a batch, "speculative"): blocks are the host-built absolute 16-frame blocks of every
 // clip, computed BEFORE the trim decision -- frames sit on the absolute hop grid because librosa.effects.trim cuts at
 // multiples of its own hop (512), so an interior frame does not depend on where the cut falls.  The kernel then also
@@ -67,7 +73,7 @@ __device__ unsigned long long g_f3_stamps[4 * 8192];
 __device__ unsigned long long g_f3_blk[65536];       // wall clock at the end of block b
 #endif
 
-template <int FMT, int WAVES, int NB0, int NB1, bool SPEC>
+template <int FMT, int WAVES, int NB0, int NB1, bool SPEC, bool XSWAP>
 __global__ __launch_bounds__(WAVES * 64) void k_frames3(const void* __restrict__ samples,
                                                         ClipInfo* __restrict__ info,
                                                         const BlockDesc* __restrict__ blocks, int nblocks,
@@ -300,8 +306,19 @@ __global__ __launch_bounds__(WAVES * 64) void k_frames3(const void* __restrict__
         for (int r = 1; r < 8; ++r) cmul2(xa[r], tw[r], xb[r], tw[r]);
         f3_dft8(xa, H); f3_dft8(xb, H);
         if (!F3_SKIP(0x2000)) {
+          if constexpr (XSWAP) {
+            // Butterfly ja = lane reads image element (a = r, k1 = lane & 15, k2 = lane >> 4 < 4): the value xa[k2] (r < 4) or
+            // xb[k2] (r >= 4) of the lane with the same k1 in row r & 3 -- a transpose between the lane row and the register
+            // index k2 < 4, done by lane swaps; only the half that butterfly jb reads (k2 >= 4) goes through the image
 #pragma unroll
-        for (int r = 0; r < 8; ++r) { stv(e2w + 16 * r, xa[r]); stv(e2w + 16 * r + 512, xb[r]); }
+            for (int r = 4; r < 8; ++r) { stv(e2w + 16 * r, xa[r]); stv(e2w + 16 * r + 512, xb[r]); }
+            f3_transpose_rows4(xa); f3_transpose_rows4(xb);
+#pragma unroll
+            for (int q = 0; q < 4; ++q) { z[q] = xa[q]; z[4 + q] = xb[q]; }
+          } else {
+#pragma unroll
+            for (int r = 0; r < 8; ++r) { stv(e2w + 16 * r, xa[r]); stv(e2w + 16 * r + 512, xb[r]); }
+          }
         } else {
 #pragma unroll
           for (int r = 0; r < 8; ++r) { z[2 * r] = xa[r]; z[2 * r + 1] = xb[r]; }
@@ -311,7 +328,7 @@ __global__ __launch_bounds__(WAVES * 64) void k_frames3(const void* __restrict__
       v2 A[8], B[8];
       if (!F3_SKIP(0x2000)) {
 #pragma unroll
-      for (int r = 0; r < 8; ++r) { A[r] = ldv(ea + 128 * r); B[r] = ldv(eb + 128 * r); }
+      for (int r = 0; r < 8; ++r) { A[r] = XSWAP ? z[r] : ldv(ea + 128 * r); B[r] = ldv(eb + 128 * r); }
       } else {
 #pragma unroll
         for (int r = 0; r < 8; ++r) { A[r] = z[r]; B[r] = z[r + 8]; }
@@ -333,6 +350,8 @@ __global__ __launch_bounds__(WAVES * 64) void k_frames3(const void* __restrict__
       for (int s = 0; s < 4; s += 2) {
         v2 p0, p1;
         sqsum2(A[s] + B[7 - s], A[s] - B[7 - s], A[s + 1] + B[6 - s], A[s + 1] - B[6 - s], p0, p1);
+        // plain stores: hipcc merges each pair into a ds_write2st64_b64.  Through stv (two ds_write_b64, as in the exchanges)
+        // they cost 2 registers more and the step is the same within the runs' scatter (profiles/xchg2_regs_ab.txt)
         ea[128 * s] = p0; ea[128 * (s + 1)] = p1;
       }
 #pragma unroll
@@ -549,13 +568,27 @@ int f3_spare_cus(const KParams& kp, int nblocks, int n_cu, bool other_in_flight)
   return std::min(r, n_cu / 4 / kF3Xcds * kF3Xcds);
 }
 
-template <int FMT, int WAVES, int NB0, int NB1, bool SPEC>
-static hipError_t launch_frames3_t(const F3Launch& L) {
-  const hipError_t e = allow_lds_once<k_frames3<FMT, WAVES, NB0, NB1, SPEC>>();
+// Exchange 2's butterfly-ja half by lane swaps or through LDS.  The switch decides for every shape; the default is per shape,
+// the swap form where same-box A/B runs had every run of it below every run of the parent library and of the all-LDS form
+// (profiles/xchg2_regs_ab.txt): both shapes that have the exchange, 1024 / 256 (-2.4 % of a step) and 2048 / 512 (-2.7 %).
+bool f3_xchg2_swap(const KParams& kp) {
+  const int forced = dev_env().f3_xchg2;
+  if (forced) return forced == 2;
+  return (kp.n_fft == 1024 && kp.hop == 256) || (kp.n_fft == 2048 && kp.hop == 512);
+}
+
+template <int FMT, int WAVES, int NB0, int NB1, bool SPEC, bool XSWAP>
+static hipError_t launch_frames3_x(const F3Launch& L) {
+  const hipError_t e = allow_lds_once<k_frames3<FMT, WAVES, NB0, NB1, SPEC, XSWAP>>();
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL((k_frames3<FMT, WAVES, NB0, NB1, SPEC>), dim3(f3_grid(L, WAVES)), dim3(WAVES * 64), frames3_lds_bytes(WAVES, L.ft), L.s,
+  hipLaunchKernelGGL((k_frames3<FMT, WAVES, NB0, NB1, SPEC, XSWAP>), dim3(f3_grid(L, WAVES)), dim3(WAVES * 64), frames3_lds_bytes(WAVES, L.ft), L.s,
                      L.samples, L.info, L.blocks, L.nblocks, L.nblocks_dev, L.ft, L.kp, L.logmel, L.blockmax, L.bsum, L.work_ctr);
   return hipGetLastError();
+}
+
+template <int FMT, int WAVES, int NB0, int NB1, bool SPEC>
+static hipError_t launch_frames3_t(const F3Launch& L) {
+  return f3_xchg2_swap(L.kp) ? launch_frames3_x<FMT, WAVES, NB0, NB1, SPEC, true>(L) : launch_frames3_x<FMT, WAVES, NB0, NB1, SPEC, false>(L);
 }
 
 template <int FMT, int WAVES, bool SPEC>

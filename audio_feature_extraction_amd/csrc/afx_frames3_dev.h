@@ -225,6 +225,28 @@ __device__ __forceinline__ float f3_add_xor32(float v) {
   const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
   return __uint_as_float(r[0]) + __uint_as_float(r[1]);
 }
+// 4 x 4 transpose between the register index and the lane row (row g = lanes 16 g .. 16 g + 15) with the same swaps: on
+// return x[i] of row g holds what x[g] of row i held, at the same position in the row.  Two steps, as for any 4 x 4
+// transpose in 2 x 2 blocks: permlane32_swap(a, b) exchanges rows 2, 3 of a with rows 0, 1 of b (bit 1 of both indices),
+// permlane16_swap(a, b) rows 1, 3 of a with rows 0, 2 of b (bit 0).  8 swaps for the two components of a float2.
+__device__ __forceinline__ void f3_swap32(float& a, float& b) {
+  const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(a), __float_as_uint(b), false, false);
+  a = __uint_as_float(r[0]); b = __uint_as_float(r[1]);
+}
+__device__ __forceinline__ void f3_swap16(float& a, float& b) {
+  const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(a), __float_as_uint(b), false, false);
+  a = __uint_as_float(r[0]); b = __uint_as_float(r[1]);
+}
+__device__ __forceinline__ void f3_transpose_rows4(v2* x) {
+  // (through local floats: an element of a vector does not bind to a reference)
+  float re[4], im[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) { re[i] = x[i].x; im[i] = x[i].y; }
+  f3_swap32(re[0], re[2]); f3_swap32(im[0], im[2]); f3_swap32(re[1], re[3]); f3_swap32(im[1], im[3]);
+  f3_swap16(re[0], re[1]); f3_swap16(im[0], im[1]); f3_swap16(re[2], re[3]); f3_swap16(im[2], im[3]);
+#pragma unroll
+  for (int i = 0; i < 4; ++i) x[i] = v2{re[i], im[i]};
+}
 // d = mask[lane] ? b : a with a wave-uniform 64-bit lane mask (one v_cndmask; the compiler's own code for a lane-indexed
 // bit test is a 64-bit shift, an and and a compare)
 __device__ __forceinline__ float f3_sel(float a, float b, unsigned long long mask) {

@@ -39,7 +39,8 @@ size_t frames3s_lds_bytes(int waves, const F3Tables& ft) {
 // NBS > 0: the mel schedule is known at compile time -- the batch counts (NBS) and lanes per filter (WDS) of up to four rounds
 // as nibbles, first round lowest (the reference's 44.1 kHz / 128 mels plans batches 3, 1, 5, 5 at widths 1, 4, 2, 4:
 // NBS 0x5513, WDS 0x4241) -- and is walked as straight-line code.  NBS = 0: any schedule, batches behind uniform branches.
-template <int FMT, int WAVES, bool SPEC, bool DESC, int NBS = 0, int WDS = 0>
+// XSWAP: exchange 2's butterfly-ja half by lane swaps instead of through the image (as in k_frames3; f3_xchg2_swap).
+template <int FMT, int WAVES, bool SPEC, bool DESC, bool XSWAP, int NBS = 0, int WDS = 0>
 __global__ __launch_bounds__(WAVES * 64) void k_frames3s(const void* __restrict__ samples,
                                                          ClipInfo* __restrict__ info,
                                                          const BlockDesc* __restrict__ blocks, int nblocks,
@@ -215,12 +216,21 @@ __global__ __launch_bounds__(WAVES * 64) void k_frames3s(const void* __restrict_
 #pragma unroll
         for (int r = 1; r < 8; ++r) cmul2(xa[r], tw[r], xb[r], tw[r]);
         f3_dft8(xa, H); f3_dft8(xb, H);
+        if constexpr (XSWAP) {
+          // as in k_frames3: butterfly ja's operands are xa[0..3] / xb[0..3], transposed between lane rows and registers
 #pragma unroll
-        for (int r = 0; r < 8; ++r) { stv(e2w + 16 * r, xa[r]); stv(e2w + 16 * r + 512, xb[r]); }
+          for (int r = 4; r < 8; ++r) { stv(e2w + 16 * r, xa[r]); stv(e2w + 16 * r + 512, xb[r]); }
+          f3_transpose_rows4(xa); f3_transpose_rows4(xb);
+#pragma unroll
+          for (int q = 0; q < 4; ++q) { z[q] = xa[q]; z[4 + q] = xb[q]; }
+        } else {
+#pragma unroll
+          for (int r = 0; r < 8; ++r) { stv(e2w + 16 * r, xa[r]); stv(e2w + 16 * r + 512, xb[r]); }
+        }
       }
       v2 A[8], B[8];
 #pragma unroll
-      for (int r = 0; r < 8; ++r) { A[r] = ldv(ea + 128 * r); B[r] = ldv(eb + 128 * r); }
+      for (int r = 0; r < 8; ++r) { A[r] = XSWAP ? z[r] : ldv(ea + 128 * r); B[r] = ldv(eb + 128 * r); }
 #pragma unroll
       for (int r = 1; r < 8; ++r) cmul2(A[r], ldv(T3a + (r - 1) * 64 + lane), B[r], ldv(T3b + (r - 1) * 64 + lane));
       f3_dft8(A, H); f3_dft8(B, H);
@@ -435,23 +445,30 @@ int frames3s_waves(const F3Tables& ft) {
   return frames3s_lds_bytes(16, ft) <= 160 * 1024 ? 16 : 12;
 }
 
-template <int FMT, int WAVES, bool SPEC, int NBS, int WDS>
-static hipError_t launch_frames3s_t(const F3Launch& L) {
-  const hipError_t e = allow_lds_once<k_frames3s<FMT, WAVES, SPEC, false, NBS, WDS>>();
+template <int FMT, int WAVES, bool SPEC, bool XSWAP, int NBS, int WDS>
+static hipError_t launch_frames3s_x(const F3Launch& L) {
+  const hipError_t e = allow_lds_once<k_frames3s<FMT, WAVES, SPEC, false, XSWAP, NBS, WDS>>();
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL((k_frames3s<FMT, WAVES, SPEC, false, NBS, WDS>), dim3(f3_grid(L, WAVES)), dim3(WAVES * 64), frames3s_lds_bytes(WAVES, L.ft), L.s,
+  hipLaunchKernelGGL((k_frames3s<FMT, WAVES, SPEC, false, XSWAP, NBS, WDS>), dim3(f3_grid(L, WAVES)), dim3(WAVES * 64), frames3s_lds_bytes(WAVES, L.ft), L.s,
                      L.samples, L.info, L.blocks, L.nblocks, L.nblocks_dev, L.ft, L.kp, L.logmel, L.blockmax, L.bsum, nullptr, nullptr, SpecBands{}, L.work_ctr);
   return hipGetLastError();
 }
 
+template <int FMT, int WAVES, bool SPEC, int NBS, int WDS>
+static hipError_t launch_frames3s_t(const F3Launch& L) {
+  return f3_xchg2_swap(L.kp) ? launch_frames3s_x<FMT, WAVES, SPEC, true, NBS, WDS>(L) : launch_frames3s_x<FMT, WAVES, SPEC, false, NBS, WDS>(L);
+}
+
+// the descriptor kernel exists in the shape's default form of exchange 2 alone (no test or A/B asks for its other form)
+constexpr bool kF3sDescSwap = true;
 template <int FMT>
 static hipError_t launch_spectral_t(hipStream_t s, const void* samples, ClipInfo* info, const BlockDesc* blocks, int nblocks,
                                     const F3Tables& ft, const KParams& kp, float* desc_out, const int64_t* desc_offs,
                                     const SpecBands& sb, int n_cu) {
-  const hipError_t e = allow_lds_once<k_frames3s<FMT, 12, false, true>>();
+  const hipError_t e = allow_lds_once<k_frames3s<FMT, 12, false, true, kF3sDescSwap>>();
   if (e != hipSuccess) return e;
   const int grid = std::max(1, std::min(n_cu, (nblocks + 11) / 12));
-  hipLaunchKernelGGL((k_frames3s<FMT, 12, false, true>), dim3(grid), dim3(12 * 64), frames3s_lds_bytes(12, ft), s,
+  hipLaunchKernelGGL((k_frames3s<FMT, 12, false, true, kF3sDescSwap>), dim3(grid), dim3(12 * 64), frames3s_lds_bytes(12, ft), s,
                      samples, info, blocks, nblocks, nullptr, ft, kp, nullptr, nullptr, nullptr, desc_out, desc_offs, sb, nullptr);
   return hipGetLastError();
 }

@@ -12,12 +12,13 @@ for grp in "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_L
   rocprofv3 --pmc $grp --output-format csv -d $OUT/$name -- $BENCH > $OUT/$name.log 2>&1 || echo "pmc $name failed"
 done
 python3 - $OUT <<'PY'
-import csv,glob,sys,os
+import csv,glob,re,sys,os
 from collections import defaultdict
 acc=defaultdict(list)
 for f in glob.glob(os.path.join(sys.argv[1],'*','**','*counter_collection.csv'),recursive=True):
     for row in csv.DictReader(open(f)):
         n=row['Kernel_Name']
-        if 'k_frames3' in n and 'true>' in n.split('(')[0]: acc[row['Counter_Name']].append(float(row['Counter_Value']))
+        # the speculative launch: k_frames3<FMT, WAVES, NB0, NB1, SPEC = true, XSWAP>
+        if re.search(r'k_frames3<[^>]*, true, (true|false)>', n.split('(')[0]): acc[row['Counter_Name']].append(float(row['Counter_Value']))
 print(' '.join(f"{c[3:] if c.startswith('SQ_') else c}={sum(acc[c])/len(acc[c])/431000:.1f}" for c in sorted(acc)), '(per pair)')
 PY
