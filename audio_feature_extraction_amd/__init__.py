@@ -3,6 +3,7 @@
 from .core.feature_extractor import AudioFeatureExtractor
 from .evaluation.evaluator import FeatureEvaluator
 from . import quality  # noqa: F401  (the recording screen and the denoising scores; a module, not one of the two exports)
+from . import loudness  # noqa: F401  (BS.1770 loudness and normalisation; a module, likewise)
 
 __version__ = '0.1.0'
 

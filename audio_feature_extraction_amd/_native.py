@@ -55,6 +55,9 @@ EZ_PREPROCESS, EZ_ENERGY, EZ_ZCR = 1, 2, 4                                    # 
 EZ_N = 12                                                                    # doubles per clip of its record
 EZ_FIELDS = ("T", "fl", "hop", "energy_mean", "energy_std", "energy_p10", "zcr_mean", "zcr_std", "zcr_local_stability",
              "peak_smooth", "peak_in", "peak_filt")
+LOUD_MEASURE, LOUD_NORM_LOUDNESS, LOUD_NORM_PEAK = 0, 1, 2                    # afx_loudness_batch: its modes
+LOUD_N = 11                                                                  # doubles per clip of its record
+LOUD_FIELDS = ("lufs", "blocks", "n1", "n2", "gamma_r", "gated_ms", "peak", "gain", "peak_out", "first_ms", "ungated_ms")
 GROUPS_STATS = 24                                                            # doubles per clip of its record
 K_NAMES = ("trim_blocks", "trim_decide", "frames", "dct", "stats")
 K_FRAMES = 2
@@ -78,6 +81,8 @@ SYMBOLS = (
     "afx_specdist_batch", "afx_clip_fft_batch", "afx_specdist_host", "afx_clip_fft_host", "afx_specdist_cost",
     "afx_smooth_geometry", "afx_savgol_tables", "afx_medfilt_host", "afx_savgol_host", "afx_energy_zcr_host",
     "afx_medfilt_batch", "afx_savgol_batch", "afx_energy_zcr_batch",
+    "afx_kweight_sos", "afx_loudness_geometry", "afx_loudness_blocks", "afx_loudness_cost", "afx_loudness_host",
+    "afx_loudness_batch",
 )
 
 
@@ -204,6 +209,14 @@ def lib() -> C.CDLL:
             L.afx_medfilt_batch.argtypes = [vp, vp, i32, i32, vp, vp, i32, i32, vp, i32, vp, vp]
             L.afx_savgol_batch.argtypes = [vp, vp, i32, i32, vp, vp, i32, i32, i32, i32, dbl, vp, i32, vp, vp]
             L.afx_energy_zcr_batch.argtypes = [vp, vp, i32, i32, vp, vp, i32, i32, i32, i32, i32, vp, vp]
+        if hasattr(L, "afx_loudness_batch"):                 # newer than version 107 says: found by their presence
+            dbl = C.c_double
+            L.afx_kweight_sos.argtypes = [i32, vp]
+            L.afx_loudness_geometry.argtypes = [vp]
+            L.afx_loudness_blocks.argtypes = [C.c_int64, i32, dbl, i64p]
+            L.afx_loudness_cost.argtypes = [i32, i32, i32, i32, vp]
+            L.afx_loudness_host.argtypes = [vp, i32, C.c_int64, i32, dbl, dbl, i32, vp, vp, vp, vp]
+            L.afx_loudness_batch.argtypes = [vp, vp, i32, i32, vp, vp, vp, i32, dbl, i32, dbl, vp, vp, vp, vp, i32, vp, vp]
         if hasattr(L, "afx_rfft_host"):                      # absent from a library built before the mixed-radix lengths
             L.afx_rfft_host.argtypes = [i32, vp, vp]
         _lib = L
@@ -630,6 +643,60 @@ def energy_zcr_host(y, frame_length: int = 2048, hop_length: int = 512, flags: i
     return {"rec": rec, "status": int(status[0])}
 
 
+def _need_loudness():
+    if not hasattr(lib(), "afx_loudness_batch"):
+        raise NotImplementedError("this libafx has no afx_loudness_batch")
+
+
+def kweight_sos(rate: int) -> np.ndarray:
+    """Host-only: afx_kweight_sos, the K-weighting of BS.1770 at ``rate`` as two sections (b0 b1 b2 1 a1 a2), float64."""
+    _need_loudness()
+    sos = np.zeros((2, 6), np.float64)
+    _check(lib().afx_kweight_sos(int(rate), sos.ctypes.data), "afx_kweight_sos")
+    return sos
+
+
+def loudness_geometry() -> dict:
+    """Host-only: the block decomposition of afx_loudness_batch (samples per block, blocks per tile) and its bounds."""
+    _need_loudness()
+    info = np.zeros(5, np.int32)
+    _check(lib().afx_loudness_geometry(info.ctypes.data), "afx_loudness_geometry")
+    return {"block": int(info[0]), "tile_blocks": int(info[1]), "tile": int(info[0]) * int(info[1]),
+            "min_rate": int(info[2]), "max_rate": int(info[3]), "max_rates": int(info[4])}
+
+
+def loudness_blocks(n: int, rate: int, block_size: float = 0.400) -> int:
+    """Host-only: afx_loudness_blocks, the gating blocks of a clip of ``n`` samples (0: too short to measure)."""
+    _need_loudness()
+    nb = C.c_int64(0)
+    _check(lib().afx_loudness_blocks(int(n), int(rate), float(block_size), C.byref(nb)), "afx_loudness_blocks")
+    return int(nb.value)
+
+
+def loudness_cost(fmt: int = FMT_F32, mem: int = MEM_HOST, out_mem: int = MEM_HOST, mode: int = LOUD_MEASURE) -> np.ndarray:
+    """Host-only: the int64 [6] cost record afx_loudness_batch cuts a batch with, for :func:`stft_chunks`."""
+    _need_loudness()
+    cost = np.zeros(6, np.int64)
+    _check(lib().afx_loudness_cost(int(fmt), int(mem), int(out_mem), int(mode), cost.ctypes.data), "afx_loudness_cost")
+    return cost
+
+
+def loudness_host(x, rate: int, block_size: float = 0.400, mode: int = LOUD_MEASURE, target: float = -23.0) -> dict:
+    """Host-only: afx_loudness_host, one int16 / float32 clip through the kernels' block decomposition and summation order
+    on the CPU.  Returns rec (float64 [LOUD_N]; LOUD_FIELDS names the entries; NaN for a failed clip), z (every z_j),
+    out (float32, the normalised clip; None in LOUD_MEASURE; the input's values when the clip failed) and status."""
+    _need_loudness()
+    x = _mono_clip(x, "x")
+    nb = loudness_blocks(x.size, rate, block_size)
+    rec, z = np.zeros(LOUD_N, np.float64), np.zeros(nb, np.float64)
+    out = None if mode == LOUD_MEASURE else (x.astype(np.float32) / np.float32(32768.0) if x.dtype == np.int16 else x.copy())
+    status = np.zeros(1, np.int32)
+    _check(lib().afx_loudness_host(x.ctypes.data, FMT_S16 if x.dtype == np.int16 else FMT_F32, int(x.size), int(rate),
+                                   float(block_size), float(target), int(mode), rec.ctypes.data, z.ctypes.data if nb else None,
+                                   _ptr(out), status.ctypes.data), "afx_loudness_host")
+    return {"rec": rec, "z": z, "out": out, "status": int(status[0])}
+
+
 def beat_track_host(env, fps: float, bpm: float, tightness: float = 100.0, trim: bool = True) -> dict:
     """Host-only: afx_beat_track_host, one float32 onset envelope through the beat tracker's definition in float64 on the
     CPU.  Returns beats (int64 frames), mask (uint8 [T]), localscore, cumscore (float64 [T]) and backlink (int32 [T])."""
@@ -1039,6 +1106,39 @@ class Context(_Owner):
                                       int(window_length), int(polyorder), int(deriv), float(delta), optr, okind,
                                       out_offsets.ctypes.data, status.ctypes.data), "afx_savgol_batch")
         return {"out": out, "offsets": out_offsets, "status": status}
+
+    def loudness_batch(self, samples, offsets, lengths, rates, block_size: float = 0.400, mode: int = LOUD_MEASURE,
+                       target: float = -23.0, want_blocks: bool = False, fmt=None, out=None, out_offsets=None) -> dict:
+        """afx_loudness_batch: BS.1770 integrated loudness of the clips samples[offsets[i] .. + lengths[i]), clip i at its own
+        rate ``rates[i]`` (a scalar: one rate for all), and in LOUD_NORM_LOUDNESS / LOUD_NORM_PEAK the clips scaled to
+        ``target`` LUFS / dB peak, float32 out.  ``samples``, ``out``, ``out_offsets``: as sosfiltfilt_batch (``out`` is neither
+        made nor written in LOUD_MEASURE).  Returns rec (float64 [n, LOUD_N]; LOUD_FIELDS names the entries; NaN for a failed
+        clip), status and, in a normalising mode, out and offsets (the output range of a clip whose status is not CLIP_OK is
+        not written); with ``want_blocks`` also z (every z_j, clip after clip) and z_offsets."""
+        _need_loudness()
+        offsets, lengths, n = _clip_arrays(offsets, lengths)
+        rates = np.ascontiguousarray(np.broadcast_to(np.asarray(rates, np.int32), (n,)))
+        fmt = _sample_fmt(samples, fmt)
+        sptr, kind = _sample_source(samples, fmt, offsets, lengths)
+        res = {}
+        optr, okind, ooff = None, MEM_HOST, None
+        if mode != LOUD_MEASURE:
+            out, out_offsets, optr, okind = self._smooth_out(lengths, n, out, out_offsets)
+            ooff = out_offsets.ctypes.data
+            res.update(out=out, offsets=out_offsets)
+        rec = np.zeros((n, LOUD_N), np.float64)
+        status = np.zeros(n, np.int32)
+        z = z_off = None
+        if want_blocks:
+            counts = np.array([loudness_blocks(int(l), int(r), block_size) for l, r in zip(lengths, rates)], np.int64)
+            z_off = packed_offsets(counts)
+            z = np.zeros(int(counts.sum()), np.float64)
+            res.update(z=z, z_offsets=z_off, z_counts=counts)
+        _check(lib().afx_loudness_batch(self.handle, sptr, int(fmt), kind, offsets.ctypes.data, lengths.ctypes.data,
+                                        rates.ctypes.data, n, float(block_size), int(mode), float(target), rec.ctypes.data,
+                                        _ptr(z), _ptr(z_off), optr, okind, ooff, status.ctypes.data), "afx_loudness_batch")
+        res.update(rec=rec, status=status)
+        return res
 
     def energy_zcr_batch(self, samples, offsets, lengths, sr: int, frame_length: int = 2048, hop_length: int = 512,
                          flags: int = EZ_PREPROCESS | EZ_ENERGY | EZ_ZCR, fmt=None) -> dict:

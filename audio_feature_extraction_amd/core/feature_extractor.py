@@ -630,6 +630,18 @@ class AudioFeatureExtractor:
             raise _status_error(int(out["status"][0]), "preprocess_experiment", int(y.size))
         return out["clips"][0]
 
+    def normalize_volume_batch(self, signals: Sequence[np.ndarray], reference_level: float = -23.0) -> List[np.ndarray]:
+        """``normalize_volume`` of many signals in one device pass (``loudness.normalize_batch`` at this extractor's ``sr``)."""
+        from .. import loudness
+        return loudness.normalize_batch(signals, self.sr, reference_level, device=self._devices()[0])[0]
+
+    def normalize_volume(self, y: np.ndarray, reference_level: float = -23.0) -> np.ndarray:
+        """音量正規化 (04_feature_extraction_experiment/process_audio.py:134-147): the BS.1770 integrated loudness of ``y`` at
+        this extractor's ``sr`` brought to ``reference_level`` LUFS (config/experiment_config.yaml:26), measured and scaled on
+        the GPU; float32.  Audio shorter than a gating block (0.4 s) comes back unchanged, as the reference's does when
+        pyloudnorm raises; so does audio without a level (silence)."""
+        return self.normalize_volume_batch([y], reference_level)[0]
+
     def preprocess_alignment_batch(self, signals: Sequence[np.ndarray]) -> List[Optional[np.ndarray]]:
         """``preprocess_alignment`` of many signals in one device pass; ``None`` for a clip of fewer than 512 samples or with
         a NaN / inf sample."""

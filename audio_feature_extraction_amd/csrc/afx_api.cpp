@@ -51,6 +51,7 @@ DevEnv::DevEnv() {
   if (const char* v = getenv("AFX_TEST_ASSESS_BUDGET")) assess_budget = std::max<int64_t>(1, atoll(v));
   if (const char* v = getenv("AFX_TEST_SPECDIST_BUDGET")) specdist_budget = std::max<int64_t>(1, atoll(v));
   if (const char* v = getenv("AFX_TEST_SMOOTH_BUDGET")) smooth_budget = std::max<int64_t>(1, atoll(v));
+  if (const char* v = getenv("AFX_TEST_LOUD_BUDGET")) loud_budget = std::max<int64_t>(1, atoll(v));
   f0_dump = getenv("AFX_F0_DUMP");
 }
 const DevEnv& dev_env() { static const DevEnv e; return e; }
@@ -86,7 +87,9 @@ extern "C" void afx_destroy(afx_ctx* ctx) {
                     &ctx->ft_w, &ctx->ft_carry, &ctx->ft_tmax, &ctx->ft_in, &ctx->ft_out, &ctx->as_clips, &ctx->as_pieces, &ctx->as_spans,
                     &ctx->as_rec, &ctx->as_bad, &ctx->as_in, &ctx->cf_tw, &ctx->cf_jobs, &ctx->cf_work, &ctx->cf_filt, &ctx->cf_rec,
                     &ctx->cf_bad, &ctx->cf_in, &ctx->sm_tab, &ctx->sm_clips, &ctx->sm_bad, &ctx->sm_in, &ctx->sm_out, &ctx->ez_clips,
-                    &ctx->ez_y, &ctx->ez_m, &ctx->ez_s, &ctx->ez_neg, &ctx->ez_peak, &ctx->ez_energy, &ctx->ez_rate, &ctx->ez_rec})
+                    &ctx->ez_y, &ctx->ez_m, &ctx->ez_s, &ctx->ez_neg, &ctx->ez_peak, &ctx->ez_energy, &ctx->ez_rate, &ctx->ez_rec, &ctx->ld_tab,
+                    &ctx->ld_clips, &ctx->ld_carry, &ctx->ld_part, &ctx->ld_tpeak, &ctx->ld_tbad, &ctx->ld_seg, &ctx->ld_z, &ctx->ld_rec,
+                    &ctx->ld_gain, &ctx->ld_in, &ctx->ld_out})
     release(*b);
   if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
   delete ctx;

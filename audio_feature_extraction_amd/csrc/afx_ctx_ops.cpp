@@ -1230,3 +1230,164 @@ extern "C" int afx_energy_zcr_batch(afx_ctx* ctx, const void* samples, int sampl
   }
   return AFX_OK;
 }
+
+// ---- BS.1770 integrated loudness and loudness / peak normalisation (pyloudnorm's Meter and normalize) ----------------------
+// A chunk (cut_stft_chunk with the record of loud_cost): the samples staged packed when they are the host's, the records
+// uploaded, the two walks around the scan, the gate; the clips' eight scalars come back, log10 and the gain are taken here
+// (loud_finish, the host executor's code), and in a normalising mode the gains go up again for one more launch.
+extern "C" int afx_loudness_batch(afx_ctx* ctx, const void* samples, int sample_fmt, int mem_kind,
+                                  const int64_t* offsets, const int64_t* lengths, const int32_t* rates, int n_clips,
+                                  double block_size, int mode, double target,
+                                  double* out_rec, double* out_blocks, const int64_t* out_block_offsets,
+                                  float* out, int out_mem_kind, const int64_t* out_offsets, int32_t* out_status) {
+  const char* who = "afx_loudness_batch";
+  if (!ctx || n_clips < 0 || (n_clips > 0 && (!offsets || !lengths || !rates || !out_rec || !out_status))) return null_arg(who);
+  if (mode != AFX_LOUD_MEASURE && mode != AFX_LOUD_NORM_LOUDNESS && mode != AFX_LOUD_NORM_PEAK) { set_error(std::string(who) + ": unknown mode"); return AFX_ERR_INVALID; }
+  const bool norm = mode != AFX_LOUD_MEASURE;
+  int rc;
+  if ((rc = check_sample_format(who, sample_fmt, mem_kind)) != AFX_OK) return rc;
+  if (norm) {
+    if (n_clips > 0 && !out_offsets) return null_arg(who);
+    if ((rc = check_sample_format(who, sample_fmt, out_mem_kind)) != AFX_OK) return rc;
+    if (!std::isfinite(target)) { set_error(std::string(who) + ": the target must be finite"); return AFX_ERR_INVALID; }
+  }
+  if ((rc = check_clip_ranges(who, offsets, lengths, norm ? out_offsets : nullptr, n_clips, INT64_MAX / 8)) != AFX_OK) return rc;
+  if (out_blocks && out_block_offsets)
+    for (int i = 0; i < n_clips; ++i)
+      if (out_block_offsets[i] < 0 || out_block_offsets[i] > INT64_MAX / 16) { set_error(std::string(who) + ": out_block_offsets out of range"); return AFX_ERR_INVALID; }
+  std::vector<int> rate_list;
+  std::vector<int32_t> tab_of((size_t)n_clips), nbk((size_t)n_clips);
+  std::vector<int64_t> zoff((size_t)n_clips);
+  const double nan = std::nan("");
+  bool any = false;
+  int64_t zpos = 0;
+  for (int i = 0; i < n_clips; ++i) {
+    int code;
+    if (const char* why = loud_refusal(rates[i], block_size, &code)) {
+      set_error(std::string(who) + ": clip " + std::to_string(i) + ": " + why);
+      return code;
+    }
+    auto it = std::find(rate_list.begin(), rate_list.end(), (int)rates[i]);
+    if (it == rate_list.end()) {
+      if ((int)rate_list.size() == kLoudMaxRates) { set_error(std::string(who) + ": more than 16 distinct rates in one call is not supported"); return AFX_ERR_UNSUPPORTED; }
+      rate_list.push_back(rates[i]);
+      it = rate_list.end() - 1;
+    }
+    tab_of[i] = (int32_t)(it - rate_list.begin());
+    nbk[i] = (int32_t)loud_n_blocks(lengths[i], rates[i], block_size);
+    zoff[i] = out_block_offsets ? out_block_offsets[i] : zpos;
+    zpos += nbk[i];
+  }
+  for (int i = 0; i < n_clips; ++i) {
+    const bool live = mode == AFX_LOUD_NORM_PEAK ? lengths[i] > 0 : nbk[i] > 0;
+    out_status[i] = live ? AFX_CLIP_OK : AFX_CLIP_TOO_SHORT;
+    std::fill(out_rec + (size_t)AFX_LOUD_N * i, out_rec + (size_t)AFX_LOUD_N * (i + 1), nan);
+    any = any || live;
+  }
+  if (!any) return AFX_OK;
+  if (!samples || (norm && !out)) { set_error(std::string(who) + ": null samples / out"); return AFX_ERR_INVALID; }
+
+  (void)hipGetLastError();
+  HIP_TRY(hipSetDevice(ctx->device));
+  hipStream_t s = ctx->stream;
+  {
+    std::vector<FiltTab> tabs(rate_list.size());
+    for (size_t r = 0; r < rate_list.size(); ++r) loud_build_tab(rate_list[r], tabs[r]);
+    if ((rc = ensure(ctx->ld_tab, tabs.size() * sizeof(FiltTab))) != AFX_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(ctx->ld_tab.p, tabs.data(), tabs.size() * sizeof(FiltTab), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipStreamSynchronize(s));                  // tabs dies here
+  }
+  const FiltTab* d_tabs = (const FiltTab*)ctx->ld_tab.p;
+  const size_t esz = sample_fmt == AFX_FMT_S16 ? 2 : 4;
+  const bool h_in = mem_kind == AFX_MEM_HOST, h_out = norm && out_mem_kind == AFX_MEM_HOST;
+  const double gate = loud_abs_gate();
+  StftCost cost;
+  loud_cost(sample_fmt, mem_kind, out_mem_kind, mode, cost);
+  StftChunk ck;
+  std::vector<LoudClip> recs;
+  std::vector<int> idx;
+  std::vector<char> stage_in;
+  std::vector<float> stage_out, h_gain;
+  std::vector<double> h_dev, h_z;
+  for (int c0 = 0; c0 < n_clips; c0 = ck.next) {
+    cut_stft_chunk(offsets, lengths, n_clips, c0, dev_env().loud_budget, cost, ck);
+    recs.clear(); idx.clear();
+    int64_t tiles = 0, segs = 0, zs = 0, in_pos = 0, out_pos = 0;
+    for (int i : ck.idx) {
+      if (out_status[i] != AFX_CLIP_OK) continue;
+      LoudClip r{};
+      r.n = lengths[i];
+      r.in_off = h_in ? in_pos : offsets[i];
+      r.out_off = !norm ? 0 : h_out ? out_pos : out_offsets[i];
+      r.seg_off = segs; r.z_off = zs;
+      r.tg = block_size; r.rate = (double)rates[i];
+      r.first_tile = (int32_t)tiles; r.n_tiles = (int32_t)((r.n + kFiltTile - 1) / kFiltTile);
+      r.n_blocks = nbk[i]; r.tab = tab_of[i];
+      recs.push_back(r); idx.push_back(i);
+      tiles += r.n_tiles; segs += nbk[i] > 0 ? (int64_t)nbk[i] + 3 : 0; zs += nbk[i];
+      in_pos += (r.n + 3) / 4 * 4; out_pos += (r.n + 3) / 4 * 4;
+    }
+    const int n = (int)recs.size(), nt = (int)tiles;
+    if (n == 0) continue;
+    if (tiles > cost.tile_cap) { set_error(std::string(who) + ": clip too large for one launch"); return AFX_ERR_UNSUPPORTED; }
+    if ((rc = ensure(ctx->ld_clips, (size_t)n * sizeof(LoudClip))) != AFX_OK) return rc;
+    if ((rc = ensure(ctx->ld_carry, (size_t)nt * kFiltB * kLoudZ * sizeof(double))) != AFX_OK) return rc;
+    if ((rc = ensure(ctx->ld_part, (size_t)nt * kFiltB * 2 * sizeof(double))) != AFX_OK) return rc;
+    if ((rc = ensure(ctx->ld_tpeak, (size_t)nt * sizeof(float))) != AFX_OK) return rc;
+    if ((rc = ensure(ctx->ld_tbad, (size_t)nt * sizeof(uint32_t))) != AFX_OK) return rc;
+    if ((rc = ensure(ctx->ld_seg, (size_t)std::max<int64_t>(segs, 1) * sizeof(double))) != AFX_OK) return rc;
+    if ((rc = ensure(ctx->ld_z, (size_t)std::max<int64_t>(zs, 1) * sizeof(double))) != AFX_OK) return rc;
+    if ((rc = ensure(ctx->ld_rec, (size_t)n * kLoudRec * sizeof(double))) != AFX_OK) return rc;
+    const void* d_in = samples;
+    if (h_in) {
+      stage_in.assign((size_t)in_pos * esz, 0);
+      for (int q = 0; q < n; ++q)
+        std::memcpy(stage_in.data() + (size_t)recs[q].in_off * esz, (const char*)samples + (size_t)offsets[idx[q]] * esz, (size_t)recs[q].n * esz);
+      if ((rc = ensure(ctx->ld_in, stage_in.size())) != AFX_OK) return rc;
+      HIP_TRY(hipMemcpyAsync(ctx->ld_in.p, stage_in.data(), stage_in.size(), hipMemcpyHostToDevice, s));
+      d_in = ctx->ld_in.p;
+    }
+    HIP_TRY(hipMemcpyAsync(ctx->ld_clips.p, recs.data(), (size_t)n * sizeof(LoudClip), hipMemcpyHostToDevice, s));
+    const LoudClip* d_clips = (const LoudClip*)ctx->ld_clips.p;
+    double *carry = (double*)ctx->ld_carry.p, *part = (double*)ctx->ld_part.p, *d_rec = (double*)ctx->ld_rec.p;
+    HIP_TRY(launch_loud_ends(s, d_in, sample_fmt, d_tabs, d_clips, n, nt, carry, (float*)ctx->ld_tpeak.p, (uint32_t*)ctx->ld_tbad.p));
+    HIP_TRY(launch_loud_scan(s, d_tabs, d_clips, n, carry));
+    HIP_TRY(launch_loud_sums(s, d_in, sample_fmt, d_tabs, d_clips, n, nt, carry, part));
+    HIP_TRY(launch_loud_gate(s, d_clips, n, part, (const float*)ctx->ld_tpeak.p, (const uint32_t*)ctx->ld_tbad.p, gate,
+                             (double*)ctx->ld_seg.p, (double*)ctx->ld_z.p, d_rec));
+    h_dev.resize((size_t)n * kLoudRec);
+    HIP_TRY(hipMemcpyAsync(h_dev.data(), d_rec, h_dev.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (out_blocks && zs > 0) {
+      h_z.resize((size_t)zs);
+      HIP_TRY(hipMemcpyAsync(h_z.data(), ctx->ld_z.p, (size_t)zs * sizeof(double), hipMemcpyDeviceToHost, s));
+    }
+    HIP_TRY(hipStreamSynchronize(s));
+    h_gain.assign((size_t)n, std::nanf(""));
+    for (int q = 0; q < n; ++q) {
+      const int i = idx[q];
+      const double* d = h_dev.data() + (size_t)q * kLoudRec;
+      if (d[kLdBad] != 0.0) { out_status[i] = AFX_CLIP_NONFINITE; continue; }   // its record stays NaN, its output range as the caller left it
+      h_gain[q] = loud_finish(d, mode, target, out_rec + (size_t)AFX_LOUD_N * i);
+      if (out_blocks && nbk[i] > 0) std::memcpy(out_blocks + zoff[i], h_z.data() + recs[q].z_off, (size_t)nbk[i] * sizeof(double));
+    }
+    if (!norm) continue;
+    float* d_out = out;
+    if (h_out) {
+      if ((rc = ensure(ctx->ld_out, (size_t)out_pos * sizeof(float))) != AFX_OK) return rc;
+      d_out = (float*)ctx->ld_out.p;
+    }
+    if ((rc = ensure(ctx->ld_gain, (size_t)n * sizeof(float))) != AFX_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(ctx->ld_gain.p, h_gain.data(), (size_t)n * sizeof(float), hipMemcpyHostToDevice, s));
+    HIP_TRY(launch_loud_gain(s, d_in, sample_fmt, d_clips, n, nt, (const float*)ctx->ld_gain.p, d_out));
+    if (h_out) {
+      stage_out.resize((size_t)out_pos);
+      HIP_TRY(hipMemcpyAsync(stage_out.data(), d_out, (size_t)out_pos * sizeof(float), hipMemcpyDeviceToHost, s));
+    }
+    HIP_TRY(hipStreamSynchronize(s));
+    if (h_out)
+      for (int q = 0; q < n; ++q)
+        if (out_status[idx[q]] == AFX_CLIP_OK)
+          std::memcpy(out + out_offsets[idx[q]], stage_out.data() + recs[q].out_off, (size_t)recs[q].n * sizeof(float));
+  }
+  return AFX_OK;
+}

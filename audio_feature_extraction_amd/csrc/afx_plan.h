@@ -21,6 +21,7 @@
 #include "afx_frames3.h"
 #include "afx_groups.h"
 #include "afx_internal.h"
+#include "afx_loudness.h"
 #include "afx_resample.h"
 #include "afx_rhythm.h"
 #include "afx_smooth.h"
@@ -64,6 +65,9 @@ struct afx_ctx {
   // median-filtered and smoothed signals, the sign plane, the smoothed peaks, the frame rows of both groups, the records
   DevBuf sm_tab, sm_clips, sm_bad, sm_in, sm_out;
   DevBuf ez_clips, ez_y, ez_m, ez_s, ez_neg, ez_peak, ez_energy, ez_rate, ez_rec;
+  // afx_loudness_batch: one table per distinct rate, a chunk's clip records, the blocks' states and partial sums, the tiles'
+  // peaks and flags, the segment sums, z_j, the clips' scalars, the gains, staging of host batches
+  DevBuf ld_tab, ld_clips, ld_carry, ld_part, ld_tpeak, ld_tbad, ld_seg, ld_z, ld_rec, ld_gain, ld_in, ld_out;
 };
 
 struct afx_plan {

@@ -4,5 +4,6 @@ to the MI355X engine in ``audio_feature_extraction_amd``.  This is an alias, not
 names are the same class objects."""
 from audio_feature_extraction_amd import AudioFeatureExtractor, FeatureEvaluator, __version__
 from audio_feature_extraction_amd import quality  # noqa: F401  (the same module object under the alias)
+from audio_feature_extraction_amd import loudness  # noqa: F401  (likewise)
 
 __all__ = ["AudioFeatureExtractor", "FeatureEvaluator"]

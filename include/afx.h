@@ -740,6 +740,76 @@ int afx_energy_zcr_batch(afx_ctx* ctx, const void* samples, int sample_fmt, int 
                          int sr, int frame_length, int hop_length, int flags,
                          double* out_rec /*[n_clips][AFX_EZ_N]*/, int32_t* out_status);
 
+/* ITU-R BS.1770-4 integrated (gated) loudness of mono clips and loudness / peak normalisation, with the semantics of
+ * pyloudnorm 0.1.x Meter(rate, block_size).integrated_loudness and normalize.loudness / normalize.peak at the experiment's
+ * call sites (04_feature_extraction_experiment/process_audio.py:134-147: K-weighting, mono).  All seven symbols are newer
+ * than AFX_VERSION 107 says: a binding detects them by their presence.
+ *
+ * The measure.  For a clip x[0 .. n) of float32 samples (S16: value / 32768) at `rate` and T_g = block_size seconds:
+ *   - K-weighting: the two sections of afx_kweight_sos, a causal cascade from zero state (scipy.signal.lfilter without zi),
+ *     both sections in float64 with no rounding between them (pyloudnorm rounds each stage to the array's float32);
+ *   - gating blocks: numBlocks = int(round_half_even((n / rate - T_g) / (T_g / 4)) + 1); block j covers the samples
+ *     [b_j, b_{j + 4}) cut at n, b_k = int(T_g * (k * 0.25) * rate) in float64 left to right -- four consecutive segments
+ *     --, z_j = sum y^2 / (T_g * rate), the divisor the same for a last block that the rounding left partial;
+ *   - gates in the linear domain: the first set z_j >= 10^((-70 + 0.691) / 10); the second z_j > (first-set mean) / 10 and
+ *     z_j > 10^((-70 + 0.691) / 10); LUFS = -0.691 + 10 log10(second-set mean), -inf when the set is empty.
+ * The K-weighted samples are never stored: the filter runs in the blocks of afx_sosfiltfilt_batch (64 samples, states
+ * carried in the per-section basis), once for the blocks' end states and once, from the true entry states, for the sums of
+ * squares (afx_loudness_geometry and DESIGN.md).  The sums are float64 in one fixed order; log10 and the gain are host
+ * double arithmetic on the gated means, the same code for the device path and the host executor.
+ *
+ * mode: AFX_LOUD_MEASURE (out may be NULL and is not written); AFX_LOUD_NORM_LOUDNESS: out = float32(gain) * x with
+ * gain = 10^((target - LUFS) / 20); AFX_LOUD_NORM_PEAK: gain = 10^(target / 20) / max|x| (the gain needs no level: the loudness
+ * fields are the measure's when the clip is long enough for it, NaN otherwise).  One rounded float32 product per sample (numpy
+ * 1.24: a float32 array times a float64 scalar).  A clip without a level -- LUFS = -inf, or a zero peak -- comes back
+ * unchanged with gain 1 (pyloudnorm would multiply by inf).
+ * out_rec holds AFX_LOUD_N doubles per clip (AFX_LOUD_*); GAIN and PEAK_OUT are NaN in AFX_LOUD_MEASURE.  out_blocks (host,
+ * NULL ok) receives every z_j of clip i at out_block_offsets[i] (NULL: packed, clip after clip; afx_loudness_blocks
+ * gives the counts).  out_status (host): AFX_CLIP_TOO_SHORT for n < block_size * rate (pyloudnorm raises; AFX_LOUD_NORM_PEAK:
+ * for n == 0 only) and AFX_CLIP_NONFINITE for a NaN / inf sample -- the record of such a clip is NaN and its output range is
+ * not written.  Results are bit-reproducible (no atomics), a clip never reads its neighbours in the packed buffer, and
+ * its result depends neither on the rest of the batch nor on how the batch was cut into chunks (afx_stft_chunks with the
+ * record of afx_loudness_cost).
+ * rates[i] is clip i's own rate: a batch may hold up to 16 distinct rates (AFX_ERR_UNSUPPORTED above).  Rates from 4000 to
+ * 192000 Hz; block_size * rate / 4 must exceed 64 samples and block_size 3600 s at most (AFX_ERR_UNSUPPORTED); a rate < 1, a
+ * block_size that is not positive and finite, a target that is not finite, an unknown mode: AFX_ERR_INVALID.
+ *
+ * afx_kweight_sos (host-only): the high shelf (+4 dB, Q = 1 / sqrt 2, 1500 Hz) and the high pass (Q = 0.5, 38 Hz) in RBJ
+ * form, divided through by a0: rows b0 b1 b2 1 a1 a2.  AFX_ERR_INVALID for a rate outside 4000 .. 192000.
+ * afx_loudness_geometry (host-only): info[5] = samples per block, blocks per tile, lowest rate, highest rate, most distinct
+ * rates of a call.
+ * afx_loudness_blocks (host-only): numBlocks of a clip of n samples (0: too short to measure).
+ * afx_loudness_host (host-only): one host clip through the same block decomposition, tables, operations and summation
+ * order on the CPU -- the specification of the kernels, bit for bit.  out_blocks (NULL ok): its z_j.
+ * afx_loudness_cost (host-only): cost[6] for afx_stft_chunks (bytes per frame, tile, sample, clip; frames per tile, most
+ * tiles): 64 bytes per block of 64 samples (512 per frame of the chunk rule), the uploads, 8 per tile, 3648 per clip. */
+enum { AFX_LOUD_MEASURE = 0, AFX_LOUD_NORM_LOUDNESS = 1, AFX_LOUD_NORM_PEAK = 2 };
+enum {
+  AFX_LOUD_LUFS = 0,        /* integrated loudness; -inf when the second set is empty */
+  AFX_LOUD_BLOCKS = 1,      /* gating blocks */
+  AFX_LOUD_N1 = 2,          /* blocks of the first set (absolute gate) */
+  AFX_LOUD_N2 = 3,          /* blocks of the second set (both gates) */
+  AFX_LOUD_GAMMA_R = 4,     /* the relative threshold, dB */
+  AFX_LOUD_GATED_MS = 5,    /* mean of z_j over the second set (0 when empty) */
+  AFX_LOUD_PEAK = 6,        /* max |x| */
+  AFX_LOUD_GAIN = 7,        /* the float32 gain applied */
+  AFX_LOUD_PEAK_OUT = 8,    /* max |out| */
+  AFX_LOUD_FIRST_MS = 9,    /* mean of z_j over the first set (0 when empty) */
+  AFX_LOUD_UNGATED_MS = 10, /* mean of every z_j */
+  AFX_LOUD_N = 11
+};
+int afx_kweight_sos(int rate, double* sos /*[2][6]*/);
+int afx_loudness_geometry(int32_t* info /*[5]*/);
+int afx_loudness_blocks(int64_t n, int rate, double block_size, int64_t* n_blocks);
+int afx_loudness_cost(int sample_fmt, int mem_kind, int out_mem_kind, int mode, int64_t* cost /*[6]*/);
+int afx_loudness_host(const void* samples, int sample_fmt, int64_t n, int rate, double block_size, double target, int mode,
+                      double* out_rec /*[AFX_LOUD_N]*/, double* out_blocks, float* out, int32_t* out_status);
+int afx_loudness_batch(afx_ctx* ctx, const void* samples, int sample_fmt, int mem_kind,
+                       const int64_t* offsets, const int64_t* lengths, const int32_t* rates, int n_clips,
+                       double block_size, int mode, double target,
+                       double* out_rec /*[n_clips][AFX_LOUD_N]*/, double* out_blocks, const int64_t* out_block_offsets,
+                       float* out, int out_mem_kind, const int64_t* out_offsets, int32_t* out_status);
+
 /* The recording screen of 00_audio_data_collection_experiment/audio_format_assessment.py:143-300 (detect_silence,
  * check_volume_levels, check_amplitude_stability, estimate_snr) and the sums behind the scores of
  * audio_quality_assessment.py:150-280 (SNR of the difference, Pearson correlation, MSE), as per-clip reductions.  All five
