@@ -57,6 +57,7 @@ EZ_FIELDS = ("T", "fl", "hop", "energy_mean", "energy_std", "energy_p10", "zcr_m
              "peak_smooth", "peak_in", "peak_filt")
 LOUD_MEASURE, LOUD_NORM_LOUDNESS, LOUD_NORM_PEAK = 0, 1, 2                    # afx_loudness_batch: its modes
 LOUD_N = 11                                                                  # doubles per clip of its record
+CLIP_TOO_LONG = 3                                                            # afx_gate_batch: more than chunk_size samples
 LOUD_FIELDS = ("lufs", "blocks", "n1", "n2", "gamma_r", "gated_ms", "peak", "gain", "peak_out", "first_ms", "ungated_ms")
 GROUPS_STATS = 24                                                            # doubles per clip of its record
 K_NAMES = ("trim_blocks", "trim_decide", "frames", "dct", "stats")
@@ -83,11 +84,23 @@ SYMBOLS = (
     "afx_medfilt_batch", "afx_savgol_batch", "afx_energy_zcr_batch",
     "afx_kweight_sos", "afx_loudness_geometry", "afx_loudness_blocks", "afx_loudness_cost", "afx_loudness_host",
     "afx_loudness_batch",
+    "afx_gate_params", "afx_gate_cost", "afx_gate_batch",
 )
 
 
 class AfxError(RuntimeError):
     pass
+
+
+class GateOpts(C.Structure):
+    """afx_gate_opts: noisereduce's arguments as afx_gate_batch takes them."""
+    _fields_ = [
+        ("sr", C.c_int32), ("n_fft", C.c_int32), ("win_length", C.c_int32), ("hop", C.c_int32),
+        ("stationary", C.c_int32), ("clip_noise", C.c_int32), ("padding", C.c_int32), ("chunk_size", C.c_int32),
+        ("prop_decrease", C.c_double), ("time_constant_s", C.c_double), ("freq_mask_smooth_hz", C.c_double),
+        ("time_mask_smooth_ms", C.c_double), ("thresh_n_mult", C.c_double), ("sigmoid_slope", C.c_double),
+        ("n_std_thresh", C.c_double),
+    ]
 
 
 class Params(C.Structure):
@@ -217,6 +230,10 @@ def lib() -> C.CDLL:
             L.afx_loudness_cost.argtypes = [i32, i32, i32, i32, vp]
             L.afx_loudness_host.argtypes = [vp, i32, C.c_int64, i32, dbl, dbl, i32, vp, vp, vp, vp]
             L.afx_loudness_batch.argtypes = [vp, vp, i32, i32, vp, vp, vp, i32, dbl, i32, dbl, vp, vp, vp, vp, i32, vp, vp]
+        if hasattr(L, "afx_gate_batch"):                     # newer than version 107 says: found by their presence
+            L.afx_gate_params.argtypes = [vp, C.c_int64, vp, vp, vp, vp]
+            L.afx_gate_cost.argtypes = [vp, i32, i32, i32, i32, vp]
+            L.afx_gate_batch.argtypes = [vp, vp, i32, i32, vp, vp, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp]
         if hasattr(L, "afx_rfft_host"):                      # absent from a library built before the mixed-radix lengths
             L.afx_rfft_host.argtypes = [i32, vp, vp]
         _lib = L
@@ -641,6 +658,50 @@ def energy_zcr_host(y, frame_length: int = 2048, hop_length: int = 512, flags: i
     _check(lib().afx_energy_zcr_host(y.ctypes.data, int(y.size), int(frame_length), int(hop_length), int(flags),
                                      rec.ctypes.data, status.ctypes.data), "afx_energy_zcr_host")
     return {"rec": rec, "status": int(status[0])}
+
+
+def _need_gate():
+    if not hasattr(lib(), "afx_gate_batch"):
+        raise NotImplementedError("this libafx has no afx_gate_batch")
+
+
+def gate_opts(sr: int, stationary: bool = False, prop_decrease: float = 1.0, time_constant_s: float = 2.0,
+              freq_mask_smooth_hz: float = 500, time_mask_smooth_ms: float = 50, thresh_n_mult_nonstationary: float = 2,
+              sigmoid_slope_nonstationary: float = 10, n_std_thresh_stationary: float = 1.5, chunk_size: int = 600000,
+              padding: int = 30000, n_fft: int = 1024, win_length=None, hop_length=None,
+              clip_noise_stationary: bool = True) -> GateOpts:
+    """noisereduce.reduce_noise's keywords (its names and defaults) as the record afx_gate_batch takes."""
+    win = int(n_fft) if win_length is None else int(win_length)
+    hop = win // 4 if hop_length is None else int(hop_length)
+    return GateOpts(int(sr), int(n_fft), win, hop, int(bool(stationary)), int(bool(clip_noise_stationary)), int(padding),
+                    int(chunk_size), float(prop_decrease), float(time_constant_s), float(freq_mask_smooth_hz),
+                    float(time_mask_smooth_ms), float(thresh_n_mult_nonstationary), float(sigmoid_slope_nonstationary),
+                    float(n_std_thresh_stationary))
+
+
+def gate_params(opts: GateOpts, length: int = 0) -> dict:
+    """Host-only: afx_gate_params, what noisereduce derives from its arguments: n_f, n_t, the frames T of a clip of
+    ``length`` samples, whether the mask is smoothed, beta, and the normalised taps of each axis of the smoothing filter.
+    ValueError where noisereduce raises."""
+    _need_gate()
+    info = np.zeros(4, np.int64)
+    beta = C.c_double()
+    tf, tt = np.zeros(257, np.float64), np.zeros(129, np.float64)
+    _check(lib().afx_gate_params(C.addressof(opts), int(length), info.ctypes.data, C.addressof(beta), tf.ctypes.data,
+                                 tt.ctypes.data), "afx_gate_params")
+    n_f, n_t = int(info[0]), int(info[1])
+    return {"n_f": n_f, "n_t": n_t, "frames": int(info[2]), "smooth": bool(info[3]), "beta": float(beta.value),
+            "taps_f": tf[:2 * n_f + 1].copy(), "taps_t": tt[:2 * n_t + 1].copy()}
+
+
+def gate_cost(opts: GateOpts, fmt: int = FMT_F32, mem: int = MEM_HOST, out_mem: int = MEM_HOST, with_noise: bool = False) -> np.ndarray:
+    """Host-only: the int64 [6] cost record afx_gate_batch cuts a batch with, for :func:`stft_chunks` (over
+    max(length, noise length) per clip)."""
+    _need_gate()
+    cost = np.zeros(6, np.int64)
+    _check(lib().afx_gate_cost(C.addressof(opts), int(fmt), int(mem), int(out_mem), int(bool(with_noise)), cost.ctypes.data),
+           "afx_gate_cost")
+    return cost
 
 
 def _need_loudness():
@@ -1138,6 +1199,53 @@ class Context(_Owner):
                                         rates.ctypes.data, n, float(block_size), int(mode), float(target), rec.ctypes.data,
                                         _ptr(z), _ptr(z_off), optr, okind, ooff, status.ctypes.data), "afx_loudness_batch")
         res.update(rec=rec, status=status)
+        return res
+
+    def gate_batch(self, samples, offsets, lengths, opts: GateOpts, noise_offsets=None, noise_lengths=None, fmt=None,
+                   out=None, out_offsets=None, want_thresh: bool = False, want_mask: bool = False) -> dict:
+        """afx_gate_batch: spectral-gating noise reduction (noisereduce.reduce_noise as :func:`gate_opts` records it) of the
+        clips samples[offsets[i] .. + lengths[i]), float32 out.  ``noise_offsets`` / ``noise_lengths``: each clip's noise clip
+        in the same buffer (stationary; None: the clip itself).  ``samples``, ``out``, ``out_offsets``: as sosfiltfilt_batch.
+        Returns out, offsets and status (CLIP_TOO_SHORT, CLIP_TOO_LONG: the clip's output range is not written;
+        CLIP_NONFINITE: zeros); stationary with ``want_thresh``: thresh, float64 [n, n_fft / 2 + 1] in dB; with ``want_mask``:
+        mask, a list of bool [n_fft / 2 + 1, T] arrays (None for a clip that is empty or too long)."""
+        _need_gate()
+        offsets, lengths, n = _clip_arrays(offsets, lengths)
+        fmt = _sample_fmt(samples, fmt)
+        sptr, kind = _sample_source(samples, fmt, offsets, lengths)
+        if (noise_offsets is None) != (noise_lengths is None):
+            raise ValueError("noise_offsets and noise_lengths come together")
+        n_off = n_len = None
+        if noise_offsets is not None:
+            n_off, n_len, nn = _clip_arrays(noise_offsets, noise_lengths)
+            if nn != n:
+                raise ValueError("noise_offsets must have one entry per clip")
+            _sample_source(samples, fmt, n_off, n_len)
+        out, out_offsets, optr, okind = self._smooth_out(lengths, n, out, out_offsets)
+        status = np.zeros(n, np.int32)
+        bins, words = opts.n_fft // 2 + 1, (opts.n_fft // 2 + 1 + 31) // 32
+        stat = bool(opts.stationary)
+        thresh = np.zeros((n, bins), np.float64) if (want_thresh and stat) else None
+        frames = [0 if (l == 0 or l > opts.chunk_size or (stat and n_len is not None and n_len[i] == 0))
+                  else 1 + (int(l) + 2 * opts.padding) // max(opts.hop, 1) for i, l in enumerate(lengths)]
+        plane = np.zeros(sum(frames) * words, np.uint32) if (want_mask and stat) else None
+        _check(lib().afx_gate_batch(self.handle, sptr, int(fmt), kind, offsets.ctypes.data, lengths.ctypes.data, n,
+                                    _ptr(n_off), _ptr(n_len), C.addressof(opts), optr, okind, out_offsets.ctypes.data,
+                                    _ptr(thresh), _ptr(plane), status.ctypes.data), "afx_gate_batch")
+        res = {"out": out, "offsets": out_offsets, "status": status}
+        if thresh is not None:
+            res["thresh"] = thresh
+        if plane is not None:
+            masks, pos = [], 0
+            for T in frames:
+                if T == 0:
+                    masks.append(None)
+                    continue
+                w = plane[pos:pos + T * words].reshape(T, words)
+                b = np.unpackbits(w.view(np.uint8), axis=1, bitorder="little")[:, :bins]
+                masks.append(np.ascontiguousarray(b.T.astype(bool)))
+                pos += T * words
+            res["mask"] = masks
         return res
 
     def energy_zcr_batch(self, samples, offsets, lengths, sr: int, frame_length: int = 2048, hop_length: int = 512,

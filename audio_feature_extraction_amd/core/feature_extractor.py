@@ -642,6 +642,56 @@ class AudioFeatureExtractor:
         pyloudnorm raises; so does audio without a level (silence)."""
         return self.normalize_volume_batch([y], reference_level)[0]
 
+    # config/experiment_config.yaml:15-22
+    _NR_WIENER = dict(stationary=True, prop_decrease=0.95)
+    _NR_SPECTRAL = dict(n_fft=2048, win_length=2048, hop_length=512)
+
+    def _nr_keywords(self, method: str, kw: dict) -> dict:
+        if method not in ("wiener", "spectral"):
+            raise ValueError(f"method={method!r} is not supported ('wiener' or 'spectral')")
+        return {**(self._NR_WIENER if method == "wiener" else self._NR_SPECTRAL), **kw}
+
+    def apply_noise_reduction_batch(self, signals: Sequence[np.ndarray], method: str = "wiener", **kw) -> List[np.ndarray]:
+        """``apply_noise_reduction`` of many signals in one device pass."""
+        from .. import effects
+        return effects.reduce_noise_batch(signals, self.sr, device=lambda: self._devices()[0], **self._nr_keywords(method, kw))
+
+    def apply_noise_reduction(self, y: np.ndarray, method: str = "wiener", **kw) -> np.ndarray:
+        """應用降噪處理 (04_feature_extraction_experiment/process_audio.py:82-98): ``noisereduce.reduce_noise`` at this
+        extractor's ``sr`` and on the GPU, with the configuration's values as defaults -- ``method="wiener"``: stationary
+        gating with ``prop_decrease=0.95`` at noisereduce's 1024 / 256 frames; ``"spectral"``: non-stationary gating at
+        2048 / 2048 / 512.  Further keywords are noisereduce's.  float32 of ``y``'s length."""
+        return self.apply_noise_reduction_batch([y], method, **kw)[0]
+
+    def process_recordings_batch(self, signals: Sequence[np.ndarray], method: str = "wiener", reference_level: float = -23.0,
+                                 **kw) -> Tuple[List[np.ndarray], List[Optional[float]]]:
+        """The conditioning of 04_feature_extraction_experiment/process_audio.py:28-61 without its VAD: ``normalize_volume``
+        then ``apply_noise_reduction``, the normalised samples staying on the device between the two.  Returns the denoised
+        signals (what the reference writes to disk) and, per signal, the integrated loudness of the *normalised* signal as
+        the reference reports it -- ``None`` where its meter raises ``ValueError`` (shorter than a gating block) and for a
+        signal that is not finite."""
+        from .. import effects, loudness
+        opts = effects._gate_opts(self.sr, self._nr_keywords(method, dict(kw)))
+        sig = effects._gate_signals([loudness._as_clip(s, f"signal {i}") for i, s in enumerate(signals)], opts,
+                                    "process_recordings_batch")
+        if not sig:
+            return [], []
+        ctx = effects._ctx(self._devices()[0])
+        buf, offsets, lengths = loudness._pack(sig)
+        dev = _native.DeviceBuffer(ctx, max(4 * buf.size, 4))
+        try:
+            norm = ctx.loudness_batch(buf, offsets, lengths, self.sr, 0.400, _native.LOUD_NORM_LOUDNESS, float(reference_level),
+                                      out=dev, out_offsets=offsets)
+            for i in np.flatnonzero(norm["status"] != _native.CLIP_OK):   # the reference keeps such audio as it is
+                dev.upload(sig[i], 4 * int(offsets[i]))
+            meas = ctx.loudness_batch(dev, offsets, lengths, self.sr, 0.400, _native.LOUD_MEASURE, fmt=_native.FMT_F32)
+            out = ctx.gate_batch(dev, offsets, lengths, opts, fmt=_native.FMT_F32)
+        finally:
+            dev.free()
+        ys = [out["out"][o:o + n].copy() for o, n in zip(out["offsets"], lengths)]
+        ls = [float(r[0]) if st == _native.CLIP_OK else None for r, st in zip(meas["rec"], meas["status"])]
+        return ys, ls
+
     def preprocess_alignment_batch(self, signals: Sequence[np.ndarray]) -> List[Optional[np.ndarray]]:
         """``preprocess_alignment`` of many signals in one device pass; ``None`` for a clip of fewer than 512 samples or with
         a NaN / inf sample."""

@@ -52,6 +52,7 @@ DevEnv::DevEnv() {
   if (const char* v = getenv("AFX_TEST_SPECDIST_BUDGET")) specdist_budget = std::max<int64_t>(1, atoll(v));
   if (const char* v = getenv("AFX_TEST_SMOOTH_BUDGET")) smooth_budget = std::max<int64_t>(1, atoll(v));
   if (const char* v = getenv("AFX_TEST_LOUD_BUDGET")) loud_budget = std::max<int64_t>(1, atoll(v));
+  if (const char* v = getenv("AFX_TEST_GATE_BUDGET")) gate_budget = std::max<int64_t>(1, atoll(v));
   f0_dump = getenv("AFX_F0_DUMP");
 }
 const DevEnv& dev_env() { static const DevEnv e; return e; }
@@ -89,7 +90,9 @@ extern "C" void afx_destroy(afx_ctx* ctx) {
                     &ctx->cf_bad, &ctx->cf_in, &ctx->sm_tab, &ctx->sm_clips, &ctx->sm_bad, &ctx->sm_in, &ctx->sm_out, &ctx->ez_clips,
                     &ctx->ez_y, &ctx->ez_m, &ctx->ez_s, &ctx->ez_neg, &ctx->ez_peak, &ctx->ez_energy, &ctx->ez_rate, &ctx->ez_rec, &ctx->ld_tab,
                     &ctx->ld_clips, &ctx->ld_carry, &ctx->ld_part, &ctx->ld_tpeak, &ctx->ld_tbad, &ctx->ld_seg, &ctx->ld_z, &ctx->ld_rec,
-                    &ctx->ld_gain, &ctx->ld_in, &ctx->ld_out})
+                    &ctx->ld_gain, &ctx->ld_in, &ctx->ld_out, &ctx->gt_tab, &ctx->gt_grids, &ctx->gt_y, &ctx->gt_bad, &ctx->gt_mag,
+                    &ctx->gt_nmag, &ctx->gt_mask, &ctx->gt_fwd, &ctx->gt_bits, &ctx->gt_thr, &ctx->gt_amp, &ctx->gt_rows, &ctx->gt_in,
+                    &ctx->gt_out})
     release(*b);
   if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
   delete ctx;

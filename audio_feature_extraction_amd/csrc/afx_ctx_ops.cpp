@@ -1391,3 +1391,228 @@ extern "C" int afx_loudness_batch(afx_ctx* ctx, const void* samples, int sample_
   }
   return AFX_OK;
 }
+
+// ---- spectral-gating noise reduction (noisereduce's reduce_noise) -----------------------------------------------------------
+// A chunk (cut_stft_chunk with the record of gate_cost over max(length, noise length)): the clips and their noise clips
+// staged packed when they are the host's, both grids' records uploaded, the samples brought to float32 with their
+// non-finite flags, then the passes of afx_gate.hip in order.  The flags, thr and the bit plane come back with the output.
+extern "C" int afx_gate_batch(afx_ctx* ctx, const void* samples, int sample_fmt, int mem_kind,
+                              const int64_t* offsets, const int64_t* lengths, int n_clips,
+                              const int64_t* noise_offsets, const int64_t* noise_lengths, const afx_gate_opts* opts,
+                              float* out, int out_mem_kind, const int64_t* out_offsets,
+                              double* out_thresh, uint32_t* out_mask, int32_t* out_status) {
+  const char* who = "afx_gate_batch";
+  if (!ctx || !opts || n_clips < 0 || (n_clips > 0 && (!offsets || !lengths || !out_offsets || !out_status))) return null_arg(who);
+  if ((noise_offsets == nullptr) != (noise_lengths == nullptr)) return null_arg(who);
+  int rc;
+  if ((rc = check_sample_format(who, sample_fmt, mem_kind)) != AFX_OK) return rc;
+  if ((rc = check_sample_format(who, sample_fmt, out_mem_kind)) != AFX_OK) return rc;
+  GateDerived gd;
+  const char* why = "";
+  if ((rc = gate_derive(*opts, gd, &why)) != AFX_OK) { set_error(std::string(who) + ": " + why); return rc; }
+  const int n_fft = opts->n_fft, hop = opts->hop, pad = opts->padding;
+  if ((n_fft != 1024 && n_fft != 2048) || hop != n_fft / 4) { set_error(std::string(who) + ": n_fft / hop must be 1024 / 256 or 2048 / 512"); return AFX_ERR_UNSUPPORTED; }
+  if ((rc = check_clip_ranges(who, offsets, lengths, out_offsets, n_clips, INT64_MAX / 8)) != AFX_OK) return rc;
+  const bool with_noise = noise_offsets != nullptr, stat = opts->stationary != 0;
+  if (with_noise && (rc = check_clip_ranges(who, noise_offsets, noise_lengths, nullptr, n_clips, INT64_MAX / 8)) != AFX_OK) return rc;
+  const int bins = gate_bins(n_fft), pitch = gate_pitch(n_fft), words = gate_words(n_fft), fpw = n_fft == 1024 ? 2 : 1;
+  const double nan = std::nan("");
+
+  // the noise clip of clip i (stationary): its own, or the clip; cut to chunk_size samples on request
+  auto noise_len = [&](int i) {
+    int64_t l = with_noise ? noise_lengths[i] : lengths[i];
+    if (opts->clip_noise && l > opts->chunk_size) l = opts->chunk_size;
+    return l;
+  };
+  std::vector<int64_t> eff((size_t)n_clips), moff((size_t)n_clips);
+  bool any = false;
+  int64_t mpos = 0;
+  for (int i = 0; i < n_clips; ++i) {
+    const int64_t L = lengths[i];
+    int st = AFX_CLIP_OK;
+    if (L == 0 || (stat && with_noise && noise_lengths[i] == 0)) st = AFX_CLIP_TOO_SHORT;
+    else if (L > opts->chunk_size) st = AFX_CLIP_TOO_LONG;
+    else if (stat && noise_len(i) > kGateMaxChunk) { set_error(std::string(who) + ": a noise clip of more than 2^24 samples is not supported"); return AFX_ERR_UNSUPPORTED; }
+    out_status[i] = st;
+    eff[i] = st != AFX_CLIP_OK ? 0 : stat ? std::max(L, noise_len(i)) : L;
+    moff[i] = mpos;
+    if (st == AFX_CLIP_OK) mpos += gate_frames(L, hop, pad) * words;
+    if (out_thresh) std::fill(out_thresh + (size_t)bins * i, out_thresh + (size_t)bins * (i + 1), nan);
+    any = any || st == AFX_CLIP_OK;
+  }
+  if (!any) return AFX_OK;
+  if (!samples || !out) { set_error(std::string(who) + ": null samples / out"); return AFX_ERR_INVALID; }
+
+  (void)hipGetLastError();
+  HIP_TRY(hipSetDevice(ctx->device));
+  hipStream_t s = ctx->stream;
+  GateTabs tb{};
+  const int n_f = gd.smooth ? gd.n_f : 0, n_t = gd.smooth ? gd.n_t : 0;
+  {
+    constexpr size_t kTapDoubles = 2 * kGateMaxNf + 1 + 2 * kGateMaxNt + 1;
+    std::vector<char> tab(kTapDoubles * sizeof(double) + ((size_t)n_fft + 4096) * sizeof(float));
+    double* td = (double*)tab.data();
+    float* tf = (float*)(tab.data() + kTapDoubles * sizeof(double));
+    if (gd.smooth) {
+      std::memcpy(td, gd.vf, (size_t)(2 * n_f + 1) * sizeof(double));
+      std::memcpy(td + 2 * kGateMaxNf + 1, gd.vt, (size_t)(2 * n_t + 1) * sizeof(double));
+    } else {
+      td[0] = 1.0; td[2 * kGateMaxNf + 1] = 1.0;
+    }
+    for (int i = 0; i < n_fft; ++i) tf[i] = (float)(0.5 - 0.5 * std::cos(2.0 * M_PI * (double)i / (double)n_fft));
+    for (int k = 0; k < 1024; ++k) {
+      tf[n_fft + 2 * k] = (float)std::cos(2.0 * M_PI * k / 1024.0); tf[n_fft + 2 * k + 1] = (float)-std::sin(2.0 * M_PI * k / 1024.0);
+      tf[n_fft + 2048 + 2 * k] = (float)std::cos(2.0 * M_PI * k / 2048.0); tf[n_fft + 2048 + 2 * k + 1] = (float)-std::sin(2.0 * M_PI * k / 2048.0);
+    }
+    if ((rc = ensure(ctx->gt_tab, tab.size())) != AFX_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(ctx->gt_tab.p, tab.data(), tab.size(), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipStreamSynchronize(s));                  // tab dies here
+    tb.vf = (const double*)ctx->gt_tab.p;
+    tb.vt = tb.vf + 2 * kGateMaxNf + 1;
+    tb.window = (const float*)(tb.vf + kTapDoubles);
+    tb.w1024 = tb.window + n_fft;
+    tb.w2048 = tb.w1024 + 2048;
+  }
+
+  const size_t esz = sample_fmt == AFX_FMT_S16 ? 2 : 4;
+  const bool h_in = mem_kind == AFX_MEM_HOST, h_out = out_mem_kind == AFX_MEM_HOST;
+  StftCost cost;
+  gate_cost(n_fft, stat, pad, sample_fmt, mem_kind, out_mem_kind, with_noise, cost);
+  StftChunk ck;
+  std::vector<GateGrid> sig, noi;
+  std::vector<HpssClip> prs, prn;
+  std::vector<char> stage_in, recs;
+  std::vector<uint32_t> h_bad, h_bits;
+  std::vector<double> h_thr;
+  for (int c0 = 0; c0 < n_clips; c0 = ck.next) {
+    cut_stft_chunk(offsets, eff.data(), n_clips, c0, dev_env().gate_budget, cost, ck);
+    const int n = (int)ck.idx.size();
+    if (n == 0) continue;
+    sig.assign((size_t)n, GateGrid{}); noi.assign((size_t)n, GateGrid{});
+    prs.assign((size_t)n, HpssClip{}); prn.clear();
+    int64_t ypos = 0, in_pos = 0, rows = 0, nrows = 0, units = 0, nunits = 0, arows = 0, max_len = 0, max_nlen = 0;
+    for (int q = 0; q < n; ++q) {
+      const int i = ck.idx[q];
+      const int64_t L = lengths[i];
+      GateGrid& g = sig[q];
+      g.y_off = ypos; g.len = L; g.out_off = h_out ? ypos : out_offsets[i];
+      g.T = (int32_t)gate_frames(L, hop, pad);
+      gate_active(L, n_fft, hop, pad, g.T, &g.ta, &g.na);
+      g.row_base = rows; g.unit_base = units; g.arow_base = arows; g.shift = pad; g.clip = q;
+      prs[q].in_off = h_in ? in_pos : offsets[i]; prs[q].y_off = ypos; prs[q].len = L;
+      ypos += (L + 3) / 4 * 4; in_pos += (L + 3) / 4 * 4;
+      rows += g.T; units += (g.na + fpw - 1) / fpw; arows += g.na; max_len = std::max(max_len, L);
+    }
+    if (stat)
+      for (int q = 0; q < n; ++q) {
+        const int i = ck.idx[q];
+        const int64_t Ln = noise_len(i);
+        GateGrid& g = noi[q];
+        g.len = Ln; g.T = (int32_t)(1 + Ln / hop); g.ta = 0; g.na = g.T; g.shift = 0; g.clip = q;
+        g.row_base = nrows; g.unit_base = nunits;
+        if (with_noise) {
+          HpssClip r{};
+          r.in_off = h_in ? in_pos : noise_offsets[i]; r.y_off = ypos; r.len = Ln;
+          prn.push_back(r);
+          g.y_off = ypos;
+          ypos += (Ln + 3) / 4 * 4; in_pos += (Ln + 3) / 4 * 4; max_nlen = std::max(max_nlen, Ln);
+        } else {
+          g.y_off = sig[q].y_off;
+        }
+        nrows += g.T; nunits += (g.na + fpw - 1) / fpw;
+      }
+    if (rows > INT32_MAX / 2 || nrows > INT32_MAX / 2) { set_error(std::string(who) + ": chunk too large for one launch"); return AFX_ERR_UNSUPPORTED; }
+
+    // the records as one upload: both grids, then the prep records of the clips and of the noise clips
+    const size_t o_noi = (size_t)n * sizeof(GateGrid), o_prs = 2 * o_noi, o_prn = o_prs + (size_t)n * sizeof(HpssClip);
+    recs.assign(o_prn + prn.size() * sizeof(HpssClip), 0);
+    std::memcpy(recs.data(), sig.data(), o_noi);
+    std::memcpy(recs.data() + o_noi, noi.data(), o_noi);
+    std::memcpy(recs.data() + o_prs, prs.data(), (size_t)n * sizeof(HpssClip));
+    if (!prn.empty()) std::memcpy(recs.data() + o_prn, prn.data(), prn.size() * sizeof(HpssClip));
+    if ((rc = ensure(ctx->gt_grids, recs.size())) != AFX_OK) return rc;
+    if ((rc = ensure(ctx->gt_y, (size_t)std::max<int64_t>(ypos, 1) * sizeof(float))) != AFX_OK) return rc;
+    if ((rc = ensure(ctx->gt_bad, (size_t)2 * n * sizeof(uint32_t))) != AFX_OK) return rc;
+    if ((rc = ensure(ctx->gt_mag, (size_t)rows * pitch * sizeof(float))) != AFX_OK) return rc;
+    if ((rc = ensure(ctx->gt_mask, (size_t)rows * pitch * sizeof(float))) != AFX_OK) return rc;
+    if ((rc = ensure(ctx->gt_rows, (size_t)std::max<int64_t>(arows, 1) * n_fft * sizeof(float))) != AFX_OK) return rc;
+    if (stat) {
+      if ((rc = ensure(ctx->gt_nmag, (size_t)nrows * pitch * sizeof(float))) != AFX_OK) return rc;
+      if ((rc = ensure(ctx->gt_bits, (size_t)rows * words * sizeof(uint32_t))) != AFX_OK) return rc;
+      if ((rc = ensure(ctx->gt_thr, (size_t)n * pitch * sizeof(double))) != AFX_OK) return rc;
+      if ((rc = ensure(ctx->gt_amp, (size_t)n * pitch * sizeof(double))) != AFX_OK) return rc;
+    } else {
+      if ((rc = ensure(ctx->gt_fwd, (size_t)rows * pitch * sizeof(double))) != AFX_OK) return rc;
+    }
+    const void* d_in = samples;
+    if (h_in) {
+      stage_in.assign((size_t)in_pos * esz, 0);
+      for (int q = 0; q < n; ++q)
+        std::memcpy(stage_in.data() + (size_t)prs[q].in_off * esz, (const char*)samples + (size_t)offsets[ck.idx[q]] * esz, (size_t)prs[q].len * esz);
+      for (size_t q = 0; q < prn.size(); ++q)
+        std::memcpy(stage_in.data() + (size_t)prn[q].in_off * esz, (const char*)samples + (size_t)noise_offsets[ck.idx[q]] * esz, (size_t)prn[q].len * esz);
+      if ((rc = ensure(ctx->gt_in, std::max<size_t>(stage_in.size(), 1))) != AFX_OK) return rc;
+      HIP_TRY(hipMemcpyAsync(ctx->gt_in.p, stage_in.data(), stage_in.size(), hipMemcpyHostToDevice, s));
+      d_in = ctx->gt_in.p;
+    }
+    float* d_out = out;
+    if (h_out) {
+      if ((rc = ensure(ctx->gt_out, (size_t)std::max<int64_t>(ypos, 1) * sizeof(float))) != AFX_OK) return rc;
+      d_out = (float*)ctx->gt_out.p;
+    }
+    HIP_TRY(hipMemcpyAsync(ctx->gt_grids.p, recs.data(), recs.size(), hipMemcpyHostToDevice, s));
+    const GateGrid* d_sig = (const GateGrid*)ctx->gt_grids.p;
+    const GateGrid* d_noi = (const GateGrid*)((const char*)ctx->gt_grids.p + o_noi);
+    const HpssClip* d_prs = (const HpssClip*)((const char*)ctx->gt_grids.p + o_prs);
+    const HpssClip* d_prn = (const HpssClip*)((const char*)ctx->gt_grids.p + o_prn);
+    float *y = (float*)ctx->gt_y.p, *mag = (float*)ctx->gt_mag.p, *mask = (float*)ctx->gt_mask.p, *trows = (float*)ctx->gt_rows.p;
+    uint32_t* bad = (uint32_t*)ctx->gt_bad.p;
+    HIP_TRY(hipMemsetAsync(bad, 0, (size_t)2 * n * sizeof(uint32_t), s));
+    HIP_TRY(hipMemsetAsync(mag, 0, (size_t)rows * pitch * sizeof(float), s));
+    HIP_TRY(launch_hpss_prep(s, d_in, sample_fmt, 0, 0.f, d_prs, n, max_len, y, bad));
+    if (!prn.empty()) HIP_TRY(launch_hpss_prep(s, d_in, sample_fmt, 0, 0.f, d_prn, n, max_nlen, y, bad + n));
+    HIP_TRY(launch_gate_mag(s, n_fft, y, d_sig, bad, n, units, tb, mag));
+    if (stat) {
+      float* nmag = (float*)ctx->gt_nmag.p;
+      double *thr = (double*)ctx->gt_thr.p, *amp = (double*)ctx->gt_amp.p;
+      uint32_t* bits = (uint32_t*)ctx->gt_bits.p;
+      HIP_TRY(launch_gate_mag(s, n_fft, y, d_noi, bad, n, nunits, tb, nmag));
+      HIP_TRY(launch_gate_stats(s, n_fft, d_sig, d_noi, n, mag, nmag, opts->n_std_thresh, thr, amp));
+      HIP_TRY(launch_gate_hard(s, n_fft, d_sig, n, rows, mag, amp, bits));
+      HIP_TRY(launch_gate_smooth(s, n_fft, d_sig, n, rows, bits, nullptr, n_f, n_t, opts->prop_decrease, tb, mask));
+    } else {
+      HIP_TRY(launch_gate_recur(s, n_fft, d_sig, n, gd.beta, opts->thresh_n_mult, opts->sigmoid_slope, mag, (double*)ctx->gt_fwd.p));
+      HIP_TRY(launch_gate_smooth(s, n_fft, d_sig, n, rows, nullptr, mag, n_f, n_t, opts->prop_decrease, tb, mask));
+    }
+    HIP_TRY(launch_gate_apply(s, n_fft, y, d_sig, bad, n, units, tb, mask, trows));
+    HIP_TRY(launch_gate_ola(s, n_fft, trows, d_sig, bad, n, max_len, tb, d_out));
+    h_bad.resize((size_t)2 * n);
+    HIP_TRY(hipMemcpyAsync(h_bad.data(), bad, h_bad.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    if (stat && out_thresh) {
+      h_thr.resize((size_t)n * pitch);
+      HIP_TRY(hipMemcpyAsync(h_thr.data(), ctx->gt_thr.p, h_thr.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+    }
+    if (stat && out_mask) {
+      h_bits.resize((size_t)rows * words);
+      HIP_TRY(hipMemcpyAsync(h_bits.data(), ctx->gt_bits.p, h_bits.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    }
+    if (h_out)
+      // straight to the caller's ranges, one copy per run of clips that lie back to back on both sides (gaps are not written)
+      for (int q = 0; q < n;) {
+        int e = q;
+        int64_t cnt = sig[q].len;
+        while (e + 1 < n && sig[e + 1].y_off == sig[q].y_off + cnt && out_offsets[ck.idx[e + 1]] == out_offsets[ck.idx[q]] + cnt) cnt += sig[++e].len;
+        HIP_TRY(hipMemcpyAsync(out + out_offsets[ck.idx[q]], d_out + sig[q].y_off, (size_t)cnt * sizeof(float), hipMemcpyDeviceToHost, s));
+        q = e + 1;
+      }
+    HIP_TRY(hipStreamSynchronize(s));
+    for (int q = 0; q < n; ++q) {
+      const int i = ck.idx[q];
+      const bool nf = (h_bad[q] | h_bad[(size_t)n + q]) != 0;
+      if (nf) out_status[i] = AFX_CLIP_NONFINITE;
+      if (stat && out_thresh && !nf) std::memcpy(out_thresh + (size_t)bins * i, h_thr.data() + (size_t)q * pitch, (size_t)bins * sizeof(double));
+      if (stat && out_mask) std::memcpy(out_mask + moff[i], h_bits.data() + sig[q].row_base * words, (size_t)sig[q].T * words * sizeof(uint32_t));
+    }
+  }
+  return AFX_OK;
+}

@@ -36,6 +36,7 @@ struct DevEnv {
   int64_t specdist_budget = (int64_t)2 << 30; // device workspace bytes of one afx_specdist_batch / afx_clip_fft_batch chunk
   int64_t smooth_budget = (int64_t)2 << 30; // device workspace bytes of one afx_medfilt_batch / afx_savgol_batch / afx_energy_zcr_batch chunk
   int64_t loud_budget = (int64_t)2 << 30;   // device workspace bytes of one afx_loudness_batch chunk
+  int64_t gate_budget = (int64_t)2 << 30;   // device workspace bytes of one afx_gate_batch chunk
   const char* f0_dump = nullptr;
   DevEnv();
 };

@@ -225,7 +225,7 @@ extern "C" int afx_stft_chunks(const int64_t* lengths, int n_clips, const int64_
   if (n_clips < 0 || !cost || (n_clips > 0 && (!lengths || !chunk_of))) { set_error("afx_stft_chunks: null/invalid argument"); return AFX_ERR_INVALID; }
   // the sums of a chunk stay below 2^63: a clip costs less than 2^55 bytes, and a chunk is cut before it passes the budget
   for (int k = 0; k < 6; ++k)
-    if (cost[k] < (k >= 4 ? 1 : 0) || cost[k] > (k >= 4 ? INT32_MAX : 1 << 20)) { set_error("afx_stft_chunks: cost out of range"); return AFX_ERR_INVALID; }
+    if (cost[k] < (k >= 4 ? 1 : 0) || cost[k] > (k >= 4 ? INT32_MAX : k == 3 ? 1 << 30 : 1 << 20)) { set_error("afx_stft_chunks: cost out of range"); return AFX_ERR_INVALID; }
   if (budget < 1 || budget > (int64_t)1 << 62) { set_error("afx_stft_chunks: budget must be in [1, 2^62]"); return AFX_ERR_INVALID; }
   for (int i = 0; i < n_clips; ++i)
     if (lengths[i] < 0 || lengths[i] > (int64_t)1 << 31) { set_error("afx_stft_chunks: lengths must be in [0, 2^31]"); return AFX_ERR_INVALID; }

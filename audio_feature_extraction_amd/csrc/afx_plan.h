@@ -21,6 +21,7 @@
 #include "afx_frames3.h"
 #include "afx_groups.h"
 #include "afx_internal.h"
+#include "afx_gate.h"
 #include "afx_loudness.h"
 #include "afx_resample.h"
 #include "afx_rhythm.h"
@@ -68,6 +69,10 @@ struct afx_ctx {
   // afx_loudness_batch: one table per distinct rate, a chunk's clip records, the blocks' states and partial sums, the tiles'
   // peaks and flags, the segment sums, z_j, the clips' scalars, the gains, staging of host batches
   DevBuf ld_tab, ld_clips, ld_carry, ld_part, ld_tpeak, ld_tbad, ld_seg, ld_z, ld_rec, ld_gain, ld_in, ld_out;
+  // afx_gate_batch: the window / twiddles / taps, a chunk's grid records, its float32 signal, the non-finite flags, the
+  // magnitude planes of both grids, the mask plane, the forward pass, the bit plane, thr and its amplitude, the time rows,
+  // staging of host batches
+  DevBuf gt_tab, gt_grids, gt_y, gt_bad, gt_mag, gt_nmag, gt_mask, gt_fwd, gt_bits, gt_thr, gt_amp, gt_rows, gt_in, gt_out;
 };
 
 struct afx_plan {

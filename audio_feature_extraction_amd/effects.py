@@ -9,6 +9,9 @@ frames (scipy itself departs from it at T = 2, i.e. 512 .. 1023 samples).
 On the same STFT, the reference's STFT-domain noise reducers (00_audio_data_collection_experiment/noise_reduction.py:15-92:
 ``spectral_subtraction``, ``wiener_filter``) and the signal conditioning in front of its DTW aligner
 (05_dtw_alignment_experiment/process_audio.py:9-54: ``preprocess_alignment``), all in ``afx_denoise_batch``.
+
+On scipy's STFT at 1024 / 256 or 2048 / 512, ``noisereduce.reduce_noise`` as the experiment's audio processor calls it
+(04_feature_extraction_experiment/process_audio.py:82-98): ``reduce_noise``, in ``afx_gate_batch``.
 """
 from __future__ import annotations
 
@@ -187,3 +190,107 @@ def preprocess_alignment(y, sr: int, *, device: int = 0) -> np.ndarray:
         raise ValueError("preprocess_alignment: " + ("fewer than 512 samples" if st == _native.CLIP_TOO_SHORT else "audio buffer is not finite everywhere"))
     o = out["out"][0]
     return o[:512 * (o.size // 512)].copy()
+
+
+# ---- spectral gating (afx_gate_batch): noisereduce.reduce_noise ----------------------------------------------------------
+_ctxs: dict = {}
+_GATE_KEYS = ("stationary", "prop_decrease", "time_constant_s", "freq_mask_smooth_hz", "time_mask_smooth_ms",
+              "thresh_n_mult_nonstationary", "sigmoid_slope_nonstationary", "n_std_thresh_stationary", "chunk_size", "padding",
+              "n_fft", "win_length", "hop_length", "clip_noise_stationary")
+
+
+def _ctx(device: int) -> _native.Context:
+    c = _ctxs.get(device)
+    if c is None:
+        c = _ctxs[device] = _native.Context(device)
+    return c
+
+
+def _gate_opts(sr, kw: dict) -> _native.GateOpts:
+    """noisereduce's keywords as the engine's record, checked without a device: the keywords the engine does not honour
+    raise ``NotImplementedError`` by name, what noisereduce refuses raises ``ValueError``."""
+    if kw.pop("use_torch", False):
+        raise NotImplementedError("use_torch=True is not supported")
+    if kw.pop("use_tqdm", False):
+        raise NotImplementedError("use_tqdm=True is not supported")
+    if kw.pop("n_jobs", 1) != 1:
+        raise NotImplementedError("n_jobs != 1 is not supported: a batch is one device pass (reduce_noise_batch)")
+    if kw.pop("tmp_folder", None) is not None:
+        raise NotImplementedError("tmp_folder is not supported: nothing is spilled to disk")
+    kw.pop("device", None)                                            # noisereduce's torch device
+    unknown = sorted(set(kw) - set(_GATE_KEYS))
+    if unknown:
+        raise TypeError(f"reduce_noise: unexpected keyword {unknown[0]!r}")
+    if int(sr) != sr or sr < 1:
+        raise ValueError("sr must be a positive integer")
+    n_fft = kw.get("n_fft", 1024)
+    win = kw.get("win_length") or n_fft
+    hop = kw.get("hop_length") or win // 4
+    if win != n_fft:
+        raise NotImplementedError(f"win_length={win!r} != n_fft={n_fft!r} is not supported")
+    if (n_fft, hop) not in ((1024, 256), (2048, 512)):
+        raise NotImplementedError(f"n_fft={n_fft!r}, hop_length={hop!r} is not supported (only 1024 / 256 and 2048 / 512)")
+    opts = _native.gate_opts(int(sr), **kw)
+    _native.gate_params(opts)                                         # ValueError / NotImplementedError before any device work
+    return opts
+
+
+def _gate_signals(clips, opts, who: str) -> List[np.ndarray]:
+    """The clips as mono float32; refuses an empty one and one longer than chunk_size, before any device work."""
+    sig = _mono_f32(clips)
+    for i, y in enumerate(sig):
+        if y.size == 0:
+            raise ValueError(f"{who}: signal {i} is empty")
+        if y.size > opts.chunk_size:
+            raise NotImplementedError(f"{who}: signal {i} has {y.size} samples, more than chunk_size={opts.chunk_size}: "
+                                      "noisereduce's chunk loop is not supported")
+    return sig
+
+
+def _gate_run(sig: List[np.ndarray], noise, opts, device: int):
+    """-> (denoised clips, status)"""
+    lengths = np.array([s.size for s in sig], np.int64)
+    n_off = n_len = None
+    parts = list(sig)
+    if noise is not None and opts.stationary:
+        n_len = np.array([z.size for z in noise], np.int64)
+        parts += list(noise)
+    all_off = _native.packed_offsets([p.size for p in parts], 4)
+    buf = np.zeros(int(all_off[-1]) + parts[-1].size if parts else 0, np.float32)
+    for o, p in zip(all_off, parts):
+        buf[o:o + p.size] = p
+    offsets = all_off[:len(sig)]
+    if n_len is not None:
+        n_off = all_off[len(sig):]
+    out = _ctx(device).gate_batch(buf, offsets, lengths, opts, noise_offsets=n_off, noise_lengths=n_len)
+    return [out["out"][o:o + n].copy() for o, n in zip(out["offsets"], lengths)], out["status"]
+
+
+def reduce_noise_batch(clips: Sequence[np.ndarray], sr: int, y_noise=None, *, device: int = 0, **kw) -> List[np.ndarray]:
+    """``noisereduce.reduce_noise(y=clip, sr=sr, **kw)`` of many mono clips in one device pass.  ``y_noise``: one noise clip
+    for all, or one per clip (stationary only, as in noisereduce).  A clip with a NaN / inf sample comes back as zeros.
+    ``device`` may be a callable that names the device: it is asked only once the arguments have passed."""
+    opts = _gate_opts(sr, dict(kw))
+    sig = _gate_signals(clips, opts, "reduce_noise")
+    noise = None
+    if y_noise is not None:
+        if isinstance(y_noise, np.ndarray) and y_noise.ndim == 1:
+            y_noise = [y_noise] * len(sig)
+        noise = _mono_f32(y_noise)
+        if len(noise) != len(sig) or any(z.size == 0 for z in noise):
+            raise ValueError("reduce_noise: y_noise must be one non-empty mono clip, or one per signal")
+    if not sig:
+        return []
+    return _gate_run(sig, noise, opts, device() if callable(device) else device)[0]
+
+
+def reduce_noise(y, sr: int, y_noise=None, *, device: int = 0, **kw) -> np.ndarray:
+    """``noisereduce.reduce_noise(y, sr, ...)`` (3.0.3) for mono audio on the GPU: spectral gating, stationary (a per-bin
+    threshold from the whole noise clip's dB statistics) or non-stationary (a sigmoid over |X| against its forward-backward
+    smoothed self), the mask smoothed over time and frequency; float32 of ``y``'s length.  noisereduce's keywords and
+    defaults; 1024 / 256 and 2048 / 512 frames; clips of at most ``chunk_size`` samples (DESIGN.md section 25 lists the
+    deviations)."""
+    y = np.asarray(y)
+    if y.ndim != 1:
+        raise NotImplementedError(f"reduce_noise: only mono audio is supported, got shape {y.shape}")
+    return reduce_noise_batch([y], sr, y_noise, device=device, **kw)[0]

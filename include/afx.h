@@ -440,8 +440,9 @@ int afx_beat_batch(afx_plan* plan, const void* samples, int sample_fmt, int mem_
  * length cost[2] + cost[3] bytes of workspace; a chunk holds at least one clip and ends before the clip that would take
  * its bytes past budget or its tiles (of cost[4] frames) past cost[5], or at 32768 clips.  chunk_of[i] = the chunk of
  * clip i, -1 for a clip of length 0 (it is in no chunk and costs nothing).  Newer than AFX_VERSION 107 says: a binding
- * detects it by its presence.  AFX_ERR_INVALID for a length outside [0, 2^31], a budget outside [1, 2^62], cost[0 .. 3]
- * outside [0, 2^20] or cost[4], cost[5] outside [1, 2^31 - 1]. */
+ * detects it by its presence.  AFX_ERR_INVALID for a length outside [0, 2^31], a budget outside [1, 2^62], cost[0 .. 2]
+ * outside [0, 2^20], cost[3] outside [0, 2^30] (afx_gate_batch's clip carries its padding's frames) or cost[4], cost[5]
+ * outside [1, 2^31 - 1]. */
 int afx_stft_chunks(const int64_t* lengths, int n_clips, const int64_t* cost /*[6]*/, int64_t budget, int32_t* chunk_of);
 
 /* The spectral, harmonic, timbre and rhythm groups of the experiment extractor in one pass
@@ -809,6 +810,61 @@ int afx_loudness_batch(afx_ctx* ctx, const void* samples, int sample_fmt, int me
                        double block_size, int mode, double target,
                        double* out_rec /*[n_clips][AFX_LOUD_N]*/, double* out_blocks, const int64_t* out_block_offsets,
                        float* out, int out_mem_kind, const int64_t* out_offsets, int32_t* out_status);
+
+/* Spectral-gating noise reduction with the semantics of noisereduce 3.0.3's reduce_noise for one mono clip of at most
+ * chunk_size samples, as the experiment's audio processor calls it (04_feature_extraction_experiment/process_audio.py:82-98).
+ * DESIGN.md section 25 is the definition and tests/gate_ref.py its float64 restatement.  All three symbols are newer than
+ * AFX_VERSION 107 says: a binding detects them by their presence.
+ *
+ * The grid: chunk = padding zeros, the clip, padding zeros; scipy.signal.stft(nperseg = n_fft, noverlap = n_fft - hop,
+ * padded = False): periodic Hann, n_fft / 2 zeros at each end, X = rfft(frame w) / sum w, T = 1 + (length + 2 padding) / hop
+ * frames; the matching istft, and the samples [padding, padding + length) of it as float32.
+ * stationary: the noise clip (noise_offsets / noise_lengths in the same buffer, or the clip itself when both are NULL; cut to
+ * chunk_size samples with clip_noise) has its own grid without the padding; N = dB of |X_n|, 20 log10(a + 2^-52) floored per
+ * bin at the row's maximum - 80; thr[b] = mean_t N + n_std_thresh std_t N (float64, one fixed order); hard[b][t] =
+ * dB of |X| (floored the same way on the signal grid) > thr[b], taken as |X| + 2^-52 > 10^(thr / 20) or floor > thr;
+ * mask = hard p + (1 - p), smoothed.
+ * non-stationary: S = scipy.signal.filtfilt([beta], [1, beta - 1], |X|, padtype=None) along time in float64,
+ * mask = 1 / (1 + exp(-((|X| - S) / S - thresh_n_mult) sigmoid_slope)), 0 where S = 0; smoothed; then mask p + (1 - p).
+ * The smoothing: the outer product of two triangles of 2 n_f + 1 bins and 2 n_t + 1 frames (afx_gate_params), normalised,
+ * with zeros beyond the array's four edges, float64; none when n_f = n_t = 1.  Y = X mask, float32.
+ *
+ * n_fft / hop must be 1024 / 256 or 2048 / 512 with win_length == n_fft (AFX_ERR_UNSUPPORTED otherwise, as for a filter of
+ * more than 128 bins or 64 frames a side, padding above 2^20 and chunk_size above 2^24); AFX_ERR_INVALID where noisereduce
+ * raises (a smoothing width below one bin / frame) and for prop_decrease outside [0, 1], a time constant that is not
+ * positive, or a value that is not finite.
+ *   out          float32, clip i at out_offsets[i], host or device memory (out_mem_kind)
+ *   out_thresh   host, NULL ok: double[n_clips][n_fft / 2 + 1], thr in dB (stationary; NaN for a failed clip)
+ *   out_mask     host, NULL ok: the hard mask on the signal grid (stationary), clip after clip in batch order, a clip of
+ *                status AFX_CLIP_OK or AFX_CLIP_NONFINITE taking T rows of ceil((n_fft / 2 + 1) / 32) uint32, frame after
+ *                frame; bin b is bit (b & 31) of word b >> 5.  Any other clip takes none.
+ *   out_status   host: AFX_CLIP_TOO_SHORT for length 0 (or a noise clip of length 0), AFX_CLIP_TOO_LONG for more than
+ *                chunk_size samples (noisereduce's chunk loop is not restated) -- neither clip's output range is written --
+ *                and AFX_CLIP_NONFINITE for a NaN / inf sample in the clip or its noise clip: zeros out.
+ * No atomics: results are bit-reproducible, and a clip's result depends neither on the rest of the batch, on the input
+ * layout, nor on how the batch was cut into chunks (afx_stft_chunks with the record of afx_gate_cost over
+ * max(length, noise length) per clip, 0 for a clip that is too long).
+ *
+ * afx_gate_params (host-only): info[4] = n_f, n_t, T of a clip of `length` samples, 1 when the mask is smoothed; beta; the
+ * taps of each axis, each normalised to sum 1 (their outer product is the filter; room for 257 and 129 doubles).  Any n_fft
+ * and hop.  beta, taps_f, taps_t may be NULL.
+ * afx_gate_cost (host-only): cost[6] for afx_stft_chunks. */
+typedef struct afx_gate_opts {
+  int32_t sr, n_fft, win_length, hop;
+  int32_t stationary;         /* 0: non-stationary */
+  int32_t clip_noise;         /* clip_noise_stationary */
+  int32_t padding, chunk_size;
+  double prop_decrease, time_constant_s, freq_mask_smooth_hz, time_mask_smooth_ms;
+  double thresh_n_mult, sigmoid_slope, n_std_thresh;
+} afx_gate_opts;
+enum { AFX_CLIP_TOO_LONG = 3 };   /* afx_gate_batch: more than chunk_size samples */
+int afx_gate_params(const afx_gate_opts* opts, int64_t length, int64_t* info /*[4]*/, double* beta, double* taps_f, double* taps_t);
+int afx_gate_cost(const afx_gate_opts* opts, int sample_fmt, int mem_kind, int out_mem_kind, int with_noise, int64_t* cost /*[6]*/);
+int afx_gate_batch(afx_ctx* ctx, const void* samples, int sample_fmt, int mem_kind,
+                   const int64_t* offsets, const int64_t* lengths, int n_clips,
+                   const int64_t* noise_offsets, const int64_t* noise_lengths, const afx_gate_opts* opts,
+                   float* out, int out_mem_kind, const int64_t* out_offsets,
+                   double* out_thresh, uint32_t* out_mask, int32_t* out_status);
 
 /* The recording screen of 00_audio_data_collection_experiment/audio_format_assessment.py:143-300 (detect_silence,
  * check_volume_levels, check_amplitude_stability, estimate_snr) and the sums behind the scores of
