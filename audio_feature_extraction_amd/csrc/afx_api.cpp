@@ -82,17 +82,15 @@ extern "C" int afx_init(int device, afx_ctx** out) {
 extern "C" void afx_destroy(afx_ctx* ctx) {
   if (!ctx) return;
   (void)hipSetDevice(ctx->device);
-  for (DevBuf* b : {&ctx->dtw_raw, &ctx->dtw_feats, &ctx->dtw_norms, &ctx->dtw_pairs, &ctx->dtw_codes, &ctx->dtw_rows, &ctx->dtw_d,
-                    &ctx->dtw_path, &ctx->dtw_cost, &ctx->dtw_status, &ctx->dtw_len, &ctx->dtw_end, &ctx->rs_g, &ctx->rs_tstart, &ctx->rs_clips,
-                    &ctx->rs_in, &ctx->rs_out, &ctx->dc_clips, &ctx->dc_in, &ctx->dc_out, &ctx->ft_tab, &ctx->ft_clips, &ctx->ft_st,
-                    &ctx->ft_w, &ctx->ft_carry, &ctx->ft_tmax, &ctx->ft_in, &ctx->ft_out, &ctx->as_clips, &ctx->as_pieces, &ctx->as_spans,
-                    &ctx->as_rec, &ctx->as_bad, &ctx->as_in, &ctx->cf_tw, &ctx->cf_jobs, &ctx->cf_work, &ctx->cf_filt, &ctx->cf_rec,
-                    &ctx->cf_bad, &ctx->cf_in, &ctx->sm_tab, &ctx->sm_clips, &ctx->sm_bad, &ctx->sm_in, &ctx->sm_out, &ctx->ez_clips,
+  for (DevBuf* b : {&ctx->wave_in, &ctx->wave_out, &ctx->dtw_raw, &ctx->dtw_feats, &ctx->dtw_norms, &ctx->dtw_pairs, &ctx->dtw_codes,
+                    &ctx->dtw_rows, &ctx->dtw_d, &ctx->dtw_path, &ctx->dtw_cost, &ctx->dtw_status, &ctx->dtw_len, &ctx->dtw_end, &ctx->rs_g,
+                    &ctx->rs_tstart, &ctx->rs_clips, &ctx->dc_clips, &ctx->ft_tab, &ctx->ft_clips, &ctx->ft_st, &ctx->ft_w, &ctx->ft_carry,
+                    &ctx->ft_tmax, &ctx->as_clips, &ctx->as_pieces, &ctx->as_spans, &ctx->as_rec, &ctx->as_bad, &ctx->cf_tw, &ctx->cf_jobs,
+                    &ctx->cf_work, &ctx->cf_filt, &ctx->cf_rec, &ctx->cf_bad, &ctx->sm_tab, &ctx->sm_clips, &ctx->sm_bad, &ctx->ez_clips,
                     &ctx->ez_y, &ctx->ez_m, &ctx->ez_s, &ctx->ez_neg, &ctx->ez_peak, &ctx->ez_energy, &ctx->ez_rate, &ctx->ez_rec, &ctx->ld_tab,
                     &ctx->ld_clips, &ctx->ld_carry, &ctx->ld_part, &ctx->ld_tpeak, &ctx->ld_tbad, &ctx->ld_seg, &ctx->ld_z, &ctx->ld_rec,
-                    &ctx->ld_gain, &ctx->ld_in, &ctx->ld_out, &ctx->gt_tab, &ctx->gt_grids, &ctx->gt_y, &ctx->gt_bad, &ctx->gt_mag,
-                    &ctx->gt_nmag, &ctx->gt_mask, &ctx->gt_fwd, &ctx->gt_bits, &ctx->gt_thr, &ctx->gt_amp, &ctx->gt_rows, &ctx->gt_in,
-                    &ctx->gt_out})
+                    &ctx->ld_gain, &ctx->gt_tab, &ctx->gt_grids, &ctx->gt_y, &ctx->gt_bad, &ctx->gt_mag, &ctx->gt_nmag, &ctx->gt_mask,
+                    &ctx->gt_fwd, &ctx->gt_bits, &ctx->gt_thr, &ctx->gt_amp, &ctx->gt_rows})
     release(*b);
   if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
   delete ctx;

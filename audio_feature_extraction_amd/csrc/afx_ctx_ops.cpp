@@ -1,5 +1,7 @@
-// The entry points of libafx.so that work on a context, not a plan: batched DTW, batched polyphase resampling, and the
-// conversion / mix-down of raw WAVE data.
+// The entry points of libafx.so that work on a context, not a plan: batched DTW, polyphase resampling, the conversion /
+// mix-down of raw WAVE data, zero-phase IIR filtering, the recording screen and the compare sums, the whole-clip DFT and
+// the spectral distance, the median and Savitzky-Golay filters with the energy and ZCR groups, BS.1770 loudness and
+// spectral gating -- and what they share: the staging of a host batch and the launches of the zero-phase filter.
 #include <algorithm>
 #include <cmath>
 #include <cstddef>
@@ -17,6 +19,76 @@
 #include "afx_internal.h"
 #include "afx_plan.h"
 #include "afx_resample.h"
+
+// ---- what the entry points share (declared in afx_plan.h; the rule of the two buffers is at afx_ctx::wave_in) ----------
+int stage_in(afx_ctx* ctx, std::vector<char>& image, int64_t total_bytes, const std::vector<HostPiece>& pieces, const void** d_in) {
+  pack_pieces(image, total_bytes, pieces);
+  if (int rc = ensure(ctx->wave_in, std::max<size_t>(image.size(), 1))) return rc;
+  HIP_TRY(hipMemcpyAsync(ctx->wave_in.p, image.data(), image.size(), hipMemcpyHostToDevice, ctx->stream));
+  *d_in = ctx->wave_in.p;
+  return AFX_OK;
+}
+
+int out_buffer(afx_ctx* ctx, float* out, int out_mem_kind, int64_t total, float** d_out) {
+  *d_out = out;
+  if (out_mem_kind != AFX_MEM_HOST) return AFX_OK;
+  if (int rc = ensure(ctx->wave_out, (size_t)total * sizeof(float))) return rc;
+  *d_out = (float*)ctx->wave_out.p;
+  return AFX_OK;
+}
+
+int fetch_out(afx_ctx* ctx, const float* d_out, int64_t total, std::vector<float>& host) {
+  host.resize((size_t)total);
+  HIP_TRY(hipMemcpyAsync(host.data(), d_out, (size_t)total * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+  return AFX_OK;
+}
+
+int run_filtfilt_chain(afx_ctx* ctx, const void* d_in, int sample_fmt, int mode, float preemph, int padlen, int n_sections,
+                       const std::vector<FiltClip>& recs, int64_t tiles, const FiltTab* d_tab, float* d_out) {
+  hipStream_t s = ctx->stream;
+  const int n = (int)recs.size(), nt = (int)tiles, S = n_sections;
+  int rc;
+  if ((rc = ensure(ctx->ft_clips, n * sizeof(FiltClip))) != AFX_OK) return rc;
+  if ((rc = ensure(ctx->ft_st, n * sizeof(FiltState))) != AFX_OK) return rc;
+  if ((rc = ensure(ctx->ft_w, (size_t)nt * kFiltTile * sizeof(double))) != AFX_OK) return rc;
+  if ((rc = ensure(ctx->ft_carry, (size_t)nt * kFiltB * kFiltZ * sizeof(double))) != AFX_OK) return rc;
+  if ((rc = ensure(ctx->ft_tmax, (size_t)nt * sizeof(double))) != AFX_OK) return rc;
+  HIP_TRY(hipMemcpyAsync(ctx->ft_clips.p, recs.data(), n * sizeof(FiltClip), hipMemcpyHostToDevice, s));
+  const FiltClip* d_clips = (const FiltClip*)ctx->ft_clips.p;
+  FiltState* d_st = (FiltState*)ctx->ft_st.p;
+  double *W = (double*)ctx->ft_w.p, *carry = (double*)ctx->ft_carry.p, *tmax = (double*)ctx->ft_tmax.p;
+  const bool plain = mode == AFX_FILT_PLAIN;
+  HIP_TRY(launch_filt_peak(s, d_in, sample_fmt, d_clips, n, d_st));
+  HIP_TRY(launch_filt_forward(s, d_in, sample_fmt, mode, -preemph, padlen, S, d_tab, d_clips, n, nt, d_st, W, carry));
+  HIP_TRY(launch_filt_scan(s, padlen, S, d_tab, d_clips, n, d_st, carry, false));
+  HIP_TRY(launch_filt_backward(s, padlen, S, d_tab, d_clips, n, nt, d_st, W, carry));
+  HIP_TRY(launch_filt_scan(s, padlen, S, d_tab, d_clips, n, d_st, carry, true));
+  HIP_TRY(launch_filt_final(s, padlen, S, d_tab, d_clips, n, nt, d_st, W, carry, tmax, plain ? d_out : nullptr));
+  HIP_TRY(launch_filt_clipmax(s, d_clips, n, tmax, d_st));
+  if (!plain) HIP_TRY(launch_filt_scale(s, padlen, d_clips, n, nt, d_st, W, d_out));
+  return AFX_OK;
+}
+
+// The argument checks of an entry point that reads clips of samples: the context and the arrays (own_ok: its own required
+// arrays are there), the sample format where the samples lie and -- out_mem_kind >= 0: it writes samples too -- where the
+// result goes, the clip ranges.
+static int clip_batch_args(const char* who, afx_ctx* ctx, int sample_fmt, int mem_kind, const int64_t* offsets, const int64_t* lengths,
+                           int n_clips, int out_mem_kind, const int64_t* out_offsets, const int32_t* out_status, bool own_ok = true) {
+  const bool writes = out_mem_kind >= 0;
+  if (!ctx || n_clips < 0 || (n_clips > 0 && (!offsets || !lengths || (writes && !out_offsets) || !out_status || !own_ok))) return null_arg(who);
+  int rc;
+  if ((rc = check_sample_format(who, sample_fmt, mem_kind)) != AFX_OK) return rc;
+  if (writes && (rc = check_sample_format(who, sample_fmt, out_mem_kind)) != AFX_OK) return rc;
+  return check_clip_ranges(who, offsets, lengths, out_offsets, n_clips, INT64_MAX / 8);
+}
+
+// n samples of esz bytes from element src_off of a host buffer, to element dst_off of the packed image
+static HostPiece clip_piece(const void* src, int64_t src_off, int64_t dst_off, int64_t n, size_t esz) {
+  return {(const char*)src + (size_t)src_off * esz, dst_off * (int64_t)esz, n * (int64_t)esz};
+}
+
+// row i of a table of n-double records, before anything is known of clip i
+static void nan_row(double* rec, int n, int i) { std::fill(rec + (size_t)n * i, rec + (size_t)n * (i + 1), std::nan("")); }
 
 // ---- batched DTW (librosa.sequence.dtw): the alignment step the reference runs on the extracted MFCC frames ----------
 // The body of afx_dtw_batch (T == nullptr: k_dtw, the default steps) and afx_dtw_steps_batch (T: k_dtw_steps).
@@ -304,19 +376,14 @@ extern "C" int afx_resample_batch(afx_ctx* ctx, const void* samples, int sample_
   const size_t esz = sample_fmt == AFX_FMT_S16 ? 2 : 4;
   const void* d_in = samples;
   std::vector<char> h_in;
+  std::vector<HostPiece> pieces;
   if (mem_kind == AFX_MEM_HOST) {
-    h_in.assign((size_t)in_pos * esz + 16, 0);
     for (int i = 0; i < n_clips; ++i)
-      if (lengths[i]) std::memcpy(h_in.data() + (size_t)recs[i].in_off * esz, (const char*)samples + (size_t)offsets[i] * esz, (size_t)lengths[i] * esz);
-    if ((rc = ensure(ctx->rs_in, h_in.size())) != AFX_OK) return rc;
-    HIP_TRY(hipMemcpyAsync(ctx->rs_in.p, h_in.data(), h_in.size(), hipMemcpyHostToDevice, s));
-    d_in = ctx->rs_in.p;
+      pieces.push_back(clip_piece(samples, offsets[i], recs[i].in_off, lengths[i], esz));
+    if ((rc = stage_in(ctx, h_in, in_pos * (int64_t)esz + 16, pieces, &d_in)) != AFX_OK) return rc;    // 16 zero bytes behind the last slot
   }
-  float* d_out = out;
-  if (out_mem_kind == AFX_MEM_HOST) {
-    if ((rc = ensure(ctx->rs_out, (size_t)total_out * sizeof(float))) != AFX_OK) return rc;
-    d_out = (float*)ctx->rs_out.p;
-  }
+  float* d_out;
+  if ((rc = out_buffer(ctx, out, out_mem_kind, total_out, &d_out)) != AFX_OK) return rc;
   if ((rc = ensure(ctx->rs_clips, recs.size() * sizeof(RsClip))) != AFX_OK) return rc;
   HIP_TRY(hipMemcpyAsync(ctx->rs_clips.p, recs.data(), recs.size() * sizeof(RsClip), hipMemcpyHostToDevice, s));
   const RsClip* d_clips = (const RsClip*)ctx->rs_clips.p;
@@ -324,11 +391,12 @@ extern "C" int afx_resample_batch(afx_ctx* ctx, const void* samples, int sample_
   else HIP_TRY(launch_resample(s, d_in, sample_fmt, d_out, d_clips, n_clips, (int)n_blocks, (const double*)ctx->rs_g.p,
                                (const int32_t*)ctx->rs_tstart.p, P));
   if (out_mem_kind == AFX_MEM_HOST) {
-    std::vector<float> h_out((size_t)total_out);
-    HIP_TRY(hipMemcpyAsync(h_out.data(), d_out, (size_t)total_out * sizeof(float), hipMemcpyDeviceToHost, s));
+    std::vector<float> h_out;
+    if ((rc = fetch_out(ctx, d_out, total_out, h_out)) != AFX_OK) return rc;
     HIP_TRY(hipStreamSynchronize(s));
-    for (int i = 0; i < n_clips; ++i)
-      if (recs[i].out_len) std::memcpy(out + out_offsets[i], h_out.data() + recs[i].out_off, (size_t)recs[i].out_len * sizeof(float));
+    pieces.clear();
+    for (int i = 0; i < n_clips; ++i) pieces.push_back({h_out.data() + recs[i].out_off, out_offsets[i] * 4, recs[i].out_len * 4});
+    scatter_pieces(out, pieces);
   } else {
     HIP_TRY(hipStreamSynchronize(s));
   }
@@ -392,30 +460,25 @@ extern "C" int afx_decode_batch(afx_ctx* ctx, const void* raw, int mem_kind, con
   HIP_TRY(hipSetDevice(ctx->device));
   hipStream_t s = ctx->stream;
   const void* d_in = raw;
-  std::vector<uint8_t> h_in;
+  std::vector<char> h_in;
+  std::vector<HostPiece> pieces;
   if (mem_kind == AFX_MEM_HOST) {
-    h_in.assign((size_t)in_pos, 0);
     for (int i : order)
-      std::memcpy(h_in.data() + recs[i].in_off, (const uint8_t*)raw + byte_offsets[i],
-                  (size_t)(frames[i] * decode_sample_bytes(kinds[i]) * channels[i]));
-    if ((rc = ensure(ctx->dc_in, h_in.size())) != AFX_OK) return rc;
-    HIP_TRY(hipMemcpyAsync(ctx->dc_in.p, h_in.data(), h_in.size(), hipMemcpyHostToDevice, s));
-    d_in = ctx->dc_in.p;
+      pieces.push_back({(const char*)raw + byte_offsets[i], recs[i].in_off, frames[i] * decode_sample_bytes(kinds[i]) * channels[i]});
+    if ((rc = stage_in(ctx, h_in, in_pos, pieces, &d_in)) != AFX_OK) return rc;
   }
-  float* d_out = out;
-  if (out_mem_kind == AFX_MEM_HOST) {
-    if ((rc = ensure(ctx->dc_out, (size_t)out_pos * sizeof(float))) != AFX_OK) return rc;
-    d_out = (float*)ctx->dc_out.p;
-  }
+  float* d_out;
+  if ((rc = out_buffer(ctx, out, out_mem_kind, out_pos, &d_out)) != AFX_OK) return rc;
   if ((rc = ensure(ctx->dc_clips, recs.size() * sizeof(DcClip))) != AFX_OK) return rc;
   HIP_TRY(hipMemcpyAsync(ctx->dc_clips.p, recs.data(), recs.size() * sizeof(DcClip), hipMemcpyHostToDevice, s));
   HIP_TRY(launch_decode(s, d_in, d_out, (const DcClip*)ctx->dc_clips.p, n_clips, (int)n_blocks));
   if (out_mem_kind == AFX_MEM_HOST) {
-    std::vector<float> h_out((size_t)out_pos);
-    HIP_TRY(hipMemcpyAsync(h_out.data(), d_out, (size_t)out_pos * sizeof(float), hipMemcpyDeviceToHost, s));
+    std::vector<float> h_out;
+    if ((rc = fetch_out(ctx, d_out, out_pos, h_out)) != AFX_OK) return rc;
     HIP_TRY(hipStreamSynchronize(s));
-    for (int i : order)
-      std::memcpy(out + out_offsets[i], h_out.data() + recs[i].out_off, (size_t)((frames[i] + 3) / 4 * 4) * sizeof(float));
+    pieces.clear();
+    for (int i : order) pieces.push_back({h_out.data() + recs[i].out_off, out_offsets[i] * 4, (frames[i] + 3) / 4 * 4 * 4});
+    scatter_pieces(out, pieces);
   } else {
     HIP_TRY(hipStreamSynchronize(s));
   }
@@ -467,7 +530,8 @@ extern "C" int afx_sosfiltfilt_batch(afx_ctx* ctx, const void* samples, int samp
   std::vector<FiltClip> recs;
   std::vector<int> idx;
   std::vector<FiltState> h_st;
-  std::vector<char> stage_in;
+  std::vector<HostPiece> pieces;
+  std::vector<char> image;
   std::vector<float> stage_out;
   for (int c0 = 0; c0 < n_clips;) {
     // one chunk: as many clips as the workspace budget holds (at least one); clips too short to filter cost nothing
@@ -492,52 +556,29 @@ extern "C" int afx_sosfiltfilt_batch(afx_ctx* ctx, const void* samples, int samp
     c0 = c1;
     if (recs.empty()) break;
     if (tiles > (1 << 24)) { set_error(std::string(who) + ": clip too large for one launch"); return AFX_ERR_UNSUPPORTED; }
-    const int n = (int)recs.size(), nt = (int)tiles;
-    if ((rc = ensure(ctx->ft_clips, n * sizeof(FiltClip))) != AFX_OK) return rc;
-    if ((rc = ensure(ctx->ft_st, n * sizeof(FiltState))) != AFX_OK) return rc;
-    if ((rc = ensure(ctx->ft_w, (size_t)nt * kFiltTile * sizeof(double))) != AFX_OK) return rc;
-    if ((rc = ensure(ctx->ft_carry, (size_t)nt * kFiltB * kFiltZ * sizeof(double))) != AFX_OK) return rc;
-    if ((rc = ensure(ctx->ft_tmax, (size_t)nt * sizeof(double))) != AFX_OK) return rc;
+    const int n = (int)recs.size();
     const void* d_in = samples;
     if (h_in) {
-      stage_in.assign((size_t)in_pos * esz, 0);
+      pieces.clear();
       for (int q = 0; q < n; ++q)
-        std::memcpy(stage_in.data() + (size_t)recs[q].in_off * esz, (const char*)samples + (size_t)offsets[idx[q]] * esz, (size_t)recs[q].n * esz);
-      if ((rc = ensure(ctx->ft_in, stage_in.size())) != AFX_OK) return rc;
-      HIP_TRY(hipMemcpyAsync(ctx->ft_in.p, stage_in.data(), stage_in.size(), hipMemcpyHostToDevice, s));
-      d_in = ctx->ft_in.p;
+        pieces.push_back(clip_piece(samples, offsets[idx[q]], recs[q].in_off, recs[q].n, esz));
+      if ((rc = stage_in(ctx, image, in_pos * (int64_t)esz, pieces, &d_in)) != AFX_OK) return rc;
     }
-    float* d_out = out;
-    if (h_out) {
-      if ((rc = ensure(ctx->ft_out, (size_t)out_pos * sizeof(float))) != AFX_OK) return rc;
-      d_out = (float*)ctx->ft_out.p;
-    }
-    HIP_TRY(hipMemcpyAsync(ctx->ft_clips.p, recs.data(), n * sizeof(FiltClip), hipMemcpyHostToDevice, s));
-    const FiltClip* d_clips = (const FiltClip*)ctx->ft_clips.p;
-    FiltState* d_st = (FiltState*)ctx->ft_st.p;
-    double *W = (double*)ctx->ft_w.p, *carry = (double*)ctx->ft_carry.p, *tmax = (double*)ctx->ft_tmax.p;
-    const bool plain = mode == AFX_FILT_PLAIN;
-    HIP_TRY(launch_filt_peak(s, d_in, sample_fmt, d_clips, n, d_st));
-    HIP_TRY(launch_filt_forward(s, d_in, sample_fmt, mode, -preemph, padlen, n_sections, d_tab, d_clips, n, nt, d_st, W, carry));
-    HIP_TRY(launch_filt_scan(s, padlen, n_sections, d_tab, d_clips, n, d_st, carry, false));
-    HIP_TRY(launch_filt_backward(s, padlen, n_sections, d_tab, d_clips, n, nt, d_st, W, carry));
-    HIP_TRY(launch_filt_scan(s, padlen, n_sections, d_tab, d_clips, n, d_st, carry, true));
-    HIP_TRY(launch_filt_final(s, padlen, n_sections, d_tab, d_clips, n, nt, d_st, W, carry, tmax, plain ? d_out : nullptr));
-    HIP_TRY(launch_filt_clipmax(s, d_clips, n, tmax, d_st));
-    if (!plain) HIP_TRY(launch_filt_scale(s, padlen, d_clips, n, nt, d_st, W, d_out));
+    float* d_out;
+    if ((rc = out_buffer(ctx, out, out_mem_kind, out_pos, &d_out)) != AFX_OK) return rc;
+    if ((rc = run_filtfilt_chain(ctx, d_in, sample_fmt, mode, preemph, padlen, n_sections, recs, tiles, d_tab, d_out)) != AFX_OK) return rc;
     h_st.resize(n);
-    HIP_TRY(hipMemcpyAsync(h_st.data(), d_st, n * sizeof(FiltState), hipMemcpyDeviceToHost, s));
-    if (h_out) {
-      stage_out.resize((size_t)out_pos);
-      HIP_TRY(hipMemcpyAsync(stage_out.data(), d_out, (size_t)out_pos * sizeof(float), hipMemcpyDeviceToHost, s));
-    }
+    HIP_TRY(hipMemcpyAsync(h_st.data(), ctx->ft_st.p, n * sizeof(FiltState), hipMemcpyDeviceToHost, s));
+    if (h_out && (rc = fetch_out(ctx, d_out, out_pos, stage_out)) != AFX_OK) return rc;
     HIP_TRY(hipStreamSynchronize(s));
+    pieces.clear();
     for (int q = 0; q < n; ++q) {
       const int i = idx[q];
       if (h_st[q].bad) { out_status[i] = AFX_CLIP_NONFINITE; continue; }     // its output range stays as the caller left it
       if (out_peak) { out_peak[2 * i] = (double)h_st[q].peak_in; out_peak[2 * i + 1] = h_st[q].peak_out; }
-      if (h_out) std::memcpy(out + out_offsets[i], stage_out.data() + recs[q].out_off, (size_t)recs[q].n * sizeof(float));
+      if (h_out) pieces.push_back({stage_out.data() + recs[q].out_off, out_offsets[i] * 4, recs[q].n * 4});
     }
+    scatter_pieces(out, pieces);
   }
   return AFX_OK;
 }
@@ -549,10 +590,8 @@ extern "C" int afx_assess_batch(afx_ctx* ctx, const void* samples, int sample_fm
                                 const int64_t* offsets, const int64_t* lengths, const int32_t* frame_short, const int32_t* frame_long,
                                 int n_clips, double threshold_db, int64_t noise_cap, double* out_rec, int32_t* out_status) {
   const char* who = "afx_assess_batch";
-  if (!ctx || n_clips < 0 || (n_clips > 0 && (!offsets || !lengths || !frame_short || !frame_long || !out_rec || !out_status))) return null_arg(who);
-  int rc;
-  if ((rc = check_sample_format(who, sample_fmt, mem_kind)) != AFX_OK) return rc;
-  if ((rc = check_clip_ranges(who, offsets, lengths, nullptr, n_clips, INT64_MAX / 8)) != AFX_OK) return rc;
+  int rc = clip_batch_args(who, ctx, sample_fmt, mem_kind, offsets, lengths, n_clips, -1, nullptr, out_status, frame_short && frame_long && out_rec);
+  if (rc != AFX_OK) return rc;
   if (const char* why = assess_refusal(0, 1, 1, threshold_db, noise_cap)) { set_error(std::string(who) + ": " + why); return AFX_ERR_INVALID; }
   bool any = false;
   for (int i = 0; i < n_clips; ++i) {
@@ -562,10 +601,9 @@ extern "C" int afx_assess_batch(afx_ctx* ctx, const void* samples, int sample_fm
     }
     any = any || lengths[i] > 0;
   }
-  const double nan = std::nan("");
   for (int i = 0; i < n_clips; ++i) {
     out_status[i] = lengths[i] == 0 ? AFX_CLIP_TOO_SHORT : AFX_CLIP_OK;
-    std::fill(out_rec + (size_t)AFX_ASSESS_N * i, out_rec + (size_t)AFX_ASSESS_N * (i + 1), nan);
+    nan_row(out_rec, AFX_ASSESS_N, i);
   }
   if (!any) return AFX_OK;
   if (!samples) { set_error(std::string(who) + ": null samples"); return AFX_ERR_INVALID; }
@@ -579,6 +617,7 @@ extern "C" int afx_assess_batch(afx_ctx* ctx, const void* samples, int sample_fm
   assess_cost(AFX_COST_ASSESS, sample_fmt, mem_kind, cost);
   StftChunk ck;
   std::vector<AsClip> recs;
+  std::vector<HostPiece> pieces;
   std::vector<char> stage;
   std::vector<double> h_rec;
   std::vector<int32_t> h_bad;
@@ -608,12 +647,10 @@ extern "C" int afx_assess_batch(afx_ctx* ctx, const void* samples, int sample_fm
     if ((rc = ensure(ctx->as_bad, (size_t)n * sizeof(int32_t))) != AFX_OK) return rc;
     const void* d_in = samples;
     if (h_in) {
-      stage.assign((size_t)in_pos * esz, 0);
+      pieces.clear();
       for (int q = 0; q < n; ++q)
-        std::memcpy(stage.data() + (size_t)recs[q].in_off * esz, (const char*)samples + (size_t)offsets[ck.idx[q]] * esz, (size_t)recs[q].len * esz);
-      if ((rc = ensure(ctx->as_in, stage.size())) != AFX_OK) return rc;
-      HIP_TRY(hipMemcpyAsync(ctx->as_in.p, stage.data(), stage.size(), hipMemcpyHostToDevice, s));
-      d_in = ctx->as_in.p;
+        pieces.push_back(clip_piece(samples, offsets[ck.idx[q]], recs[q].in_off, recs[q].len, esz));
+      if ((rc = stage_in(ctx, stage, in_pos * (int64_t)esz, pieces, &d_in)) != AFX_OK) return rc;
     }
     HIP_TRY(hipMemcpyAsync(ctx->as_clips.p, recs.data(), (size_t)n * sizeof(AsClip), hipMemcpyHostToDevice, s));
     HIP_TRY(launch_assess(s, d_in, sample_fmt, (const AsClip*)ctx->as_clips.p, n, (int)spans, thr_ratio, (double*)ctx->as_pieces.p,
@@ -635,18 +672,15 @@ extern "C" int afx_compare_batch(afx_ctx* ctx, const void* ref, const void* deg,
                                  const int64_t* ref_offsets, const int64_t* ref_lengths, const int64_t* deg_offsets,
                                  const int64_t* deg_lengths, int n_pairs, double* out_rec, int32_t* out_status) {
   const char* who = "afx_compare_batch";
-  if (!ctx || n_pairs < 0 || (n_pairs > 0 && (!ref_offsets || !ref_lengths || !deg_offsets || !deg_lengths || !out_rec || !out_status))) return null_arg(who);
-  int rc;
-  if ((rc = check_sample_format(who, sample_fmt, mem_kind)) != AFX_OK) return rc;
-  if ((rc = check_clip_ranges(who, ref_offsets, ref_lengths, nullptr, n_pairs, INT64_MAX / 8)) != AFX_OK) return rc;
+  int rc = clip_batch_args(who, ctx, sample_fmt, mem_kind, ref_offsets, ref_lengths, n_pairs, -1, nullptr, out_status, deg_offsets && deg_lengths && out_rec);
+  if (rc != AFX_OK) return rc;
   if ((rc = check_clip_ranges(who, deg_offsets, deg_lengths, nullptr, n_pairs, INT64_MAX / 8)) != AFX_OK) return rc;
   std::vector<int64_t> lens((size_t)n_pairs);
-  const double nan = std::nan("");
   bool any = false;
   for (int i = 0; i < n_pairs; ++i) {
     lens[i] = std::min(ref_lengths[i], deg_lengths[i]);
     out_status[i] = lens[i] == 0 ? AFX_CLIP_TOO_SHORT : AFX_CLIP_OK;
-    std::fill(out_rec + (size_t)AFX_COMPARE_N * i, out_rec + (size_t)AFX_COMPARE_N * (i + 1), nan);
+    nan_row(out_rec, AFX_COMPARE_N, i);
     any = any || lens[i] > 0;
   }
   if (!any) return AFX_OK;
@@ -660,6 +694,7 @@ extern "C" int afx_compare_batch(afx_ctx* ctx, const void* ref, const void* deg,
   assess_cost(AFX_COST_COMPARE, sample_fmt, mem_kind, cost);
   StftChunk ck;
   std::vector<CmpPair> recs;
+  std::vector<HostPiece> pieces;
   std::vector<char> stage;
   std::vector<double> h_rec;
   std::vector<int32_t> h_bad;
@@ -686,15 +721,14 @@ extern "C" int afx_compare_batch(afx_ctx* ctx, const void* ref, const void* deg,
     if ((rc = ensure(ctx->as_bad, (size_t)n * sizeof(int32_t))) != AFX_OK) return rc;
     const void *d_ref = ref, *d_deg = deg;
     if (h_in) {
-      stage.assign((size_t)in_pos * esz, 0);
+      pieces.clear();
       for (int q = 0; q < n; ++q) {
         const int i = ck.idx[q];
-        std::memcpy(stage.data() + (size_t)recs[q].r_off * esz, (const char*)ref + (size_t)ref_offsets[i] * esz, (size_t)recs[q].n * esz);
-        std::memcpy(stage.data() + (size_t)recs[q].d_off * esz, (const char*)deg + (size_t)deg_offsets[i] * esz, (size_t)recs[q].n * esz);
+        pieces.push_back(clip_piece(ref, ref_offsets[i], recs[q].r_off, recs[q].n, esz));
+        pieces.push_back(clip_piece(deg, deg_offsets[i], recs[q].d_off, recs[q].n, esz));
       }
-      if ((rc = ensure(ctx->as_in, stage.size())) != AFX_OK) return rc;
-      HIP_TRY(hipMemcpyAsync(ctx->as_in.p, stage.data(), stage.size(), hipMemcpyHostToDevice, s));
-      d_ref = d_deg = ctx->as_in.p;
+      if ((rc = stage_in(ctx, stage, in_pos * (int64_t)esz, pieces, &d_ref)) != AFX_OK) return rc;
+      d_deg = d_ref;
     }
     HIP_TRY(hipMemcpyAsync(ctx->as_clips.p, recs.data(), (size_t)n * sizeof(CmpPair), hipMemcpyHostToDevice, s));
     HIP_TRY(launch_compare(s, d_ref, d_deg, sample_fmt, (const CmpPair*)ctx->as_clips.p, n, (int)spans, (double*)ctx->as_pieces.p,
@@ -739,6 +773,7 @@ static int cfft_run(const char* who, afx_ctx* ctx, const void* ref, const void* 
   std::vector<CfJob> jobs, filt_jobs;
   std::vector<int> order, slot_of;
   std::vector<int64_t> distinct, in_r, in_d;
+  std::vector<HostPiece> pieces;
   std::vector<char> stage;
   std::vector<double> h_rec;
   std::vector<int32_t> h_bad;
@@ -798,16 +833,14 @@ static int cfft_run(const char* who, afx_ctx* ctx, const void* ref, const void* 
     if ((rc = ensure(ctx->cf_bad, (size_t)n * 2 * sizeof(int32_t))) != AFX_OK) return rc;
     const void *d_ref = ref, *d_deg = deg;
     if (h_in) {
-      stage.assign((size_t)std::max<int64_t>(in_pos, 1) * esz, 0);
+      pieces.clear();
       for (int q = 0; q < n; ++q) {
         const int i = ck.idx[q];
-        std::memcpy(stage.data() + (size_t)in_r[q] * esz, (const char*)ref + (size_t)ref_offsets[i] * esz, (size_t)lens[i] * esz);
-        if (pair) std::memcpy(stage.data() + (size_t)in_d[q] * esz, (const char*)deg + (size_t)deg_offsets[i] * esz, (size_t)lens[i] * esz);
+        pieces.push_back(clip_piece(ref, ref_offsets[i], in_r[q], lens[i], esz));
+        if (pair) pieces.push_back(clip_piece(deg, deg_offsets[i], in_d[q], lens[i], esz));
       }
-      if ((rc = ensure(ctx->cf_in, stage.size())) != AFX_OK) return rc;
-      HIP_TRY(hipMemcpyAsync(ctx->cf_in.p, stage.data(), stage.size(), hipMemcpyHostToDevice, s));
-      d_ref = ctx->cf_in.p;
-      d_deg = pair ? ctx->cf_in.p : nullptr;
+      if ((rc = stage_in(ctx, stage, std::max<int64_t>(in_pos, 1) * (int64_t)esz, pieces, &d_ref)) != AFX_OK) return rc;
+      d_deg = pair ? d_ref : nullptr;
     }
     CfJob* d_fjobs = (CfJob*)ctx->cf_jobs.p;
     CfJob* d_jobs = d_fjobs + nf;
@@ -848,10 +881,8 @@ extern "C" int afx_specdist_batch(afx_ctx* ctx, const void* ref, const void* deg
                                   const int64_t* ref_offsets, const int64_t* ref_lengths, const int64_t* deg_offsets,
                                   const int64_t* deg_lengths, int n_pairs, double* out_rec, int32_t* out_status) {
   const char* who = "afx_specdist_batch";
-  if (!ctx || n_pairs < 0 || (n_pairs > 0 && (!ref_offsets || !ref_lengths || !deg_offsets || !deg_lengths || !out_rec || !out_status))) return null_arg(who);
-  int rc;
-  if ((rc = check_sample_format(who, sample_fmt, mem_kind)) != AFX_OK) return rc;
-  if ((rc = check_clip_ranges(who, ref_offsets, ref_lengths, nullptr, n_pairs, INT64_MAX / 8)) != AFX_OK) return rc;
+  int rc = clip_batch_args(who, ctx, sample_fmt, mem_kind, ref_offsets, ref_lengths, n_pairs, -1, nullptr, out_status, deg_offsets && deg_lengths && out_rec);
+  if (rc != AFX_OK) return rc;
   if ((rc = check_clip_ranges(who, deg_offsets, deg_lengths, nullptr, n_pairs, INT64_MAX / 8)) != AFX_OK) return rc;
   std::vector<int64_t> lens((size_t)n_pairs);
   bool any = false;
@@ -863,10 +894,9 @@ extern "C" int afx_specdist_batch(afx_ctx* ctx, const void* ref, const void* deg
     }
     any = any || lens[i] > 0;
   }
-  const double nan = std::nan("");
   for (int i = 0; i < n_pairs; ++i) {
     out_status[i] = lens[i] == 0 ? AFX_CLIP_TOO_SHORT : AFX_CLIP_OK;
-    std::fill(out_rec + (size_t)AFX_SPECDIST_N * i, out_rec + (size_t)AFX_SPECDIST_N * (i + 1), nan);
+    nan_row(out_rec, AFX_SPECDIST_N, i);
   }
   if (!any) return AFX_OK;
   if (!ref || !deg) { set_error(std::string(who) + ": null samples"); return AFX_ERR_INVALID; }
@@ -943,7 +973,8 @@ static int smooth_run(const char* who, afx_ctx* ctx, const void* samples, int sa
   std::vector<SmClip> recs;
   std::vector<int> idx;
   std::vector<uint32_t> h_bad;
-  std::vector<char> stage_in;
+  std::vector<HostPiece> pieces;
+  std::vector<char> image;
   std::vector<float> stage_out;
   for (int c0 = 0; c0 < n_clips;) {
     recs.clear(); idx.clear();
@@ -971,18 +1002,13 @@ static int smooth_run(const char* who, afx_ctx* ctx, const void* samples, int sa
     if ((rc = ensure(ctx->sm_bad, n * sizeof(uint32_t))) != AFX_OK) return rc;
     const void* d_in = samples;
     if (h_in) {
-      stage_in.assign((size_t)in_pos * esz, 0);
+      pieces.clear();
       for (int q = 0; q < n; ++q)
-        std::memcpy(stage_in.data() + (size_t)recs[q].in_off * esz, (const char*)samples + (size_t)offsets[idx[q]] * esz, (size_t)recs[q].n * esz);
-      if ((rc = ensure(ctx->sm_in, stage_in.size())) != AFX_OK) return rc;
-      HIP_TRY(hipMemcpyAsync(ctx->sm_in.p, stage_in.data(), stage_in.size(), hipMemcpyHostToDevice, s));
-      d_in = ctx->sm_in.p;
+        pieces.push_back(clip_piece(samples, offsets[idx[q]], recs[q].in_off, recs[q].n, esz));
+      if ((rc = stage_in(ctx, image, in_pos * (int64_t)esz, pieces, &d_in)) != AFX_OK) return rc;
     }
-    float* d_out = out;
-    if (h_out) {
-      if ((rc = ensure(ctx->sm_out, (size_t)out_pos * sizeof(float))) != AFX_OK) return rc;
-      d_out = (float*)ctx->sm_out.p;
-    }
+    float* d_out;
+    if ((rc = out_buffer(ctx, out, out_mem_kind, out_pos, &d_out)) != AFX_OK) return rc;
     HIP_TRY(hipMemcpyAsync(ctx->sm_clips.p, recs.data(), n * sizeof(SmClip), hipMemcpyHostToDevice, s));
     const SmClip* d_clips = (const SmClip*)ctx->sm_clips.p;
     uint32_t* d_bad = (uint32_t*)ctx->sm_bad.p;
@@ -991,27 +1017,17 @@ static int smooth_run(const char* who, afx_ctx* ctx, const void* samples, int sa
     else HIP_TRY(launch_medfilt(s, d_in, sample_fmt, K, d_clips, n, nt, d_bad, 1, d_out));
     h_bad.resize(n);
     HIP_TRY(hipMemcpyAsync(h_bad.data(), d_bad, n * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    if (h_out) {
-      stage_out.resize((size_t)out_pos);
-      HIP_TRY(hipMemcpyAsync(stage_out.data(), d_out, (size_t)out_pos * sizeof(float), hipMemcpyDeviceToHost, s));
-    }
+    if (h_out && (rc = fetch_out(ctx, d_out, out_pos, stage_out)) != AFX_OK) return rc;
     HIP_TRY(hipStreamSynchronize(s));
+    pieces.clear();
     for (int q = 0; q < n; ++q) {
       const int i = idx[q];
       if (h_bad[q]) { out_status[i] = AFX_CLIP_NONFINITE; continue; }       // its output range stays as the caller left it
-      if (h_out) std::memcpy(out + out_offsets[i], stage_out.data() + recs[q].out_off, (size_t)recs[q].n * sizeof(float));
+      if (h_out) pieces.push_back({stage_out.data() + recs[q].out_off, out_offsets[i] * 4, recs[q].n * 4});
     }
+    scatter_pieces(out, pieces);
   }
   return AFX_OK;
-}
-
-static int smooth_args(const char* who, afx_ctx* ctx, int sample_fmt, int mem_kind, const int64_t* offsets, const int64_t* lengths,
-                       int n_clips, int out_mem_kind, const int64_t* out_offsets, const int32_t* out_status) {
-  if (!ctx || n_clips < 0 || (n_clips > 0 && (!offsets || !lengths || !out_offsets || !out_status))) return null_arg(who);
-  int rc;
-  if ((rc = check_sample_format(who, sample_fmt, mem_kind)) != AFX_OK) return rc;
-  if ((rc = check_sample_format(who, sample_fmt, out_mem_kind)) != AFX_OK) return rc;
-  return check_clip_ranges(who, offsets, lengths, out_offsets, n_clips, INT64_MAX / 8);
 }
 
 extern "C" int afx_medfilt_batch(afx_ctx* ctx, const void* samples, int sample_fmt, int mem_kind,
@@ -1020,7 +1036,7 @@ extern "C" int afx_medfilt_batch(afx_ctx* ctx, const void* samples, int sample_f
   const char* who = "afx_medfilt_batch";
   int code;
   if (const char* why = medfilt_refusal(kernel_size, &code)) { set_error(std::string(who) + ": " + why); return code; }
-  if (int rc = smooth_args(who, ctx, sample_fmt, mem_kind, offsets, lengths, n_clips, out_mem_kind, out_offsets, out_status)) return rc;
+  if (int rc = clip_batch_args(who, ctx, sample_fmt, mem_kind, offsets, lengths, n_clips, out_mem_kind, out_offsets, out_status)) return rc;
   return smooth_run(who, ctx, samples, sample_fmt, mem_kind, offsets, lengths, n_clips, kernel_size, nullptr, 1, out, out_mem_kind,
                     out_offsets, out_status);
 }
@@ -1032,14 +1048,14 @@ extern "C" int afx_savgol_batch(afx_ctx* ctx, const void* samples, int sample_fm
   const char* who = "afx_savgol_batch";
   int code;
   if (const char* why = savgol_refusal(window_length, polyorder, deriv, delta, &code)) { set_error(std::string(who) + ": " + why); return code; }
-  if (int rc = smooth_args(who, ctx, sample_fmt, mem_kind, offsets, lengths, n_clips, out_mem_kind, out_offsets, out_status)) return rc;
+  if (int rc = clip_batch_args(who, ctx, sample_fmt, mem_kind, offsets, lengths, n_clips, out_mem_kind, out_offsets, out_status)) return rc;
   SgTab tab;
   savgol_build_tab(window_length, polyorder, deriv, delta, tab);
   return smooth_run(who, ctx, samples, sample_fmt, mem_kind, offsets, lengths, n_clips, 0, &tab, window_length, out, out_mem_kind,
                     out_offsets, out_status);
 }
 
-// One upload, the preprocess with the launchers and in the order of afx_sosfiltfilt_batch, the ZCR chain with the launchers
+// One upload, the preprocess (run_filtfilt_chain, as afx_sosfiltfilt_batch's), the ZCR chain with the launchers
 // of the two entry points above, the frame rows of both groups in one launch, the statistics; only the records come back.
 extern "C" int afx_energy_zcr_batch(afx_ctx* ctx, const void* samples, int sample_fmt, int mem_kind,
                                     const int64_t* offsets, const int64_t* lengths, int n_clips,
@@ -1053,11 +1069,10 @@ extern "C" int afx_energy_zcr_batch(afx_ctx* ctx, const void* samples, int sampl
   const bool pre = flags & AFX_EZ_PREPROCESS, en = flags & AFX_EZ_ENERGY, zc = flags & AFX_EZ_ZCR;
   constexpr int kPadlen = 18;                  // scipy's default for the experiment's 5th-order filter
   const int64_t min_n = pre ? kPadlen + 1 : 1;
-  const double nan = std::nan("");
   bool any = false;
   for (int i = 0; i < n_clips; ++i) {
     out_status[i] = lengths[i] >= min_n ? AFX_CLIP_OK : AFX_CLIP_TOO_SHORT;
-    std::fill(out_rec + (size_t)AFX_EZ_N * i, out_rec + (size_t)AFX_EZ_N * (i + 1), nan);
+    nan_row(out_rec, AFX_EZ_N, i);
     any = any || lengths[i] >= min_n;
   }
   if (!any) return AFX_OK;
@@ -1097,7 +1112,8 @@ extern "C" int afx_energy_zcr_batch(afx_ctx* ctx, const void* samples, int sampl
   std::vector<uint32_t> h_bad;
   std::vector<float> h_peak;
   std::vector<double> h_rec;
-  std::vector<char> stage_in;
+  std::vector<HostPiece> pieces;
+  std::vector<char> image;
   for (int c0 = 0; c0 < n_clips;) {
     frecs.clear(); erecs.clear(); idx.clear();
     int64_t bytes = 0, ftiles = 0, stiles = 0, frames = 0, in_pos = 0, pos = 0;
@@ -1124,7 +1140,7 @@ extern "C" int afx_energy_zcr_batch(afx_ctx* ctx, const void* samples, int sampl
       set_error(std::string(who) + ": clip too large for one launch");
       return AFX_ERR_UNSUPPORTED;
     }
-    const int n = (int)erecs.size(), nft = (int)ftiles, nst = (int)stiles;
+    const int n = (int)erecs.size(), nst = (int)stiles;
     // the ZCR chain's tile records: [0, n) from the groups' input into the workspace (the median), [n, 2 n) within it
     srecs.resize((size_t)2 * n);
     for (int q = 0, t = 0; q < n; ++q) {
@@ -1135,12 +1151,10 @@ extern "C" int afx_energy_zcr_batch(afx_ctx* ctx, const void* samples, int sampl
     }
     const void* d_in = samples;
     if (h_in) {
-      stage_in.assign((size_t)in_pos * esz, 0);
+      pieces.clear();
       for (int q = 0; q < n; ++q)
-        std::memcpy(stage_in.data() + (size_t)frecs[q].in_off * esz, (const char*)samples + (size_t)offsets[idx[q]] * esz, (size_t)frecs[q].n * esz);
-      if ((rc = ensure(ctx->sm_in, stage_in.size())) != AFX_OK) return rc;
-      HIP_TRY(hipMemcpyAsync(ctx->sm_in.p, stage_in.data(), stage_in.size(), hipMemcpyHostToDevice, s));
-      d_in = ctx->sm_in.p;
+        pieces.push_back(clip_piece(samples, offsets[idx[q]], frecs[q].in_off, frecs[q].n, esz));
+      if ((rc = stage_in(ctx, image, in_pos * (int64_t)esz, pieces, &d_in)) != AFX_OK) return rc;
     }
     if ((rc = ensure(ctx->ez_clips, n * sizeof(EzClip))) != AFX_OK) return rc;
     if ((rc = ensure(ctx->sm_clips, 2 * n * sizeof(SmClip))) != AFX_OK) return rc;
@@ -1154,25 +1168,9 @@ extern "C" int afx_energy_zcr_batch(afx_ctx* ctx, const void* samples, int sampl
     const uint32_t* d_bad;
     int bad_stride;
     if (pre) {
-      if ((rc = ensure(ctx->ft_clips, n * sizeof(FiltClip))) != AFX_OK) return rc;
-      if ((rc = ensure(ctx->ft_st, n * sizeof(FiltState))) != AFX_OK) return rc;
-      if ((rc = ensure(ctx->ft_w, (size_t)nft * kFiltTile * sizeof(double))) != AFX_OK) return rc;
-      if ((rc = ensure(ctx->ft_carry, (size_t)nft * kFiltB * kFiltZ * sizeof(double))) != AFX_OK) return rc;
-      if ((rc = ensure(ctx->ft_tmax, (size_t)nft * sizeof(double))) != AFX_OK) return rc;
       if ((rc = ensure(ctx->ez_y, (size_t)pos * sizeof(float))) != AFX_OK) return rc;
-      HIP_TRY(hipMemcpyAsync(ctx->ft_clips.p, frecs.data(), n * sizeof(FiltClip), hipMemcpyHostToDevice, s));
-      const FiltTab* d_tab = (const FiltTab*)ctx->ft_tab.p;
-      const FiltClip* d_fclips = (const FiltClip*)ctx->ft_clips.p;
-      FiltState* d_st = (FiltState*)ctx->ft_st.p;
-      double *W = (double*)ctx->ft_w.p, *carry = (double*)ctx->ft_carry.p, *tmax = (double*)ctx->ft_tmax.p;
-      HIP_TRY(launch_filt_peak(s, d_in, sample_fmt, d_fclips, n, d_st));
-      HIP_TRY(launch_filt_forward(s, d_in, sample_fmt, AFX_FILT_EXPERIMENT, -0.98f, kPadlen, kSections, d_tab, d_fclips, n, nft, d_st, W, carry));
-      HIP_TRY(launch_filt_scan(s, kPadlen, kSections, d_tab, d_fclips, n, d_st, carry, false));
-      HIP_TRY(launch_filt_backward(s, kPadlen, kSections, d_tab, d_fclips, n, nft, d_st, W, carry));
-      HIP_TRY(launch_filt_scan(s, kPadlen, kSections, d_tab, d_fclips, n, d_st, carry, true));
-      HIP_TRY(launch_filt_final(s, kPadlen, kSections, d_tab, d_fclips, n, nft, d_st, W, carry, tmax, nullptr));
-      HIP_TRY(launch_filt_clipmax(s, d_fclips, n, tmax, d_st));
-      HIP_TRY(launch_filt_scale(s, kPadlen, d_fclips, n, nft, d_st, W, (float*)ctx->ez_y.p));
+      if ((rc = run_filtfilt_chain(ctx, d_in, sample_fmt, AFX_FILT_EXPERIMENT, 0.98f, kPadlen, kSections, frecs, ftiles,
+                                   (const FiltTab*)ctx->ft_tab.p, (float*)ctx->ez_y.p)) != AFX_OK) return rc;
       d_y = ctx->ez_y.p; y_fmt = AFX_FMT_F32;
       static_assert(offsetof(FiltState, bad) == 12 && sizeof(FiltState) == 16, "the flag of record c is word 4 c + 3");
       d_bad = (const uint32_t*)ctx->ft_st.p + 3; bad_stride = 4;
@@ -1258,7 +1256,6 @@ extern "C" int afx_loudness_batch(afx_ctx* ctx, const void* samples, int sample_
   std::vector<int> rate_list;
   std::vector<int32_t> tab_of((size_t)n_clips), nbk((size_t)n_clips);
   std::vector<int64_t> zoff((size_t)n_clips);
-  const double nan = std::nan("");
   bool any = false;
   int64_t zpos = 0;
   for (int i = 0; i < n_clips; ++i) {
@@ -1281,7 +1278,7 @@ extern "C" int afx_loudness_batch(afx_ctx* ctx, const void* samples, int sample_
   for (int i = 0; i < n_clips; ++i) {
     const bool live = mode == AFX_LOUD_NORM_PEAK ? lengths[i] > 0 : nbk[i] > 0;
     out_status[i] = live ? AFX_CLIP_OK : AFX_CLIP_TOO_SHORT;
-    std::fill(out_rec + (size_t)AFX_LOUD_N * i, out_rec + (size_t)AFX_LOUD_N * (i + 1), nan);
+    nan_row(out_rec, AFX_LOUD_N, i);
     any = any || live;
   }
   if (!any) return AFX_OK;
@@ -1306,7 +1303,8 @@ extern "C" int afx_loudness_batch(afx_ctx* ctx, const void* samples, int sample_
   StftChunk ck;
   std::vector<LoudClip> recs;
   std::vector<int> idx;
-  std::vector<char> stage_in;
+  std::vector<HostPiece> pieces;
+  std::vector<char> image;
   std::vector<float> stage_out, h_gain;
   std::vector<double> h_dev, h_z;
   for (int c0 = 0; c0 < n_clips; c0 = ck.next) {
@@ -1340,13 +1338,13 @@ extern "C" int afx_loudness_batch(afx_ctx* ctx, const void* samples, int sample_
     if ((rc = ensure(ctx->ld_rec, (size_t)n * kLoudRec * sizeof(double))) != AFX_OK) return rc;
     const void* d_in = samples;
     if (h_in) {
-      stage_in.assign((size_t)in_pos * esz, 0);
+      pieces.clear();
       for (int q = 0; q < n; ++q)
-        std::memcpy(stage_in.data() + (size_t)recs[q].in_off * esz, (const char*)samples + (size_t)offsets[idx[q]] * esz, (size_t)recs[q].n * esz);
-      if ((rc = ensure(ctx->ld_in, stage_in.size())) != AFX_OK) return rc;
-      HIP_TRY(hipMemcpyAsync(ctx->ld_in.p, stage_in.data(), stage_in.size(), hipMemcpyHostToDevice, s));
-      d_in = ctx->ld_in.p;
+        pieces.push_back(clip_piece(samples, offsets[idx[q]], recs[q].in_off, recs[q].n, esz));
+      if ((rc = stage_in(ctx, image, in_pos * (int64_t)esz, pieces, &d_in)) != AFX_OK) return rc;
     }
+    float* d_out = nullptr;                    // a normalising mode writes it behind the chunk's first synchronise
+    if (norm && (rc = out_buffer(ctx, out, out_mem_kind, out_pos, &d_out)) != AFX_OK) return rc;
     HIP_TRY(hipMemcpyAsync(ctx->ld_clips.p, recs.data(), (size_t)n * sizeof(LoudClip), hipMemcpyHostToDevice, s));
     const LoudClip* d_clips = (const LoudClip*)ctx->ld_clips.p;
     double *carry = (double*)ctx->ld_carry.p, *part = (double*)ctx->ld_part.p, *d_rec = (double*)ctx->ld_rec.p;
@@ -1371,23 +1369,15 @@ extern "C" int afx_loudness_batch(afx_ctx* ctx, const void* samples, int sample_
       if (out_blocks && nbk[i] > 0) std::memcpy(out_blocks + zoff[i], h_z.data() + recs[q].z_off, (size_t)nbk[i] * sizeof(double));
     }
     if (!norm) continue;
-    float* d_out = out;
-    if (h_out) {
-      if ((rc = ensure(ctx->ld_out, (size_t)out_pos * sizeof(float))) != AFX_OK) return rc;
-      d_out = (float*)ctx->ld_out.p;
-    }
     if ((rc = ensure(ctx->ld_gain, (size_t)n * sizeof(float))) != AFX_OK) return rc;
     HIP_TRY(hipMemcpyAsync(ctx->ld_gain.p, h_gain.data(), (size_t)n * sizeof(float), hipMemcpyHostToDevice, s));
     HIP_TRY(launch_loud_gain(s, d_in, sample_fmt, d_clips, n, nt, (const float*)ctx->ld_gain.p, d_out));
-    if (h_out) {
-      stage_out.resize((size_t)out_pos);
-      HIP_TRY(hipMemcpyAsync(stage_out.data(), d_out, (size_t)out_pos * sizeof(float), hipMemcpyDeviceToHost, s));
-    }
+    if (h_out && (rc = fetch_out(ctx, d_out, out_pos, stage_out)) != AFX_OK) return rc;
     HIP_TRY(hipStreamSynchronize(s));
-    if (h_out)
-      for (int q = 0; q < n; ++q)
-        if (out_status[idx[q]] == AFX_CLIP_OK)
-          std::memcpy(out + out_offsets[idx[q]], stage_out.data() + recs[q].out_off, (size_t)recs[q].n * sizeof(float));
+    pieces.clear();
+    for (int q = 0; q < n; ++q)
+      if (h_out && out_status[idx[q]] == AFX_CLIP_OK) pieces.push_back({stage_out.data() + recs[q].out_off, out_offsets[idx[q]] * 4, recs[q].n * 4});
+    scatter_pieces(out, pieces);
   }
   return AFX_OK;
 }
@@ -1416,7 +1406,6 @@ extern "C" int afx_gate_batch(afx_ctx* ctx, const void* samples, int sample_fmt,
   const bool with_noise = noise_offsets != nullptr, stat = opts->stationary != 0;
   if (with_noise && (rc = check_clip_ranges(who, noise_offsets, noise_lengths, nullptr, n_clips, INT64_MAX / 8)) != AFX_OK) return rc;
   const int bins = gate_bins(n_fft), pitch = gate_pitch(n_fft), words = gate_words(n_fft), fpw = n_fft == 1024 ? 2 : 1;
-  const double nan = std::nan("");
 
   // the noise clip of clip i (stationary): its own, or the clip; cut to chunk_size samples on request
   auto noise_len = [&](int i) {
@@ -1437,7 +1426,7 @@ extern "C" int afx_gate_batch(afx_ctx* ctx, const void* samples, int sample_fmt,
     eff[i] = st != AFX_CLIP_OK ? 0 : stat ? std::max(L, noise_len(i)) : L;
     moff[i] = mpos;
     if (st == AFX_CLIP_OK) mpos += gate_frames(L, hop, pad) * words;
-    if (out_thresh) std::fill(out_thresh + (size_t)bins * i, out_thresh + (size_t)bins * (i + 1), nan);
+    if (out_thresh) nan_row(out_thresh, bins, i);
     any = any || st == AFX_CLIP_OK;
   }
   if (!any) return AFX_OK;
@@ -1481,7 +1470,8 @@ extern "C" int afx_gate_batch(afx_ctx* ctx, const void* samples, int sample_fmt,
   StftChunk ck;
   std::vector<GateGrid> sig, noi;
   std::vector<HpssClip> prs, prn;
-  std::vector<char> stage_in, recs;
+  std::vector<HostPiece> pieces;
+  std::vector<char> image, recs;
   std::vector<uint32_t> h_bad, h_bits;
   std::vector<double> h_thr;
   for (int c0 = 0; c0 < n_clips; c0 = ck.next) {
@@ -1546,20 +1536,15 @@ extern "C" int afx_gate_batch(afx_ctx* ctx, const void* samples, int sample_fmt,
     }
     const void* d_in = samples;
     if (h_in) {
-      stage_in.assign((size_t)in_pos * esz, 0);
+      pieces.clear();
       for (int q = 0; q < n; ++q)
-        std::memcpy(stage_in.data() + (size_t)prs[q].in_off * esz, (const char*)samples + (size_t)offsets[ck.idx[q]] * esz, (size_t)prs[q].len * esz);
+        pieces.push_back(clip_piece(samples, offsets[ck.idx[q]], prs[q].in_off, prs[q].len, esz));
       for (size_t q = 0; q < prn.size(); ++q)
-        std::memcpy(stage_in.data() + (size_t)prn[q].in_off * esz, (const char*)samples + (size_t)noise_offsets[ck.idx[q]] * esz, (size_t)prn[q].len * esz);
-      if ((rc = ensure(ctx->gt_in, std::max<size_t>(stage_in.size(), 1))) != AFX_OK) return rc;
-      HIP_TRY(hipMemcpyAsync(ctx->gt_in.p, stage_in.data(), stage_in.size(), hipMemcpyHostToDevice, s));
-      d_in = ctx->gt_in.p;
+        pieces.push_back(clip_piece(samples, noise_offsets[ck.idx[q]], prn[q].in_off, prn[q].len, esz));
+      if ((rc = stage_in(ctx, image, in_pos * (int64_t)esz, pieces, &d_in)) != AFX_OK) return rc;
     }
-    float* d_out = out;
-    if (h_out) {
-      if ((rc = ensure(ctx->gt_out, (size_t)std::max<int64_t>(ypos, 1) * sizeof(float))) != AFX_OK) return rc;
-      d_out = (float*)ctx->gt_out.p;
-    }
+    float* d_out;
+    if ((rc = out_buffer(ctx, out, out_mem_kind, std::max<int64_t>(ypos, 1), &d_out)) != AFX_OK) return rc;
     HIP_TRY(hipMemcpyAsync(ctx->gt_grids.p, recs.data(), recs.size(), hipMemcpyHostToDevice, s));
     const GateGrid* d_sig = (const GateGrid*)ctx->gt_grids.p;
     const GateGrid* d_noi = (const GateGrid*)((const char*)ctx->gt_grids.p + o_noi);

@@ -1021,7 +1021,7 @@ static int groups_setup(afx_plan* pl) {
   return AFX_OK;
 }
 
-// The experiment preprocess of a cut chunk, with the launchers and in the order of afx_sosfiltfilt_batch: the clips of ck
+// The experiment preprocess of a cut chunk (run_filtfilt_chain, as afx_sosfiltfilt_batch's): the clips of ck
 // (in_off: the caller's offsets) from the caller's device buffer or a copy of [lo, hi) in gp_in to gp_filt at y_off; the
 // records then name gp_filt as their input.  The states stay in the context's ft_st, one per record.
 static int groups_preprocess_chunk(afx_plan* pl, const void* samples, int sample_fmt, int mem_kind, int n_sections,
@@ -1047,27 +1047,9 @@ static int groups_preprocess_chunk(afx_plan* pl, const void* samples, int sample
     tiles += nt;
     if (tiles > (1 << 24)) { set_error("afx_groups_batch: clip too large for one launch"); return AFX_ERR_UNSUPPORTED; }
   }
-  const int nt = (int)tiles;
-  if ((rc = ensure(ctx->ft_clips, n * sizeof(FiltClip))) != AFX_OK) return rc;
-  if ((rc = ensure(ctx->ft_st, n * sizeof(FiltState))) != AFX_OK) return rc;
-  if ((rc = ensure(ctx->ft_w, (size_t)nt * kFiltTile * sizeof(double))) != AFX_OK) return rc;
-  if ((rc = ensure(ctx->ft_carry, (size_t)nt * kFiltB * kFiltZ * sizeof(double))) != AFX_OK) return rc;
-  if ((rc = ensure(ctx->ft_tmax, (size_t)nt * sizeof(double))) != AFX_OK) return rc;
   if ((rc = ensure(pl->gp_filt, (size_t)ck.samples * sizeof(float) + 64)) != AFX_OK) return rc;
-  HIP_TRY(hipMemcpyAsync(ctx->ft_clips.p, frecs.data(), n * sizeof(FiltClip), hipMemcpyHostToDevice, s));
-  const FiltTab* d_tab = (const FiltTab*)ctx->ft_tab.p;
-  const FiltClip* d_clips = (const FiltClip*)ctx->ft_clips.p;
-  FiltState* d_st = (FiltState*)ctx->ft_st.p;
-  double *W = (double*)ctx->ft_w.p, *carry = (double*)ctx->ft_carry.p, *tmax = (double*)ctx->ft_tmax.p;
-  const int padlen = kGroupsPadlen, S = n_sections;
-  HIP_TRY(launch_filt_peak(s, d_in, sample_fmt, d_clips, n, d_st));
-  HIP_TRY(launch_filt_forward(s, d_in, sample_fmt, AFX_FILT_EXPERIMENT, -0.98f, padlen, S, d_tab, d_clips, n, nt, d_st, W, carry));
-  HIP_TRY(launch_filt_scan(s, padlen, S, d_tab, d_clips, n, d_st, carry, false));
-  HIP_TRY(launch_filt_backward(s, padlen, S, d_tab, d_clips, n, nt, d_st, W, carry));
-  HIP_TRY(launch_filt_scan(s, padlen, S, d_tab, d_clips, n, d_st, carry, true));
-  HIP_TRY(launch_filt_final(s, padlen, S, d_tab, d_clips, n, nt, d_st, W, carry, tmax, nullptr));
-  HIP_TRY(launch_filt_clipmax(s, d_clips, n, tmax, d_st));
-  HIP_TRY(launch_filt_scale(s, padlen, d_clips, n, nt, d_st, W, (float*)pl->gp_filt.p));
+  if ((rc = run_filtfilt_chain(ctx, d_in, sample_fmt, AFX_FILT_EXPERIMENT, 0.98f, kGroupsPadlen, n_sections, frecs, tiles,
+                               (const FiltTab*)ctx->ft_tab.p, (float*)pl->gp_filt.p)) != AFX_OK) return rc;
   for (HpssClip& r : ck.recs) r.in_off = r.y_off;
   return AFX_OK;
 }

@@ -1,5 +1,6 @@
 // Host-only part of libafx.so: the error string, the version, and the builders that need no device -- the clip records of
-// a batch (what prepare_descriptors uploads), the chunk cut of the STFT-based groups (cut_stft_chunk, afx_stft_chunks), the
+// a batch (what prepare_descriptors uploads), the packed image of a host batch (pack_pieces, scatter_pieces), the chunk cut
+// of the STFT-based groups (cut_stft_chunk, afx_stft_chunks), the
 // pYIN tables, the pYIN kernel dispatch (afx_f0_dispatch), the chroma filterbank (afx_chroma_filters) and the tempo table
 // (afx_tempo_table).  Together with afx_tables.cpp, afx_f0_tables.cpp and afx_wav.cpp this is everything that parses
 // caller- or file-supplied data on the host; `make asan` builds exactly these files (plus afx_host_stubs.cpp) with
@@ -117,6 +118,17 @@ void groups_dct_table(int n_mels, float* out) {
   for (int k = 0; k < kGroupsMfcc; ++k)
     for (int m = 0; m < n_mels; ++m)
       out[k * kRhMels + m] = (float)(std::sqrt((k == 0 ? 1.0 : 2.0) / M) * std::cos(M_PI * (double)k * (2.0 * m + 1.0) / (2.0 * M)));
+}
+
+// The packed image a context entry point uploads for a host batch, and the way back of a downloaded one.
+void scatter_pieces(void* dst, const std::vector<HostPiece>& pieces) {
+  for (const HostPiece& p : pieces)
+    if (p.n_bytes > 0) std::memcpy((char*)dst + p.dst_bytes, p.src, (size_t)p.n_bytes);
+}
+
+void pack_pieces(std::vector<char>& image, int64_t total_bytes, const std::vector<HostPiece>& pieces) {
+  image.assign((size_t)total_bytes, 0);
+  scatter_pieces(image.data(), pieces);
 }
 
 // One Stockham pass of radix R over N2 points, butterfly by butterfly as k_frames_mr's lanes take them.

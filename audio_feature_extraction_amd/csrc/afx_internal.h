@@ -67,4 +67,15 @@ struct BatchGeom {
 bool build_clip_descs(int hop, int trim_hop, const int64_t* offsets, const int64_t* lengths, int n, ClipDesc* out,
                       BatchGeom& g, std::string& why);
 
+// afx_host.cpp: n_bytes at src belong at byte dst_bytes of a destination (host-only; a clip of a host batch in the packed
+// image that is uploaded, or a clip of a downloaded image in the caller's output)
+struct HostPiece {
+  const void* src;
+  int64_t dst_bytes, n_bytes;
+};
+// image = total_bytes of zero with every piece copied in.  The pieces may be empty, come in any order and from any buffers.
+void pack_pieces(std::vector<char>& image, int64_t total_bytes, const std::vector<HostPiece>& pieces);
+// every piece copied to dst + dst_bytes; the bytes between the pieces are not written
+void scatter_pieces(void* dst, const std::vector<HostPiece>& pieces);
+
 }  // namespace afx

@@ -1,6 +1,6 @@
 // The state behind the opaque handles of include/afx.h (afx_ctx, afx_plan) and the front end every batch entry point
 // shares: argument checks, sample staging, the preprocessing chain, per-frame output ranges.  Internal to libafx.so:
-// included by afx_api.cpp (which defines the helpers), afx_features.cpp and afx_ctx_ops.cpp.
+// included by afx_api.cpp (which defines the plan's helpers), afx_features.cpp and afx_ctx_ops.cpp (which defines the context's).
 #pragma once
 #include <algorithm>
 #include <cstdint>
@@ -42,37 +42,40 @@ struct afx_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
   DevBuf dtw_raw, dtw_feats, dtw_norms, dtw_pairs, dtw_codes, dtw_rows, dtw_d, dtw_path, dtw_cost, dtw_status, dtw_len, dtw_end;   // afx_dtw_batch, afx_dtw_steps_batch
-  // afx_resample_batch: the tables of the last rate pair (or caller-supplied filter) used, and the staging of host batches
+  // Staging of host batches, shared by every entry point below: the packed input image (stage_in) and the packed result
+  // (out_buffer).  A chunk stages its input once and obtains its output buffer once, before its first launch, and nothing
+  // calls ensure on either again until the chunk's synchronise: ensure frees the old buffer when it grows.
+  DevBuf wave_in, wave_out;
+  // afx_resample_batch: the tables of the last rate pair (or caller-supplied filter) used
   struct {
     bool valid = false, custom = false;
     int up = 0, down = 0;
     std::vector<double> taps;        // the caller's filter the tables were built from (custom only)
     RsTables t;
   } rs;
-  DevBuf rs_g, rs_tstart, rs_clips, rs_in, rs_out;
-  DevBuf dc_clips, dc_in, dc_out;      // afx_decode_batch: clip records, staging of host batches
-  // afx_sosfiltfilt_batch: tables, a chunk's clip records and states, the float64 workspace, the blocks' carries, the tile
-  // maxima, staging of host batches
-  DevBuf ft_tab, ft_clips, ft_st, ft_w, ft_carry, ft_tmax, ft_in, ft_out;
+  DevBuf rs_g, rs_tstart, rs_clips;
+  DevBuf dc_clips;                     // afx_decode_batch: clip records
+  // afx_sosfiltfilt_batch: tables and, filled by run_filtfilt_chain, a chunk's clip records and states, the float64
+  // workspace, the blocks' carries, the tile maxima
+  DevBuf ft_tab, ft_clips, ft_st, ft_w, ft_carry, ft_tmax;
   // afx_assess_batch / afx_compare_batch: a chunk's records, the pieces (the spans' sums of a pair), the span records, the
-  // results and flags, staging of host batches
-  DevBuf as_clips, as_pieces, as_spans, as_rec, as_bad, as_in;
+  // results and flags
+  DevBuf as_clips, as_pieces, as_spans, as_rec, as_bad;
   // afx_specdist_batch / afx_clip_fft_batch: the stage twiddle table (built at first use), a chunk's job records, the
-  // transforms' points, the filter spectra, the results and flags, staging of host batches
-  DevBuf cf_tw, cf_jobs, cf_work, cf_filt, cf_rec, cf_bad, cf_in;
+  // transforms' points, the filter spectra, the results and flags
+  DevBuf cf_tw, cf_jobs, cf_work, cf_filt, cf_rec, cf_bad;
   bool cf_tw_ready = false;
-  // afx_medfilt_batch / afx_savgol_batch: the Savitzky-Golay tables, a chunk's clip records and non-finite flags, staging of
-  // host batches.  afx_energy_zcr_batch (with these and the filter workspace above): the frame records, the preprocessed,
+  // afx_medfilt_batch / afx_savgol_batch: the Savitzky-Golay tables, a chunk's clip records and non-finite flags.
+  // afx_energy_zcr_batch (with these and the filter workspace above): the frame records, the preprocessed,
   // median-filtered and smoothed signals, the sign plane, the smoothed peaks, the frame rows of both groups, the records
-  DevBuf sm_tab, sm_clips, sm_bad, sm_in, sm_out;
+  DevBuf sm_tab, sm_clips, sm_bad;
   DevBuf ez_clips, ez_y, ez_m, ez_s, ez_neg, ez_peak, ez_energy, ez_rate, ez_rec;
   // afx_loudness_batch: one table per distinct rate, a chunk's clip records, the blocks' states and partial sums, the tiles'
-  // peaks and flags, the segment sums, z_j, the clips' scalars, the gains, staging of host batches
-  DevBuf ld_tab, ld_clips, ld_carry, ld_part, ld_tpeak, ld_tbad, ld_seg, ld_z, ld_rec, ld_gain, ld_in, ld_out;
+  // peaks and flags, the segment sums, z_j, the clips' scalars, the gains
+  DevBuf ld_tab, ld_clips, ld_carry, ld_part, ld_tpeak, ld_tbad, ld_seg, ld_z, ld_rec, ld_gain;
   // afx_gate_batch: the window / twiddles / taps, a chunk's grid records, its float32 signal, the non-finite flags, the
-  // magnitude planes of both grids, the mask plane, the forward pass, the bit plane, thr and its amplitude, the time rows,
-  // staging of host batches
-  DevBuf gt_tab, gt_grids, gt_y, gt_bad, gt_mag, gt_nmag, gt_mask, gt_fwd, gt_bits, gt_thr, gt_amp, gt_rows, gt_in, gt_out;
+  // magnitude planes of both grids, the mask plane, the forward pass, the bit plane, thr and its amplitude, the time rows
+  DevBuf gt_tab, gt_grids, gt_y, gt_bad, gt_mag, gt_nmag, gt_mask, gt_fwd, gt_bits, gt_thr, gt_amp, gt_rows;
 };
 
 struct afx_plan {
@@ -218,5 +221,19 @@ int run_spectral(afx_plan* pl, const void* d_signal, int n, const KParams& kp, c
                  const SpecBands& sb);
 // downloads the clip records (synchronises the stream): AFX_CLIP_NONFINITE or AFX_CLIP_OK per clip
 int statuses_from_info(afx_plan* pl, int n, int32_t* out_status);
+
+// ---- what the context entry points share (afx_ctx_ops.cpp), all on ctx->stream; see the rule at afx_ctx::wave_in ----
+// the pieces packed into image (total_bytes, zero between them; pack_pieces), uploaded to ctx->wave_in: *d_in
+int stage_in(afx_ctx* ctx, std::vector<char>& image, int64_t total_bytes, const std::vector<HostPiece>& pieces, const void** d_in);
+// where a chunk's kernels write: the caller's out if it is device memory, else ctx->wave_out grown to total floats
+int out_buffer(afx_ctx* ctx, float* out, int out_mem_kind, int64_t total, float** d_out);
+// one copy of total floats at d_out into host, not waited for; scatter_pieces hands them on after the caller's synchronise
+int fetch_out(afx_ctx* ctx, const float* d_out, int64_t total, std::vector<float>& host);
+// scipy's sosfiltfilt over the tiles of recs, from d_in (sample_fmt) to d_out: its workspace in the context's ft_*
+// buffers, the records uploaded, then k_filt_peak, forward, scan, backward, scan, final and clipmax.  AFX_FILT_PLAIN:
+// k_filt_final writes d_out; AFX_FILT_EXPERIMENT (pre-emphasis preemph): k_filt_scale does.  The clips' FiltState records
+// are left in ctx->ft_st, one per record.
+int run_filtfilt_chain(afx_ctx* ctx, const void* d_in, int sample_fmt, int mode, float preemph, int padlen, int n_sections,
+                       const std::vector<FiltClip>& recs, int64_t tiles, const FiltTab* d_tab, float* d_out);
 
 #pragma GCC visibility pop
