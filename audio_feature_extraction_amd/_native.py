@@ -58,6 +58,8 @@ EZ_FIELDS = ("T", "fl", "hop", "energy_mean", "energy_std", "energy_p10", "zcr_m
 LOUD_MEASURE, LOUD_NORM_LOUDNESS, LOUD_NORM_PEAK = 0, 1, 2                    # afx_loudness_batch: its modes
 LOUD_N = 11                                                                  # doubles per clip of its record
 CLIP_TOO_LONG = 3                                                            # afx_gate_batch: more than chunk_size samples
+PAD_CONSTANT, PAD_REFLECT = 0, 1                                             # afx_stft_batch: its pad modes
+STFT_COMPLEX, STFT_MAG, STFT_POWER = 0, 1, 2                                 # and output kinds
 LOUD_FIELDS = ("lufs", "blocks", "n1", "n2", "gamma_r", "gated_ms", "peak", "gain", "peak_out", "first_ms", "ungated_ms")
 GROUPS_STATS = 24                                                            # doubles per clip of its record
 K_NAMES = ("trim_blocks", "trim_decide", "frames", "dct", "stats")
@@ -85,6 +87,7 @@ SYMBOLS = (
     "afx_kweight_sos", "afx_loudness_geometry", "afx_loudness_blocks", "afx_loudness_cost", "afx_loudness_host",
     "afx_loudness_batch",
     "afx_gate_params", "afx_gate_cost", "afx_gate_batch",
+    "afx_stft_frames", "afx_istft_samples", "afx_stft_cost", "afx_stft_batch", "afx_istft_batch",
 )
 
 
@@ -101,6 +104,12 @@ class GateOpts(C.Structure):
         ("time_mask_smooth_ms", C.c_double), ("thresh_n_mult", C.c_double), ("sigmoid_slope", C.c_double),
         ("n_std_thresh", C.c_double),
     ]
+
+
+class StftOpts(C.Structure):
+    """afx_stft_opts: the framing of afx_stft_batch / afx_istft_batch."""
+    _fields_ = [("n_fft", C.c_int32), ("hop", C.c_int32), ("center", C.c_int32), ("pad_mode", C.c_int32),
+                ("out_kind", C.c_int32), ("reserved", C.c_int32 * 3)]
 
 
 class Params(C.Structure):
@@ -234,6 +243,13 @@ def lib() -> C.CDLL:
             L.afx_gate_params.argtypes = [vp, C.c_int64, vp, vp, vp, vp]
             L.afx_gate_cost.argtypes = [vp, i32, i32, i32, i32, vp]
             L.afx_gate_batch.argtypes = [vp, vp, i32, i32, vp, vp, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp]
+        if hasattr(L, "afx_stft_batch"):                     # newer than version 107 says: found by their presence
+            i64 = C.c_int64
+            L.afx_stft_frames.argtypes = [vp, i64, vp, vp]
+            L.afx_istft_samples.argtypes = [vp, i64, i64, vp, vp]
+            L.afx_stft_cost.argtypes = [vp, i32, i32, i32, i32, vp]
+            L.afx_stft_batch.argtypes = [vp, vp, i32, i32, vp, vp, i32, vp, vp, vp, i32, vp, vp]
+            L.afx_istft_batch.argtypes = [vp, vp, i32, vp, vp, i32, vp, vp, vp, vp, i32, vp, vp]
         if hasattr(L, "afx_rfft_host"):                      # absent from a library built before the mixed-radix lengths
             L.afx_rfft_host.argtypes = [i32, vp, vp]
         _lib = L
@@ -702,6 +718,56 @@ def gate_cost(opts: GateOpts, fmt: int = FMT_F32, mem: int = MEM_HOST, out_mem: 
     _check(lib().afx_gate_cost(C.addressof(opts), int(fmt), int(mem), int(out_mem), int(bool(with_noise)), cost.ctypes.data),
            "afx_gate_cost")
     return cost
+
+
+def _need_stft():
+    if not hasattr(lib(), "afx_stft_batch"):
+        raise NotImplementedError("this libafx has no afx_stft_batch")
+
+
+def stft_opts(n_fft: int = 2048, hop_length=None, center: bool = True, pad_mode="constant", out_kind: int = STFT_COMPLEX) -> StftOpts:
+    """librosa.stft's framing keywords as the record afx_stft_batch / afx_istft_batch take (hop_length None: n_fft // 4).
+    ``pad_mode``: "constant", "reflect" or a PAD_* value; ValueError for any other, as for the modes librosa refuses."""
+    modes = {"constant": PAD_CONSTANT, "reflect": PAD_REFLECT, PAD_CONSTANT: PAD_CONSTANT, PAD_REFLECT: PAD_REFLECT}
+    if isinstance(pad_mode, bool) or pad_mode not in modes:
+        raise ValueError(f"pad_mode {pad_mode!r} is not supported (constant, reflect)")
+    hop = int(n_fft) // 4 if hop_length is None else int(hop_length)
+    return StftOpts(int(n_fft), hop, int(bool(center)), modes[pad_mode], int(out_kind))
+
+
+def stft_frames(opts: StftOpts, length: int):
+    """Host-only: afx_stft_frames -> (T, status) of a clip of ``length`` samples (T = 0 unless CLIP_OK).
+    NotImplementedError for an n_fft other than 1024 / 2048 or a hop outside [1, n_fft]."""
+    _need_stft()
+    T, st = C.c_int64(0), C.c_int32(0)
+    _check(lib().afx_stft_frames(C.addressof(opts), int(length), C.addressof(T), C.addressof(st)), "afx_stft_frames")
+    return int(T.value), int(st.value)
+
+
+def istft_samples(opts: StftOpts, T: int, length=None):
+    """Host-only: afx_istft_samples -> (frames used, samples written) by istft of ``T`` frames (``length`` None: natural)."""
+    _need_stft()
+    nf, no = C.c_int64(0), C.c_int64(0)
+    _check(lib().afx_istft_samples(C.addressof(opts), int(T), -1 if length is None else int(length), C.addressof(nf),
+                                   C.addressof(no)), "afx_istft_samples")
+    return int(nf.value), int(no.value)
+
+
+def stft_cost(opts: StftOpts, fmt: int = FMT_F32, mem: int = MEM_HOST, out_mem: int = MEM_HOST, inverse: bool = False) -> np.ndarray:
+    """Host-only: the int64 [6] cost record afx_stft_batch (over the clips' lengths, 0 for a clip that is too short) or
+    afx_istft_batch (``inverse``: over frames used + ceil(samples written / hop)) cuts a batch with, for :func:`stft_chunks`."""
+    _need_stft()
+    cost = np.zeros(6, np.int64)
+    _check(lib().afx_stft_cost(C.addressof(opts), int(fmt), int(mem), int(out_mem), int(bool(inverse)), cost.ctypes.data),
+           "afx_stft_cost")
+    return cost
+
+
+def _stft_window(opts: StftOpts, window) -> np.ndarray:
+    window = np.ascontiguousarray(window, np.float32).reshape(-1)
+    if window.shape[0] != opts.n_fft:
+        raise ValueError("window must hold n_fft values (pad a shorter one centred, as librosa.util.pad_center does)")
+    return window
 
 
 def _need_loudness():
@@ -1247,6 +1313,78 @@ class Context(_Owner):
                 pos += T * words
             res["mask"] = masks
         return res
+
+    def stft_batch(self, samples, offsets, lengths, opts: StftOpts, window, fmt=None, out=None, out_offsets=None) -> dict:
+        """afx_stft_batch: librosa.stft of the clips samples[offsets[i] .. + lengths[i]) with the framing of ``opts``
+        (:func:`stft_opts`) and ``window`` (n_fft float32 values).  Clip i takes frames[i] rows of n_fft / 2 + 1 elements
+        (complex64, or float32 for STFT_MAG / STFT_POWER) from element ``out_offsets[i]`` (default: packed) of ``out``: None
+        (a new host array), a numpy array of the element type, or a DeviceBuffer / device address the result stays in.
+        Returns out, offsets, frames, status (CLIP_TOO_SHORT: no rows; CLIP_NONFINITE: zeros) and, for a host result, spec:
+        per clip the [n_fft / 2 + 1, frames] view in librosa's memory order (None for a failed clip)."""
+        _need_stft()
+        offsets, lengths, n = _clip_arrays(offsets, lengths)
+        fmt = _sample_fmt(samples, fmt)
+        sptr, kind = _sample_source(samples, fmt, offsets, lengths)
+        window = _stft_window(opts, window)
+        bins = opts.n_fft // 2 + 1
+        dt = np.complex64 if opts.out_kind == STFT_COMPLEX else np.float32
+        frames = np.array([stft_frames(opts, int(l))[0] for l in lengths], np.int64)
+        if out_offsets is None:
+            out_offsets = packed_offsets(frames * bins)
+        out_offsets = np.ascontiguousarray(out_offsets, np.int64).reshape(-1)
+        if out_offsets.shape[0] != n:
+            raise ValueError("out_offsets must have one entry per clip")
+        need = int((out_offsets + frames * bins).max()) if n else 0
+        if out is None:
+            out = np.zeros(need, dt)
+        if isinstance(out, np.ndarray):
+            if out.dtype != dt or not out.flags.c_contiguous or out.size < need:
+                raise ValueError(f"out must be a C-contiguous {np.dtype(dt).name} array that holds every clip")
+            optr, okind = out.ctypes.data, MEM_HOST
+        else:
+            if isinstance(out, DeviceBuffer) and out.nbytes < np.dtype(dt).itemsize * need:
+                raise ValueError("the output DeviceBuffer is too small")
+            optr, okind = (out.ptr if isinstance(out, DeviceBuffer) else int(out)), MEM_DEVICE
+        status = np.zeros(n, np.int32)
+        _check(lib().afx_stft_batch(self.handle, sptr, int(fmt), kind, offsets.ctypes.data, lengths.ctypes.data, n,
+                                    C.addressof(opts), window.ctypes.data, optr, okind, out_offsets.ctypes.data,
+                                    status.ctypes.data), "afx_stft_batch")
+        res = {"out": out, "offsets": out_offsets, "frames": frames, "status": status}
+        if okind == MEM_HOST:
+            flat = out.reshape(-1)
+            res["spec"] = [flat[o:o + T * bins].reshape(T, bins).T if st == CLIP_OK else None
+                           for o, T, st in zip(out_offsets, frames, status)]
+        return res
+
+    def istft_batch(self, spec, spec_offsets, n_frames, opts: StftOpts, window, lengths=None, out=None, out_offsets=None) -> dict:
+        """afx_istft_batch: librosa.istft of the spectra in ``spec``, a C-contiguous complex64 numpy array or a DeviceBuffer /
+        device address: clip i is n_frames[i] rows of n_fft / 2 + 1 bins from element ``spec_offsets[i]``, frame after frame
+        (the memory of librosa's Fortran-ordered array).  ``lengths``: None, or per clip the ``length`` asked for (negative:
+        none).  ``out`` / ``out_offsets``: as sosfiltfilt_batch.  Returns out, offsets, samples (written per clip), status."""
+        _need_stft()
+        spec_offsets, n_frames, n = _clip_arrays(spec_offsets, n_frames)
+        window = _stft_window(opts, window)
+        bins = opts.n_fft // 2 + 1
+        if isinstance(spec, np.ndarray):
+            if spec.dtype != np.complex64 or not spec.flags.c_contiguous:
+                raise ValueError("spec must be a C-contiguous complex64 array")
+            if n and int((spec_offsets + n_frames * bins).max()) > spec.size:
+                raise ValueError("a clip extends past the spectrum buffer")
+            sptr, kind = spec.ctypes.data, MEM_HOST
+        else:
+            sptr, kind = (spec.ptr if isinstance(spec, DeviceBuffer) else int(spec)), MEM_DEVICE
+        if lengths is not None:
+            lengths = np.ascontiguousarray(lengths, np.int64).reshape(-1)
+            if lengths.shape[0] != n:
+                raise ValueError("lengths must have one entry per clip")
+        samples = np.array([istft_samples(opts, int(T), None if lengths is None or lengths[i] < 0 else int(lengths[i]))[1]
+                            for i, T in enumerate(n_frames)], np.int64)
+        out, out_offsets, optr, okind = self._smooth_out(samples, n, out, out_offsets)
+        status = np.zeros(n, np.int32)
+        _check(lib().afx_istft_batch(self.handle, sptr, kind, spec_offsets.ctypes.data, n_frames.ctypes.data, n,
+                                     C.addressof(opts), window.ctypes.data, _ptr(lengths), optr, okind,
+                                     out_offsets.ctypes.data, status.ctypes.data), "afx_istft_batch")
+        return {"out": out, "offsets": out_offsets, "samples": samples, "status": status}
 
     def energy_zcr_batch(self, samples, offsets, lengths, sr: int, frame_length: int = 2048, hop_length: int = 512,
                          flags: int = EZ_PREPROCESS | EZ_ENERGY | EZ_ZCR, fmt=None) -> dict:

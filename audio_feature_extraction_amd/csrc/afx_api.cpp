@@ -53,6 +53,7 @@ DevEnv::DevEnv() {
   if (const char* v = getenv("AFX_TEST_SMOOTH_BUDGET")) smooth_budget = std::max<int64_t>(1, atoll(v));
   if (const char* v = getenv("AFX_TEST_LOUD_BUDGET")) loud_budget = std::max<int64_t>(1, atoll(v));
   if (const char* v = getenv("AFX_TEST_GATE_BUDGET")) gate_budget = std::max<int64_t>(1, atoll(v));
+  if (const char* v = getenv("AFX_TEST_STFT_BUDGET")) stft_budget = std::max<int64_t>(1, atoll(v));
   f0_dump = getenv("AFX_F0_DUMP");
 }
 const DevEnv& dev_env() { static const DevEnv e; return e; }
@@ -90,7 +91,8 @@ extern "C" void afx_destroy(afx_ctx* ctx) {
                     &ctx->ez_y, &ctx->ez_m, &ctx->ez_s, &ctx->ez_neg, &ctx->ez_peak, &ctx->ez_energy, &ctx->ez_rate, &ctx->ez_rec, &ctx->ld_tab,
                     &ctx->ld_clips, &ctx->ld_carry, &ctx->ld_part, &ctx->ld_tpeak, &ctx->ld_tbad, &ctx->ld_seg, &ctx->ld_z, &ctx->ld_rec,
                     &ctx->ld_gain, &ctx->gt_tab, &ctx->gt_grids, &ctx->gt_y, &ctx->gt_bad, &ctx->gt_mag, &ctx->gt_nmag, &ctx->gt_mask,
-                    &ctx->gt_fwd, &ctx->gt_bits, &ctx->gt_thr, &ctx->gt_amp, &ctx->gt_rows})
+                    &ctx->gt_fwd, &ctx->gt_bits, &ctx->gt_thr, &ctx->gt_amp, &ctx->gt_rows, &ctx->st_tab, &ctx->st_recs, &ctx->st_y,
+                    &ctx->st_bad, &ctx->st_rows})
     release(*b);
   if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
   delete ctx;

@@ -1,7 +1,7 @@
 // The entry points of libafx.so that work on a context, not a plan: batched DTW, polyphase resampling, the conversion /
 // mix-down of raw WAVE data, zero-phase IIR filtering, the recording screen and the compare sums, the whole-clip DFT and
-// the spectral distance, the median and Savitzky-Golay filters with the energy and ZCR groups, BS.1770 loudness and
-// spectral gating -- and what they share: the staging of a host batch and the launches of the zero-phase filter.
+// the spectral distance, the median and Savitzky-Golay filters with the energy and ZCR groups, BS.1770 loudness,
+// spectral gating and librosa-style stft / istft -- and what they share: the staging of a host batch and the launches of the zero-phase filter.
 #include <algorithm>
 #include <cmath>
 #include <cstddef>
@@ -1598,6 +1598,211 @@ extern "C" int afx_gate_batch(afx_ctx* ctx, const void* samples, int sample_fmt,
       if (stat && out_thresh && !nf) std::memcpy(out_thresh + (size_t)bins * i, h_thr.data() + (size_t)q * pitch, (size_t)bins * sizeof(double));
       if (stat && out_mask) std::memcpy(out_mask + moff[i], h_bits.data() + sig[q].row_base * words, (size_t)sig[q].T * words * sizeof(uint32_t));
     }
+  }
+  return AFX_OK;
+}
+
+// ---- librosa-style stft / istft at n_fft 1024 and 2048 -----------------------------------------------------------------------
+// The caller's window and the twiddles of both transforms, uploaded once per call (the window is the caller's to change).
+static int stft_tables(afx_ctx* ctx, int n_fft, const float* window, StftTabs& tb) {
+  std::vector<float> tab((size_t)n_fft + 4096);
+  std::memcpy(tab.data(), window, (size_t)n_fft * sizeof(float));
+  for (int k = 0; k < 1024; ++k) {
+    tab[n_fft + 2 * k] = (float)std::cos(2.0 * M_PI * k / 1024.0); tab[n_fft + 2 * k + 1] = (float)-std::sin(2.0 * M_PI * k / 1024.0);
+    tab[n_fft + 2048 + 2 * k] = (float)std::cos(2.0 * M_PI * k / 2048.0); tab[n_fft + 2048 + 2 * k + 1] = (float)-std::sin(2.0 * M_PI * k / 2048.0);
+  }
+  if (int rc = ensure(ctx->st_tab, tab.size() * sizeof(float))) return rc;
+  HIP_TRY(hipMemcpyAsync(ctx->st_tab.p, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));            // tab dies here
+  tb.window = (const float*)ctx->st_tab.p;
+  tb.w1024 = tb.window + n_fft;
+  tb.w2048 = tb.w1024 + 2048;
+  return AFX_OK;
+}
+
+static int stft_opts_arg(const char* who, const afx_stft_opts* opts) {
+  const char* why = "";
+  const int rc = stft_check_opts(*opts, &why);
+  if (rc != AFX_OK) set_error(std::string(who) + ": " + why);
+  return rc;
+}
+
+// A chunk (cut_stft_chunk with the record of stft_cost over the lengths, 0 for a clip that is too short): the clips staged
+// packed when they are the host's, the records uploaded, the samples brought to float32 with their non-finite flags
+// (k_hpss_prep), then one launch of k_stft_frames into the caller's device memory or into the packed image that goes home.
+extern "C" int afx_stft_batch(afx_ctx* ctx, const void* samples, int sample_fmt, int mem_kind,
+                              const int64_t* offsets, const int64_t* lengths, int n_clips,
+                              const afx_stft_opts* opts, const float* window,
+                              void* out, int out_mem_kind, const int64_t* out_offsets, int32_t* out_status) {
+  const char* who = "afx_stft_batch";
+  int rc;
+  if ((rc = clip_batch_args(who, ctx, sample_fmt, mem_kind, offsets, lengths, n_clips, out_mem_kind, out_offsets, out_status,
+                            opts && window)) != AFX_OK) return rc;
+  if (!opts || !window) return null_arg(who);
+  if ((rc = stft_opts_arg(who, opts)) != AFX_OK) return rc;
+  const afx_stft_opts o = *opts;
+  const int n_fft = o.n_fft, bins = stft_bins(n_fft), fpw = n_fft == 1024 ? 2 : 1;
+  const int fpe = o.out_kind == AFX_STFT_COMPLEX ? 2 : 1;        // floats per output element
+  std::vector<int64_t> eff((size_t)n_clips), frames((size_t)n_clips);
+  bool any = false;
+  for (int i = 0; i < n_clips; ++i) {
+    stft_frames(o, lengths[i], &frames[i], &out_status[i]);
+    eff[i] = out_status[i] == AFX_CLIP_OK ? lengths[i] : 0;
+    any = any || out_status[i] == AFX_CLIP_OK;
+  }
+  if (!any) return AFX_OK;
+  if (!samples || !out) { set_error(std::string(who) + ": null samples / out"); return AFX_ERR_INVALID; }
+
+  (void)hipGetLastError();
+  HIP_TRY(hipSetDevice(ctx->device));
+  hipStream_t s = ctx->stream;
+  StftTabs tb{};
+  if ((rc = stft_tables(ctx, n_fft, window, tb)) != AFX_OK) return rc;
+
+  const size_t esz = sample_fmt == AFX_FMT_S16 ? 2 : 4;
+  const bool h_in = mem_kind == AFX_MEM_HOST, h_out = out_mem_kind == AFX_MEM_HOST;
+  StftCost cost;
+  stft_cost(o, sample_fmt, mem_kind, out_mem_kind, 0, cost);
+  StftChunk ck;
+  std::vector<StftClip> recs;
+  std::vector<HpssClip> prs;
+  std::vector<HostPiece> pieces;
+  std::vector<char> image, up;
+  std::vector<uint32_t> h_bad;
+  std::vector<float> stage_out;
+  for (int c0 = 0; c0 < n_clips; c0 = ck.next) {
+    cut_stft_chunk(offsets, eff.data(), n_clips, c0, dev_env().stft_budget, cost, ck);
+    const int n = (int)ck.idx.size();
+    if (n == 0) continue;
+    recs.assign((size_t)n, StftClip{}); prs.assign((size_t)n, HpssClip{});
+    int64_t ypos = 0, in_pos = 0, opos = 0, rows = 0, units = 0, max_len = 0;
+    for (int q = 0; q < n; ++q) {
+      const int i = ck.idx[q];
+      const int64_t L = lengths[i], T = frames[i];
+      StftClip& r = recs[q];
+      r.y_off = ypos; r.len = L; r.out_off = h_out ? opos : out_offsets[i]; r.unit_base = units; r.T = (int32_t)T; r.clip = q;
+      prs[q].in_off = h_in ? in_pos : offsets[i]; prs[q].y_off = ypos; prs[q].len = L;
+      ypos += (L + 3) / 4 * 4; in_pos += (L + 3) / 4 * 4; opos += T * bins;
+      rows += T; units += (T + fpw - 1) / fpw; max_len = std::max(max_len, L);
+    }
+    if (rows > INT32_MAX / 2) { set_error(std::string(who) + ": chunk too large for one launch"); return AFX_ERR_UNSUPPORTED; }
+
+    const size_t o_prs = (size_t)n * sizeof(StftClip);
+    up.assign(o_prs + (size_t)n * sizeof(HpssClip), 0);
+    std::memcpy(up.data(), recs.data(), o_prs);
+    std::memcpy(up.data() + o_prs, prs.data(), (size_t)n * sizeof(HpssClip));
+    if ((rc = ensure(ctx->st_recs, up.size())) != AFX_OK) return rc;
+    if ((rc = ensure(ctx->st_y, (size_t)std::max<int64_t>(ypos, 1) * sizeof(float))) != AFX_OK) return rc;
+    if ((rc = ensure(ctx->st_bad, (size_t)n * sizeof(uint32_t))) != AFX_OK) return rc;
+    const void* d_in = samples;
+    if (h_in) {
+      pieces.clear();
+      for (int q = 0; q < n; ++q) pieces.push_back(clip_piece(samples, offsets[ck.idx[q]], prs[q].in_off, prs[q].len, esz));
+      if ((rc = stage_in(ctx, image, in_pos * (int64_t)esz, pieces, &d_in)) != AFX_OK) return rc;
+    }
+    float* d_out;
+    if ((rc = out_buffer(ctx, (float*)out, out_mem_kind, std::max<int64_t>(opos * fpe, 1), &d_out)) != AFX_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(ctx->st_recs.p, up.data(), up.size(), hipMemcpyHostToDevice, s));
+    const StftClip* d_recs = (const StftClip*)ctx->st_recs.p;
+    const HpssClip* d_prs = (const HpssClip*)((const char*)ctx->st_recs.p + o_prs);
+    float* y = (float*)ctx->st_y.p;
+    uint32_t* bad = (uint32_t*)ctx->st_bad.p;
+    HIP_TRY(hipMemsetAsync(bad, 0, (size_t)n * sizeof(uint32_t), s));
+    HIP_TRY(launch_hpss_prep(s, d_in, sample_fmt, 0, 0.f, d_prs, n, max_len, y, bad));
+    HIP_TRY(launch_stft_frames(s, o, y, d_recs, bad, n, units, tb, d_out));
+    h_bad.resize((size_t)n);
+    HIP_TRY(hipMemcpyAsync(h_bad.data(), bad, h_bad.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    if (h_out && (rc = fetch_out(ctx, d_out, opos * fpe, stage_out)) != AFX_OK) return rc;
+    HIP_TRY(hipStreamSynchronize(s));
+    pieces.clear();
+    for (int q = 0; q < n; ++q) {
+      const int i = ck.idx[q];
+      if (h_bad[q]) out_status[i] = AFX_CLIP_NONFINITE;
+      if (h_out) pieces.push_back({stage_out.data() + recs[q].out_off * fpe, out_offsets[i] * 4 * fpe, frames[i] * bins * 4 * fpe});
+    }
+    scatter_pieces(out, pieces);
+  }
+  return AFX_OK;
+}
+
+// A chunk (cut_stft_chunk over istft_weight per clip): the kept rows staged packed when they are the host's, the records
+// uploaded, k_istft_frames into the time rows, k_istft_ola into the caller's device memory or the packed image.
+extern "C" int afx_istft_batch(afx_ctx* ctx, const void* spec, int mem_kind,
+                               const int64_t* spec_offsets, const int64_t* n_frames, int n_clips,
+                               const afx_stft_opts* opts, const float* window, const int64_t* lengths,
+                               float* out, int out_mem_kind, const int64_t* out_offsets, int32_t* out_status) {
+  const char* who = "afx_istft_batch";
+  int rc;
+  if ((rc = clip_batch_args(who, ctx, AFX_FMT_F32, mem_kind, spec_offsets, n_frames, n_clips, out_mem_kind, out_offsets, out_status,
+                            opts && window)) != AFX_OK) return rc;
+  if (!opts || !window) return null_arg(who);
+  if ((rc = stft_opts_arg(who, opts)) != AFX_OK) return rc;
+  const afx_stft_opts o = *opts;
+  const int n_fft = o.n_fft, bins = stft_bins(n_fft), fpw = n_fft == 1024 ? 2 : 1;
+  std::vector<int64_t> eff((size_t)n_clips), nfs((size_t)n_clips), nout((size_t)n_clips);
+  bool any = false;
+  for (int i = 0; i < n_clips; ++i) {
+    const int64_t want = lengths && lengths[i] >= 0 ? lengths[i] : -1;
+    if (want > (int64_t)1 << 31) { set_error(std::string(who) + ": lengths must be at most 2^31"); return AFX_ERR_INVALID; }
+    out_status[i] = n_frames[i] == 0 ? AFX_CLIP_TOO_SHORT : AFX_CLIP_OK;
+    nfs[i] = nout[i] = 0;
+    if (out_status[i] == AFX_CLIP_OK) istft_samples(o, n_frames[i], want, &nfs[i], &nout[i]);
+    eff[i] = nout[i] > 0 ? istft_weight(o, nfs[i], nout[i]) : 0;           // nothing to write: nothing to run
+    any = any || eff[i] > 0;
+  }
+  if (!any) return AFX_OK;
+  if (!spec || !out) { set_error(std::string(who) + ": null spec / out"); return AFX_ERR_INVALID; }
+
+  (void)hipGetLastError();
+  HIP_TRY(hipSetDevice(ctx->device));
+  hipStream_t s = ctx->stream;
+  StftTabs tb{};
+  if ((rc = stft_tables(ctx, n_fft, window, tb)) != AFX_OK) return rc;
+
+  const bool h_in = mem_kind == AFX_MEM_HOST, h_out = out_mem_kind == AFX_MEM_HOST;
+  StftCost cost;
+  stft_cost(o, AFX_FMT_F32, mem_kind, out_mem_kind, 1, cost);
+  StftChunk ck;
+  std::vector<IstftClip> recs;
+  std::vector<HostPiece> pieces;
+  std::vector<char> image;
+  std::vector<float> stage_out;
+  for (int c0 = 0; c0 < n_clips; c0 = ck.next) {
+    cut_stft_chunk(spec_offsets, eff.data(), n_clips, c0, dev_env().stft_budget, cost, ck);
+    const int n = (int)ck.idx.size();
+    if (n == 0) continue;
+    recs.assign((size_t)n, IstftClip{});
+    int64_t in_pos = 0, opos = 0, rows = 0, units = 0, max_out = 0;
+    for (int q = 0; q < n; ++q) {
+      const int i = ck.idx[q];
+      IstftClip& r = recs[q];
+      r.spec_off = h_in ? in_pos : spec_offsets[i]; r.row_base = rows; r.unit_base = units;
+      r.out_off = h_out ? opos : out_offsets[i]; r.n_out = nout[i]; r.n_frames = (int32_t)nfs[i];
+      in_pos += nfs[i] * bins; opos += (nout[i] + 3) / 4 * 4;
+      rows += nfs[i]; units += (nfs[i] + fpw - 1) / fpw; max_out = std::max(max_out, nout[i]);
+    }
+    if (rows > INT32_MAX / 2) { set_error(std::string(who) + ": chunk too large for one launch"); return AFX_ERR_UNSUPPORTED; }
+    if ((rc = ensure(ctx->st_recs, (size_t)n * sizeof(IstftClip))) != AFX_OK) return rc;
+    if ((rc = ensure(ctx->st_rows, (size_t)std::max<int64_t>(rows, 1) * n_fft * sizeof(float))) != AFX_OK) return rc;
+    const void* d_in = spec;
+    if (h_in) {
+      pieces.clear();
+      for (int q = 0; q < n; ++q) pieces.push_back(clip_piece(spec, spec_offsets[ck.idx[q]], recs[q].spec_off, (int64_t)recs[q].n_frames * bins, 8));
+      if ((rc = stage_in(ctx, image, in_pos * 8, pieces, &d_in)) != AFX_OK) return rc;
+    }
+    float* d_out;
+    if ((rc = out_buffer(ctx, out, out_mem_kind, std::max<int64_t>(opos, 1), &d_out)) != AFX_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(ctx->st_recs.p, recs.data(), (size_t)n * sizeof(IstftClip), hipMemcpyHostToDevice, s));
+    const IstftClip* d_recs = (const IstftClip*)ctx->st_recs.p;
+    float* trows = (float*)ctx->st_rows.p;
+    HIP_TRY(launch_istft_frames(s, n_fft, (const float2*)d_in, d_recs, n, units, tb, trows));
+    HIP_TRY(launch_istft_ola(s, o, trows, d_recs, n, max_out, tb, d_out));
+    if (h_out && (rc = fetch_out(ctx, d_out, opos, stage_out)) != AFX_OK) return rc;
+    HIP_TRY(hipStreamSynchronize(s));
+    pieces.clear();
+    for (int q = 0; q < n; ++q)
+      if (h_out) pieces.push_back({stage_out.data() + recs[q].out_off, out_offsets[ck.idx[q]] * 4, recs[q].n_out * 4});
+    scatter_pieces(out, pieces);
   }
   return AFX_OK;
 }

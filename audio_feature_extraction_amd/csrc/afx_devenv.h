@@ -37,6 +37,7 @@ struct DevEnv {
   int64_t smooth_budget = (int64_t)2 << 30; // device workspace bytes of one afx_medfilt_batch / afx_savgol_batch / afx_energy_zcr_batch chunk
   int64_t loud_budget = (int64_t)2 << 30;   // device workspace bytes of one afx_loudness_batch chunk
   int64_t gate_budget = (int64_t)2 << 30;   // device workspace bytes of one afx_gate_batch chunk
+  int64_t stft_budget = (int64_t)2 << 30;   // device workspace bytes of one afx_stft_batch / afx_istft_batch chunk
   const char* f0_dump = nullptr;
   DevEnv();
 };

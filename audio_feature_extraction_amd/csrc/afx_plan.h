@@ -26,6 +26,7 @@
 #include "afx_resample.h"
 #include "afx_rhythm.h"
 #include "afx_smooth.h"
+#include "afx_stft.h"
 
 namespace afx {
 
@@ -76,6 +77,9 @@ struct afx_ctx {
   // afx_gate_batch: the window / twiddles / taps, a chunk's grid records, its float32 signal, the non-finite flags, the
   // magnitude planes of both grids, the mask plane, the forward pass, the bit plane, thr and its amplitude, the time rows
   DevBuf gt_tab, gt_grids, gt_y, gt_bad, gt_mag, gt_nmag, gt_mask, gt_fwd, gt_bits, gt_thr, gt_amp, gt_rows;
+  // afx_stft_batch / afx_istft_batch: the window and twiddles, a chunk's clip records, its float32 signal and non-finite
+  // flags (forward), the time rows the overlap-add reads (inverse)
+  DevBuf st_tab, st_recs, st_y, st_bad, st_rows;
 };
 
 struct afx_plan {

@@ -866,6 +866,56 @@ int afx_gate_batch(afx_ctx* ctx, const void* samples, int sample_fmt, int mem_ki
                    float* out, int out_mem_kind, const int64_t* out_offsets,
                    double* out_thresh, uint32_t* out_mask, int32_t* out_status);
 
+/* librosa.stft / librosa.istft (librosa 0.11) of mono clips at n_fft 1024 or 2048, the transforms behind the reference's
+ * own spectral steps (00_audio_data_collection_experiment/noise_reduction.py:31-84, 05_dtw_alignment_experiment/
+ * process_audio.py:21-33, visualization.py:194-208).  DESIGN.md section 26 is the definition and tests/stft_ref.py its
+ * numpy restatement.  All five symbols are newer than AFX_VERSION 107 says: a binding detects them by their presence.
+ *
+ * window: n_fft floats in host memory, the caller's window already zero-padded centred to n_fft (librosa.util.pad_center).
+ * hop in [1, n_fft]; any other n_fft or hop is AFX_ERR_UNSUPPORTED; a center, pad_mode or out_kind that is none of the
+ * values below is AFX_ERR_INVALID.
+ *
+ * Forward: with center the clip is padded by n_fft / 2 at each end, with zeros (AFX_PAD_CONSTANT) or as
+ * np.pad(mode="reflect") does (AFX_PAD_REFLECT, clips longer than n_fft / 2 only); T = 1 + (padded length - n_fft) / hop
+ * frames, frame t = padded[t hop .. t hop + n_fft), D[:, t] = rfft(frame x window) in float32.  Clip i takes T rows of
+ * n_fft / 2 + 1 elements at element out_offsets[i] of out, frame after frame with nothing between the rows -- the memory
+ * of the Fortran-ordered [1 + n_fft / 2, T] array librosa returns: complex64 (AFX_STFT_COMPLEX; out must be 8-byte
+ * aligned), or float32 |D| (AFX_STFT_MAG: sqrt(re re + im im), each operation rounded once) or |D|^2 (AFX_STFT_POWER).
+ * out_status: AFX_CLIP_TOO_SHORT (nothing written) for length 0, for length < n_fft without center and for
+ * length <= n_fft / 2 under AFX_PAD_REFLECT; AFX_CLIP_NONFINITE for a NaN / inf sample: zeros out.
+ *
+ * Inverse: clip i is n_frames[i] rows of n_fft / 2 + 1 complex64 at element spec_offsets[i] of spec, laid out as above.
+ * s = n_fft / 2 with center, else 0; with a length >= 0 only the first min(T, ceil((length + 2 s) / hop)) frames are used;
+ * full = n_fft + hop (frames - 1); acc[m] = sum_t window[m - t hop] irfft(D[:, t])[m - t hop] and wss[m] = sum_t
+ * float32(window^2)[m - t hop] over the frames that cover m, in increasing t, in float32 (the imaginary parts of bins 0 and
+ * n_fft / 2 are ignored); out[j] = acc[s + j] / wss[s + j] where wss > FLT_MIN, acc[s + j] elsewhere, 0 for s + j >= full,
+ * for j < length, or j < full - 2 s when none is given.  There is no non-finite check: a frame with a NaN / inf bin makes
+ * the samples it covers NaN and no others.  out_status: AFX_CLIP_TOO_SHORT for no frames.
+ *
+ * No atomics in any sum: results are bit-reproducible, and a clip's result depends neither on the rest of the batch, on the
+ * input layout, on host or device memory, nor on how the batch was cut into chunks (afx_stft_chunks with the record of
+ * afx_stft_cost: forward over the lengths, 0 for a clip that is too short; inverse over frames used + ceil(samples written
+ * / hop) per clip).
+ *
+ * afx_stft_frames (host-only): T and the status of a clip of `length` samples (T = 0 unless AFX_CLIP_OK).
+ * afx_istft_samples (host-only): the frames used and the samples written for T frames (both 0 for T = 0).
+ * afx_stft_cost (host-only): cost[6] for afx_stft_chunks; every byte is charged per unit of length and per clip. */
+enum { AFX_PAD_CONSTANT = 0, AFX_PAD_REFLECT = 1 };
+enum { AFX_STFT_COMPLEX = 0, AFX_STFT_MAG = 1, AFX_STFT_POWER = 2 };
+typedef struct afx_stft_opts { int32_t n_fft, hop, center, pad_mode, out_kind, reserved[3]; } afx_stft_opts;
+int afx_stft_frames(const afx_stft_opts* opts, int64_t length, int64_t* T, int32_t* clip_status);
+int afx_istft_samples(const afx_stft_opts* opts, int64_t T, int64_t length /* < 0: none */, int64_t* n_frames, int64_t* n_out);
+int afx_stft_cost(const afx_stft_opts* opts, int sample_fmt, int mem_kind, int out_mem_kind, int inverse, int64_t* cost /*[6]*/);
+int afx_stft_batch(afx_ctx* ctx, const void* samples, int sample_fmt, int mem_kind,
+                   const int64_t* offsets, const int64_t* lengths, int n_clips,
+                   const afx_stft_opts* opts, const float* window /*[n_fft], host*/,
+                   void* out, int out_mem_kind, const int64_t* out_offsets /* in output elements */, int32_t* out_status);
+int afx_istft_batch(afx_ctx* ctx, const void* spec /* complex64 rows */, int mem_kind,
+                    const int64_t* spec_offsets /* complex elements */, const int64_t* n_frames, int n_clips,
+                    const afx_stft_opts* opts, const float* window,
+                    const int64_t* lengths /* NULL, or per clip, < 0: none */,
+                    float* out, int out_mem_kind, const int64_t* out_offsets, int32_t* out_status);
+
 /* The recording screen of 00_audio_data_collection_experiment/audio_format_assessment.py:143-300 (detect_silence,
  * check_volume_levels, check_amplitude_stability, estimate_snr) and the sums behind the scores of
  * audio_quality_assessment.py:150-280 (SNR of the difference, Pearson correlation, MSE), as per-clip reductions.  All five
