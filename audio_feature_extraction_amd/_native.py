@@ -60,6 +60,7 @@ LOUD_N = 11                                                                  # d
 CLIP_TOO_LONG = 3                                                            # afx_gate_batch: more than chunk_size samples
 PAD_CONSTANT, PAD_REFLECT = 0, 1                                             # afx_stft_batch: its pad modes
 STFT_COMPLEX, STFT_MAG, STFT_POWER = 0, 1, 2                                 # and output kinds
+PVOC_TILE = 32                                                               # afx_pvoc_batch: output steps per summation tile
 LOUD_FIELDS = ("lufs", "blocks", "n1", "n2", "gamma_r", "gated_ms", "peak", "gain", "peak_out", "first_ms", "ungated_ms")
 GROUPS_STATS = 24                                                            # doubles per clip of its record
 K_NAMES = ("trim_blocks", "trim_decide", "frames", "dct", "stats")
@@ -88,6 +89,8 @@ SYMBOLS = (
     "afx_loudness_batch",
     "afx_gate_params", "afx_gate_cost", "afx_gate_batch",
     "afx_stft_frames", "afx_istft_samples", "afx_stft_cost", "afx_stft_batch", "afx_istft_batch",
+    "afx_pvoc_frames", "afx_time_stretch_samples", "afx_pvoc_cost", "afx_time_stretch_cost", "afx_pvoc_host",
+    "afx_pvoc_batch", "afx_time_stretch_batch",
 )
 
 
@@ -250,6 +253,15 @@ def lib() -> C.CDLL:
             L.afx_stft_cost.argtypes = [vp, i32, i32, i32, i32, vp]
             L.afx_stft_batch.argtypes = [vp, vp, i32, i32, vp, vp, i32, vp, vp, vp, i32, vp, vp]
             L.afx_istft_batch.argtypes = [vp, vp, i32, vp, vp, i32, vp, vp, vp, vp, i32, vp, vp]
+        if hasattr(L, "afx_pvoc_batch"):                     # newer than version 107 says: found by their presence
+            i64, dbl = C.c_int64, C.c_double
+            L.afx_pvoc_frames.argtypes = [i32, i32, i64, dbl, vp, vp]
+            L.afx_time_stretch_samples.argtypes = [vp, i64, dbl, vp, vp, vp, vp]
+            L.afx_pvoc_cost.argtypes = [i32, i32, i32, vp]
+            L.afx_time_stretch_cost.argtypes = [vp, i32, i32, i32, vp]
+            L.afx_pvoc_host.argtypes = [vp, i64, dbl, i32, i32, vp, vp]
+            L.afx_pvoc_batch.argtypes = [vp, vp, i32, vp, vp, vp, i32, i32, i32, vp, i32, vp, vp]
+            L.afx_time_stretch_batch.argtypes = [vp, vp, i32, i32, vp, vp, vp, i32, vp, vp, vp, i32, vp, vp]
         if hasattr(L, "afx_rfft_host"):                      # absent from a library built before the mixed-radix lengths
             L.afx_rfft_host.argtypes = [i32, vp, vp]
         _lib = L
@@ -768,6 +780,68 @@ def _stft_window(opts: StftOpts, window) -> np.ndarray:
     if window.shape[0] != opts.n_fft:
         raise ValueError("window must hold n_fft values (pad a shorter one centred, as librosa.util.pad_center does)")
     return window
+
+
+def _need_pvoc():
+    if not hasattr(lib(), "afx_pvoc_batch"):
+        raise NotImplementedError("this libafx has no afx_pvoc_batch")
+
+
+def pvoc_frames(n_fft: int, hop: int, T: int, rate: float):
+    """Host-only: afx_pvoc_frames -> (T_out, status) of a clip of ``T`` rows stretched by ``rate``: T_out = ceil(T / rate).
+    ValueError for a rate that is not finite and > 0; NotImplementedError for an odd n_fft, an n_fft outside [2, 4096], a
+    hop outside [1, n_fft] or T_out x bins >= 2^31."""
+    _need_pvoc()
+    To, st = C.c_int64(0), C.c_int32(0)
+    _check(lib().afx_pvoc_frames(int(n_fft), int(hop), int(T), float(rate), C.addressof(To), C.addressof(st)), "afx_pvoc_frames")
+    return int(To.value), int(st.value)
+
+
+def time_stretch_samples(opts: StftOpts, length: int, rate: float):
+    """Host-only: afx_time_stretch_samples -> (T, T_out, n_out, status): the frames of a clip of ``length`` samples, the rows
+    of its stretch by ``rate`` and the samples written, round(length / rate) as Python rounds."""
+    _need_pvoc()
+    T, To, no, st = C.c_int64(0), C.c_int64(0), C.c_int64(0), C.c_int32(0)
+    _check(lib().afx_time_stretch_samples(C.addressof(opts), int(length), float(rate), C.addressof(T), C.addressof(To),
+                                          C.addressof(no), C.addressof(st)), "afx_time_stretch_samples")
+    return int(T.value), int(To.value), int(no.value), int(st.value)
+
+
+def pvoc_cost(n_fft: int, mem: int = MEM_HOST, out_mem: int = MEM_HOST) -> np.ndarray:
+    """Host-only: the int64 [6] cost record afx_pvoc_batch cuts a batch with (over T + T_out per clip), for :func:`stft_chunks`."""
+    _need_pvoc()
+    cost = np.zeros(6, np.int64)
+    _check(lib().afx_pvoc_cost(int(n_fft), int(mem), int(out_mem), cost.ctypes.data), "afx_pvoc_cost")
+    return cost
+
+
+def time_stretch_cost(opts: StftOpts, fmt: int = FMT_F32, mem: int = MEM_HOST, out_mem: int = MEM_HOST) -> np.ndarray:
+    """Host-only: the int64 [6] cost record afx_time_stretch_batch cuts a batch with (over T + T_out + ceil(length / hop) +
+    ceil(n_out / hop) per clip, 0 for a clip with nothing to run), for :func:`stft_chunks`."""
+    _need_pvoc()
+    cost = np.zeros(6, np.int64)
+    _check(lib().afx_time_stretch_cost(C.addressof(opts), int(fmt), int(mem), int(out_mem), cost.ctypes.data), "afx_time_stretch_cost")
+    return cost
+
+
+def pvoc_host(D, rate: float, hop_length=None, n_fft=None):
+    """Host-only: afx_pvoc_host, the phase vocoder's definition in plain C++ for one [bins, T] complex64 spectrum ->
+    (the [bins, T_out] complex64 result in librosa's memory order, or None for T = 0; status)."""
+    _need_pvoc()
+    D = np.asarray(D)
+    if D.ndim != 2:
+        raise NotImplementedError(f"a spectrum must be 2-D (mono), got shape {D.shape}")
+    bins, T = D.shape
+    n_fft = 2 * (bins - 1) if n_fft is None else int(n_fft)
+    hop = n_fft // 4 if hop_length is None else int(hop_length)
+    if n_fft // 2 + 1 != bins:
+        raise ValueError(f"the spectrum must have 1 + n_fft / 2 = {n_fft // 2 + 1} rows")
+    T_out, st = pvoc_frames(n_fft, hop, T, rate)
+    rows = np.ascontiguousarray(np.asarray(D, np.complex64).T)
+    out = np.zeros((T_out, bins), np.complex64)
+    status = C.c_int32(0)
+    _check(lib().afx_pvoc_host(rows.ctypes.data, int(T), float(rate), n_fft, hop, out.ctypes.data, C.addressof(status)), "afx_pvoc_host")
+    return (out.T if T else None), int(status.value)
 
 
 def _need_loudness():
@@ -1385,6 +1459,75 @@ class Context(_Owner):
                                      C.addressof(opts), window.ctypes.data, _ptr(lengths), optr, okind,
                                      out_offsets.ctypes.data, status.ctypes.data), "afx_istft_batch")
         return {"out": out, "offsets": out_offsets, "samples": samples, "status": status}
+
+    def pvoc_batch(self, spec, spec_offsets, n_frames, rates, n_fft: int, hop: int, out=None, out_offsets=None) -> dict:
+        """afx_pvoc_batch: librosa.phase_vocoder of the spectra in ``spec`` (as istft_batch takes them), clip i stretched by
+        ``rates[i]``.  Clip i takes frames[i] = ceil(n_frames[i] / rates[i]) rows of n_fft / 2 + 1 complex64 from element
+        ``out_offsets[i]`` (default: packed) of ``out``: None (a new host array), a complex64 numpy array, or a DeviceBuffer /
+        device address.  Returns out, offsets, frames, status (CLIP_TOO_SHORT: no rows; CLIP_NONFINITE: zeros) and, for a
+        host result, spec: per clip the [n_fft / 2 + 1, frames] view in librosa's memory order (None for a failed clip)."""
+        _need_pvoc()
+        spec_offsets, n_frames, n = _clip_arrays(spec_offsets, n_frames)
+        rates = np.ascontiguousarray(rates, np.float64).reshape(-1)
+        if rates.shape[0] != n:
+            raise ValueError("rates must have one entry per clip")
+        n_fft, hop = int(n_fft), int(hop)
+        bins = n_fft // 2 + 1
+        if isinstance(spec, np.ndarray):
+            if spec.dtype != np.complex64 or not spec.flags.c_contiguous:
+                raise ValueError("spec must be a C-contiguous complex64 array")
+            if n and int((spec_offsets + n_frames * bins).max()) > spec.size:
+                raise ValueError("a clip extends past the spectrum buffer")
+            sptr, kind = spec.ctypes.data, MEM_HOST
+        else:
+            sptr, kind = (spec.ptr if isinstance(spec, DeviceBuffer) else int(spec)), MEM_DEVICE
+        frames = np.array([pvoc_frames(n_fft, hop, int(T), float(r))[0] for T, r in zip(n_frames, rates)], np.int64)
+        if out_offsets is None:
+            out_offsets = packed_offsets(frames * bins)
+        out_offsets = np.ascontiguousarray(out_offsets, np.int64).reshape(-1)
+        if out_offsets.shape[0] != n:
+            raise ValueError("out_offsets must have one entry per clip")
+        need = int((out_offsets + frames * bins).max()) if n else 0
+        if out is None:
+            out = np.zeros(need, np.complex64)
+        if isinstance(out, np.ndarray):
+            if out.dtype != np.complex64 or not out.flags.c_contiguous or out.size < need:
+                raise ValueError("out must be a C-contiguous complex64 array that holds every clip")
+            optr, okind = out.ctypes.data, MEM_HOST
+        else:
+            if isinstance(out, DeviceBuffer) and out.nbytes < 8 * need:
+                raise ValueError("the output DeviceBuffer is too small")
+            optr, okind = (out.ptr if isinstance(out, DeviceBuffer) else int(out)), MEM_DEVICE
+        status = np.zeros(n, np.int32)
+        _check(lib().afx_pvoc_batch(self.handle, sptr, kind, spec_offsets.ctypes.data, n_frames.ctypes.data, rates.ctypes.data, n,
+                                    n_fft, hop, optr, okind, out_offsets.ctypes.data, status.ctypes.data), "afx_pvoc_batch")
+        res = {"out": out, "offsets": out_offsets, "frames": frames, "status": status}
+        if okind == MEM_HOST:
+            flat = out.reshape(-1)
+            res["spec"] = [flat[o:o + T * bins].reshape(T, bins).T if st == CLIP_OK else None
+                           for o, T, st in zip(out_offsets, frames, status)]
+        return res
+
+    def time_stretch_batch(self, samples, offsets, lengths, rates, opts: StftOpts, window, fmt=None, out=None, out_offsets=None) -> dict:
+        """afx_time_stretch_batch: librosa.effects.time_stretch of the clips samples[offsets[i] .. + lengths[i]) by ``rates[i]``
+        with the framing of ``opts`` and ``window``: stft, phase vocoder and istft in one call, the spectra staying on the
+        device.  ``samples``, ``out``, ``out_offsets``: as sosfiltfilt_batch.  Returns out, offsets, samples (written per clip:
+        round(length / rate)) and status."""
+        _need_pvoc()
+        offsets, lengths, n = _clip_arrays(offsets, lengths)
+        rates = np.ascontiguousarray(rates, np.float64).reshape(-1)
+        if rates.shape[0] != n:
+            raise ValueError("rates must have one entry per clip")
+        fmt = _sample_fmt(samples, fmt)
+        sptr, kind = _sample_source(samples, fmt, offsets, lengths)
+        window = _stft_window(opts, window)
+        n_out = np.array([time_stretch_samples(opts, int(L), float(r))[2] for L, r in zip(lengths, rates)], np.int64)
+        out, out_offsets, optr, okind = self._smooth_out(n_out, n, out, out_offsets)
+        status = np.zeros(n, np.int32)
+        _check(lib().afx_time_stretch_batch(self.handle, sptr, int(fmt), kind, offsets.ctypes.data, lengths.ctypes.data,
+                                            rates.ctypes.data, n, C.addressof(opts), window.ctypes.data, optr, okind,
+                                            out_offsets.ctypes.data, status.ctypes.data), "afx_time_stretch_batch")
+        return {"out": out, "offsets": out_offsets, "samples": n_out, "status": status}
 
     def energy_zcr_batch(self, samples, offsets, lengths, sr: int, frame_length: int = 2048, hop_length: int = 512,
                          flags: int = EZ_PREPROCESS | EZ_ENERGY | EZ_ZCR, fmt=None) -> dict:

@@ -663,6 +663,28 @@ class AudioFeatureExtractor:
         2048 / 2048 / 512.  Further keywords are noisereduce's.  float32 of ``y``'s length."""
         return self.apply_noise_reduction_batch([y], method, **kw)[0]
 
+    def stretch_to_length_batch(self, signals: Sequence[np.ndarray], n_samples, **kw) -> List[Optional[np.ndarray]]:
+        """``stretch_to_length`` of many signals in one device pass; ``n_samples``: one length for all, or one per signal.
+        None for a signal the transform refuses (empty, not finite)."""
+        from .. import effects
+        signals = [np.asarray(s) for s in signals]
+        lengths = [n_samples] * len(signals) if np.isscalar(n_samples) else list(n_samples)
+        if len(lengths) != len(signals) or any(int(n) < 1 for n in lengths):
+            raise ValueError("n_samples must be at least 1, one per signal or one for all")
+        # istft's length is round(len / rate): len / (len / n) is n to a few parts in 2^52, far from a half
+        rates = [max(s.size, 1) / int(n) for s, n in zip(signals, lengths)]
+        return effects.time_stretch_batch(signals, rates, device=lambda: self._devices()[0], **kw)
+
+    def stretch_to_length(self, y: np.ndarray, n_samples: int, **kw) -> np.ndarray:
+        """``y`` brought to exactly ``n_samples`` samples without a change of pitch -- what puts a student take on a
+        teacher's clock before the two are compared: ``librosa.effects.time_stretch`` at ``rate = len(y) / n_samples`` on the
+        GPU, with ``n_samples`` taken as istft's ``length``.  Further keywords are time_stretch's (n_fft 2048 or 1024,
+        hop_length, window, pad_mode); float32."""
+        out, = self.stretch_to_length_batch([y], [int(n_samples)], **kw)
+        if out is None:
+            raise ValueError("stretch_to_length: y is too short for this framing or not finite everywhere")
+        return out
+
     def process_recordings_batch(self, signals: Sequence[np.ndarray], method: str = "wiener", reference_level: float = -23.0,
                                  **kw) -> Tuple[List[np.ndarray], List[Optional[float]]]:
         """The conditioning of 04_feature_extraction_experiment/process_audio.py:28-61 without its VAD: ``normalize_volume``

@@ -7,6 +7,9 @@ The spectrum comes back in librosa's own shape, dtype and memory order ([1 + n_f
 contiguous) without a transpose pass: the device writes frame after frame and the result is a view of that buffer.
 ``magphase``, ``amplitude_to_db`` and ``power_to_db`` are librosa's numpy helpers, here for the calls that follow a
 transform.
+
+``phase_vocoder`` is ``librosa.phase_vocoder`` on such a spectrum, in ``afx_pvoc_batch``: float32
+magnitudes, float64 phases as a prefix sum in a fixed order.  ``effects.time_stretch`` is the whole stretch in one call.
 """
 from __future__ import annotations
 
@@ -158,6 +161,64 @@ def istft(D, hop_length: Optional[int] = None, win_length: Optional[int] = None,
     if y is None:
         raise ValueError("istft: D has no frames")
     return y
+
+
+def _rate(rate, i=None) -> float:
+    what = "rate" if i is None else f"rate {i}"
+    rate = float(rate)
+    if not (np.isfinite(rate) and rate > 0):
+        raise ValueError(f"{what} must be finite and > 0, got {rate!r}")
+    return rate
+
+
+def _pvoc_framing(bins: int, hop_length, n_fft):
+    n_fft = 2 * (bins - 1) if n_fft is None else int(n_fft)
+    if n_fft < 2 or n_fft > 4096 or n_fft % 2:
+        raise NotImplementedError(f"n_fft={n_fft} is not supported (even, 2 .. 4096)")
+    hop = n_fft // 4 if hop_length is None else int(hop_length)
+    if not 1 <= hop <= n_fft:
+        raise NotImplementedError(f"hop_length={hop} is not supported (1 .. n_fft)")
+    return n_fft, hop
+
+
+def phase_vocoder_batch(spectra: Sequence[np.ndarray], rates, hop_length: Optional[int] = None, n_fft: Optional[int] = None,
+                        device: int = 0) -> List[Optional[np.ndarray]]:
+    """``librosa.phase_vocoder`` of many spectra of one framing in one device pass, spectrum i by ``rates[i]`` (or one rate
+    for all): per spectrum the complex64 [1 + n_fft / 2, ceil(T / rate)] result, or None where the single call would raise
+    (no frames, a NaN / inf bin)."""
+    specs = [np.asarray(D) for D in spectra]
+    rates = [rates] * len(specs) if np.isscalar(rates) else list(rates)
+    if len(rates) != len(specs):
+        raise ValueError("rates must have one entry per spectrum")
+    rates = [_rate(r, i) for i, r in enumerate(rates)]
+    if not specs:
+        return []
+    for D in specs:
+        if D.ndim != 2:
+            raise NotImplementedError(f"a spectrum must be 2-D (mono), got shape {D.shape}")
+    n_fft, hop = _pvoc_framing(specs[0].shape[0], hop_length, n_fft)
+    bins = n_fft // 2 + 1
+    if any(D.shape[0] != bins for D in specs):
+        raise ValueError(f"every spectrum must have 1 + n_fft / 2 = {bins} rows")
+    frames = np.array([D.shape[1] for D in specs], np.int64)
+    offsets = _native.packed_offsets(frames * bins)
+    buf = np.zeros(max(int(frames.sum()) * bins, 1), np.complex64)
+    for o, D in zip(offsets, specs):
+        buf[o:o + D.size] = np.asfortranarray(D, np.complex64).ravel(order="F")
+    r = _ctx(device).pvoc_batch(buf, offsets, frames, rates, n_fft, hop)
+    return list(r["spec"])
+
+
+def phase_vocoder(D, *, rate, hop_length: Optional[int] = None, n_fft: Optional[int] = None, device: int = 0) -> np.ndarray:
+    """``librosa.phase_vocoder(D, rate=rate, hop_length=hop_length, n_fft=n_fft)``: complex64 [1 + n_fft / 2, ceil(T / rate)]
+    in librosa's memory order.  ValueError for a rate that is not finite and > 0, a spectrum without frames, and -- where
+    librosa lets the bin poison its row -- a NaN / inf bin; NotImplementedError for an odd n_fft, an n_fft beyond 4096 or a
+    hop outside 1 .. n_fft."""
+    rate = _rate(rate)
+    P, = phase_vocoder_batch([D], [rate], hop_length, n_fft, device)
+    if P is None:
+        raise ValueError("phase_vocoder: D has no frames" if np.asarray(D).shape[1] == 0 else "phase_vocoder: D is not finite everywhere")
+    return P
 
 
 # ---- librosa's numpy helpers around a transform ---------------------------------------------------------------------------

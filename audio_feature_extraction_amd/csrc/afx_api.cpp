@@ -92,7 +92,8 @@ extern "C" void afx_destroy(afx_ctx* ctx) {
                     &ctx->ld_clips, &ctx->ld_carry, &ctx->ld_part, &ctx->ld_tpeak, &ctx->ld_tbad, &ctx->ld_seg, &ctx->ld_z, &ctx->ld_rec,
                     &ctx->ld_gain, &ctx->gt_tab, &ctx->gt_grids, &ctx->gt_y, &ctx->gt_bad, &ctx->gt_mag, &ctx->gt_nmag, &ctx->gt_mask,
                     &ctx->gt_fwd, &ctx->gt_bits, &ctx->gt_thr, &ctx->gt_amp, &ctx->gt_rows, &ctx->st_tab, &ctx->st_recs, &ctx->st_y,
-                    &ctx->st_bad, &ctx->st_rows})
+                    &ctx->st_bad, &ctx->st_rows, &ctx->pv_recs, &ctx->pv_bad, &ctx->pv_ang, &ctx->pv_mag, &ctx->pv_sum,
+                    &ctx->pv_spec, &ctx->pv_out})
     release(*b);
   if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
   delete ctx;

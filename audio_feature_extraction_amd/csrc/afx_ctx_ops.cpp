@@ -1,7 +1,7 @@
 // The entry points of libafx.so that work on a context, not a plan: batched DTW, polyphase resampling, the conversion /
 // mix-down of raw WAVE data, zero-phase IIR filtering, the recording screen and the compare sums, the whole-clip DFT and
 // the spectral distance, the median and Savitzky-Golay filters with the energy and ZCR groups, BS.1770 loudness,
-// spectral gating and librosa-style stft / istft -- and what they share: the staging of a host batch and the launches of the zero-phase filter.
+// spectral gating, librosa-style stft / istft, the phase vocoder and time stretching -- and what they share: the staging of a host batch and the launches of the zero-phase filter.
 #include <algorithm>
 #include <cmath>
 #include <cstddef>
@@ -1802,6 +1802,253 @@ extern "C" int afx_istft_batch(afx_ctx* ctx, const void* spec, int mem_kind,
     pieces.clear();
     for (int q = 0; q < n; ++q)
       if (h_out) pieces.push_back({stage_out.data() + recs[q].out_off, out_offsets[ck.idx[q]] * 4, recs[q].n_out * 4});
+    scatter_pieces(out, pieces);
+  }
+  return AFX_OK;
+}
+
+// ---- librosa-style phase_vocoder and effects.time_stretch ------------------------------------------------------------------
+static int pvoc_rates_arg(const char* who, const double* rates, int n_clips) {
+  for (int i = 0; i < n_clips; ++i)
+    if (!pvoc_rate_ok(rates[i])) { set_error(std::string(who) + ": clip " + std::to_string(i) + ": rate must be finite and > 0"); return AFX_ERR_INVALID; }
+  return AFX_OK;
+}
+
+// The planes of a chunk's vocoder passes: angle and magnitude per input element, a sum per tile and bin
+static int pvoc_planes(afx_ctx* ctx, int bins, int64_t rows, int64_t tiles) {
+  int rc;
+  if ((rc = ensure(ctx->pv_ang, (size_t)std::max<int64_t>(rows, 1) * bins * sizeof(double))) != AFX_OK) return rc;
+  if ((rc = ensure(ctx->pv_mag, (size_t)std::max<int64_t>(rows, 1) * bins * sizeof(float))) != AFX_OK) return rc;
+  return ensure(ctx->pv_sum, (size_t)std::max<int64_t>(tiles, 1) * bins * sizeof(double));
+}
+
+// k_pvoc_prep, k_pvoc_tiles, k_pvoc_carry, k_pvoc_apply over the n clips of a chunk
+static int pvoc_passes(afx_ctx* ctx, int n_fft, int hop, const float2* spec, const PvocClip* d_recs, int n, int64_t rows,
+                       int64_t tiles, uint32_t* bad, float2* out) {
+  hipStream_t s = ctx->stream;
+  const int bins = stft_bins(n_fft);
+  double *ang = (double*)ctx->pv_ang.p, *sums = (double*)ctx->pv_sum.p;
+  float* mag = (float*)ctx->pv_mag.p;
+  HIP_TRY(launch_pvoc_prep(s, bins, spec, d_recs, n, rows, ang, mag, bad));
+  HIP_TRY(launch_pvoc_tiles(s, n_fft, hop, d_recs, n, tiles, ang, sums));
+  HIP_TRY(launch_pvoc_carry(s, bins, d_recs, n, ang, sums));
+  HIP_TRY(launch_pvoc_apply(s, n_fft, hop, d_recs, n, tiles, ang, mag, sums, bad, out));
+  return AFX_OK;
+}
+
+// A chunk (cut_stft_chunk with the record of pvoc_cost over rows in + rows out): the rows staged packed when they are the
+// host's, the records uploaded, the four passes into the caller's device memory or into the packed image that goes home.
+extern "C" int afx_pvoc_batch(afx_ctx* ctx, const void* spec, int mem_kind, const int64_t* spec_offsets, const int64_t* n_frames,
+                              const double* rates, int n_clips, int n_fft, int hop,
+                              void* out, int out_mem_kind, const int64_t* out_offsets, int32_t* out_status) {
+  const char* who = "afx_pvoc_batch";
+  int rc;
+  if ((rc = clip_batch_args(who, ctx, AFX_FMT_F32, mem_kind, spec_offsets, n_frames, n_clips, out_mem_kind, out_offsets, out_status,
+                            rates != nullptr)) != AFX_OK) return rc;
+  if ((rc = pvoc_rates_arg(who, rates, n_clips)) != AFX_OK) return rc;
+  const char* why = "";
+  if ((rc = pvoc_check(n_fft, hop, &why)) != AFX_OK) { set_error(std::string(who) + ": " + why); return rc; }
+  const int bins = stft_bins(n_fft);
+  std::vector<int64_t> eff((size_t)n_clips), tout((size_t)n_clips);
+  bool any = false;
+  for (int i = 0; i < n_clips; ++i) {
+    out_status[i] = n_frames[i] == 0 ? AFX_CLIP_TOO_SHORT : AFX_CLIP_OK;
+    tout[i] = eff[i] = 0;
+    if (out_status[i] != AFX_CLIP_OK) continue;
+    if (!pvoc_frames(n_fft, n_frames[i], rates[i], &tout[i])) {
+      set_error(std::string(who) + ": clip " + std::to_string(i) + ": T_out x bins must be below 2^31");
+      return AFX_ERR_UNSUPPORTED;
+    }
+    eff[i] = pvoc_weight(n_frames[i], tout[i]);
+    any = true;
+  }
+  if (!any) return AFX_OK;
+  if (!spec || !out) { set_error(std::string(who) + ": null spec / out"); return AFX_ERR_INVALID; }
+
+  (void)hipGetLastError();
+  HIP_TRY(hipSetDevice(ctx->device));
+  hipStream_t s = ctx->stream;
+  const bool h_in = mem_kind == AFX_MEM_HOST, h_out = out_mem_kind == AFX_MEM_HOST;
+  StftCost cost;
+  pvoc_cost(n_fft, mem_kind, out_mem_kind, cost);
+  StftChunk ck;
+  std::vector<PvocClip> recs;
+  std::vector<HostPiece> pieces;
+  std::vector<char> image;
+  std::vector<uint32_t> h_bad;
+  std::vector<float> stage_out;
+  for (int c0 = 0; c0 < n_clips; c0 = ck.next) {
+    cut_stft_chunk(spec_offsets, eff.data(), n_clips, c0, dev_env().stft_budget, cost, ck);
+    const int n = (int)ck.idx.size();
+    if (n == 0) continue;
+    recs.assign((size_t)n, PvocClip{});
+    int64_t in_pos = 0, opos = 0, rows = 0, tiles = 0;
+    for (int q = 0; q < n; ++q) {
+      const int i = ck.idx[q];
+      PvocClip& r = recs[q];
+      r.spec_off = h_in ? in_pos : spec_offsets[i]; r.row_base = rows; r.out_off = h_out ? opos : out_offsets[i];
+      r.tile_base = tiles; r.rate = rates[i]; r.T = (int32_t)n_frames[i]; r.T_out = (int32_t)tout[i]; r.clip = q;
+      in_pos += n_frames[i] * bins; opos += tout[i] * bins; rows += n_frames[i]; tiles += (tout[i] + kPvocTile - 1) / kPvocTile;
+    }
+    if (rows > INT32_MAX / 2 || tiles > INT32_MAX / 2) { set_error(std::string(who) + ": chunk too large for one launch"); return AFX_ERR_UNSUPPORTED; }
+    if ((rc = ensure(ctx->pv_recs, (size_t)n * sizeof(PvocClip))) != AFX_OK) return rc;
+    if ((rc = ensure(ctx->pv_bad, (size_t)n * sizeof(uint32_t))) != AFX_OK) return rc;
+    if ((rc = pvoc_planes(ctx, bins, rows, tiles)) != AFX_OK) return rc;
+    const void* d_in = spec;
+    if (h_in) {
+      pieces.clear();
+      for (int q = 0; q < n; ++q) pieces.push_back(clip_piece(spec, spec_offsets[ck.idx[q]], recs[q].spec_off, (int64_t)recs[q].T * bins, 8));
+      if ((rc = stage_in(ctx, image, in_pos * 8, pieces, &d_in)) != AFX_OK) return rc;
+    }
+    float* d_out;
+    if ((rc = out_buffer(ctx, (float*)out, out_mem_kind, std::max<int64_t>(opos * 2, 1), &d_out)) != AFX_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(ctx->pv_recs.p, recs.data(), (size_t)n * sizeof(PvocClip), hipMemcpyHostToDevice, s));
+    uint32_t* bad = (uint32_t*)ctx->pv_bad.p;
+    HIP_TRY(hipMemsetAsync(bad, 0, (size_t)n * sizeof(uint32_t), s));
+    if ((rc = pvoc_passes(ctx, n_fft, hop, (const float2*)d_in, (const PvocClip*)ctx->pv_recs.p, n, rows, tiles, bad, (float2*)d_out)) != AFX_OK) return rc;
+    h_bad.resize((size_t)n);
+    HIP_TRY(hipMemcpyAsync(h_bad.data(), bad, h_bad.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    if (h_out && (rc = fetch_out(ctx, d_out, opos * 2, stage_out)) != AFX_OK) return rc;
+    HIP_TRY(hipStreamSynchronize(s));
+    pieces.clear();
+    for (int q = 0; q < n; ++q) {
+      const int i = ck.idx[q];
+      if (h_bad[q]) out_status[i] = AFX_CLIP_NONFINITE;
+      if (h_out) pieces.push_back({stage_out.data() + recs[q].out_off * 2, out_offsets[i] * 8, tout[i] * bins * 8});
+    }
+    scatter_pieces(out, pieces);
+  }
+  return AFX_OK;
+}
+
+// A chunk (cut_stft_chunk with the record of stretch_cost over stretch_weight): afx_stft_batch's launches into a spectrum
+// that stays in the workspace, the vocoder's four passes over it, afx_istft_batch's two launches on the vocoded rows -- the
+// same kernels on the same records as the three entry points, so the same bits.
+extern "C" int afx_time_stretch_batch(afx_ctx* ctx, const void* samples, int sample_fmt, int mem_kind,
+                                      const int64_t* offsets, const int64_t* lengths, const double* rates, int n_clips,
+                                      const afx_stft_opts* opts, const float* window,
+                                      float* out, int out_mem_kind, const int64_t* out_offsets, int32_t* out_status) {
+  const char* who = "afx_time_stretch_batch";
+  int rc;
+  if ((rc = clip_batch_args(who, ctx, sample_fmt, mem_kind, offsets, lengths, n_clips, out_mem_kind, out_offsets, out_status,
+                            opts && window && rates)) != AFX_OK) return rc;
+  if (!opts || !window) return null_arg(who);
+  if ((rc = pvoc_rates_arg(who, rates, n_clips)) != AFX_OK) return rc;
+  if ((rc = stft_opts_arg(who, opts)) != AFX_OK) return rc;
+  afx_stft_opts o = *opts;
+  o.out_kind = AFX_STFT_COMPLEX;
+  const int n_fft = o.n_fft, bins = stft_bins(n_fft), fpw = n_fft == 1024 ? 2 : 1;
+  std::vector<int64_t> eff((size_t)n_clips), frames((size_t)n_clips), tout((size_t)n_clips), nfs((size_t)n_clips), nout((size_t)n_clips);
+  bool any = false;
+  for (int i = 0; i < n_clips; ++i) {
+    stft_frames(o, lengths[i], &frames[i], &out_status[i]);
+    eff[i] = tout[i] = nfs[i] = nout[i] = 0;
+    if (out_status[i] != AFX_CLIP_OK) continue;
+    if (!stretch_length(lengths[i], rates[i], &nout[i])) {
+      set_error(std::string(who) + ": clip " + std::to_string(i) + ": length / rate must be at most 2^31");
+      return AFX_ERR_INVALID;
+    }
+    if (!pvoc_frames(n_fft, frames[i], rates[i], &tout[i])) {
+      set_error(std::string(who) + ": clip " + std::to_string(i) + ": T_out x bins must be below 2^31");
+      return AFX_ERR_UNSUPPORTED;
+    }
+    if (nout[i] == 0) continue;                                  // nothing to write: nothing to run
+    int64_t n_out = 0;
+    istft_samples(o, tout[i], nout[i], &nfs[i], &n_out);
+    eff[i] = stretch_weight(o, lengths[i], frames[i], tout[i], nout[i]);
+    any = true;
+  }
+  if (!any) return AFX_OK;
+  if (!samples || !out) { set_error(std::string(who) + ": null samples / out"); return AFX_ERR_INVALID; }
+
+  (void)hipGetLastError();
+  HIP_TRY(hipSetDevice(ctx->device));
+  hipStream_t s = ctx->stream;
+  StftTabs tb{};
+  if ((rc = stft_tables(ctx, n_fft, window, tb)) != AFX_OK) return rc;
+
+  const size_t esz = sample_fmt == AFX_FMT_S16 ? 2 : 4;
+  const bool h_in = mem_kind == AFX_MEM_HOST, h_out = out_mem_kind == AFX_MEM_HOST;
+  StftCost cost;
+  stretch_cost(o, sample_fmt, mem_kind, out_mem_kind, cost);
+  StftChunk ck;
+  std::vector<StftClip> fwd;
+  std::vector<HpssClip> prs;
+  std::vector<PvocClip> pvs;
+  std::vector<IstftClip> inv;
+  std::vector<HostPiece> pieces;
+  std::vector<char> image, up;
+  std::vector<uint32_t> h_bad;
+  std::vector<float> stage_out;
+  for (int c0 = 0; c0 < n_clips; c0 = ck.next) {
+    cut_stft_chunk(offsets, eff.data(), n_clips, c0, dev_env().stft_budget, cost, ck);
+    const int n = (int)ck.idx.size();
+    if (n == 0) continue;
+    fwd.assign((size_t)n, StftClip{}); prs.assign((size_t)n, HpssClip{}); pvs.assign((size_t)n, PvocClip{}); inv.assign((size_t)n, IstftClip{});
+    int64_t ypos = 0, in_pos = 0, dpos = 0, ppos = 0, opos = 0, rows = 0, units = 0, tiles = 0, irows = 0, iunits = 0, max_len = 0, max_out = 0;
+    for (int q = 0; q < n; ++q) {
+      const int i = ck.idx[q];
+      const int64_t L = lengths[i], T = frames[i], nf = nfs[i];
+      StftClip& f = fwd[q];
+      f.y_off = ypos; f.len = L; f.out_off = dpos; f.unit_base = units; f.T = (int32_t)T; f.clip = q;
+      prs[q].in_off = h_in ? in_pos : offsets[i]; prs[q].y_off = ypos; prs[q].len = L;
+      PvocClip& p = pvs[q];                                      // only the rows istft keeps are made
+      p.spec_off = dpos; p.row_base = rows; p.out_off = ppos; p.tile_base = tiles; p.rate = rates[i]; p.T = (int32_t)T; p.T_out = (int32_t)nf; p.clip = q;
+      IstftClip& r = inv[q];
+      r.spec_off = ppos; r.row_base = irows; r.unit_base = iunits; r.out_off = h_out ? opos : out_offsets[i]; r.n_out = nout[i]; r.n_frames = (int32_t)nf;
+      ypos += (L + 3) / 4 * 4; in_pos += (L + 3) / 4 * 4; dpos += T * bins; ppos += nf * bins; opos += (nout[i] + 3) / 4 * 4;
+      rows += T; units += (T + fpw - 1) / fpw; tiles += (nf + kPvocTile - 1) / kPvocTile; irows += nf; iunits += (nf + fpw - 1) / fpw;
+      max_len = std::max(max_len, L); max_out = std::max(max_out, nout[i]);
+    }
+    if (rows > INT32_MAX / 2 || irows > INT32_MAX / 2 || tiles > INT32_MAX / 2) { set_error(std::string(who) + ": chunk too large for one launch"); return AFX_ERR_UNSUPPORTED; }
+
+    const size_t o_prs = (size_t)n * sizeof(StftClip), o_pvs = o_prs + (size_t)n * sizeof(HpssClip), o_inv = o_pvs + (size_t)n * sizeof(PvocClip);
+    up.assign(o_inv + (size_t)n * sizeof(IstftClip), 0);
+    std::memcpy(up.data(), fwd.data(), o_prs);
+    std::memcpy(up.data() + o_prs, prs.data(), (size_t)n * sizeof(HpssClip));
+    std::memcpy(up.data() + o_pvs, pvs.data(), (size_t)n * sizeof(PvocClip));
+    std::memcpy(up.data() + o_inv, inv.data(), (size_t)n * sizeof(IstftClip));
+    if ((rc = ensure(ctx->pv_recs, up.size())) != AFX_OK) return rc;
+    if ((rc = ensure(ctx->pv_bad, (size_t)n * sizeof(uint32_t))) != AFX_OK) return rc;
+    if ((rc = ensure(ctx->st_y, (size_t)std::max<int64_t>(ypos, 1) * sizeof(float))) != AFX_OK) return rc;
+    if ((rc = ensure(ctx->pv_spec, (size_t)std::max<int64_t>(dpos, 1) * 8)) != AFX_OK) return rc;
+    if ((rc = ensure(ctx->pv_out, (size_t)std::max<int64_t>(ppos, 1) * 8)) != AFX_OK) return rc;
+    if ((rc = ensure(ctx->st_rows, (size_t)std::max<int64_t>(irows, 1) * n_fft * sizeof(float))) != AFX_OK) return rc;
+    if ((rc = pvoc_planes(ctx, bins, rows, tiles)) != AFX_OK) return rc;
+    const void* d_in = samples;
+    if (h_in) {
+      pieces.clear();
+      for (int q = 0; q < n; ++q) pieces.push_back(clip_piece(samples, offsets[ck.idx[q]], prs[q].in_off, prs[q].len, esz));
+      if ((rc = stage_in(ctx, image, in_pos * (int64_t)esz, pieces, &d_in)) != AFX_OK) return rc;
+    }
+    float* d_out;
+    if ((rc = out_buffer(ctx, out, out_mem_kind, std::max<int64_t>(opos, 1), &d_out)) != AFX_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(ctx->pv_recs.p, up.data(), up.size(), hipMemcpyHostToDevice, s));
+    const char* base = (const char*)ctx->pv_recs.p;
+    const StftClip* d_fwd = (const StftClip*)base;
+    const HpssClip* d_prs = (const HpssClip*)(base + o_prs);
+    const PvocClip* d_pvs = (const PvocClip*)(base + o_pvs);
+    const IstftClip* d_inv = (const IstftClip*)(base + o_inv);
+    float* y = (float*)ctx->st_y.p;
+    uint32_t* bad = (uint32_t*)ctx->pv_bad.p;
+    float2 *D = (float2*)ctx->pv_spec.p, *P = (float2*)ctx->pv_out.p;
+    float* trows = (float*)ctx->st_rows.p;
+    HIP_TRY(hipMemsetAsync(bad, 0, (size_t)n * sizeof(uint32_t), s));
+    HIP_TRY(launch_hpss_prep(s, d_in, sample_fmt, 0, 0.f, d_prs, n, max_len, y, bad));
+    HIP_TRY(launch_stft_frames(s, o, y, d_fwd, bad, n, units, tb, D));
+    if ((rc = pvoc_passes(ctx, n_fft, o.hop, D, d_pvs, n, rows, tiles, bad, P)) != AFX_OK) return rc;
+    HIP_TRY(launch_istft_frames(s, n_fft, P, d_inv, n, iunits, tb, trows));
+    HIP_TRY(launch_istft_ola(s, o, trows, d_inv, n, max_out, tb, d_out));
+    h_bad.resize((size_t)n);
+    HIP_TRY(hipMemcpyAsync(h_bad.data(), bad, h_bad.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    if (h_out && (rc = fetch_out(ctx, d_out, opos, stage_out)) != AFX_OK) return rc;
+    HIP_TRY(hipStreamSynchronize(s));
+    pieces.clear();
+    for (int q = 0; q < n; ++q) {
+      const int i = ck.idx[q];
+      if (h_bad[q]) out_status[i] = AFX_CLIP_NONFINITE;
+      if (h_out) pieces.push_back({stage_out.data() + inv[q].out_off, out_offsets[i] * 4, inv[q].n_out * 4});
+    }
     scatter_pieces(out, pieces);
   }
   return AFX_OK;

@@ -1,6 +1,6 @@
 // Device entry points of the HOST-ONLY build (libafx_host_asan.so, `make asan`): every one fails loudly with
 // AFX_ERR_NO_DEVICE.  The sanitizer build exists to run the host-side parsers and table builders (afx_wav.cpp,
-// afx_tables.cpp, afx_f0_tables.cpp, afx_resample_tables.cpp, afx_filt_host.cpp, afx_beat_host.cpp, afx_assess_host.cpp, afx_cfft_host.cpp, afx_smooth_host.cpp, afx_loudness_host.cpp, afx_gate_host.cpp, afx_stft_host.cpp, afx_host.cpp) under AddressSanitizer + UBSan on the CPU; GPU sanitizers are not
+// afx_tables.cpp, afx_f0_tables.cpp, afx_resample_tables.cpp, afx_filt_host.cpp, afx_beat_host.cpp, afx_assess_host.cpp, afx_cfft_host.cpp, afx_smooth_host.cpp, afx_loudness_host.cpp, afx_gate_host.cpp, afx_stft_host.cpp, afx_pvoc_host.cpp, afx_host.cpp) under AddressSanitizer + UBSan on the CPU; GPU sanitizers are not
 // available on the target pool.  Never linked into libafx.so.
 #include <cstddef>
 #include <cstdint>
@@ -129,5 +129,13 @@ int afx_stft_batch(afx_ctx*, const void*, int, int, const int64_t*, const int64_
 int afx_istft_batch(afx_ctx*, const void*, int, const int64_t*, const int64_t*, int, const afx_stft_opts*, const float*,
                     const int64_t*, float*, int, const int64_t*, int32_t*) {
   return no_device("afx_istft_batch");
+}
+int afx_pvoc_batch(afx_ctx*, const void*, int, const int64_t*, const int64_t*, const double*, int, int, int, void*, int,
+                   const int64_t*, int32_t*) {
+  return no_device("afx_pvoc_batch");
+}
+int afx_time_stretch_batch(afx_ctx*, const void*, int, int, const int64_t*, const int64_t*, const double*, int, const afx_stft_opts*,
+                           const float*, float*, int, const int64_t*, int32_t*) {
+  return no_device("afx_time_stretch_batch");
 }
 }

@@ -27,6 +27,7 @@
 #include "afx_rhythm.h"
 #include "afx_smooth.h"
 #include "afx_stft.h"
+#include "afx_pvoc.h"
 
 namespace afx {
 
@@ -80,6 +81,9 @@ struct afx_ctx {
   // afx_stft_batch / afx_istft_batch: the window and twiddles, a chunk's clip records, its float32 signal and non-finite
   // flags (forward), the time rows the overlap-add reads (inverse)
   DevBuf st_tab, st_recs, st_y, st_bad, st_rows;
+  // afx_pvoc_batch / afx_time_stretch_batch: a chunk's clip records and non-finite flags, the angle and magnitude planes,
+  // the tile sums; the stretch's spectrum and its vocoded rows (it takes the window, y and the time rows from the st_ set)
+  DevBuf pv_recs, pv_bad, pv_ang, pv_mag, pv_sum, pv_spec, pv_out;
 };
 
 struct afx_plan {

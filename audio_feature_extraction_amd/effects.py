@@ -294,3 +294,46 @@ def reduce_noise(y, sr: int, y_noise=None, *, device: int = 0, **kw) -> np.ndarr
     if y.ndim != 1:
         raise NotImplementedError(f"reduce_noise: only mono audio is supported, got shape {y.shape}")
     return reduce_noise_batch([y], sr, y_noise, device=device, **kw)[0]
+
+
+# ---- time stretching (afx_time_stretch_batch): librosa.effects.time_stretch -------------------------------------------------
+def time_stretch_batch(signals: Sequence[np.ndarray], rates, *, n_fft: int = 2048, hop_length: Optional[int] = None,
+                       win_length: Optional[int] = None, window="hann", center: bool = True, pad_mode: str = "constant",
+                       device: int = 0) -> List[Optional[np.ndarray]]:
+    """``librosa.effects.time_stretch(signal, rate=rates[i], ...)`` of many mono signals in one device pass (one rate for all,
+    or one per signal): stft, phase vocoder and istft with the spectra never leaving the device.  Per signal float32 of
+    round(len / rate) samples, or None where the single call would raise.  ``device`` may be a callable that names the
+    device: it is asked only once the arguments have passed."""
+    from .core import spectrum as S
+    opts = S._opts(n_fft, hop_length, win_length, center, pad_mode)
+    table = S._window(window, win_length, opts.n_fft)
+    sig = [S._signal(s, i) for i, s in enumerate(signals)]
+    rates = [rates] * len(sig) if np.isscalar(rates) else list(rates)
+    if len(rates) != len(sig):
+        raise ValueError("rates must have one entry per signal")
+    rates = [S._rate(r, i) for i, r in enumerate(rates)]
+    if not sig:
+        return []
+    if len({s.dtype for s in sig}) > 1:
+        sig = [s if s.dtype == np.float32 else s.astype(np.float32) / np.float32(32768.0) for s in sig]
+    size = np.array([s.size for s in sig], np.int64)
+    offsets = _native.packed_offsets(size, 4)
+    buf = np.zeros(max(int((offsets + size).max()), 1), sig[0].dtype)
+    for o, s in zip(offsets, sig):
+        buf[o:o + s.size] = s
+    r = _ctx(device() if callable(device) else device).time_stretch_batch(buf, offsets, size, rates, opts, table)
+    return [r["out"][o:o + n].copy() if st == _native.CLIP_OK else None for o, n, st in zip(r["offsets"], r["samples"], r["status"])]
+
+
+def time_stretch(y, *, rate, n_fft: int = 2048, hop_length: Optional[int] = None, win_length: Optional[int] = None,
+                 window="hann", center: bool = True, pad_mode: str = "constant", device: int = 0) -> np.ndarray:
+    """``librosa.effects.time_stretch(y, rate=rate, ...)`` for mono audio on the GPU: ``istft(phase_vocoder(stft(y), rate),
+    length=round(len(y) / rate))`` in one device call; float32.  ``rate > 1`` speeds up.  stft's
+    limits apply (n_fft 1024 or 2048); ValueError for a rate that is not finite and > 0 and for a clip stft refuses."""
+    from .core import spectrum as S
+    rate = S._rate(rate)
+    out, = time_stretch_batch([y], [rate], n_fft=n_fft, hop_length=hop_length, win_length=win_length, window=window,
+                              center=center, pad_mode=pad_mode, device=device)
+    if out is None:
+        raise ValueError("time_stretch: y is too short for this framing or not finite everywhere")
+    return out

@@ -916,7 +916,51 @@ int afx_istft_batch(afx_ctx* ctx, const void* spec /* complex64 rows */, int mem
                     const int64_t* lengths /* NULL, or per clip, < 0: none */,
                     float* out, int out_mem_kind, const int64_t* out_offsets, int32_t* out_status);
 
-/* The recording screen of 00_audio_data_collection_experiment/audio_format_assessment.py:143-300 (detect_silence,
+/* librosa.phase_vocoder and librosa.effects.time_stretch (librosa 0.11) of mono clips: what brings a student take to a
+ * teacher's duration without changing its pitch.  DESIGN.md section 27 is the definition and tests/pvoc_ref.py its numpy
+ * restatement.  All seven symbols are newer than AFX_VERSION 107 says: a binding detects them by their presence.
+ *
+ * phase_vocoder: clip i is n_frames[i] = T rows of bins = n_fft / 2 + 1 complex64 at element spec_offsets[i] of spec, frame
+ * after frame (afx_stft_batch's layout); n_fft even in [2, 4096], hop in [1, n_fft] (anything else: AFX_ERR_UNSUPPORTED).
+ * rates[i] must be finite and > 0 (AFX_ERR_INVALID before any device work).  T_out = ceil(T / rate) in float64 rows go to
+ * element out_offsets[i] of out; T_out x bins >= 2^31 is AFX_ERR_UNSUPPORTED.  Step t: s = double(t) rate, j = floor(s),
+ * a = s - j; c0 = D[:, j], c1 = D[:, j + 1], columns T and beyond being +0 + 0i; mag = float32(1 - a) |c0| + float32(a) |c1|
+ * in float32 (|c| = sqrt(re re + im im), every operation rounded once); the phase in float64: phi[k] = 2 pi hop k / n_fft,
+ * acc_0 = angle(D[:, 0]), acc_{t+1} = acc_t + phi + wrap(angle(c1) - angle(c0) - phi), wrap(d) = d - 2 pi rint(d / 2 pi);
+ * out[:, t] = complex64(mag cos(acc_t), mag sin(acc_t)).  The sum runs in a fixed order: within a tile of AFX_PVOC_TILE
+ * steps in increasing t from 0.0, then tile after tile, and the accumulator is reduced to [-pi, pi] after every tile
+ * (only acc mod 2 pi is observable).  out_status: AFX_CLIP_TOO_SHORT (nothing written) for T = 0; AFX_CLIP_NONFINITE for a
+ * NaN / inf bin anywhere in the clip's D: zeros out, where librosa lets the bin poison its row from there on.
+ *
+ * time_stretch: stft -> phase_vocoder -> istft(length = n_out), n_out = rint(length / rate) in float64, halves to even, in
+ * one call on one workspace with the kernels and records of the three entry points, so bit for bit what they give one after
+ * another; the spectra never leave the device.  opts and window as afx_stft_batch takes them (out_kind AFX_STFT_COMPLEX);
+ * out_status as afx_stft_batch gives it, and AFX_CLIP_NONFINITE (zeros out) for a spectrum that overflowed as well.
+ *
+ * No atomics in any sum: a clip's result is bit-identical whatever the rest of the batch, the order of the clips, host or
+ * device memory and the chunk cut (afx_stft_chunks with the record of afx_pvoc_cost over T + T_out per clip, or of
+ * afx_time_stretch_cost over T + T_out + ceil(length / hop) + ceil(n_out / hop); 0 for a clip with nothing to run).
+ *
+ * afx_pvoc_frames (host-only): T_out and the status of a clip of T rows.
+ * afx_time_stretch_samples (host-only): the frames of the clip, the rows of the stretch and the samples written.
+ * afx_pvoc_host (host-only): the same definition in plain C++ for one clip, the kernels' specification; out holds T_out
+ * rows.  The kernels agree with it to rounding (libm's atan2 / cos / sin against the device's). */
+enum { AFX_PVOC_TILE = 32 };
+int afx_pvoc_frames(int n_fft, int hop, int64_t T, double rate, int64_t* T_out, int32_t* clip_status);
+int afx_time_stretch_samples(const afx_stft_opts* opts, int64_t length, double rate, int64_t* T, int64_t* T_out, int64_t* n_out,
+                             int32_t* clip_status);
+int afx_pvoc_cost(int n_fft, int mem_kind, int out_mem_kind, int64_t* cost /*[6]*/);
+int afx_time_stretch_cost(const afx_stft_opts* opts, int sample_fmt, int mem_kind, int out_mem_kind, int64_t* cost /*[6]*/);
+int afx_pvoc_host(const void* spec /* complex64 rows */, int64_t T, double rate, int n_fft, int hop, void* out, int32_t* clip_status);
+int afx_pvoc_batch(afx_ctx* ctx, const void* spec /* complex64 rows */, int mem_kind,
+                   const int64_t* spec_offsets /* complex elements */, const int64_t* n_frames, const double* rates, int n_clips,
+                   int n_fft, int hop, void* out, int out_mem_kind, const int64_t* out_offsets, int32_t* out_status);
+int afx_time_stretch_batch(afx_ctx* ctx, const void* samples, int sample_fmt, int mem_kind,
+                           const int64_t* offsets, const int64_t* lengths, const double* rates, int n_clips,
+                           const afx_stft_opts* opts, const float* window /*[n_fft], host*/,
+                           float* out, int out_mem_kind, const int64_t* out_offsets, int32_t* out_status);
+
+/* The recording screen of00_audio_data_collection_experiment/audio_format_assessment.py:143-300 (detect_silence,
  * check_volume_levels, check_amplitude_stability, estimate_snr) and the sums behind the scores of
  * audio_quality_assessment.py:150-280 (SNR of the difference, Pearson correlation, MSE), as per-clip reductions.  All five
  * symbols are newer than AFX_VERSION 107 says: a binding detects them by their presence.
