@@ -12,7 +12,7 @@ pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SIZES = [1, 2, 63, 64, 65, 127, 128, 129, 300, 1000]
-DIMS = [1, 7, 13, 39, 64, 65, 120, 128]
+DIMS = [1, 7, 13, 39, 64, 65, 120, 128, 20]
 BANDS = [None, 0.1, 0.25, 0.5]
 
 
@@ -35,8 +35,11 @@ def _cases():
     out = []
     for c in range(60):
         n, m = int(rng.choice(SIZES)), int(rng.choice(SIZES))
-        out.append((c, n, m, DIMS[c % len(DIMS)], BANDS[(c // len(DIMS)) % len(BANDS)], c % 10 == 9))
+        out.append((c, n, m, DIMS[c % 8], BANDS[(c // 8) % len(BANDS)], c % 10 == 9))   # the first eight dims: ids as before
     out += [(60, 64, 64, 13, None, True), (61, 129, 65, 39, 0.25, True), (62, 1, 1, 1, None, False)]
+    # dim 20 (librosa's n_mfcc default): the 24-wide instance, on both sides of a strip edge, with every band
+    out += [(63, 65, 129, 20, None, False), (64, 129, 65, 20, 0.1, False), (65, 64, 300, 20, 0.25, False),
+            (66, 300, 127, 20, 0.5, False), (67, 128, 128, 20, None, True), (68, 2, 63, 20, 0.25, False)]
     return out
 
 

@@ -16,7 +16,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # strip boundaries (lanes 0 and 1 read both boundary rows at 64 / 65 / 66 and 128 / 129 / 130), tile edges (multiples of 8
 # and their neighbours) and ring edges (the 72-column ring wraps at 72)
 SIZES = [1, 2, 3, 7, 8, 9, 63, 64, 65, 66, 71, 72, 73, 127, 128, 129, 130, 200]
-DIMS = [1, 13, 39, 64, 128]
+DIMS = [1, 13, 39, 64, 128, 20]
 W_MUL = [1.0, 1.5, 2.0, 3.0]
 W_ADD = [0.0, 0.5, 1.0]
 SLOPE = [[1, 1], [1, 2], [2, 1]]
@@ -61,11 +61,20 @@ def _cases():
                 weighted = name == "defw" or c % 2 == 1
                 wa = rng.choice(W_ADD, size=k).tolist() if weighted else None
                 wm = rng.choice(W_MUL, size=k).tolist() if weighted else None
-                out.append((name, subseq, c, n, m, DIMS[(c + len(out)) % len(DIMS)], wa, wm, None))
+                out.append((name, subseq, c, n, m, DIMS[(c + len(out)) % 5], wa, wm, None))   # the first five dims: ids as before
     for c in range(PER_GROUP):                     # default steps + weights + band, with subseq
         n, m = int(rng.choice(SIZES[1:])), int(rng.choice(SIZES[1:]))
-        out.append(("defw-band", True, c, n, m, DIMS[c % len(DIMS)], rng.choice(W_ADD, size=3).tolist(),
+        out.append(("defw-band", True, c, n, m, DIMS[c % 5], rng.choice(W_ADD, size=3).tolist(),
                     rng.choice(W_MUL, size=3).tolist(), [0.25, 0.5][c % 2]))
+    # dim 20 (librosa's n_mfcc default): the 24-wide instance, one weighted case per list, with and without subseq, drawn
+    # after every case above so that those keep their shapes
+    for name in LISTS:
+        for subseq in (False, True):
+            n, m = _shape(rng, name, subseq, PER_GROUP)
+            k = 3 if LISTS[name] is None else len(LISTS[name])
+            out.append((name, subseq, PER_GROUP, n, m, 20, rng.choice(W_ADD, size=k).tolist(),
+                        rng.choice(W_MUL, size=k).tolist(), None))
+    out.append(("defw-band", True, PER_GROUP, 129, 72, 20, [0.0, 0.5, 1.0], [1.0, 1.5, 2.0], 0.25))
     return out
 
 
